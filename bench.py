@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: coinrun, 65 536 envs per GPU, synthetic random actions, observations in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--game coinrun]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--game coinrun] [--full] [--dump-outputs DIR]
     python bench.py --workload mixed [--gather]      # BASELINE.json configs[4]: all seven games, envs split 7 ways
 
 One "step" = one pass of the hot path over the whole batch: the logic kernel (auto-reset or 4 physics
@@ -15,11 +15,17 @@ and relays rank 0's line.  --dry-launch prints that command instead of running i
 
 The timed region is preceded by --warmup steps AND --settle steps (default 512, untimed, reported): all envs are
 made in the same step, and the first few hundred steps after that have almost no resets in them, so a short run would
-time a transient that is ≈ 8 % faster than steady state.  The roofline leg is always measured on its own window of
-≥ 256 steps after the timed region (`roofline.window`), whatever --steps says.
+time a transient that is ≈ 8 % faster than steady state.
 
-Prints ONE JSON line (rank 0) with `roofline` (render kernel, HIP-event timed on the engine's stream) and,
-at N=1, `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, all host cores).
+Prints ONE JSON line (rank 0): `value` (env-steps/s of the timed region) and `ms_per_step` (milliseconds of one timed
+step).  A plain run does only that.  --full adds what takes runs of its own: `roofline` (render kernel and per-phase HIP
+events on the engine's stream, measured on its own window of ≥ 256 steps after the timed region, `roofline.window`,
+whatever --steps says; the device-to-device copy rate; the profiled traffic), the latency percentiles of that window
+and, at N=1, `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, all host cores).
+
+--dump-outputs DIR writes what the last timed step handed its caller, before anything else runs on the envs
+(dump_outputs): the inputs are fixed by the arguments (seeds, device-hashed actions), so two builds can be compared
+output for output.
 """
 import argparse
 import ctypes
@@ -39,6 +45,32 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 # 0.03 % of it.)
 ALGO_BYTES_PER_ENV_STEP = 12297
 HBM_PEAK_GBPS = 8000.0           # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+# --dump-outputs: observations of at most DUMP_OBS_ENVS envs (a float32 frame is 49 152 B: 1 024 of them are 48 MiB),
+# rewards and dones of at most DUMP_SCALAR_ENVS (8 MiB for both): under 64 MB in all, whatever --envs is.
+DUMP_OBS_ENVS = 1024
+DUMP_SCALAR_ENVS = 1 << 20
+
+
+def dump_outputs(directory, obs, reward, done):
+    """What one step handed its caller (obs u8 [N,64,64,3], reward f32 [N], done u8 [N] on the device) as float32 .npy
+    files in `directory`: obs.npy of the envs at dump_rows(N, DUMP_OBS_ENVS), reward.npy and done.npy of those at
+    dump_rows(N, DUMP_SCALAR_ENVS) — every env of the default 65 536."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    n = obs.shape[0]
+    for name, t, limit in (("obs", obs, DUMP_OBS_ENVS), ("reward", reward, DUMP_SCALAR_ENVS), ("done", done, DUMP_SCALAR_ENVS)):
+        rows = torch.as_tensor(dump_rows(n, limit), device=t.device)
+        np.save(os.path.join(directory, name + ".npy"), t.index_select(0, rows).to(torch.float32).cpu().numpy())
+
+
+def dump_rows(n, limit):
+    """The envs whose outputs dump_outputs writes, in order: all n when n <= limit, else a fixed sample of `limit` of them
+    (numpy's default_rng(0), sorted) — the same rows in every run with the same --envs."""
+    import numpy as np
+    if n <= limit:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n, size=limit, replace=False)).astype(np.int64)
 
 
 def csrc_fingerprint():
@@ -225,6 +257,9 @@ class FirstContact:
         try:
             return fn()
         except BaseException as exc:
+            # The stage has ended: disarm the watchdog before reporting, or a slow report (a cold `import torch`) outlasts
+            # the timeout and the watchdog replaces this report with "timed out".
+            timer.cancel()
             first_contact_report(name, self.rank, self.local_rank, self.world, exc)
             raise SystemExit(3)
         finally:
@@ -251,6 +286,14 @@ def main():
                     help="untimed steps before the warm-up so that episode ends are spread out (steady state)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N > 1 and no WORLD_SIZE: print the torch.distributed.run command and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline window (per-phase HIP "
+                         "events, latency percentiles), the device-to-device copy rate, the profiled traffic and, at "
+                         "one GPU, the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them handed its caller as DIR/<name>.npy "
+                         "(float32; rank 0): obs of at most %d envs, reward and done of at most %d (a fixed sample "
+                         "beyond that: bench.dump_rows)" % (DUMP_OBS_ENVS, DUMP_SCALAR_ENVS))
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be >= 1")
@@ -315,27 +358,30 @@ def main():
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, env.obs, env.reward, env.done)  # before --full's window steps overwrite them
     fence()
-    # Roofline leg and latency percentiles: the dominant kernel's launch durations and the per-step times over their own
-    # steady-state window (HIP events on the engine's stream), independent of how short the timed region was asked to be.
-    window = max(256, a.steps)
-    ph = env.step_phases(window, run_seed)
-    import numpy as np
-    step_ms = ph["step"]
-    render_avg_ms = float(ph["render"].mean())
-    prepass_avg_ms, logic_avg_ms, late_avg_ms = float(ph["prepass"].mean()), float(ph["logic"].mean()), float(ph["late"].mean())
-    p50_ms, mean_ms = float(np.median(step_ms)), float(step_ms.mean())
+    # --full: roofline leg and latency percentiles: the dominant kernel's launch durations and the per-step times over their
+    # own steady-state window (HIP events on the engine's stream), independent of how short the timed region was asked to be.
+    window_ms = []
+    if a.full:
+        window = max(256, a.steps)
+        ph = env.step_phases(window, run_seed)
+        import numpy as np
+        step_ms = ph["step"]
+        window_ms = [float(ph["render"].mean()), float(np.median(step_ms)), float(step_ms.mean()), float(ph["prepass"].mean()),
+                     float(ph["logic"].mean()), float(ph["late"].mean())]
     per_rank_ms = [elapsed / a.steps * 1e3]
     if distributed:
-        t = torch.tensor([elapsed, render_avg_ms, p50_ms, mean_ms, prepass_avg_ms, logic_avg_ms, late_avg_ms], dtype=torch.float64, device="cuda")
+        t = torch.tensor([elapsed] + window_ms, dtype=torch.float64, device="cuda")
         mine = torch.tensor([elapsed / a.steps * 1e3], dtype=torch.float64, device="cuda")
         every = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)  # a straggler rank shows in the first SCALE record
         per_rank_ms = [float(x[0]) for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, render_avg_ms, p50_ms, mean_ms, prepass_avg_ms, logic_avg_ms, late_avg_ms = (float(x) for x in t)
+        elapsed, window_ms = float(t[0]), [float(x) for x in t[1:]]
     fence()
-    copy_gbps = measured_copy_bandwidth(torch, env.device, a.envs * 12288) if rank == 0 else None
+    copy_gbps = measured_copy_bandwidth(torch, env.device, a.envs * 12288) if a.full and rank == 0 else None
 
     done_frac = float(env.done.float().mean().item())
     env.close()
@@ -343,14 +389,7 @@ def main():
     if rank == 0:
         total_steps = float(n_gpus) * a.envs * a.steps
         value = total_steps / elapsed
-        algo = ALGO_BYTES_PER_ENV_STEP * a.envs
-        achieved = algo / (render_avg_ms * 1e-3) / 1e9
-        # The path, not a launch: everything that turns the step's state into the frame (pre-pass + render kernel + late /
-        # list kernels), and the whole step as `value` times it — a fraction that cannot rise by moving work across a
-        # launch boundary.
-        path_ms = prepass_avg_ms + render_avg_ms + late_avg_ms
         ms_per_step = elapsed / a.steps * 1e3
-        traffic, traffic_src, traffic_stale = measured_traffic(a.game) if a.envs == 65536 and not a.mode else (None, None, None)
         line = {
             "metric": "env-steps/sec at 65536 envs, 64x64x3 obs",
             "value": value,
@@ -361,8 +400,6 @@ def main():
             "settle_steps": a.settle,
             "ms_per_step": ms_per_step,
             "per_rank_ms": per_rank_ms,
-            "p50_ms_per_step": p50_ms,
-            "mean_ms_per_step_window": mean_ms,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -372,32 +409,42 @@ def main():
                                    "next-step auto-reset, seeds 1+global env index" % (a.game, a.envs),
                        "game": a.game, "distribution_mode": a.mode or "default", "envs_per_gpu": a.envs, "obs": "64x64x3 uint8", "parallelism": "env-shard x%d, no collective" % n_gpus},
             "obs_write_GBps": value * 12288 / 1e9,
-            "roofline": {"bound": "hbm", "kernel": "%s::render_kernel" % a.game, "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                         "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                         "whole_step_frac": algo / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                         "render_path": {"achieved": algo / (path_ms * 1e-3) / 1e9, "frac": algo / (path_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                         "avg_ms": path_ms, "what": "render pre-pass + render kernel + late / list kernels"},
-                         "kernels": [{"name": "logic kernels (auto-reset install, agent / entities / resolve or the game's logic kernel)", "avg_us": logic_avg_ms * 1e3},
-                                     {"name": "%s::setup_kernel (render pre-pass)" % a.game, "avg_us": prepass_avg_ms * 1e3},
-                                     {"name": "%s::render_kernel" % a.game, "avg_us": render_avg_ms * 1e3},
-                                     {"name": "late pass / list kernels behind the render launch", "avg_us": late_avg_ms * 1e3}],
-                         "peak_measured": copy_gbps,
-                         "peak_measured_how": "device-to-device copy of %d bytes (read + written bytes per second, best "
-                                              "of 5), outside the timed region" % (a.envs * 12288),
-                         "frac_of_measured": (achieved / copy_gbps) if copy_gbps else None,
-                         "algorithmic_bytes_per_launch": algo,
-                         "avg_launch_ms": render_avg_ms,
-                         "window": "%d steps after the timed region (steps %d..%d since make), HIP events on the engine's "
-                                   "stream between the phases of every step (pgv_step_phases): `frac` is the render kernel "
-                                   "alone, `render_path` adds the pre-pass in front of it and what follows it inside the "
-                                   "step, `whole_step_frac` is the same bytes over ms_per_step of the timed region"
-                                   % (window, a.settle + max(1, a.warmup) + a.steps,
-                                      a.settle + max(1, a.warmup) + a.steps + window - 1)},
             "done_fraction_last_step": done_frac,
         }
-        if n_gpus == 1 and not a.no_cpu_baseline and not a.mode:
-            line["cpu_baseline"] = cpu_baseline(a.game, run_seed)
+        if a.full:
+            render_avg_ms, p50_ms, mean_ms, prepass_avg_ms, logic_avg_ms, late_avg_ms = window_ms
+            algo = ALGO_BYTES_PER_ENV_STEP * a.envs
+            achieved = algo / (render_avg_ms * 1e-3) / 1e9
+            # The path, not a launch: everything that turns the step's state into the frame (pre-pass + render kernel + late /
+            # list kernels), and the whole step as `value` times it — a fraction that cannot rise by moving work across a
+            # launch boundary.
+            path_ms = prepass_avg_ms + render_avg_ms + late_avg_ms
+            traffic, traffic_src, traffic_stale = measured_traffic(a.game) if a.envs == 65536 and not a.mode else (None, None, None)
+            line["p50_ms_per_step"], line["mean_ms_per_step_window"] = p50_ms, mean_ms
+            line["roofline"] = {"bound": "hbm", "kernel": "%s::render_kernel" % a.game, "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                                "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+                                "whole_step_frac": algo / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                "render_path": {"achieved": algo / (path_ms * 1e-3) / 1e9, "frac": algo / (path_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                                "avg_ms": path_ms, "what": "render pre-pass + render kernel + late / list kernels"},
+                                "kernels": [{"name": "logic kernels (auto-reset install, agent / entities / resolve or the game's logic kernel)", "avg_us": logic_avg_ms * 1e3},
+                                            {"name": "%s::setup_kernel (render pre-pass)" % a.game, "avg_us": prepass_avg_ms * 1e3},
+                                            {"name": "%s::render_kernel" % a.game, "avg_us": render_avg_ms * 1e3},
+                                            {"name": "late pass / list kernels behind the render launch", "avg_us": late_avg_ms * 1e3}],
+                                "peak_measured": copy_gbps,
+                                "peak_measured_how": "device-to-device copy of %d bytes (read + written bytes per second, best "
+                                                     "of 5), outside the timed region" % (a.envs * 12288),
+                                "frac_of_measured": (achieved / copy_gbps) if copy_gbps else None,
+                                "algorithmic_bytes_per_launch": algo,
+                                "avg_launch_ms": render_avg_ms,
+                                "window": "%d steps after the timed region (steps %d..%d since make), HIP events on the engine's "
+                                          "stream between the phases of every step (pgv_step_phases): `frac` is the render kernel "
+                                          "alone, `render_path` adds the pre-pass in front of it and what follows it inside the "
+                                          "step, `whole_step_frac` is the same bytes over ms_per_step of the timed region"
+                                          % (window, a.settle + max(1, a.warmup) + a.steps,
+                                             a.settle + max(1, a.warmup) + a.steps + window - 1)}
+            if n_gpus == 1 and not a.no_cpu_baseline and not a.mode:
+                line["cpu_baseline"] = cpu_baseline(a.game, run_seed)
         print(json.dumps(line), flush=True)
     if distributed:
         dist.destroy_process_group()
@@ -491,13 +538,15 @@ def mixed(a, torch, ProcgenVecEnv, distributed, world, rank, local_rank, n_gpus,
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *local)  # the rank's slab, every game's block of it
     fence()
-    # Per-game phases over a window of their own, all seven stepping side by side as in the timed region (events on each
-    # game's stream; the streams overlap, so a game's numbers are what its stream saw, not a share of the wall clock).
-    from procgen2_amd.vec_env import step_phases_many
-    import numpy as np
-    window = 128
-    ph = step_phases_many(envs, window, run_seed).mean(axis=2)  # [game][step, logic, prepass, render, late]
+    if a.full:
+        # Per-game phases over a window of their own, all seven stepping side by side as in the timed region (events on each
+        # game's stream; the streams overlap, so a game's numbers are what its stream saw, not a share of the wall clock).
+        from procgen2_amd.vec_env import step_phases_many
+        window = 128
+        ph = step_phases_many(envs, window, run_seed).mean(axis=2)  # [game][step, logic, prepass, render, late]
     per_rank_ms = [elapsed / a.steps * 1e3]
     if distributed:
         mine = torch.tensor([elapsed / a.steps * 1e3], dtype=torch.float64, device="cuda")
@@ -509,15 +558,6 @@ def mixed(a, torch, ProcgenVecEnv, distributed, world, rank, local_rank, n_gpus,
         e.close()
     if rank == 0:
         value = float(n_gpus) * a.envs * a.steps / elapsed
-        algo = ALGO_BYTES_PER_ENV_STEP * a.envs
-        achieved = algo / (elapsed / a.steps) / 1e9
-        kernels, paths = [], {}
-        for g, (game, count) in enumerate(zip(GAMES, counts)):
-            for j, what in ((1, "logic kernels"), (2, "setup_kernel (render pre-pass)"), (3, "render_kernel"), (4, "late pass / list kernels")):
-                kernels.append({"name": "%s: %s" % (game, what), "avg_us": float(ph[g][j]) * 1e3})
-            path_ms = float(ph[g][2] + ph[g][3] + ph[g][4])
-            paths[game] = {"envs": count, "avg_ms": path_ms, "achieved": ALGO_BYTES_PER_ENV_STEP * count / (path_ms * 1e-3) / 1e9,
-                           "step_ms": float(ph[g][0])}
         line = {
             "metric": "env-steps/sec, all 7 games mixed, 64x64x3 obs",
             "value": value, "unit": "env-steps/s", "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
@@ -530,20 +570,30 @@ def mixed(a, torch, ProcgenVecEnv, distributed, world, rank, local_rank, n_gpus,
                        "parallelism": "env-shard x%d, %s" % (n_gpus, "rooted RCCL gather to rank 0 every step"
                                                              if a.gather and distributed else "no collective")},
             "obs_write_GBps": value * 12288 / 1e9,
-            "roofline": {"bound": "hbm", "kernel": "whole step, all games (wall clock, not one kernel)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "whole_step_frac": achieved / HBM_PEAK_GBPS,
-                         "render_path": {"per_game": paths,
-                                         "what": "per game, on its own stream while the other six run beside it: render pre-pass + "
-                                                 "render kernel + late / list kernels of its share of the slab (the streams "
-                                                 "overlap: these do not add up to the wall clock)"},
-                         "kernels": kernels,
-                         "window": "%d steps after the timed region, all seven games side by side, HIP events on each game's "
-                                   "stream (pgv_step_phases_many)" % window,
-                         "traffic": None},
         }
-        if n_gpus == 1 and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline_mixed(list(GAMES), counts, run_seed)
+        if a.full:
+            algo = ALGO_BYTES_PER_ENV_STEP * a.envs
+            achieved = algo / (elapsed / a.steps) / 1e9
+            kernels, paths = [], {}
+            for g, (game, count) in enumerate(zip(GAMES, counts)):
+                for j, what in ((1, "logic kernels"), (2, "setup_kernel (render pre-pass)"), (3, "render_kernel"), (4, "late pass / list kernels")):
+                    kernels.append({"name": "%s: %s" % (game, what), "avg_us": float(ph[g][j]) * 1e3})
+                path_ms = float(ph[g][2] + ph[g][3] + ph[g][4])
+                paths[game] = {"envs": count, "avg_ms": path_ms, "achieved": ALGO_BYTES_PER_ENV_STEP * count / (path_ms * 1e-3) / 1e9,
+                               "step_ms": float(ph[g][0])}
+            line["roofline"] = {"bound": "hbm", "kernel": "whole step, all games (wall clock, not one kernel)",
+                                "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                                "whole_step_frac": achieved / HBM_PEAK_GBPS,
+                                "render_path": {"per_game": paths,
+                                                "what": "per game, on its own stream while the other six run beside it: render pre-pass + "
+                                                        "render kernel + late / list kernels of its share of the slab (the streams "
+                                                        "overlap: these do not add up to the wall clock)"},
+                                "kernels": kernels,
+                                "window": "%d steps after the timed region, all seven games side by side, HIP events on each game's "
+                                          "stream (pgv_step_phases_many)" % window,
+                                "traffic": None}
+            if n_gpus == 1 and not a.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline_mixed(list(GAMES), counts, run_seed)
         print(json.dumps(line), flush=True)
     if distributed:
         dist.destroy_process_group()

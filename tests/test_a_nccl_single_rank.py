@@ -46,14 +46,14 @@ def _bench_under_the_launcher(args, timeout=600):
 
 def test_mixed_workload_with_the_rooted_gather_runs_over_nccl_on_one_rank():
     line = _bench_under_the_launcher(["--workload", "mixed", "--gather", "--steps", "8", "--warmup", "2", "--settle", "0",
-                                      "--envs", "7168"])
+                                      "--envs", "7168", "--full"])
     assert line["n_gpus"] == 1 and line["steps"] == 8 and line["value"] > 0
     assert "gather" in line["config"]["parallelism"], line["config"]["parallelism"]
     assert line["scaling"] == "weak"
 
 
 def test_headline_workload_runs_as_a_rank_of_a_process_group():
-    line = _bench_under_the_launcher(["--steps", "8", "--warmup", "2", "--settle", "0", "--no-cpu-baseline"])
+    line = _bench_under_the_launcher(["--steps", "8", "--warmup", "2", "--settle", "0", "--no-cpu-baseline", "--full"])
     assert line["n_gpus"] == 1 and line["steps"] == 8 and line["value"] > 0
     assert line["config"]["parallelism"].startswith("env-shard x1")
     assert line["roofline"]["frac"] > 0 and "cpu_baseline" not in line

@@ -1,9 +1,11 @@
 """The bench line's regression gate (tools/check_bench.py) and bench.py's first-contact guard: host
-logic only, no GPU."""
+logic only, no GPU; and bench.py's plain run with --dump-outputs (one GPU test)."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -74,3 +76,43 @@ def test_first_contact_reports_a_raising_and_a_hanging_stage():
         assert "first barrier" in report["bench_error"]
         assert report["env"]["MASTER_ADDR"] == "127.0.0.1" and report["env"]["NCCL_DEBUG"] == "WARN"
         assert ("ZeroDivisionError" in report["error"]) == (mode == "raise")
+
+
+def test_dump_rows_are_a_fixed_sample_and_the_dump_stays_under_64_mb():
+    """bench.py --dump-outputs: the same envs in every run with the same --envs, all of them while they fit, and the
+    float32 files under 64 MB in all whatever --envs is."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    assert np.array_equal(bench.dump_rows(700, bench.DUMP_OBS_ENVS), np.arange(700))
+    rows = bench.dump_rows(65536, bench.DUMP_OBS_ENVS)
+    assert np.array_equal(rows, bench.dump_rows(65536, bench.DUMP_OBS_ENVS))
+    assert rows.shape == (bench.DUMP_OBS_ENVS,) and np.all(np.diff(rows) > 0) and rows[-1] < 65536
+    assert np.array_equal(bench.dump_rows(65536, bench.DUMP_SCALAR_ENVS), np.arange(65536))
+    most = bench.DUMP_OBS_ENVS * 64 * 64 * 3 * 4 + 2 * bench.DUMP_SCALAR_ENVS * 4
+    assert most <= 64e6, most
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_its_dumped_outputs_repeat(tmp_path):
+    """A plain bench.py run times its --steps and prints the headline only (no roofline window, no CPU baseline);
+    --dump-outputs writes the last timed step's outputs, the same in two runs with the same arguments."""
+    import numpy as np
+    envs, steps = 4096, 6
+    dumps = []
+    for k in range(2):
+        out = os.path.join(tmp_path, "run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                            "--settle", "16", "--envs", str(envs), "--dump-outputs", out],
+                           cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-4000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["unit"] == "env-steps/s" and line["higher_is_better"] is True
+        assert "roofline" not in line and "cpu_baseline" not in line
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 - envs) < 1e-6 * envs
+        dumps.append({n: np.load(os.path.join(out, n + ".npy")) for n in ("obs", "reward", "done")})
+    assert dumps[0]["obs"].shape == (1024, 64, 64, 3) and dumps[0]["reward"].shape == (envs,)
+    assert all(d.dtype == np.float32 for d in dumps[0].values())
+    assert dumps[0]["obs"].max() > 0  # a rendered frame, not an untouched buffer
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
