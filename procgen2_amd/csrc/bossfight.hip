@@ -1455,42 +1455,21 @@ class BossfightGame final : public Game {
         for (int k = 0; k < 4; k++) plain(kTexPlayer + k, 0.05f, 1.0f);
         stamps_at_ = append_stamps(atlas, kTexCount, specs);
     }
-    static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-    struct Layout {
-        size_t mt, f, i, ashot, abnc, bshot, boom, rock, total;
-    };
-    static Layout layout(int n) {
-        Layout l{};
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            size_t at = off;
-            off += align256(bytes);
-            return at;
-        };
-        l.mt = take(size_t(n) * kMtWords * 4);
-        l.f = take(size_t(F_COUNT) * n * 4);
-        l.i = take(size_t(I_COUNT) * n * 4);
-        l.ashot = take(size_t(S_COUNT) * kAgentShots * n * 4);
-        l.abnc = take(size_t(kAgentShots) * n);
-        l.bshot = take(size_t(S_COUNT) * kBossShots * n * 4);
-        l.boom = take(size_t(3) * kBooms * n * 4);
-        l.rock = take(size_t(3) * kRocks * n * 4);
-        l.total = off;
-        return l;
+    // The state block, in order (state_bytes and bind).
+    static void carve(Carve& c, State& s, int n) {
+        c.take(s.mt, size_t(n) * kMtWords * 4);
+        c.take(s.f, size_t(F_COUNT) * n * 4);
+        c.take(s.i, size_t(I_COUNT) * n * 4);
+        c.take(s.ashot, size_t(S_COUNT) * kAgentShots * n * 4);
+        c.take(s.abnc, size_t(kAgentShots) * n);
+        c.take(s.bshot, size_t(S_COUNT) * kBossShots * n * 4);
+        c.take(s.boom, size_t(3) * kBooms * n * 4);
+        c.take(s.rock, size_t(3) * kRocks * n * 4);
     }
-    size_t state_bytes(int n) const override { return layout(n).total; }
+    size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        uint8_t* p = static_cast<uint8_t*>(d_state);
-        const Layout l = layout(n);
+        Carve::bind(carve, d_state, s_, n);
         s_.n = n;
-        s_.mt = reinterpret_cast<uint32_t*>(p + l.mt);
-        s_.f = reinterpret_cast<float*>(p + l.f);
-        s_.i = reinterpret_cast<int32_t*>(p + l.i);
-        s_.ashot = reinterpret_cast<float*>(p + l.ashot);
-        s_.abnc = p + l.abnc;
-        s_.bshot = reinterpret_cast<float*>(p + l.bshot);
-        s_.boom = reinterpret_cast<float*>(p + l.boom);
-        s_.rock = reinterpret_cast<float*>(p + l.rock);
         s_.stamps = stamps_at_;
         atlas_ = atlas;
     }
@@ -1525,63 +1504,41 @@ class BossfightGame final : public Game {
         else
             hipLaunchKernelGGL(render_full_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);
     }
-    static size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-    size_t scratch_bytes(int n) const override {
-        return up256(size_t(kBackdrops) * 128 * 4) + up256(size_t(n) * 4) + up256(size_t(n) * kBossShots * kBulletWords * 4) +
-               up256(size_t(n) * kPrepDraws * kBlitWords * 4) + up256(size_t(n) * kMtN * 4) + up256(size_t(n)) +
-               up256(size_t(kBackdrops) * kFbWords * 4);
+    // Scratch, in order (scratch_bytes and bind_scratch).
+    static void carve_scratch(Carve& c, State& s, int n) {
+        c.take(s.prep.backdrops, size_t(kBackdrops) * 128 * 4);
+        c.take(s.prep.meta, size_t(n) * 4);
+        c.take(s.prep.bullets, size_t(n) * kBossShots * kBulletWords * 4);
+        c.take(s.prep.draws, size_t(n) * kPrepDraws * kBlitWords * 4);
+        c.take(s.mt_other, size_t(n) * kMtN * 4);
+        c.take(s.mt_sel, size_t(n));  // (the engine zeroes the scratch block: every stream is at home, nothing is made ahead)
+        c.take(s.prep.backdrop_px, size_t(kBackdrops) * kFbWords * 4);
     }
-    void state_loaded(hipStream_t st) override {
-        hipMemsetAsync(s_.mt_sel, 0, size_t(s_.n), st);  // the streams that were just loaded are in mt[env]; what was made ahead is not theirs
+    size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
+    void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_, n); }
+    hipError_t state_loaded(hipStream_t st) override {
+        return hipMemsetAsync(s_.mt_sel, 0, size_t(s_.n), st);  // the streams that were just loaded are in mt[env]; what was made ahead is not theirs
     }
     // A snapshot takes the streams from mt[env]: the ones whose gang has moved on to the second buffer come home first.
     void prepare_save(hipStream_t st) override {
         hipLaunchKernelGGL(streams_home_kernel, dim3((s_.n + 63) / 64), dim3(64), 0, st, s_);
     }
-    void bind_scratch(void* d_scratch, int n) override {
-        uint8_t* p = static_cast<uint8_t*>(d_scratch);
-        s_.prep.backdrops = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(kBackdrops) * 128 * 4);
-        s_.prep.meta = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * 4);
-        s_.prep.bullets = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * kBossShots * kBulletWords * 4);
-        s_.prep.draws = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * kPrepDraws * kBlitWords * 4);
-        s_.mt_other = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * kMtN * 4);
-        s_.mt_sel = p;  // (the engine zeroes the scratch block: every stream is at home, nothing is made ahead)
-        p += up256(size_t(n));
-        s_.prep.backdrop_px = reinterpret_cast<uint32_t*>(p);
-    }
     // Same layout as oracle/pgo_bossfight.cpp Bossfight::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {
         hipStreamSynchronize(st);
         const size_t n = s_.n;
-        auto rf = [&](const float* base, size_t idx) {
-            float v;
-            hipMemcpy(&v, base + idx, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto f = [&](int field) { return rf(s_.f, size_t(field) * n + env); };
-        auto iv = [&](int field) {
-            int32_t v;
-            hipMemcpy(&v, s_.i + size_t(field) * n + env, 4, hipMemcpyDeviceToHost);
-            return static_cast<float>(v);
-        };
-        int32_t flags;
-        hipMemcpy(&flags, s_.i + size_t(I_FLAGS) * n + env, 4, hipMemcpyDeviceToHost);
+        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
+        auto iv = [&](int field) { return static_cast<float>(read_one(s_.i + size_t(field) * n + env)); };
+        const int32_t flags = read_one(s_.i + size_t(I_FLAGS) * n + env);
         std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), (flags & kFlagAlive) ? 1.0f : 0.0f, f(F_ATIMER),
                                 iv(I_A_NEXT), iv(I_A_COUNT), f(F_BX), f(F_BY), f(F_BVX), f(F_BVY), f(F_PHASE_T),
                                 iv(I_PHASE), iv(I_WEAPON), f(F_ATTACK_T), iv(I_HP), iv(I_B_NEXT), iv(I_B_COUNT),
                                 iv(I_X_NEXT), iv(I_X_COUNT), f(F_EXPLO_T), f(F_DAMAGE_T), f(F_MOVE_T), iv(I_NROCKS)};
         for (int k = 0; k < kAgentShots; k++)
-            for (int fld : {S_X, S_Y, S_FRAME}) v.push_back(rf(s_.ashot, (size_t(env) * S_COUNT + fld) * kAgentShots + k));
+            for (int fld : {S_X, S_Y, S_FRAME}) v.push_back(read_one(s_.ashot + (size_t(env) * S_COUNT + fld) * kAgentShots + k));
         for (int k = 0; k < kBossShots; k++)
-            for (int fld : {S_X, S_Y, S_FRAME}) v.push_back(rf(s_.bshot, (size_t(env) * S_COUNT + fld) * kBossShots + k));
-        const int m = cap < static_cast<int>(v.size()) ? cap : static_cast<int>(v.size());
-        for (int k = 0; k < m; k++) out[k] = v[k];
-        return static_cast<int>(v.size());
+            for (int fld : {S_X, S_Y, S_FRAME}) v.push_back(read_one(s_.bshot + (size_t(env) * S_COUNT + fld) * kBossShots + k));
+        return dump_out(v, out, cap);
     }
     int dump_tiles(hipStream_t, int, uint8_t*, int) override { return 0; }
 

@@ -1306,7 +1306,7 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
     }
 }
 
-class CaveflyerGame final : public Game {
+class CaveflyerGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "caveflyer"; }
     std::vector<std::string> texture_names() const override {
@@ -1324,82 +1324,50 @@ class CaveflyerGame final : public Game {
     std::string check_atlas(const std::vector<std::pair<int, int>>& sizes) const override {
         return static_cast<int>(sizes.size()) == kTexCount ? "" : "caveflyer: unexpected texture count";
     }
-    static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-    struct Layout {
-        size_t shadow, slot, mt, tiles, cols, f, i, ef, eb, sh, pf, total;
-    };
-    static Layout layout(int n) {
-        Layout l{};
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            size_t at = off;
-            off += align256(bytes);
-            return at;
-        };
-        l.shadow = take(size_t(n) * sizeof(Level));
-        l.slot = take(size_t(n) * 4);
-        l.mt = take(size_t(n) * kMtWords * 4);
-        l.tiles = take(size_t(n) * kTileStride);
-        l.cols = take(size_t(n) * W * 8);
-        l.f = take(size_t(F_COUNT) * n * 4);
-        l.i = take(size_t(I_COUNT) * n * 4);
-        l.ef = take(size_t(EF_COUNT) * kEntStride * n * 4);
-        l.eb = take(size_t(EB_COUNT) * kEntStride * n);
-        l.sh = take(size_t(SH_COUNT) * kShots * n * 4);
-        l.pf = take(size_t(PF_COUNT) * kPuffSlots * n * 4);
-        l.total = off;
-        return l;
+    // The state block, in order (state_bytes and bind).
+    static void carve(Carve& c, State& s, int n) {
+        c.take(s.shadow, size_t(n) * sizeof(Level));
+        c.take(s.slot, size_t(n) * 4);
+        c.take(s.mt, size_t(n) * kMtWords * 4);
+        c.take(s.tiles, size_t(n) * kTileStride);
+        c.take(s.cols, size_t(n) * W * 8);
+        c.take(s.f, size_t(F_COUNT) * n * 4);
+        c.take(s.i, size_t(I_COUNT) * n * 4);
+        c.take(s.ef, size_t(EF_COUNT) * kEntStride * n * 4);
+        c.take(s.eb, size_t(EB_COUNT) * kEntStride * n);
+        c.take(s.sh, size_t(SH_COUNT) * kShots * n * 4);
+        c.take(s.pf, size_t(PF_COUNT) * kPuffSlots * n * 4);
     }
-    size_t state_bytes(int n) const override { return layout(n).total; }
+    size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        uint8_t* p = static_cast<uint8_t*>(d_state);
-        const Layout l = layout(n);
+        Carve::bind(carve, d_state, s_, n);
         s_.n = n;
-        s_.shadow = reinterpret_cast<Level*>(p + l.shadow);
-        s_.slot = reinterpret_cast<int32_t*>(p + l.slot);
-        s_.mt = reinterpret_cast<uint32_t*>(p + l.mt);
-        s_.tiles = p + l.tiles;
-        s_.cols = reinterpret_cast<uint64_t*>(p + l.cols);
-        s_.f = reinterpret_cast<float*>(p + l.f);
-        s_.i = reinterpret_cast<int32_t*>(p + l.i);
-        s_.ef = reinterpret_cast<float*>(p + l.ef);
-        s_.eb = p + l.eb;
-        s_.sh = reinterpret_cast<float*>(p + l.sh);
-        s_.pf = reinterpret_cast<float*>(p + l.pf);
         s_.ranks = atlas.sort_ranks;
         atlas_ = atlas;
     }
     int blocks() const { return (s_.n + 63) / 64; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
         hipLaunchKernelGGL(make_kernel, dim3(blocks()), dim3(64), 0, st, s_, seed_base, env_offset);
-        LevelLaunch<Gen>::make(st, s_, prefetch(), seed_base, env_offset, plan);
-    }
-    void launch_reset(hipStream_t st, const uint8_t* mask, const int32_t* seeds, StepIO io) override {
-        LevelLaunch<Gen>::reset(st, s_, prefetch(), mask, seeds, io, plan);
+        make_levels(st, seed_base, env_offset);
     }
     int pregen_every() const override { return 2; }  // (pg_engine.h)
-    bool launch_pregen(hipStream_t side, bool bulk) override {
-        if (!prefetch()) return false;
-        LevelLaunch<Gen>::pregen(side, s_, bulk, plan);
-        return true;
-    }
-    int prefetch() const { return (debug_flags & kDebugNoPrefetch) ? 0 : 1; }
     void launch_logic(hipStream_t st, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
                       StepIO io) override {
         // prefetched levels are installed beside the logic (its second row of blocks); the level kernel behind it
         // generates, synchronously, the levels that were not ready — none in steady state (pg_prefetch.h install_prefetched)
         const bool fused = prefetch() != 0;
-        if (!fused) LevelLaunch<Gen>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, reset_served_mark(step_index), reset_due_mark(step_index));
+        reset_before_logic(st, step_index, io);
         hipLaunchKernelGGL(logic_kernel, dim3((s_.n * kGang + 63) / 64, fused ? 2 : 1), dim3(64), 0, st, s_, actions, run_seed, step_index,
                            env_offset, io, prefetch(), plan);
-        if (fused) LevelLaunch<Gen>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, reset_served_mark(step_index), reset_due_mark(step_index));
+        reset_after_logic(st, step_index, io);
     }
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
     }
-    size_t scratch_bytes(int n) const override { return prep_bytes(n, kGrid, kBlitWords, false); }
-    void bind_scratch(void* d_scratch, int n) override { s_.prep = prep_bind(d_scratch, n, kGrid, kBlitWords, false); }
+    static void carve_scratch(Carve& c, PrepOut& p, int n) { prep_carve(c, p, n, kGrid, kBlitWords, false); }
+    size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
+    void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_.prep, n); }
     void launch_prepass(hipStream_t st, const uint8_t* mask) override {
         if (!(debug_flags & (1 | kDebugNoPrepass)))
             hipLaunchKernelGGL(setup_kernel, dim3((s_.n + kPrepEnvs - 1) / kPrepEnvs), dim3(kPrepThreads), 0, st, s_, atlas_, mask, debug_flags);
@@ -1411,31 +1379,21 @@ class CaveflyerGame final : public Game {
     int dump_state(hipStream_t st, int env, float* out, int cap) override {
         hipStreamSynchronize(st);
         const size_t n = s_.n;
-        auto rf = [&](const float* base, size_t idx) {
-            float v;
-            hipMemcpy(&v, base + idx, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto ri = [&](int field) {
-            int32_t v;
-            hipMemcpy(&v, s_.i + size_t(field) * n + env, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto f = [&](int field) { return rf(s_.f, size_t(field) * n + env); };
+        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
+        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
         const int flags = ri(I_FLAGS), n_ent = ri(I_NENT);
         std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), f(F_ROT), f(F_CAMX), f(F_CAMY),
                                 static_cast<float>(ri(I_BACKDROP)), f(F_BGSHIFT), static_cast<float>(ri(I_SNEXT)),
                                 static_cast<float>(ri(I_SCOUNT)), f(F_STIMER), f(F_PTIMER),
                                 (flags & kFlagPuffOn) ? 1.0f : 0.0f, static_cast<float>(n_ent)};
         for (int k = 0; k < kShots; k++)
-            for (int fld : {SH_X, SH_Y, SH_FRAME}) v.push_back(rf(s_.sh, (size_t(env) * SH_COUNT + fld) * kShots + k));
+            for (int fld : {SH_X, SH_Y, SH_FRAME}) v.push_back(read_one(s_.sh + (size_t(env) * SH_COUNT + fld) * kShots + k));
         for (int k = 0; k < kPuffs; k++)
-            for (int fld : {PF_X, PF_Y, PF_LIFE}) v.push_back(rf(s_.pf, (size_t(env) * PF_COUNT + fld) * kPuffSlots + k));
+            for (int fld : {PF_X, PF_Y, PF_LIFE}) v.push_back(read_one(s_.pf + (size_t(env) * PF_COUNT + fld) * kPuffSlots + k));
         for (int e = 0; e < n_ent; e++) {
             if (e == 1) continue;
-            uint8_t info;
-            hipMemcpy(&info, s_.eb + (size_t(env) * EB_COUNT + EB_INFO) * kEntStride + e, 1, hipMemcpyDeviceToHost);
-            auto ef = [&](int field) { return rf(s_.ef, (size_t(env) * EF_COUNT + field) * kEntStride + e); };
+            const uint8_t info = read_one(s_.eb + (size_t(env) * EB_COUNT + EB_INFO) * kEntStride + e);
+            auto ef = [&](int field) { return read_one(s_.ef + (size_t(env) * EF_COUNT + field) * kEntStride + e); };
             v.push_back((info & kAlive) ? 1.0f : 0.0f);
             v.push_back(static_cast<float>(info & kKindMask));
             v.push_back(ef(EF_X));
@@ -1443,19 +1401,13 @@ class CaveflyerGame final : public Game {
             v.push_back(ef(EF_VX));
             v.push_back(ef(EF_VY));
         }
-        const int m = cap < static_cast<int>(v.size()) ? cap : static_cast<int>(v.size());
-        for (int k = 0; k < m; k++) out[k] = v[k];
-        return static_cast<int>(v.size());
+        return dump_out(v, out, cap);
     }
     int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        hipStreamSynchronize(st);
-        const int m = cap < kCells ? cap : kCells;
-        hipMemcpy(out, s_.tiles + size_t(env) * kTileStride, m, hipMemcpyDeviceToHost);
-        return m;
+        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
     }
 
    private:
-    State s_{};
     AtlasView atlas_{};
 };
 

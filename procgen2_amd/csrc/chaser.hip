@@ -1505,58 +1505,31 @@ class ChaserGame final : public Game {
         while (atlas.texel_bytes() % 16) atlas.append_words({0u});  // (the kernels read the table 16 bytes at a time)
         s_.stamps = atlas.append_words(words);
     }
-    static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-    struct Layout {
-        size_t shadow, slot, mt, tiles, f, i, mf, mb, eb, reset_list, reset_count, due_list, due_count, prepared, total;
-    };
-    static Layout layout(int n) {
-        Layout l{};
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            size_t at = off;
-            off += align256(bytes);
-            return at;
-        };
-        l.shadow = take(sizeof(Level));  // unused: this game never prefetches
-        l.slot = take(size_t(n) * 4);
-        l.mt = take(size_t(n) * kMtWords * 4);
-        l.tiles = take(size_t(n) * kTileStride);
-        l.f = take(size_t(F_COUNT) * n * 4);
-        l.i = take(size_t(I_COUNT) * n * 4);
-        l.mf = take(size_t(MF_COUNT) * kMobs * n * 4);
-        l.mb = take(size_t(2) * kMobs * n);
-        l.eb = take(size_t(EB_COUNT) * kMaxEnt * n);  // (same size either way round)
-        l.reset_list = take(size_t(n) * 4);
-        l.reset_count = take(8);
-        l.due_list = take(size_t(2) * n * 4);
-        l.due_count = take(8);
-        l.prepared = take(sizeof(ComposeHand));
-        l.total = off;
-        return l;
+    // The state block, in order (state_bytes and bind).
+    static void carve(Carve& c, State& s, int n) {
+        c.take(s.shadow, sizeof(Level));  // unused: this game never prefetches
+        c.take(s.slot, size_t(n) * 4);
+        c.take(s.mt, size_t(n) * kMtWords * 4);
+        c.take(s.tiles, size_t(n) * kTileStride);
+        c.take(s.f, size_t(F_COUNT) * n * 4);
+        c.take(s.i, size_t(I_COUNT) * n * 4);
+        c.take(s.mf, size_t(MF_COUNT) * kMobs * n * 4);
+        c.take(s.mb, size_t(2) * kMobs * n);
+        c.take(s.eb, size_t(EB_COUNT) * kMaxEnt * n);  // (same size either way round)
+        c.take(s.reset_list, size_t(n) * 4);
+        c.take(s.reset_count, 8);
+        c.take(s.due_list, size_t(2) * n * 4);
+        c.take(s.due_count, 8);
+        c.take(s.prepared, sizeof(ComposeHand));
     }
-    size_t state_bytes(int n) const override { return layout(n).total; }
+    size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     bool set_game_flags(uint32_t flags) override {  // include/procgen2_vec.h PGV_CHASER_FLOAT_ABS
         s_.float_abs = (flags & PGV_CHASER_FLOAT_ABS) ? 1 : 0;
         return (flags & ~PGV_CHASER_FLOAT_ABS) == 0;
     }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        uint8_t* p = static_cast<uint8_t*>(d_state);
-        const Layout l = layout(n);
+        Carve::bind(carve, d_state, s_, n);
         s_.n = n;
-        s_.shadow = reinterpret_cast<Level*>(p + l.shadow);
-        s_.slot = reinterpret_cast<int32_t*>(p + l.slot);
-        s_.mt = reinterpret_cast<uint32_t*>(p + l.mt);
-        s_.tiles = p + l.tiles;
-        s_.f = reinterpret_cast<float*>(p + l.f);
-        s_.i = reinterpret_cast<int32_t*>(p + l.i);
-        s_.mf = reinterpret_cast<float*>(p + l.mf);
-        s_.mb = p + l.mb;
-        s_.eb = p + l.eb;
-        s_.reset_list = reinterpret_cast<int32_t*>(p + l.reset_list);
-        s_.reset_count = reinterpret_cast<int32_t*>(p + l.reset_count);
-        s_.due_list = reinterpret_cast<int32_t*>(p + l.due_list);
-        s_.due_count = reinterpret_cast<int32_t*>(p + l.due_count);
-        s_.prepared = reinterpret_cast<ComposeHand*>(p + l.prepared);
         s_.ranks = atlas.sort_ranks;
         atlas_ = atlas;
     }
@@ -1605,33 +1578,27 @@ class ChaserGame final : public Game {
             hipLaunchKernelGGL(render_kernel<false>, dim3(s_.n), dim3(128), 0, st, s_, atlas_, nullptr, io, debug_flags, 1);
         base_valid_ = true;  // (either way every env's layer has been written by now, or is by this launch and the late pass)
     }
-    static size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-    size_t scratch_bytes(int n) const override {
-        return up256(size_t(2) * kCells * kBlitWords * 4) + up256(size_t(n) * kMovers * kBlitWords * 4) + up256(size_t(n) * 8 * 4) +
-               up256(size_t(n) * kFbWords * 4) + up256(size_t(n) * kMtN * 4) + up256(size_t(n));
+    // Scratch, in order (scratch_bytes and bind_scratch).
+    static void carve_scratch(Carve& c, State& s, int n) {
+        c.take(s.prep.cell_blits, size_t(2) * kCells * kBlitWords * 4);
+        c.take(s.prep.movers, size_t(n) * kMovers * kBlitWords * 4);
+        c.take(s.prep.bg, size_t(n) * 8 * 4);
+        c.take(s.base, size_t(n) * kFbWords * 4);
+        c.take(s.mt_other, size_t(n) * kMtN * 4);
+        c.take(s.mt_sel, size_t(n));  // (the engine zeroes the scratch block: every stream is at home, nothing is made ahead)
     }
-    void state_loaded(hipStream_t st) override {
+    size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
+    void bind_scratch(void* d_scratch, int n) override {
+        Carve::bind(carve_scratch, d_scratch, s_, n);
         base_valid_ = false;
-        hipMemsetAsync(s_.mt_sel, 0, size_t(s_.n), st);  // the streams that were just loaded are in mt[env]; what was made ahead is not theirs
+    }
+    hipError_t state_loaded(hipStream_t st) override {
+        base_valid_ = false;
+        return hipMemsetAsync(s_.mt_sel, 0, size_t(s_.n), st);  // the streams that were just loaded are in mt[env]; what was made ahead is not theirs
     }
     // A snapshot takes the streams from mt[env]: the ones whose gang has moved on to the second buffer come home first.
     void prepare_save(hipStream_t st) override {
         hipLaunchKernelGGL(streams_home_kernel, dim3((s_.n + 63) / 64), dim3(64), 0, st, s_);
-    }
-    void bind_scratch(void* d_scratch, int n) override {
-        uint8_t* p = static_cast<uint8_t*>(d_scratch);
-        s_.prep.cell_blits = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(2) * kCells * kBlitWords * 4);
-        s_.prep.movers = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * kMovers * kBlitWords * 4);
-        s_.prep.bg = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * 8 * 4);
-        s_.base = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * kFbWords * 4);
-        s_.mt_other = reinterpret_cast<uint32_t*>(p);
-        p += up256(size_t(n) * kMtN * 4);
-        s_.mt_sel = p;  // (the engine zeroes the scratch block: every stream is at home, nothing is made ahead)
-        base_valid_ = false;
     }
     bool launch_render_late(hipStream_t st, StepIO io) override {
         const int groups = s_.n < 1024 ? s_.n : 1024;
@@ -1642,42 +1609,28 @@ class ChaserGame final : public Game {
     int dump_state(hipStream_t st, int env, float* out, int cap) override {
         hipStreamSynchronize(st);
         const size_t n = s_.n;
-        auto rf = [&](const float* base, size_t idx) {
-            float v;
-            hipMemcpy(&v, base + idx, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto rb = [&](const uint8_t* base, size_t idx) {
-            uint8_t v;
-            hipMemcpy(&v, base + idx, 1, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto ri = [&](int field) {
-            int32_t v;
-            hipMemcpy(&v, s_.i + size_t(field) * n + env, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto f = [&](int field) { return rf(s_.f, size_t(field) * n + env); };
+        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
+        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
+        auto eb = [&](int field, int e) { return read_one(s_.eb + (size_t(env) * EB_COUNT + field) * kMaxEnt + e); };
         const int n_ent = ri(I_NENT);
         std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), f(F_NVX), f(F_NVY), f(F_INPUT_T), f(F_ANIM_T),
                                 static_cast<float>(ri(I_ANIM_I)), f(F_EAT_T), static_cast<float>(ri(I_BG)), f(F_BGSHIFT),
                                 static_cast<float>(n_ent)};
         for (int e = 0; e < n_ent; e++) {
-            const int info = rb(s_.eb, (size_t(env) * EB_COUNT + EB_INFO) * kMaxEnt + e);
-            const int cell = rb(s_.eb, (size_t(env) * EB_COUNT + EB_CELL) * kMaxEnt + e) |
-                             (kWideCells ? rb(s_.eb, (size_t(env) * EB_COUNT + EB_CELL_HI) * kMaxEnt + e) << 8 : 0);
+            const int info = eb(EB_INFO, e);
+            const int cell = eb(EB_CELL, e) | (kWideCells ? eb(EB_CELL_HI, e) << 8 : 0);
             const int kind = info & kKindMask;
             v.push_back((info & kAlive) ? 1.0f : 0.0f);
             v.push_back(static_cast<float>(kind));
             if (kind == kEgg) {
                 const int m = e - kOrbs;
-                auto mf = [&](int field) { return rf(s_.mf, (size_t(field) * kMobs + m) * n + env); };
+                auto mf = [&](int field) { return read_one(s_.mf + (size_t(field) * kMobs + m) * n + env); };
                 v.push_back(mf(MF_X));
                 v.push_back(mf(MF_Y));
                 v.push_back(mf(MF_VX));
                 v.push_back(mf(MF_VY));
                 v.push_back(mf(MF_HATCH));
-                v.push_back(static_cast<float>(rb(s_.mb, (size_t(0) * kMobs + m) * n + env)));
+                v.push_back(static_cast<float>(read_one(s_.mb + (size_t(0) * kMobs + m) * n + env)));
             } else {
                 v.push_back(static_cast<float>(cell / H) + 0.5f);
                 v.push_back(static_cast<float>(H - 1 - cell % H) + 0.5f);
@@ -1687,15 +1640,10 @@ class ChaserGame final : public Game {
                 v.push_back(0.0f);
             }
         }
-        const int m = cap < static_cast<int>(v.size()) ? cap : static_cast<int>(v.size());
-        for (int k = 0; k < m; k++) out[k] = v[k];
-        return static_cast<int>(v.size());
+        return dump_out(v, out, cap);
     }
     int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        hipStreamSynchronize(st);
-        const int m = cap < kCells ? cap : kCells;
-        hipMemcpy(out, s_.tiles + size_t(env) * kTileStride, m, hipMemcpyDeviceToHost);
-        return m;
+        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
     }
 
    private:

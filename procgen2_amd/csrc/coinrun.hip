@@ -1792,7 +1792,7 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-class CoinrunGame final : public Game {
+class CoinrunGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "coinrun"; }
     bool set_game_flags(uint32_t flags) override {
@@ -1848,73 +1848,38 @@ class CoinrunGame final : public Game {
         return "";
     }
 
-    static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-    struct Layout {
-        size_t shadow, slot, mt, tiles, f, i, ey, eb, df, db, spark, scratch, total;
-    };
-    static Layout layout(int n) {
-        Layout l{};
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            size_t at = off;
-            off += align256(bytes);
-            return at;
-        };
-        l.shadow = take(size_t(n) * sizeof(Level));
-        l.slot = take(size_t(n) * 4);
-        l.mt = take(size_t(n) * kMtWords * 4);
-        l.tiles = take(size_t(n) * W * H);
-        l.f = take(size_t(F_COUNT) * n * 4);
-        l.i = take(size_t(I_COUNT) * n * 4);
-        l.ey = take(size_t(kMaxEnt) * n * 4);
-        l.eb = take(size_t(EB_COUNT) * kMaxEnt * n);
-        l.df = take(size_t(2) * DF_COUNT * kMaxEnt * n * 4);
-        l.db = take(size_t(2) * kMaxEnt * n);
-        l.spark = take(size_t(2) * 3 * kMaxEnt * kSparkRow * n * 4);
-        l.scratch = take(size_t(SC_COUNT) * n * 4);
-        l.total = off;
-        return l;
+    // The state block, in order (state_bytes and bind).
+    static void carve(Carve& c, State& s, int n) {
+        c.take(s.shadow, size_t(n) * sizeof(Level));
+        c.take(s.slot, size_t(n) * 4);
+        c.take(s.mt, size_t(n) * kMtWords * 4);
+        c.take(s.tiles, size_t(n) * W * H);
+        c.take(s.f, size_t(F_COUNT) * n * 4);
+        c.take(s.i, size_t(I_COUNT) * n * 4);
+        c.take(s.ey, size_t(kMaxEnt) * n * 4);
+        c.take(s.eb, size_t(EB_COUNT) * kMaxEnt * n);
+        c.take(s.df, size_t(2) * DF_COUNT * kMaxEnt * n * 4);
+        c.take(s.db, size_t(2) * kMaxEnt * n);
+        c.take(s.spark, size_t(2) * 3 * kMaxEnt * kSparkRow * n * 4);
+        c.take(s.scratch, size_t(SC_COUNT) * n * 4);
     }
-    size_t state_bytes(int n) const override { return layout(n).total; }
+    size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        uint8_t* p = static_cast<uint8_t*>(d_state);
-        const Layout l = layout(n);
+        Carve::bind(carve, d_state, s_, n);
         s_.n = n;
-        s_.shadow = reinterpret_cast<Level*>(p + l.shadow);
-        s_.slot = reinterpret_cast<int32_t*>(p + l.slot);
-        s_.mt = reinterpret_cast<uint32_t*>(p + l.mt);
-        s_.tiles = p + l.tiles;
-        s_.f = reinterpret_cast<float*>(p + l.f);
-        s_.i = reinterpret_cast<int32_t*>(p + l.i);
-        s_.ey = reinterpret_cast<float*>(p + l.ey);
-        s_.eb = p + l.eb;
-        s_.df = reinterpret_cast<float*>(p + l.df);
-        s_.db = p + l.db;
-        s_.spark = reinterpret_cast<float*>(p + l.spark);
-        s_.scratch = reinterpret_cast<float*>(p + l.scratch);
         atlas_ = atlas;
     }
     int blocks() const { return (s_.n + 63) / 64; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
         hipLaunchKernelGGL(make_kernel, dim3(blocks()), dim3(64), 0, st, s_, seed_base, env_offset);
-        LevelLaunch<Gen>::make(st, s_, prefetch(), seed_base, env_offset, plan);
+        make_levels(st, seed_base, env_offset);
     }
-    void launch_reset(hipStream_t st, const uint8_t* mask, const int32_t* seeds, StepIO io) override {
-        LevelLaunch<Gen>::reset(st, s_, prefetch(), mask, seeds, io, plan);
-    }
-    bool launch_pregen(hipStream_t side, bool bulk) override {
-        if (!prefetch()) return false;
-        LevelLaunch<Gen>::pregen(side, s_, bulk, plan);
-        return true;
-    }
-    int prefetch() const { return (debug_flags & kDebugNoPrefetch) ? 0 : 1; }
     void launch_logic(hipStream_t st, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
                       StepIO io) override {
         // the auto-resets: a prefetched level is installed beside the agents (logic_kernel's row 1); the levels that were
         // not ready — none in steady state — are generated synchronously behind it
         const bool fused = prefetch() != 0;
-        const int served = reset_served_mark(step_index), due = reset_due_mark(step_index);
-        if (!fused) LevelLaunch<Gen>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, served, due);
+        reset_before_logic(st, step_index, io);
         // agents, prefetched installs and entities side by side (logic_kernel)
         const dim3 blocks((s_.n + 63) / 64, 2 + kMobRows + kStaticRows);
         // (bit 24: no reach — the tests' way to resolve_kernel's fallback, see hazard_near)
@@ -1943,80 +1908,43 @@ class CoinrunGame final : public Game {
     }
     // Scratch (not state, not in snapshots): the pre-pass's hand-over, then the hazards' boxes — written by logic_kernel's
     // entity lanes and read by resolve_kernel of the same step, only where a candidate bit of that step says so.
-    static size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-    size_t scratch_bytes(int n) const override {
-        return up256(prep_bytes(n, kGrid, kBlitWords, false)) + up256(size_t(kMaxEnt) * n * sizeof(float4)) +
-               up256(size_t(kMaxEnt) * n * sizeof(float2));
+    static void carve_scratch(Carve& c, State& s, int n) {
+        prep_carve(c, s.prep, n, kGrid, kBlitWords, false);
+        c.take(s.hazx, size_t(kMaxEnt) * n * sizeof(float4));
+        c.take(s.hazy, size_t(kMaxEnt) * n * sizeof(float2));
     }
-    void bind_scratch(void* d_scratch, int n) override {
-        s_.prep = prep_bind(d_scratch, n, kGrid, kBlitWords, false);
-        uint8_t* p = static_cast<uint8_t*>(d_scratch) + up256(prep_bytes(n, kGrid, kBlitWords, false));
-        s_.hazx = reinterpret_cast<float4*>(p);
-        s_.hazy = reinterpret_cast<float2*>(p + up256(size_t(kMaxEnt) * n * sizeof(float4)));
-    }
+    size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
+    void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_, n); }
 
     // Same layout as oracle/pgo_coinrun.cpp Coinrun::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {
         hipStreamSynchronize(st);
-        auto rd_f = [&](const float* base, size_t idx) {
-            float v;
-            hipMemcpy(&v, base + idx, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto rd_i = [&](size_t idx) {
-            int32_t v;
-            hipMemcpy(&v, s_.i + idx, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto rd_b = [&](const uint8_t* base, size_t idx) {
-            uint8_t v;
-            hipMemcpy(&v, base + idx, 1, hipMemcpyDeviceToHost);
-            return v;
-        };
         const size_t n = s_.n;
-        auto f = [&](int field) { return rd_f(s_.f, size_t(field) * n + env); };
-        const int flags = rd_i(size_t(I_FLAGS) * n + env), themes = rd_i(size_t(I_THEMES) * n + env);
-        const int n_ent = rd_i(size_t(I_NENT) * n + env);
+        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
+        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
+        const int flags = ri(I_FLAGS), themes = ri(I_THEMES), n_ent = ri(I_NENT);
         const int buf = (flags & kFlagBuf) ? 1 : 0;
-        std::vector<float> v;
-        v.push_back(f(F_AX));
-        v.push_back(f(F_AY));
-        v.push_back(f(F_AVX));
-        v.push_back(f(F_AVY));
-        v.push_back((flags & kFlagGround) ? 1.0f : 0.0f);
-        v.push_back((flags & kFlagForward) ? 1.0f : 0.0f);
-        v.push_back(f(F_APHASE));
-        v.push_back(f(F_CAMX));
-        v.push_back(f(F_CAMY));
-        v.push_back(static_cast<float>(themes & 0xff));
-        v.push_back(f(F_BGSHIFT));
-        v.push_back(static_cast<float>((themes >> 8) & 0xff));
-        v.push_back(static_cast<float>((themes >> 16) & 0xff));
-        v.push_back(static_cast<float>(n_ent));
+        std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), (flags & kFlagGround) ? 1.0f : 0.0f,
+                                (flags & kFlagForward) ? 1.0f : 0.0f, f(F_APHASE), f(F_CAMX), f(F_CAMY),
+                                static_cast<float>(themes & 0xff), f(F_BGSHIFT), static_cast<float>((themes >> 8) & 0xff),
+                                static_cast<float>((themes >> 16) & 0xff), static_cast<float>(n_ent)};
         for (int e = 0; e < n_ent; e++) {
-            const int kind = rd_b(s_.eb, (size_t(EB_KIND) * kMaxEnt + e) * n + env);
-            const int dyn = rd_b(s_.db, (size_t(buf) * kMaxEnt + e) * n + env);
-            auto df = [&](int field) { return rd_f(s_.df, ((size_t(buf) * DF_COUNT + field) * kMaxEnt + e) * n + env); };
+            const int kind = read_one(s_.eb + (size_t(EB_KIND) * kMaxEnt + e) * n + env);
+            const int dyn = read_one(s_.db + (size_t(buf) * kMaxEnt + e) * n + env);
+            auto df = [&](int field) { return read_one(s_.df + ((size_t(buf) * DF_COUNT + field) * kMaxEnt + e) * n + env); };
             v.push_back(df(DF_X));
-            v.push_back(rd_f(s_.ey, size_t(e) * n + env));
+            v.push_back(read_one(s_.ey + size_t(e) * n + env));
             v.push_back(kind == kMob ? df(DF_VX) : 0.0f);
             v.push_back((dyn & kDynFrame) ? 1.0f : 0.0f);
             v.push_back(kind == kCoin ? 0.0f : df(DF_ANIM_T));
         }
-        const int m = cap < static_cast<int>(v.size()) ? cap : static_cast<int>(v.size());
-        for (int k = 0; k < m; k++) out[k] = v[k];
-        return static_cast<int>(v.size());
+        return dump_out(v, out, cap);
     }
     int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        hipStreamSynchronize(st);
-        const int m = cap < W * H ? cap : W * H;
-        hipMemcpy(out, s_.tiles + size_t(env) * W * H, m, hipMemcpyDeviceToHost);
-        for (int k = 0; k < m; k++) out[k] &= 7;
-        return m;
+        return dump_env_tiles(st, s_.tiles, W * H, W * H, env, out, cap, 7);
     }
 
    private:
-    State s_{};
     AtlasView atlas_{};
 };
 

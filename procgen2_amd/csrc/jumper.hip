@@ -1451,7 +1451,7 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
     }
 }
 
-class JumperGame final : public Game {
+class JumperGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "jumper"; }
     std::vector<std::string> texture_names() const override {
@@ -1480,31 +1480,19 @@ class JumperGame final : public Game {
     std::string check_atlas(const std::vector<std::pair<int, int>>& sizes) const override {
         return static_cast<int>(sizes.size()) == kTexCount ? "" : "jumper: unexpected texture count";
     }
-    static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-    struct Layout {
-        size_t shadow, slot, mt, tiles, f, i, pf, spike, draw, total;
-    };
-    static Layout layout(int n) {
-        Layout l{};
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            size_t at = off;
-            off += align256(bytes);
-            return at;
-        };
-        l.shadow = take(size_t(n) * sizeof(Level));
-        l.slot = take(size_t(n) * 4);
-        l.mt = take(size_t(n) * kMtWords * 4);
-        l.tiles = take(size_t(n) * kTileStride);
-        l.f = take(size_t(F_COUNT) * n * 4);
-        l.i = take(size_t(I_COUNT) * n * 4);
-        l.pf = take(size_t(PF_COUNT) * kPuffSlots * n * 4);
-        l.spike = take(size_t(kSpikeSlots) * n * 2);
-        l.draw = take(size_t(kSpikeSlots) * n);
-        l.total = off;
-        return l;
+    // The state block, in order (state_bytes and bind).
+    static void carve(Carve& c, State& s, int n) {
+        c.take(s.shadow, size_t(n) * sizeof(Level));
+        c.take(s.slot, size_t(n) * 4);
+        c.take(s.mt, size_t(n) * kMtWords * 4);
+        c.take(s.tiles, size_t(n) * kTileStride);
+        c.take(s.f, size_t(F_COUNT) * n * 4);
+        c.take(s.i, size_t(I_COUNT) * n * 4);
+        c.take(s.pf, size_t(PF_COUNT) * kPuffSlots * n * 4);
+        c.take(s.spike_cell, size_t(kSpikeSlots) * n * 2);
+        c.take(s.draw, size_t(kSpikeSlots) * n);
     }
-    size_t state_bytes(int n) const override { return layout(n).total; }
+    size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     // The compass ring (jumper.cpp:485-489: SDL_RenderTextureRotated(circle, NULL, &dst, 0°) at a fixed screen rectangle,
     // drawn for the observation too, D17) lands on the same pixels with the same texels in every frame: sample it once
     // here, under raster spec S1-S3, for the 64×64 observation (the human-size frame keeps the general path).
@@ -1599,53 +1587,35 @@ class JumperGame final : public Game {
         return (flags & ~PGV_JUMPER_FLOAT_ABS) == 0;
     }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        uint8_t* p = static_cast<uint8_t*>(d_state);
-        const Layout l = layout(n);
+        Carve::bind(carve, d_state, s_, n);
         s_.n = n;
-        s_.shadow = reinterpret_cast<Level*>(p + l.shadow);
-        s_.slot = reinterpret_cast<int32_t*>(p + l.slot);
-        s_.mt = reinterpret_cast<uint32_t*>(p + l.mt);
-        s_.tiles = p + l.tiles;
-        s_.f = reinterpret_cast<float*>(p + l.f);
-        s_.i = reinterpret_cast<int32_t*>(p + l.i);
-        s_.pf = reinterpret_cast<float*>(p + l.pf);
-        s_.spike_cell = reinterpret_cast<uint16_t*>(p + l.spike);
-        s_.draw = p + l.draw;
         atlas_ = atlas;
     }
     int blocks() const { return (s_.n + 63) / 64; }
-    int prefetch() const { return (debug_flags & kDebugNoPrefetch) ? 0 : 1; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
         hipLaunchKernelGGL(make_kernel, dim3(blocks()), dim3(64), 0, st, s_);
-        LevelLaunch<Gen>::make(st, s_, prefetch(), seed_base, env_offset, plan);
-    }
-    void launch_reset(hipStream_t st, const uint8_t* mask, const int32_t* seeds, StepIO io) override {
-        LevelLaunch<Gen>::reset(st, s_, prefetch(), mask, seeds, io, plan);
-    }
-    bool launch_pregen(hipStream_t side, bool bulk) override {
-        if (!prefetch()) return false;
-        LevelLaunch<Gen>::pregen(side, s_, bulk, plan);
-        return true;
+        make_levels(st, seed_base, env_offset);
     }
     void launch_logic(hipStream_t st, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
                       StepIO io) override {
         // prefetched levels are installed beside the logic (its second row of blocks); the level kernel behind it
         // generates, synchronously, the levels that were not ready — none in steady state (pg_prefetch.h install_prefetched)
         const bool fused = prefetch() != 0;
-        if (!fused) LevelLaunch<Gen>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, reset_served_mark(step_index), reset_due_mark(step_index));
+        reset_before_logic(st, step_index, io);
         hipLaunchKernelGGL(logic_kernel, dim3((s_.n + 63) / 64, fused ? 2 : 1), dim3(64), 0, st, s_, actions, run_seed, step_index,
                            env_offset, io, prefetch(), plan);
-        if (fused) LevelLaunch<Gen>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, reset_served_mark(step_index), reset_due_mark(step_index));
+        reset_after_logic(st, step_index, io);
     }
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
     }
-    size_t scratch_bytes(int n) const override { return prep_bytes(n, kGrid, kBlitWords, true) + size_t(n + 1) * 4; }
-    void bind_scratch(void* d_scratch, int n) override {
-        s_.prep = prep_bind(d_scratch, n, kGrid, kBlitWords, true);
-        s_.fat = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + prep_bytes(n, kGrid, kBlitWords, true));  // (zeroed by the engine)
+    static void carve_scratch(Carve& c, State& s, int n) {
+        prep_carve(c, s.prep, n, kGrid, kBlitWords, true);
+        c.take(s.fat, size_t(n + 1) * 4, 1);  // (zeroed by the engine)
     }
+    size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
+    void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_, n); }
     bool lean() const { return !(debug_flags & (1 | kDebugNoPrepass)); }
     void launch_prepass(hipStream_t st, const uint8_t* mask) override {
         if (lean()) hipLaunchKernelGGL(setup_kernel, dim3((s_.n + kPrepEnvs - 1) / kPrepEnvs), dim3(kPrepThreads), 0, st, s_, atlas_, mask, debug_flags);
@@ -1662,17 +1632,8 @@ class JumperGame final : public Game {
     int dump_state(hipStream_t st, int env, float* out, int cap) override {
         hipStreamSynchronize(st);
         const size_t n = s_.n;
-        auto rf = [&](const float* base, size_t idx) {
-            float v;
-            hipMemcpy(&v, base + idx, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto ri = [&](int field) {
-            int32_t v;
-            hipMemcpy(&v, s_.i + size_t(field) * n + env, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto f = [&](int field) { return rf(s_.f, size_t(field) * n + env); };
+        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
+        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
         const int flags = ri(I_FLAGS), themes = ri(I_THEMES), n_spikes = ri(I_NSPIKES);
         std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), (flags & kFlagGround) ? 1.0f : 0.0f,
                                 (flags & kFlagForward) ? 1.0f : 0.0f, f(F_APHASE), f(F_JUMP_T),
@@ -1681,26 +1642,19 @@ class JumperGame final : public Game {
                                 f(F_PTIMER), (flags & kFlagPuffOn) ? 1.0f : 0.0f, f(F_GX), f(F_GY),
                                 static_cast<float>(n_spikes)};
         for (int k = 0; k < kPuffs; k++)
-            for (int fld : {PF_X, PF_Y, PF_LIFE}) v.push_back(rf(s_.pf, (size_t(env) * PF_COUNT + fld) * kPuffSlots + k));
+            for (int fld : {PF_X, PF_Y, PF_LIFE}) v.push_back(read_one(s_.pf + (size_t(env) * PF_COUNT + fld) * kPuffSlots + k));
         for (int k = 0; k < n_spikes; k++) {
-            uint16_t cell;
-            hipMemcpy(&cell, s_.spike_cell + size_t(env) * kSpikeSlots + k, 2, hipMemcpyDeviceToHost);
+            const uint16_t cell = read_one(s_.spike_cell + size_t(env) * kSpikeSlots + k);
             v.push_back(static_cast<float>(cell / H) + 0.5f);
             v.push_back(static_cast<float>(H - 1 - cell % H) + 0.5f);
         }
-        const int m = cap < static_cast<int>(v.size()) ? cap : static_cast<int>(v.size());
-        for (int k = 0; k < m; k++) out[k] = v[k];
-        return static_cast<int>(v.size());
+        return dump_out(v, out, cap);
     }
     int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        hipStreamSynchronize(st);
-        const int m = cap < kCells ? cap : kCells;
-        hipMemcpy(out, s_.tiles + size_t(env) * kTileStride, m, hipMemcpyDeviceToHost);
-        return m;
+        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
     }
 
    private:
-    State s_{};
     AtlasView atlas_{};
 };
 

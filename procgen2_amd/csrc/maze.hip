@@ -420,7 +420,7 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
            kUnitPx / P.desc(kTexMouse).y * 1.0f, 1.0f, (sflags & kFlagForward) != 0);
 }
 
-class MazeGame final : public Game {
+class MazeGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "maze"; }
     std::vector<std::string> texture_names() const override {
@@ -429,53 +429,37 @@ class MazeGame final : public Game {
         for (int k = 1; k <= 8; k++) v.push_back("topdown_backgrounds/backgrounddetailed" + std::to_string(k) + ".png");
         return v;
     }
-    static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-    size_t state_bytes(int n) const override {
-        return align256(size_t(n) * sizeof(Level)) + align256(size_t(n) * 4) + align256(size_t(n) * kMtWords * 4) +
-               align256(size_t(n) * kTileStride) +
-               align256(size_t(F_COUNT) * n * 4) + align256(size_t(I_COUNT) * n * 4) + align256(sizeof(ComposeHand));
+    // The state block, in order (state_bytes and bind).
+    static void carve(Carve& c, State& s, int n) {
+        c.take(s.shadow, size_t(n) * sizeof(Level));
+        c.take(s.slot, size_t(n) * 4);
+        c.take(s.mt, size_t(n) * kMtWords * 4);
+        c.take(s.tiles, size_t(n) * kTileStride);
+        c.take(s.f, size_t(F_COUNT) * n * 4);
+        c.take(s.i, size_t(I_COUNT) * n * 4);
+        c.take(s.prepared, sizeof(ComposeHand));
     }
+    size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        uint8_t* p = static_cast<uint8_t*>(d_state);
-        auto take = [&](size_t bytes) {
-            uint8_t* q = p;
-            p += align256(bytes);
-            return q;
-        };
+        Carve::bind(carve, d_state, s_, n);
         s_.n = n;
-        s_.shadow = reinterpret_cast<Level*>(take(size_t(n) * sizeof(Level)));
-        s_.slot = reinterpret_cast<int32_t*>(take(size_t(n) * 4));
-        s_.mt = reinterpret_cast<uint32_t*>(take(size_t(n) * kMtWords * 4));
-        s_.tiles = take(size_t(n) * kTileStride);
-        s_.f = reinterpret_cast<float*>(take(size_t(F_COUNT) * n * 4));
-        s_.i = reinterpret_cast<int32_t*>(take(size_t(I_COUNT) * n * 4));
-        s_.prepared = reinterpret_cast<ComposeHand*>(take(sizeof(ComposeHand)));
         atlas_ = atlas;
     }
     int blocks() const { return (s_.n + 63) / 64; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
-        LevelLaunch<Gen>::make(st, s_, prefetch(), seed_base, env_offset, plan);
+        make_levels(st, seed_base, env_offset);
         if (!kCentred) hipLaunchKernelGGL(prepare_kernel, dim3(1), dim3(128), 0, st, s_, atlas_);
     }
-    void launch_reset(hipStream_t st, const uint8_t* mask, const int32_t* seeds, StepIO io) override {
-        LevelLaunch<Gen>::reset(st, s_, prefetch(), mask, seeds, io, plan);
-    }
     int pregen_every() const override { return 2; }  // (pg_engine.h)
-    bool launch_pregen(hipStream_t side, bool bulk) override {
-        if (!prefetch()) return false;
-        LevelLaunch<Gen>::pregen(side, s_, bulk, plan);
-        return true;
-    }
-    int prefetch() const { return (debug_flags & kDebugNoPrefetch) ? 0 : 1; }
     void launch_logic(hipStream_t st, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
                       StepIO io) override {
         // prefetched levels are installed beside the logic (its second row of blocks); the level kernel behind it
         // generates, synchronously, the levels that were not ready — none in steady state (pg_prefetch.h install_prefetched)
         const bool fused = prefetch() != 0;
-        if (!fused) LevelLaunch<Gen>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, reset_served_mark(step_index), reset_due_mark(step_index));
+        reset_before_logic(st, step_index, io);
         hipLaunchKernelGGL(logic_kernel, dim3((s_.n + 63) / 64, fused ? 2 : 1), dim3(64), 0, st, s_, actions, run_seed, step_index,
                            env_offset, io, prefetch(), plan);
-        if (fused) LevelLaunch<Gen>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, reset_served_mark(step_index), reset_due_mark(step_index));
+        reset_after_logic(st, step_index, io);
     }
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
@@ -493,41 +477,26 @@ class MazeGame final : public Game {
         else
             hipLaunchKernelGGL(render_kernel<false>, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);
     }
-    static size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-    size_t scratch_bytes(int n) const override { return up256(size_t(n) * 2 * kBlitWords * 4) + up256(size_t(n) * 8 * 4); }
-    void bind_scratch(void* d_scratch, int n) override {
-        uint8_t* p = static_cast<uint8_t*>(d_scratch);
-        s_.prep.draws = reinterpret_cast<uint32_t*>(p);
-        s_.prep.bg = reinterpret_cast<uint32_t*>(p + up256(size_t(n) * 2 * kBlitWords * 4));
+    static void carve_scratch(Carve& c, State::Prep& p, int n) {
+        c.take(p.draws, size_t(n) * 2 * kBlitWords * 4);
+        c.take(p.bg, size_t(n) * 8 * 4);
     }
+    size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
+    void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_.prep, n); }
     // Same layout as oracle/pgo_maze.cpp Maze::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {
         hipStreamSynchronize(st);
-        auto f = [&](int field) {
-            float v;
-            hipMemcpy(&v, s_.f + size_t(field) * s_.n + env, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        auto iv = [&](int field) {
-            int32_t v;
-            hipMemcpy(&v, s_.i + size_t(field) * s_.n + env, 4, hipMemcpyDeviceToHost);
-            return v;
-        };
-        const float v[10] = {f(F_AX), f(F_AY), (iv(I_FLAGS) & kFlagForward) ? 1.0f : 0.0f, f(F_GX), f(F_GY),
-                             static_cast<float>(iv(I_STEPS)), static_cast<float>(iv(I_BG)), f(F_BGSHIFT), f(F_CAMX),
-                             f(F_CAMY)};
-        for (int k = 0; k < 10 && k < cap; k++) out[k] = v[k];
-        return 10;
+        auto f = [&](int field) { return read_one(s_.f + size_t(field) * s_.n + env); };
+        auto iv = [&](int field) { return read_one(s_.i + size_t(field) * s_.n + env); };
+        return dump_out({f(F_AX), f(F_AY), (iv(I_FLAGS) & kFlagForward) ? 1.0f : 0.0f, f(F_GX), f(F_GY),
+                         static_cast<float>(iv(I_STEPS)), static_cast<float>(iv(I_BG)), f(F_BGSHIFT), f(F_CAMX), f(F_CAMY)},
+                        out, cap);
     }
     int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        hipStreamSynchronize(st);
-        const int m = cap < kCells ? cap : kCells;
-        hipMemcpy(out, s_.tiles + size_t(env) * kTileStride, m, hipMemcpyDeviceToHost);
-        return m;
+        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
     }
 
    private:
-    State s_{};
     AtlasView atlas_{};
 };
 

@@ -145,8 +145,8 @@ class Game {
     virtual bool launch_render_late(hipStream_t s, StepIO io) { return false; }
 
     // Called after pgv_load_state has replaced the state blob: whatever a game derives from its state and keeps OUTSIDE the
-    // blob (chaser: the base layer of every env's frame, pg chaser.hip) is stale from here on.
-    virtual void state_loaded(hipStream_t st) { (void)st; }
+    // blob (chaser: the base layer of every env's frame, pg chaser.hip) is stale from here on.  An error fails the load.
+    virtual hipError_t state_loaded(hipStream_t st) { (void)st; return hipSuccess; }
 
     // Device memory a game's kernels hand results to each other through within one frame (the render pre-pass,
     // pg_prepass.h): allocated by the engine beside the state, never part of a snapshot.
@@ -169,6 +169,53 @@ constexpr int kDebugNoPrepass = 1 << 21;  // (clear of the -DPG_ABLATE experimen
 constexpr int kDebugFatThirds = 1 << 23;
 constexpr int kDebugCoinrunNoReach = 1 << 24;
 constexpr int kDebugChaserSerialMobs = 1 << 25;  // chaser: the enemies one after the other on the stream itself (chaser.hip advance)
+
+// A block of device memory listed as consecutive regions, each rounded up to 256 bytes (or to `align`).  A game writes
+// its listing once, as a function list(c, s, n) that takes every region into a pointer of s; run without a base it only
+// adds up the bytes (state_bytes, scratch_bytes), with one it also hands out the addresses (bind, bind_scratch), so the
+// size and the binding cannot disagree.  A region of no bytes gets nullptr.
+struct Carve {
+    uint8_t* base = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    void take(T*& p, size_t len, size_t align = 256) {
+        p = base && len ? reinterpret_cast<T*>(base + bytes) : nullptr;
+        bytes += (len + align - 1) / align * align;
+    }
+    template <class S>
+    static size_t size(void (*list)(Carve&, S&, int), int n) {
+        Carve c;
+        S s{};
+        list(c, s, n);
+        return c.bytes;
+    }
+    template <class S>
+    static void bind(void (*list)(Carve&, S&, int), void* base, S& s, int n) {
+        Carve c{static_cast<uint8_t*>(base)};
+        list(c, s, n);
+    }
+};
+
+// The debug dumps (Game::dump_state, dump_tiles): one element of device memory; a dump's values copied out as far as cap
+// allows, returning how many there are; one env's tile bytes (each masked with `mask`).
+template <class T>
+T read_one(const T* p) {
+    T v;
+    (void)hipMemcpy(&v, p, sizeof(T), hipMemcpyDeviceToHost);
+    return v;
+}
+inline int dump_out(const std::vector<float>& v, float* out, int cap) {
+    for (int k = 0; k < cap && k < static_cast<int>(v.size()); k++) out[k] = v[k];
+    return static_cast<int>(v.size());
+}
+inline int dump_env_tiles(hipStream_t st, const uint8_t* tiles, size_t stride, int count, int env, uint8_t* out, int cap,
+                          uint8_t mask = 0xff) {
+    (void)hipStreamSynchronize(st);
+    const int m = cap < count ? cap : count;
+    (void)hipMemcpy(out, tiles + size_t(env) * stride, m, hipMemcpyDeviceToHost);
+    for (int k = 0; k < m; k++) out[k] &= mask;
+    return m;
+}
 
 // Factories, one per compiled variant of a game (pg_defs.h PG_VARIANT; v0 = the reference's compile-time default).
 std::unique_ptr<Game> make_coinrun_v0();

@@ -297,6 +297,42 @@ struct LevelLaunch {
                            nullptr, nullptr, StepIO{}, plan, 2, 1);
     }
 };
+
+// The host side a prefetching game shares (coinrun, maze, climber, caveflyer, jumper): its state, the reset and generator
+// launches, the level part of make, and the auto-resets around a logic launch that installs the prefetched levels in its
+// own grid (install_prefetched) — without prefetch the level kernel serves every reset in front of the logic, with it only
+// the levels that were not ready, behind.  The game launches its own logic kernels.
+template <class G>
+class PrefetchingGame : public Game {
+   public:
+    void launch_reset(hipStream_t st, const uint8_t* mask, const int32_t* seeds, StepIO io) override {
+        LevelLaunch<G>::reset(st, s_, prefetch(), mask, seeds, io, plan);
+    }
+    bool launch_pregen(hipStream_t side, bool bulk) override {
+        if (!prefetch()) return false;
+        LevelLaunch<G>::pregen(side, s_, bulk, plan);
+        return true;
+    }
+
+   protected:
+    int prefetch() const { return (debug_flags & kDebugNoPrefetch) ? 0 : 1; }
+    void make_levels(hipStream_t st, uint32_t seed_base, int env_offset) {
+        LevelLaunch<G>::make(st, s_, prefetch(), seed_base, env_offset, plan);
+    }
+    void reset_before_logic(hipStream_t st, uint32_t step_index, StepIO io) {
+        if (!prefetch()) auto_reset(st, step_index, io);
+    }
+    void reset_after_logic(hipStream_t st, uint32_t step_index, StepIO io) {
+        if (prefetch()) auto_reset(st, step_index, io);
+    }
+    typename G::State s_{};
+
+   private:
+    void auto_reset(hipStream_t st, uint32_t step_index, StepIO io) {
+        LevelLaunch<G>::auto_reset(st, s_, prefetch(), io, plan, PG_RESET_SPAN, reset_served_mark(step_index),
+                                   reset_due_mark(step_index));
+    }
+};
 #endif
 
 }  // namespace pg

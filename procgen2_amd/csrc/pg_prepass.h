@@ -46,25 +46,13 @@ struct PrepOut {
     uint32_t* meta;   // [n][kPrepMetaWords]
     uint32_t* draws;  // [n][kPrepDraws][kBlitWords]  (+ 2 words for games with rotated draws: see the game)
 };
-inline size_t prep_bytes(int n, int grid, int draw_words, bool second) {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return up(size_t(n) * 128 * 4) + up(second ? size_t(n) * 64 * 4 : 0) + up(size_t(n) * grid * grid) +
-           up(size_t(n) * kPrepMetaWords * 4) + up(size_t(n) * kPrepDraws * draw_words * 4);
-}
-inline PrepOut prep_bind(void* base, int n, int grid, int draw_words, bool second) {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    uint8_t* p = static_cast<uint8_t*>(base);
-    PrepOut o{};
-    o.axes = reinterpret_cast<uint32_t*>(p);
-    p += up(size_t(n) * 128 * 4);
-    o.axes2 = second ? reinterpret_cast<uint32_t*>(p) : nullptr;
-    p += up(second ? size_t(n) * 64 * 4 : 0);
-    o.cells = p;
-    p += up(size_t(n) * grid * grid);
-    o.meta = reinterpret_cast<uint32_t*>(p);
-    p += up(size_t(n) * kPrepMetaWords * 4);
-    o.draws = reinterpret_cast<uint32_t*>(p);
-    return o;
+// The scratch regions of PrepOut, for a game's scratch listing (pg_engine.h Carve).
+inline void prep_carve(Carve& c, PrepOut& o, int n, int grid, int draw_words, bool second) {
+    c.take(o.axes, size_t(n) * 128 * 4);
+    c.take(o.axes2, second ? size_t(n) * 64 * 4 : 0);
+    c.take(o.cells, size_t(n) * grid * grid);
+    c.take(o.meta, size_t(n) * kPrepMetaWords * 4);
+    c.take(o.draws, size_t(n) * kPrepDraws * draw_words * 4);
 }
 
 #if defined(__HIPCC__)
