@@ -379,6 +379,21 @@ void pgo_vec_step(void* h, const int32_t* actions, uint32_t run_seed, int env_of
     v->step_counter++;
 }
 
+// `steps` vector steps with synthetic actions (pgo_vec_step with actions nullptr, one thread), nothing copied out;
+// ends[i] (nullptr: not counted) grows by the number of them at which env i's episode ended.  One call for a whole
+// rollout: the replays of bench.py's dumped rows (tests/bench_replay.py) run many small vectors side by side.
+void pgo_vec_run(void* h, int steps, uint32_t run_seed, int env_offset, int32_t* ends) {
+    auto* v = static_cast<VecState*>(h);
+    const int n = static_cast<int>(v->envs.size());
+    std::vector<uint8_t> done(n);
+    for (int s = 0; s < steps; s++) {
+        vec_step_range(v, 0, n, nullptr, run_seed, env_offset, nullptr, nullptr, done.data());
+        v->step_counter++;
+        if (ends)
+            for (int i = 0; i < n; i++) ends[i] += done[i];
+    }
+}
+
 void pgo_vec_obs(void* h, uint8_t* obs_out) {
     auto* v = static_cast<VecState*>(h);
     for (size_t i = 0; i < v->envs.size(); i++)

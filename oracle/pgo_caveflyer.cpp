@@ -81,9 +81,8 @@ class Caveflyer final : public Env {
         return static_cast<int>(v.size());
     }
     int dump_tiles(uint8_t* out, int cap) const override {
-        int n = std::min<int>(cap, W * H);
-        std::memcpy(out, tiles_.data(), n);
-        return n;
+        std::memcpy(out, tiles_.data(), std::min<int>(cap, W * H));
+        return W * H;
     }
 
    protected:

@@ -94,9 +94,8 @@ class Coinrun final : public Env {
 
     int dump_state(float* out, int cap) const override;
     int dump_tiles(uint8_t* out, int cap) const override {
-        int n = std::min<int>(cap, W * H);
-        std::memcpy(out, tiles_.data(), n);
-        return n;
+        std::memcpy(out, tiles_.data(), std::min<int>(cap, W * H));
+        return W * H;
     }
 
    protected:

@@ -214,7 +214,7 @@ inline int dump_env_tiles(hipStream_t st, const uint8_t* tiles, size_t stride, i
     const int m = cap < count ? cap : count;
     (void)hipMemcpy(out, tiles + size_t(env) * stride, m, hipMemcpyDeviceToHost);
     for (int k = 0; k < m; k++) out[k] &= mask;
-    return m;
+    return count;
 }
 
 // Factories, one per compiled variant of a game (pg_defs.h PG_VARIANT; v0 = the reference's compile-time default).

@@ -15,6 +15,18 @@ from procgen2_amd import lib as pglib  # noqa: E402
 OBS_BYTES = pglib.OBS_BYTES
 
 
+def _dump(fn, ctype, dtype, cap=None):
+    """One parity dump whole, fn(buf, cap) being a dump call: its length first (the ABI returns the full length whatever
+    it copies), then that many items, or at most `cap` of them."""
+    n = fn((ctype * 1)(), 0)
+    if n < 0:
+        raise IndexError("no such env to dump")
+    n = n if cap is None else min(n, cap)
+    buf = (ctype * max(1, n))()
+    assert fn(buf, n) >= n
+    return np.array(buf[:n], dtype)
+
+
 class EngineVec:
     def __init__(self, game, n, seed_base=1, env_offset=0, device=0, lib_path=None, num_levels=0, start_level=0, mode=None, game_flags=0):
         self.L = pglib.load(lib_path)
@@ -74,15 +86,13 @@ class EngineVec:
     def set_debug(self, flags):
         pglib.check(self.L, self.L.pgv_set_debug(self.h, flags), "pgv_set_debug")
 
-    def state(self, env, cap=512):
-        buf = (c_float * cap)()
-        n = self.L.pgv_dump_state(self.h, env, buf, cap)
-        return np.array(buf[:min(n, cap)], np.float32)
+    def state(self, env, cap=None):
+        """The env's whole state vector (pgv_dump_state), or its first `cap` floats when a cap is given."""
+        return _dump(lambda buf, m: self.L.pgv_dump_state(self.h, env, buf, m), c_float, np.float32, cap)
 
-    def tiles(self, env, cap=4096):
-        buf = (c_uint8 * cap)()
-        n = self.L.pgv_dump_tiles(self.h, env, buf, cap)
-        return np.array(buf[:n], np.uint8)
+    def tiles(self, env, cap=None):
+        """The env's whole tile map (pgv_dump_tiles), or its first `cap` bytes when a cap is given."""
+        return _dump(lambda buf, m: self.L.pgv_dump_tiles(self.h, env, buf, m), c_uint8, np.uint8, cap)
 
     def timed(self, steps, run_seed=0):
         total, render = ctypes.c_double(), ctypes.c_double()

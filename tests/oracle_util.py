@@ -88,6 +88,8 @@ def oracle():
     L.pgo_vec_close.argtypes = [c_void_p]
     L.pgo_vec_set_render.argtypes = [c_void_p, c_int]
     L.pgo_vec_step.argtypes = [c_void_p, c_void_p, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.pgo_vec_run.argtypes = [c_void_p, c_int, c_uint32, c_int, c_void_p]
+    L.pgo_vec_run.restype = None
     L.pgo_vec_obs.argtypes = [c_void_p, c_void_p]
     L.pgo_vec_dump_state.argtypes = [c_void_p, c_int, POINTER(c_float), c_int]
     L.pgo_vec_dump_tiles.argtypes = [c_void_p, c_int, POINTER(c_uint8), c_int]
@@ -117,6 +119,30 @@ def register_textures(game):
         arr = np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
         L.pgo_put_texture(("assets/" + rel).encode(), im.size[0], im.size[1], arr.ctypes.data_as(c_void_p))
         _registered.add(rel)
+
+
+def _dump(fn, ctype, dtype, cap=None):
+    """One parity dump whole, fn(buf, cap) being a dump call: its length first (a dump returns its full length whatever it
+    copies), then that many items, or at most `cap` of them."""
+    n = fn((ctype * 1)(), 0)
+    n = n if cap is None else min(n, cap)
+    buf = (ctype * max(1, n))()
+    assert fn(buf, n) >= n
+    return np.array(buf[:n], dtype)
+
+
+def oracle_state(h, cap=None):
+    """The whole state vector of a single oracle env (pgo_make), or its first `cap` floats."""
+    return _dump(lambda buf, m: oracle().pgo_dump_state(h, buf, m), c_float, np.float32, cap)
+
+
+def assert_same_dump(got, want, what):
+    """Two parity dumps of the same env (state floats or tile bytes, engine and oracle) are equal: the same full length
+    first, then every value (floats by bit pattern)."""
+    assert got.size == want.size, "%s: %d values, the oracle's has %d" % (what, got.size, want.size)
+    if got.dtype == np.float32:
+        got, want = got.view(np.uint32), want.view(np.uint32)
+    assert np.array_equal(got, want), what
 
 
 class OracleVec:
@@ -172,15 +198,13 @@ class OracleVec:
         """Drawing on / off from the next step on (logic is unaffected; obs is only meaningful for steps drawn)."""
         self.L.pgo_vec_set_render(self.h, 1 if on else 0)
 
-    def state(self, env, cap=512):
-        buf = (c_float * cap)()
-        n = self.L.pgo_vec_dump_state(self.h, env, buf, cap)
-        return np.array(buf[:min(n, cap)], np.float32)
+    def state(self, env, cap=None):
+        """The env's whole state vector (Env::dump_state), or its first `cap` floats when a cap is given."""
+        return _dump(lambda buf, m: self.L.pgo_vec_dump_state(self.h, env, buf, m), c_float, np.float32, cap)
 
-    def tiles(self, env, cap=4096):
-        buf = (c_uint8 * cap)()
-        n = self.L.pgo_vec_dump_tiles(self.h, env, buf, cap)
-        return np.array(buf[:n], np.uint8)
+    def tiles(self, env, cap=None):
+        """The env's whole tile map (Env::dump_tiles), or its first `cap` bytes when a cap is given."""
+        return _dump(lambda buf, m: self.L.pgo_vec_dump_tiles(self.h, env, buf, m), c_uint8, np.uint8, cap)
 
     def close(self):
         if self.h:

@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from oracle_util import OBS_BYTES, OracleVec, oracle, register_textures
+from oracle_util import OBS_BYTES, OracleVec, assert_same_dump, oracle, register_textures
 
 GAMES = ["coinrun", "maze", "bossfight", "climber", "caveflyer", "chaser", "jumper"]
 
@@ -143,8 +143,8 @@ def test_engine_level_mode_matches_oracle(game, steps, prefetch):
             seeds = (np.arange(n, dtype=np.int32) % 4) - 1
             assert np.array_equal(eng.reset(mask=mask, seeds=seeds), ora.reset(mask=mask, seeds=seeds)), "masked reset"
     for e in range(0, n, 12):
-        assert np.array_equal(eng.state(e).view(np.uint32), ora.state(e).view(np.uint32)), "state env %d" % e
-        assert np.array_equal(eng.tiles(e), ora.tiles(e)), "tiles env %d" % e
+        assert_same_dump(eng.state(e), ora.state(e), "state env %d" % e)
+        assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d" % e)
     assert ends > 0 or game in ("climber", "jumper", "coinrun", "caveflyer"), ends
     eng.close()
     ora.close()

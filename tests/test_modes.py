@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from oracle_util import OracleVec, oracle, register_textures
+from oracle_util import OracleVec, assert_same_dump, oracle, register_textures
 
 from procgen2_amd import lib as pglib
 
@@ -24,6 +24,8 @@ TABLE = {
     "jumper": (HARD, {EASY, HARD, MEMORY}),
 }
 NON_DEFAULT = sorted((g, m) for g, (d, ms) in TABLE.items() for m in ms if m != d)
+# chaser's state dump: 13 floats, then 8 per entity (70, 96, 198 of them) — longer than 512 in every mode
+CHASER_STATE_FLOATS = {EASY: 573, HARD: 781, EXTREME: 1597}
 
 
 def test_engine_mode_table_matches_the_oracle():
@@ -79,6 +81,25 @@ def test_oracle_climber_easy_spawns_fewer_enemies():
     assert enemies(EASY) < enemies(HARD)
 
 
+def test_chaser_states_are_read_whole_in_every_mode():
+    """Chaser's state is longer than the 512 floats the state helpers once stopped at, in every mode, so OracleVec.state
+    (and EngineVec.state, the same code) must ask for the length and read it all."""
+    sizes = CHASER_STATE_FLOATS
+    cells = {EASY: 11 * 11, HARD: 13 * 13, EXTREME: 19 * 19}
+    L = oracle()
+    for mode, size in sizes.items():
+        v = OracleVec("chaser", 4, seed_base=5, render=False, mode=mode)
+        for s in range(30):
+            v.step(None, run_seed=2)
+        for e in range(4):
+            st = v.state(e)
+            assert st.size == size == L.pgo_vec_dump_state(v.h, e, (ctypes.c_float * 1)(), 0), (mode, e, st.size)
+            assert (st.size - 13) // 8 == st[12], (mode, e)  # the entity count the dump begins with
+            assert np.array_equal(v.state(e, 512).view(np.uint32), st[:512].view(np.uint32))  # a cap still truncates
+            assert v.tiles(e).size == cells[mode] == L.pgo_vec_dump_tiles(v.h, e, (ctypes.c_uint8 * 1)(), 0)
+        v.close()
+
+
 def test_oracle_bossfight_easy_bullets_are_slower():
     a, _, _ = _rollout("bossfight", EASY, n=16, steps=200)
     b, _, _ = _rollout("bossfight", HARD, n=16, steps=200)
@@ -107,8 +128,10 @@ def test_engine_mode_matches_oracle(game, mode):
             bad = np.nonzero((oe != oo).any(axis=1))[0]
             raise AssertionError("obs differ at step %d in %d envs (first env %d)" % (s, bad.size, bad[0]))
     for e in range(0, n, 16):
-        assert np.array_equal(eng.state(e).view(np.uint32), ora.state(e).view(np.uint32)), "state env %d" % e
-        assert np.array_equal(eng.tiles(e), ora.tiles(e)), "tiles env %d" % e
+        assert_same_dump(eng.state(e), ora.state(e), "state env %d" % e)
+        assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d" % e)
+        if game == "chaser":  # every entity compared, not the first 512 floats' worth
+            assert eng.state(e).size == CHASER_STATE_FLOATS[mode], e
     eng.close()
     ora.close()
 
@@ -186,7 +209,7 @@ def test_engine_coinrun_switches_match_oracle(flags):
         assert np.array_equal(de, do) and np.array_equal(re_.view(np.uint32), ro.view(np.uint32)), s
         assert np.array_equal(oe, oo), s
     for e in range(0, n, 16):
-        assert np.array_equal(eng.tiles(e), ora.tiles(e)), e
+        assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d" % e)
     eng.close()
     ora.close()
 

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from engine_util import EngineVec
-from oracle_util import OracleVec, oracle
+from oracle_util import OracleVec, assert_same_dump, oracle, oracle_state
 
 pytestmark = pytest.mark.gpu
 
@@ -45,8 +45,8 @@ def _lockstep(game, n, steps, seed_base=1, run_seed=0, check_state_every=0, game
         resets += int(do.sum())
         if check_state_every and s % check_state_every == 0:
             for e in range(0, n, max(1, n // 8)):
-                assert np.array_equal(eng.state(e).view(np.uint32), ora.state(e).view(np.uint32)), "state env %d" % e
-                assert np.array_equal(eng.tiles(e), ora.tiles(e)), "tiles env %d" % e
+                assert_same_dump(eng.state(e), ora.state(e), "state env %d" % e)
+                assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d" % e)
     eng.close()
     ora.close()
     return resets
@@ -206,7 +206,7 @@ def test_bossfight_fire_heavy_actions():
         assert np.array_equal(de, do) and np.array_equal(re_.view(np.uint32), ro.view(np.uint32)), s
         assert np.array_equal(oe, oo), s
     for e in range(0, n, 8):
-        assert np.array_equal(eng.state(e, 400).view(np.uint32), ora.state(e, 400).view(np.uint32)), e
+        assert_same_dump(eng.state(e), ora.state(e), "state env %d" % e)
     eng.close()
     ora.close()
 
@@ -231,8 +231,8 @@ def test_caveflyer_lockstep_with_fire():
         rew += float(ro.sum())
         if s % 100 == 0:
             for e in range(0, n, 20):
-                assert np.array_equal(eng.state(e).view(np.uint32), ora.state(e).view(np.uint32)), (s, e)
-                assert np.array_equal(eng.tiles(e), ora.tiles(e)), (s, e)
+                assert_same_dump(eng.state(e), ora.state(e), "state env %d, step %d" % (e, s))
+                assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d, step %d" % (e, s))
     assert ends > 10 and rew > 0.0, (ends, rew)
     eng.close()
     ora.close()
@@ -282,8 +282,8 @@ def test_chaser_lockstep_steering_actions():
         rew += float(ro.sum())
         if s % 100 == 0:
             for e in range(0, n, 24):
-                assert np.array_equal(eng.state(e, 1024).view(np.uint32), ora.state(e, 1024).view(np.uint32)), (s, e)
-                assert np.array_equal(eng.tiles(e), ora.tiles(e)), (s, e)
+                assert_same_dump(eng.state(e), ora.state(e), "state env %d, step %d" % (e, s))
+                assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d, step %d" % (e, s))
     assert ends > 50 and rew > 50.0, (ends, rew)
     eng.close()
     ora.close()
@@ -308,8 +308,8 @@ def test_jumper_lockstep_jump_heavy_actions():
         rew += float(ro.sum())
         if s % 160 == 0:
             for e in range(0, n, 20):
-                assert np.array_equal(eng.state(e).view(np.uint32), ora.state(e).view(np.uint32)), (s, e)
-                assert np.array_equal(eng.tiles(e), ora.tiles(e)), (s, e)
+                assert_same_dump(eng.state(e), ora.state(e), "state env %d, step %d" % (e, s))
+                assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d, step %d" % (e, s))
     assert ends > 40, (ends, rew)
     eng.close()
     ora.close()
@@ -411,8 +411,8 @@ def test_climber_lockstep_jump_heavy_actions():
         rew += float(ro.sum())
         if s % 150 == 0:
             for e in range(0, n, 24):
-                assert np.array_equal(eng.state(e).view(np.uint32), ora.state(e).view(np.uint32)), (s, e)
-                assert np.array_equal(eng.tiles(e), ora.tiles(e)), (s, e)
+                assert_same_dump(eng.state(e), ora.state(e), "state env %d, step %d" % (e, s))
+                assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d, step %d" % (e, s))
     assert ends > 50 and rew > 10.0, (ends, rew)
     eng.close()
     ora.close()
@@ -783,7 +783,7 @@ def test_chaser_float_abs_variant_lockstep():
         ends += int(do.sum())
         if s % 100 == 0:
             for e in range(0, n, 24):
-                assert np.array_equal(eng.state(e, 1024).view(np.uint32), ora.state(e, 1024).view(np.uint32)), (s, e)
+                assert_same_dump(eng.state(e), ora.state(e), "state env %d, step %d" % (e, s))
     assert ends > 20 and differs, "the variant must actually change the game"
     for v in (eng, ora, plain):
         v.close()
@@ -811,9 +811,9 @@ def test_mixed_seven_game_slice_of_configs4():
     import torch
     from oracle_util import register_textures
     from procgen2_amd.vec_env import GAMES, ProcgenVecEnv
+    from bench_replay import mixed_blocks
     per_gpu, rank, first, steps = 65536, 3, 48, 200
-    base = per_gpu // len(GAMES)
-    counts = [base] * (len(GAMES) - 1) + [per_gpu - base * (len(GAMES) - 1)]
+    counts = [count for _, _, count in mixed_blocks(per_gpu)]
     assert counts == [9362] * 6 + [9364]
     slab = (torch.zeros((per_gpu, 64, 64, 3), dtype=torch.uint8, device="cuda"),
             torch.zeros(per_gpu, dtype=torch.float32, device="cuda"), torch.zeros(per_gpu, dtype=torch.uint8, device="cuda"))
@@ -926,7 +926,7 @@ def test_bossfight_step_and_reset_after_a_non_square_human_frame():
                 L.pgo_reset(hs[3], 0, 0)
                 pending[3] = False
                 assert np.array_equal(o[3], np.ctypeslib.as_array(L.pgo_obs(hs[3]), shape=(12288,))), s
-                assert np.array_equal(eng.state(3, 400).view(np.uint32), _oracle_state(L, hs[3], 400).view(np.uint32)), s
+                assert_same_dump(eng.state(3), oracle_state(hs[3]), "state env 3, step %d" % s)
         a = np.where(np.arange(n) % 2 == 0, 9, _actions(L, 3, s, n)).astype(np.int32)
         oe, re_, de = eng.step(a)
         for i, h in enumerate(hs):
@@ -961,12 +961,6 @@ def test_bossfight_step_and_reset_after_a_non_square_human_frame():
         assert np.array_equal(obs["screen"], np.ctypeslib.as_array(L.pgo_obs(h), shape=(12288,))), k
     env.close()
     L.pgo_close(h)
-
-
-def _oracle_state(L, h, cap):
-    buf = (ctypes.c_float * cap)()
-    m = L.pgo_dump_state(h, buf, cap)
-    return np.array(buf[:min(m, cap)], np.float32)
 
 
 def _seven_game_slab(per_game, rank=0):
