@@ -160,6 +160,17 @@ PGV_API int32_t pgv_load_state(pgv_env* env, const void* h_buffer, int64_t size)
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);
 
+/* The W x H human frames (cenv_render, render_game(false)) of `count` envs of the batch into DEVICE memory:
+ * u8 [count][height][width][3], row-major RGB.  d_indices: device int32[count], or NULL for envs 0 .. count-1; the same
+ * env may be named more than once, and an index outside the batch gives a frame of zeros.  1 <= width, height <= 4096;
+ * count = 0 succeeds and does nothing.  Enqueued on the env's stream; nothing is synchronised, nothing allocated.  One
+ * workgroup paints one 64x64 tile of one frame (pg_frame.h), so the whole device works on a batch at any size. */
+PGV_API int32_t pgv_render_frames(pgv_env* env, const int32_t* d_indices, int32_t count, int32_t width, int32_t height,
+                                  uint8_t* d_rgb);
+/* Host-pointer convenience (synchronous; allocates and frees its device buffers), as pgv_step_host is to pgv_step. */
+PGV_API int32_t pgv_render_frames_host(pgv_env* env, const int32_t* h_indices, int32_t count, int32_t width,
+                                       int32_t height, uint8_t* h_rgb);
+
 /* Measurement helper for bench.py: runs `steps` synthetic steps and returns, from HIP events recorded
  * on the env's stream, the total time of the region and the summed time of the dominant (render)
  * kernel launches inside it. */

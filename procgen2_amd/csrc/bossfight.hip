@@ -1333,12 +1333,15 @@ __global__ void __launch_bounds__(64, 5) render_kernel(State s, AtlasView atlas,
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// cenv_render's frame (render_game(false)) for one env: pg_frame.h; the draw list of render_kernel, one draw at a time.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    const float fw = static_cast<float>(t.w), fh = static_cast<float>(t.h);
+// cenv_render's frame (render_game(false)): the draw list of render_kernel, one draw at a time, for either painter of pg_frame.h.
+template <class Painter>
+__device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Painter& P) {
+    const float fw = P.width(), fh = P.height();  // (from the target, never from F_CAMW / F_CAMH: see below)
     const float sc = 1.0f * fw / 64.0f;
-    FramePainter P{t, atlas, Camera{0.0f, 0.0f, fw, fh, sc}, static_cast<int>(threadIdx.x), kFrameThreads};
-    if (threadIdx.x == 0) {  // render_game(false) leaves the window's size in gr (D15, see take_view)
+    P.begin(atlas, Camera{0.0f, 0.0f, fw, fh, sc});
+    // render_game(false) leaves the window's size in gr (D15, see take_view): one thread per rendered frame writes it, and
+    // no painter reads it — the tiles of a frame (pg_frame.h TilePainter) run side by side
+    if (P.lead()) {
         SF(s, F_CAMW, env) = fw;
         SF(s, F_CAMH, env) = fh;
     }
@@ -1408,6 +1411,21 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
         const float size = 0.05f;
         P.draw(tex, ax * kUnitPx - size * d.y * 0.5f, ay * kUnitPx - size * d.z * 0.5f, size);
     }
+}
+
+// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
+__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
+    FramePainter P(t);
+    frame_draws(s, atlas, env, P);
+}
+
+// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
+__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
+    __shared__ uint32_t tile[kTilePx];
+    TilePainter P(tile, fb);
+    const int env = P.env(fb);
+    if (env >= 0) frame_draws(s, atlas, env, P);
+    P.store(fb);
 }
 
 class BossfightGame final : public Game {
@@ -1489,6 +1507,9 @@ class BossfightGame final : public Game {
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
+    }
+    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
+        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     // (every flag that changes the frame's path — the draw-list replay, kDebugNoPrepass, the timing experiments — takes the complete kernel)
     bool lean() const { return (debug_flags & ~kDebugNoPrefetch) == 0; }

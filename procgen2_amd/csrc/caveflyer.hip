@@ -1246,11 +1246,11 @@ __global__ void __launch_bounds__(128, 4) render_kernel(State s, AtlasView atlas
     PG_TL_END(6, true, io.obs + size_t(env) * kObsBytes + half * (kObsBytes / 2));
 }
 
-// cenv_render's frame (render_game(false)) for one env: pg_frame.h; the draw list of render_kernel, one draw at a time.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    const float fw = static_cast<float>(t.w), fh = static_cast<float>(t.h);
-    FramePainter P{t, atlas, Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), fw, fh, 0.5f * fw / 64.0f},
-                   static_cast<int>(threadIdx.x), kFrameThreads};
+// cenv_render's frame (render_game(false)): the draw list of render_kernel, one draw at a time, for either painter of pg_frame.h.
+template <class Painter>
+__device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Painter& P) {
+    const float fw = P.width(), fh = P.height();
+    P.begin(atlas, Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), fw, fh, 0.5f * fw / 64.0f});
     const int sflags = SI(s, I_FLAGS, env);
     const int n_draw = (sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;
     const int s_next = SI(s, I_SNEXT, env), s_count = SI(s, I_SCOUNT, env);
@@ -1304,6 +1304,21 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
         P.draw_rotated(kTexShip, SF(s, F_AX, env) * kUnitPx - size * d.y * 0.5f, SF(s, F_AY, env) * kUnitPx - size * d.z * 0.5f,
                        static_cast<float>(SF(s, F_ROT, env) + kPi * 0.5f), size);
     }
+}
+
+// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
+__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
+    FramePainter P(t);
+    frame_draws(s, atlas, env, P);
+}
+
+// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
+__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
+    __shared__ uint32_t tile[kTilePx];
+    TilePainter P(tile, fb);
+    const int env = P.env(fb);
+    if (env >= 0) frame_draws(s, atlas, env, P);
+    P.store(fb);
 }
 
 class CaveflyerGame final : public PrefetchingGame<Gen> {
@@ -1364,6 +1379,9 @@ class CaveflyerGame final : public PrefetchingGame<Gen> {
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
+    }
+    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
+        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     static void carve_scratch(Carve& c, PrepOut& p, int n) { prep_carve(c, p, n, kGrid, kBlitWords, false); }
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }

@@ -907,11 +907,11 @@ __global__ void __launch_bounds__(128, 4) render_kernel(State s, AtlasView atlas
     wave_store_rows(fb, io.obs + size_t(env) * kObsBytes, lane, row_lo, row_hi);
 }
 
-// cenv_render's frame (render_game(false)) for one env: pg_frame.h; the draw list of render_kernel, one draw at a time.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    const float fw = static_cast<float>(t.w), fh = static_cast<float>(t.h);
-    FramePainter P{t, atlas, Camera{W / 2.0f * kUnitPx, SF(s, F_CAMY, env), fw, fh, 0.2f * fw / 64.0f},
-                   static_cast<int>(threadIdx.x), kFrameThreads};
+// cenv_render's frame (render_game(false)): the draw list of render_kernel, one draw at a time, for either painter of pg_frame.h.
+template <class Painter>
+__device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Painter& P) {
+    const float fw = P.width(), fh = P.height();
+    P.begin(atlas, Camera{W / 2.0f * kUnitPx, SF(s, F_CAMY, env), fw, fh, 0.2f * fw / 64.0f});
     const int themes = SI(s, I_THEMES, env), sflags = SI(s, I_FLAGS, env);
     const int backdrop = themes & 0xff, suit = (themes >> 8) & 0xff, theme = (themes >> 16) & 0xff;
     const int n_draw = (sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;
@@ -956,6 +956,21 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
         const float px = SF(s, F_AX, env) - 0.5f, py = SF(s, F_AY, env) - 1.0f;
         P.draw(tex, px * kUnitPx, py * kUnitPx, 0.8f * kUnitPx / P.desc(tex).y, 1.0f, (sflags & kFlagForward) == 0);
     }
+}
+
+// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
+__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
+    FramePainter P(t);
+    frame_draws(s, atlas, env, P);
+}
+
+// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
+__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
+    __shared__ uint32_t tile[kTilePx];
+    TilePainter P(tile, fb);
+    const int env = P.env(fb);
+    if (env >= 0) frame_draws(s, atlas, env, P);
+    P.store(fb);
 }
 
 class ClimberGame final : public PrefetchingGame<Gen> {
@@ -1019,6 +1034,9 @@ class ClimberGame final : public PrefetchingGame<Gen> {
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
+    }
+    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
+        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     static void carve_scratch(Carve& c, PrepOut& p, int n) { prep_carve(c, p, n, kGrid, kBlitWords, true); }
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }

@@ -1712,12 +1712,11 @@ __global__ void __launch_bounds__(64 * kRenderWaves, PG_COINRUN_RENDER_WAVES) re
     PG_TL_END(6, true, io.obs + size_t(env) * kObsBytes + half * (kObsBytes / 2));
 }
 
-// cenv_render's frame (coinrun.cpp:393-411 → render_game(false), :443-470) for one env: pg_frame.h.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    FramePainter P{t, atlas,
-                   Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), static_cast<float>(t.w), static_cast<float>(t.h),
-                          0.3f * static_cast<float>(t.w) / 64.0f},
-                   static_cast<int>(threadIdx.x), kFrameThreads};
+// cenv_render's frame (coinrun.cpp:393-411 → render_game(false), :443-470) as a draw list for either painter of pg_frame.h.
+template <class Painter>
+__device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Painter& P) {
+    const float fw = P.width(), fh = P.height();
+    P.begin(atlas, Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), fw, fh, 0.3f * fw / 64.0f});
     const int themes = SI(s, I_THEMES, env), sflags = SI(s, I_FLAGS, env);
     const int buf = (sflags & kFlagBuf) ? 1 : 0;
     const int backdrop = themes & 0xff, alien = (themes >> 8) & 0xff, ground_theme = (themes >> 16) & 0xff;
@@ -1787,6 +1786,21 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
         const float px = SF(s, F_AX, env) - 0.5f, py = SF(s, F_AY, env) - 2.0f;
         P.draw(tex, px * kUnitPx, py * kUnitPx, kUnitPx / P.desc(tex).y, 1.0f, (sflags & kFlagForward) == 0);
     }
+}
+
+// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
+__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
+    FramePainter P(t);
+    frame_draws(s, atlas, env, P);
+}
+
+// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
+__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
+    __shared__ uint32_t tile[kTilePx];
+    TilePainter P(tile, fb);
+    const int env = P.env(fb);
+    if (env >= 0) frame_draws(s, atlas, env, P);
+    P.store(fb);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1897,6 +1911,9 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
+    }
+    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
+        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     void launch_prepass(hipStream_t st, const uint8_t* mask) override {
         if (!(debug_flags & (1 | kDebugNoPrepass)) && !PG_ABL(debug_flags, 1 << 22))  // (experiment: the last frame's pre-pass again)

@@ -817,6 +817,45 @@ int32_t pgv_render_frame(pgv_env* e, int32_t index, int32_t width, int32_t heigh
     return 0;
 }
 
+int32_t pgv_render_frames(pgv_env* e, const int32_t* d_indices, int32_t count, int32_t width, int32_t height, uint8_t* d_rgb) {
+    if (!e) return fail("pgv_render_frames: env is NULL");
+    if (count < 0) return fail("pgv_render_frames: count is negative");
+    if (width < 1 || height < 1 || width > 4096 || height > 4096 || !d_rgb)
+        return fail("pgv_render_frames: bad frame size or NULL buffer");
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    e->game->launch_frames(e->stream, d_indices, count, d_rgb, width, height);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_render_frames_host(pgv_env* e, const int32_t* h_indices, int32_t count, int32_t width, int32_t height,
+                               uint8_t* h_rgb) {
+    if (!e) return fail("pgv_render_frames_host: env is NULL");
+    if (count < 0) return fail("pgv_render_frames_host: count is negative");
+    if (width < 1 || height < 1 || width > 4096 || height > 4096 || !h_rgb)
+        return fail("pgv_render_frames_host: bad frame size or NULL buffer");
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    const size_t bytes = size_t(count) * size_t(height) * size_t(width) * 3;
+    uint8_t* d_rgb = nullptr;
+    int32_t* d_indices = nullptr;
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_rgb), bytes);
+    if (err == hipSuccess && h_indices) {
+        err = hipMalloc(reinterpret_cast<void**>(&d_indices), size_t(count) * 4);
+        if (err == hipSuccess) err = hipMemcpyAsync(d_indices, h_indices, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
+    }
+    int32_t rc = 0;
+    if (err == hipSuccess) rc = pgv_render_frames(e, d_indices, count, width, height, d_rgb);
+    if (err == hipSuccess && rc == 0) err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess && rc == 0) err = hipMemcpy(h_rgb, d_rgb, bytes, hipMemcpyDeviceToHost);
+    if (err != hipSuccess || rc != 0) (void)hipStreamSynchronize(e->stream);  // nothing may still be using what is freed next
+    if (d_indices) (void)hipFree(d_indices);
+    if (d_rgb) (void)hipFree(d_rgb);
+    if (err != hipSuccess) return fail(std::string("pgv_render_frames_host: ") + hipGetErrorString(err));
+    return rc;
+}
+
 int32_t pgv_set_debug(pgv_env* e, int32_t flags) {
     if (!e) return fail("pgv_set_debug: env is NULL");
 #ifndef PG_ABLATE

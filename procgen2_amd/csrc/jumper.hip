@@ -1357,12 +1357,12 @@ __global__ void __launch_bounds__(128, PG_RENDER_WAVES) render_kernel(State s, A
     PG_TL_END(8, s.hud_image != 0u, io.obs + size_t(env) * kObsBytes + half * (kObsBytes / 2));
 }
 
-// cenv_render's frame (render_game(false)) for one env: pg_frame.h; the draw list of render_kernel, one draw at a time.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    const float fw = static_cast<float>(t.w), fh = static_cast<float>(t.h);
+// cenv_render's frame (render_game(false)): the draw list of render_kernel, one draw at a time, for either painter of pg_frame.h.
+template <class Painter>
+__device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Painter& P) {
+    const float fw = P.width(), fh = P.height();
     const float game_zoom = 0.3f;
-    FramePainter P{t, atlas, Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), fw, fh, game_zoom * fw / 64.0f},
-                   static_cast<int>(threadIdx.x), kFrameThreads};
+    P.begin(atlas, Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), fw, fh, game_zoom * fw / 64.0f});
     const int themes = SI(s, I_THEMES, env), sflags = SI(s, I_FLAGS, env);
     const int backdrop = themes & 0xff, theme = (themes >> 8) & 0xff;
     const int n_draw = (sflags & kFlagListed) ? SI(s, I_NSPIKES, env) + 1 : 0;
@@ -1449,6 +1449,21 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
                  compass_size * game_zoom + offset_y * game_zoom, compass_size * game_zoom * ratio,
                  compass_size * 0.15f * game_zoom, 0.0);
     }
+}
+
+// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
+__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
+    FramePainter P(t);
+    frame_draws(s, atlas, env, P);
+}
+
+// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
+__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
+    __shared__ uint32_t tile[kTilePx];
+    TilePainter P(tile, fb);
+    const int env = P.env(fb);
+    if (env >= 0) frame_draws(s, atlas, env, P);
+    P.store(fb);
 }
 
 class JumperGame final : public PrefetchingGame<Gen> {
@@ -1609,6 +1624,9 @@ class JumperGame final : public PrefetchingGame<Gen> {
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
+    }
+    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
+        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     static void carve_scratch(Carve& c, State& s, int n) {
         prep_carve(c, s.prep, n, kGrid, kBlitWords, true);

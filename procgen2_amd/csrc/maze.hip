@@ -391,12 +391,12 @@ __global__ void __launch_bounds__(128, 4) render_kernel(State s, AtlasView atlas
     wave_store_rows(fb, io.obs + size_t(env) * kObsBytes, lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
 }
 
-// cenv_render's frame (render_game(false)) for one env: pg_frame.h; the draw list of render_kernel, one draw at a time.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    const float fw = static_cast<float>(t.w), fh = static_cast<float>(t.h);
+// cenv_render's frame (render_game(false)): the draw list of render_kernel, one draw at a time, for either painter of pg_frame.h.
+template <class Painter>
+__device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Painter& P) {
+    const float fw = P.width(), fh = P.height();
     const float zoom = fw / (kUnitPx * static_cast<float>(kVisible));  // maze.cpp:397-400
-    FramePainter P{t, atlas, Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), fw, fh, zoom}, static_cast<int>(threadIdx.x),
-                   kFrameThreads};
+    P.begin(atlas, Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), fw, fh, zoom});
     const int sflags = SI(s, I_FLAGS, env);
     const uint8_t* tiles = s.tiles + size_t(env) * kTileStride;
     P.clear();
@@ -418,6 +418,21 @@ __global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView
     }
     P.draw(kTexMouse, (SF(s, F_AX, env) + -0.5f) * kUnitPx, (SF(s, F_AY, env) + -0.5f) * kUnitPx,
            kUnitPx / P.desc(kTexMouse).y * 1.0f, 1.0f, (sflags & kFlagForward) != 0);
+}
+
+// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
+__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
+    FramePainter P(t);
+    frame_draws(s, atlas, env, P);
+}
+
+// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
+__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
+    __shared__ uint32_t tile[kTilePx];
+    TilePainter P(tile, fb);
+    const int env = P.env(fb);
+    if (env >= 0) frame_draws(s, atlas, env, P);
+    P.store(fb);
 }
 
 class MazeGame final : public PrefetchingGame<Gen> {
@@ -464,6 +479,9 @@ class MazeGame final : public PrefetchingGame<Gen> {
     bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
         hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
         return true;
+    }
+    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
+        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     // (the draw-list replay and kDebugNoPrepass take the kernel that resolves its own draws)
     bool lean() const { return !(debug_flags & (1 | kDebugNoPrepass)); }

@@ -116,6 +116,10 @@ class Game {
     // cenv_render's human-size frame (render_game(false)) of one env into a w×h target of 0x00BBGGRR words in device
     // memory (pg_frame.h).  False = not implemented for this game.
     virtual bool launch_frame(hipStream_t s, int env, uint32_t* d_px, int w, int h) { return false; }
+    // The same frames for `count` envs at once, as packed RGB into d_rgb = u8 [count][h][w][3] in device memory, tile by
+    // tile (pg_frame.h TilePainter).  d_indices: device int32[count] or nullptr for envs 0 .. count-1; an index outside
+    // the batch gives a frame of zeros.  Every game has it; a batch too big for one grid goes out in several launches.
+    virtual void launch_frames(hipStream_t s, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) = 0;
     // Debug tap used by the parity tests: game-defined float dump of one env (host pointer).
     virtual int dump_state(hipStream_t s, int env, float* out, int cap) = 0;
     virtual int dump_tiles(hipStream_t s, int env, uint8_t* out, int cap) = 0;

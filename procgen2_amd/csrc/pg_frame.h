@@ -1,93 +1,50 @@
 // The human-size frame of cenv_render (games/*/<game>.cpp `render_game(false)`): the same draw list as
-// the observation, rasterised at W×H with camera_scale = zoom · W / 64, for ONE env.
+// the observation, rasterised at W×H with camera_scale = zoom · W / 64.
 //
-// This is a debugging / viewer path, not the hot path, and it is deliberately plain: one workgroup, a W×H target of
-// 0x00BBGGRR words in global memory, every draw resolved by all threads (uniform arguments → uniform control flow)
-// and rasterised by all of them with the same raster spec as the observation (pg_geom.h S1–S6), a barrier after
-// every draw.  No row composer, no LDS target: neither fits an arbitrary W×H, and a frame is needed once per
-// keystroke, not 65 536 times per millisecond.
+// A game writes its draw list once, as `template <class Painter> frame_draws(State, AtlasView, env, Painter&)`, and
+// reaches the target only through the painter's methods (begin, clear, draw, draw_rotated, screen, window, desc, cam,
+// width / height, lead).  Two painters take it, with one statement of the raster spec between them (pg_raster.h, which
+// the host tests compile too):
+//
+//   FramePainter  ONE env, one workgroup, a W×H target of 0x00BBGGRR words in global memory: pgv_render_frame, the
+//                 debugging / viewer path ("a frame per keystroke"), deliberately plain — every draw resolved by all
+//                 threads (uniform arguments → uniform control flow) and rasterised by all of them, a barrier after it.
+//   TilePainter   one 64×64 tile of one env's frame in LDS, one workgroup per (frame, tile): pgv_render_frames, many
+//                 envs at any size into the caller's u8 [K][H][W][3] on the device.  The camera is the whole frame's, so
+//                 a draw resolves to exactly the numbers FramePainter sees; only the rasterised region is cut.  A draw
+//                 that does not reach the tile returns before any barrier (its arguments are uniform over the workgroup,
+//                 so the decision is); the others stride over their intersection with the tile.  The tile leaves as packed
+//                 RGB with the widest stores each row's alignment allows.  Every tile walks the whole draw list: the
+//                 tile-layer window is NOT narrowed per tile (padding, D8 / S2, lets a cell a little outside the naive
+//                 range reach in; the early return already makes a draw that misses cost its resolve and nothing else).
 #pragma once
 
 #include "pg_engine.h"
 #include "pg_geom.h"
+#include "pg_raster.h"
 #include "pg_sincos.h"
 
 namespace pg {
+
+constexpr int kFrameThreads = 256;
 
 struct FrameTarget {
     uint32_t* px;  // [h][w]
     int w, h;
 };
 
-struct FramePainter {
-    FrameTarget t;
+// The calls of a draw list that do not depend on where the pixels go: Derived supplies blit(), clear(), width(), height(), lead().
+template <class Derived>
+struct PainterCalls {
     AtlasView atlas;
     Camera cam;
-    int tid, nt;
 
+    PG_D Derived& self() { return *static_cast<Derived*>(this); }
     PG_D int4 desc(int tex) const { return atlas.desc[tex]; }
-
-    PG_D void clear() {  // SDL_RenderClear with (0,0,0,255)
-        for (int k = tid; k < t.w * t.h; k += nt) t.px[k] = 0;
-        __syncthreads();
-    }
-
-    // All threads rasterise one resolved draw (raster spec S3–S6), then meet: the next draw may touch these pixels.
-    PG_D void blit(const Blit& b) {
-        int x_lo, y_lo, x_hi, y_hi;  // inclusive
-        const bool rotated = (b.flip_mod & kRotated) != 0;
-        if (rotated) {
-            long long reach = 1;
-            const long long diag2 = (long long)b.dw * b.dw + (long long)b.dh * b.dh;
-            while (reach * reach * 4 < diag2) reach++;
-            reach += 1;
-            const long long cx2 = 2LL * b.dx + b.dw, cy2 = 2LL * b.dy + b.dh;
-            x_lo = static_cast<int>((cx2 - 2 * reach) / 2 - 1);
-            x_hi = static_cast<int>((cx2 + 2 * reach) / 2 + 1);
-            y_lo = static_cast<int>((cy2 - 2 * reach) / 2 - 1);
-            y_hi = static_cast<int>((cy2 + 2 * reach) / 2 + 1);
-        } else {
-            x_lo = b.dx;
-            y_lo = b.dy;
-            x_hi = b.dx + b.dw - 1;
-            y_hi = b.dy + b.dh - 1;
-        }
-        if (x_lo < 0) x_lo = 0;
-        if (y_lo < 0) y_lo = 0;
-        if (x_hi > t.w - 1) x_hi = t.w - 1;
-        if (y_hi > t.h - 1) y_hi = t.h - 1;
-        const int fw = x_hi - x_lo + 1, fh = y_hi - y_lo + 1;
-        const int mod = b.flip_mod & 0xff;
-        if (fw > 0 && fh > 0) {
-            const long long total = (long long)fw * fh;
-            for (long long p = tid; p < total; p += nt) {
-                const int ry = static_cast<int>(p / fw);
-                const int X = x_lo + static_cast<int>(p - (long long)ry * fw), Y = y_lo + ry;
-                int i, j;
-                if (rotated) {
-                    const long long px = 2LL * (X - b.dx) + 1 - b.dw, py = 2LL * (Y - b.dy) + 1 - b.dh;
-                    const long long lx = px * b.rot_cs + py * b.rot_sn + (long long)b.dw * 65536;
-                    const long long ly = -px * b.rot_sn + py * b.rot_cs + (long long)b.dh * 65536;
-                    if (lx < 0 || ly < 0 || lx >= 2LL * b.dw * 65536 || ly >= 2LL * b.dh * 65536) continue;
-                    i = static_cast<int>(lx >> 17);
-                    j = static_cast<int>(ly >> 17);
-                } else {
-                    i = X - b.dx;
-                    j = Y - b.dy;
-                    if (b.flip_mod & kFlipH) i = b.dw - 1 - i;
-                    if (b.flip_mod & kFlipV) j = b.dh - 1 - j;
-                }
-                const int u = b.sx + static_cast<int>(((2LL * i + 1) * b.sw) / (2LL * b.dw));
-                const int v = b.sy + static_cast<int>(((2LL * j + 1) * b.sh) / (2LL * b.dh));
-                const uint32_t texel = atlas.texels[b.tex_off + v * b.tex_w + u];
-                int a = static_cast<int>(texel >> 24);
-                if (mod != 255) a = static_cast<int>(div255(static_cast<uint32_t>(a * mod)));
-                if (a == 0) continue;
-                uint32_t* d = &t.px[Y * t.w + X];
-                *d = blend_px(*d, texel, a);
-            }
-        }
-        __syncthreads();
+    // First call of a draw list: the game's camera for this frame (its size is the painter's width() × height()).
+    PG_D void begin(const AtlasView& a, const Camera& c) {
+        atlas = a;
+        cam = c;
     }
 
     // Renderer::render_texture (renderer.cpp:5-82)
@@ -95,7 +52,7 @@ struct FramePainter {
                    bool flip_v = false) {
         const int4 d = desc(tex);
         Blit b;
-        if (resolve_draw(cam, d.y, d.z, d.x, px, py, scale, alpha, flip_h, flip_v, b)) blit(b);
+        if (resolve_draw(cam, d.y, d.z, d.x, px, py, scale, alpha, flip_h, flip_v, b)) self().blit(b);
     }
     // Renderer::render_texture_rotated (renderer.cpp:84-101)
     PG_D void draw_rotated(int tex, float px, float py, float rotation, float scale, float alpha = 1.0f) {
@@ -134,7 +91,7 @@ struct FramePainter {
             b.rot_cs = static_cast<int>(floor(static_cast<double>(sc_cosf(theta)) * 65536.0 + 0.5));
             b.flip_mod |= kRotated;
         }
-        blit(b);
+        self().blit(b);
     }
     // The tile window of System_Tilemap::render (e.g. coinrun/tilemap.cpp:294-304): inclusive cell ranges.
     PG_D void window(int& x0, int& y0, int& x1, int& y1) const {
@@ -148,6 +105,107 @@ struct FramePainter {
     }
 };
 
-constexpr int kFrameThreads = 256;
+struct FramePainter : PainterCalls<FramePainter> {
+    FrameTarget t;
+    int tid;
+
+    PG_D explicit FramePainter(const FrameTarget& target) : t(target), tid(static_cast<int>(threadIdx.x)) {}
+    PG_D float width() const { return static_cast<float>(t.w); }
+    PG_D float height() const { return static_cast<float>(t.h); }
+    PG_D bool lead() const { return tid == 0; }  // one thread per rendered frame (bossfight, D15)
+
+    PG_D void clear() {  // SDL_RenderClear with (0,0,0,255)
+        for (int k = tid; k < t.w * t.h; k += kFrameThreads) t.px[k] = 0;
+        __syncthreads();
+    }
+    // All threads rasterise one resolved draw (raster spec S3–S6), then meet: the next draw may touch these pixels.
+    PG_D void blit(const Blit& b) {
+        PixRect r = draw_reach(b);
+        if (rect_clip(r, PixRect{0, 0, t.w - 1, t.h - 1})) paint_rect(b, atlas.texels, r, t.px, t.w, 0, 0, tid, kFrameThreads);
+        __syncthreads();
+    }
+};
+
+// One pgv_render_frames launch: block b0 + blockIdx.x paints tile (b % tiles) of frame (b / tiles).
+struct FrameBatch {
+    const int32_t* indices;  // [count] env of frame k, or nullptr: env k
+    uint8_t* rgb;            // [count][h][w][3]
+    int w, h, tiles, n;      // tiles per frame; n envs in the batch (an index outside [0, n) gives a frame of zeros)
+    long long b0;            // first block of this launch (a batch too big for one grid takes several)
+};
+
+struct TilePainter : PainterCalls<TilePainter> {
+    uint32_t* tile;  // LDS, [kTile][kTile], pixel (X, Y) of the frame at [(Y − at.y0)·kTile + (X − at.x0)]
+    PixRect at;      // the tile's pixels in the frame
+    int w, h, tid, frame, index;
+
+    PG_D TilePainter(uint32_t* lds, const FrameBatch& fb) : tile(lds), w(fb.w), h(fb.h), tid(static_cast<int>(threadIdx.x)) {
+        block_place(fb.b0 + blockIdx.x, fb.tiles, frame, index);
+        at = tile_rect(w, h, index);
+    }
+    PG_D float width() const { return static_cast<float>(w); }
+    PG_D float height() const { return static_cast<float>(h); }
+    PG_D bool lead() const { return tid == 0 && index == 0; }  // exactly one thread of one tile per rendered frame
+
+    // The env this workgroup paints, or -1 (tile cleared) for an index outside the batch: never dereferenced.
+    PG_D int env(const FrameBatch& fb) {
+        const int e = fb.indices ? fb.indices[frame] : frame;
+        if (e >= 0 && e < fb.n) return e;
+        clear();
+        return -1;
+    }
+    PG_D void clear() {
+        for (int k = tid; k < kTilePx; k += kFrameThreads) tile[k] = 0;
+        __syncthreads();
+    }
+    PG_D void blit(const Blit& b) {
+        PixRect r = draw_reach(b);
+        if (!rect_clip(r, at)) return;  // uniform over the workgroup: nothing written, no barrier needed
+        paint_rect(b, atlas.texels, r, tile, kTile, at.x0, at.y0, tid, kFrameThreads);
+        __syncthreads();
+    }
+    // The finished tile into the caller's frame (every clear and blit ended with a barrier): kRowSlots lanes a row, each
+    // with one store of the width pg_raster.h row_plan found for its piece of the row.
+    PG_D void store(const FrameBatch& fb) const {
+        const int rows = at.y1 - at.y0 + 1, last = at.x1 - at.x0, nb = 3 * (last + 1);
+        uint8_t* out = fb.rgb + static_cast<size_t>(frame) * h * w * 3;
+        for (int k = tid; k < rows * kRowSlots; k += kFrameThreads) {
+            const int row = k / kRowSlots, slot = k % kRowSlots;
+            uint8_t* dst = out + (static_cast<size_t>(at.y0 + row) * w + at.x0) * 3;
+            const uint32_t* src = tile + row * kTile;
+            const RowPlan plan = row_plan(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst)), nb);
+            int off;
+            const int width = row_slot(plan, slot, off);
+            if (width == 16)
+                *reinterpret_cast<uint4*>(dst + off) = make_uint4(row_word(src, off, last), row_word(src, off + 4, last),
+                                                                  row_word(src, off + 8, last), row_word(src, off + 12, last));
+            else if (width == 4)
+                *reinterpret_cast<uint32_t*>(dst + off) = row_word(src, off, last);
+            else if (width == 1)
+                dst[off] = static_cast<uint8_t>(row_word(src, off, last));
+        }
+    }
+};
+
+// The blocks one launch may have: the device's limit on a grid's first dimension, and the 2^32 threads a grid may hold.
+inline long long frame_grid_limit() {
+    int dev = 0, most = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&most, hipDeviceAttributeMaxGridDimX, dev) != hipSuccess || most < 1)
+        most = 65535;
+    long long limit = most;
+    if (limit > 0xffffffffLL / kFrameThreads) limit = 0xffffffffLL / kFrameThreads;
+    return limit;
+}
+
+// A game's frames_kernel over count · tiles blocks, in as many launches as the grid limit asks for.
+template <class Kernel, class State>
+void launch_frames_tiled(Kernel kernel, hipStream_t st, const State& s, const AtlasView& atlas, const int32_t* d_indices,
+                         int count, uint8_t* d_rgb, int w, int h, int n) {
+    FrameBatch fb{d_indices, d_rgb, w, h, tiles_across(w) * tiles_across(h), n, 0};
+    const long long total = static_cast<long long>(count) * fb.tiles, limit = frame_grid_limit();
+    for (; fb.b0 < total; fb.b0 += limit)
+        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(launch_blocks(total, fb.b0, limit))), dim3(kFrameThreads), 0, st, s,
+                           atlas, fb);
+}
 
 }  // namespace pg

@@ -231,6 +231,23 @@ class GymVectorAdapter(_VectorBase):
         w, h = self.render_size
         return self.engine.render_frame(int(index), w, h)
 
+    def render_batch(self, indices=None):
+        """The human-size frames of the sub-envs `indices` (None: all of them, in order) at render_size: uint8
+        [K, H, W, 3] in the adapter's `output` kind.  None unless the env was made with render_mode="rgb_array".  An engine
+        with render_frames (ProcgenVecEnv: one batched call, the frames stay on the device for output="torch") is used as
+        such; any other has its render_frame called once per env."""
+        if self.render_mode != "rgb_array":
+            return None
+        w, h = self.render_size
+        if hasattr(self.engine, "render_frames"):
+            return self._out(self.engine.render_frames(indices, w, h))
+        which = range(self.num_envs) if indices is None else [int(k) for k in np.asarray(indices).reshape(-1)]
+        frames = np.stack([self.engine.render_frame(k, w, h) for k in which]) if len(which) else np.zeros((0, h, w, 3), np.uint8)
+        if self.output == "numpy":
+            return frames
+        import torch
+        return torch.from_numpy(frames)
+
     def close(self, **kwargs):
         if not self.closed:
             self.engine.close()

@@ -104,6 +104,8 @@ def load(path=None):
         "pgv_stream": (P, [P]),
         "pgv_copy_out": (c_int32, [P, P, P, P]),
         "pgv_render_frame": (c_int32, [P, c_int32, c_int32, c_int32, P]),
+        "pgv_render_frames": (c_int32, [P, P, c_int32, c_int32, c_int32, P]),
+        "pgv_render_frames_host": (c_int32, [P, P, c_int32, c_int32, c_int32, P]),
         "pgv_snapshot_bytes": (c_int64, [P]),
         "pgv_save_state": (c_int32, [P, P, c_int64]),
         "pgv_load_state": (c_int32, [P, P, c_int64]),
@@ -134,7 +136,7 @@ def check(lib, rc, what):
 EXPORTED_VEC_SYMBOLS = [
     "pgv_game_name", "pgv_game_id", "pgv_make", "pgv_make_levels", "pgv_make_config", "pgv_game_modes", "pgv_mode", "pgv_close", "pgv_reset", "pgv_step", "pgv_step_synthetic", "pgv_step_synthetic_many",
     "pgv_synthetic_action", "pgv_step_host", "pgv_reset_host", "pgv_decode_png", "pgv_sync", "pgv_generator_launches", "pgv_obs", "pgv_reward", "pgv_done", "pgv_bind_outputs", "pgv_num_envs",
-    "pgv_device", "pgv_stream", "pgv_copy_out", "pgv_render_frame", "pgv_snapshot_bytes", "pgv_save_state", "pgv_load_state", "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
+    "pgv_device", "pgv_stream", "pgv_copy_out", "pgv_render_frame", "pgv_render_frames", "pgv_render_frames_host", "pgv_snapshot_bytes", "pgv_save_state", "pgv_load_state", "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_last_error",
 ]
 EXPORTED_CENV_SYMBOLS = [

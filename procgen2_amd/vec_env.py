@@ -159,6 +159,33 @@ class ProcgenVecEnv:
                     "pgv_render_frame")
         return out
 
+    def render_frames(self, indices=None, width=512, height=512, out=None):
+        """The human-size frames of the envs `indices` (None: all of them, in order; otherwise anything torch.as_tensor
+        takes — an env may appear more than once, an index outside the batch gives a frame of zeros): uint8
+        [K, height, width, 3] on this env's device, rendered there in one batched call (pgv_render_frames) with the same
+        stream hand-shake as step() and no host synchronisation.  out: a caller-owned contiguous tensor of that shape to
+        write into (and return)."""
+        width, height = int(width), int(height)
+        idx = None
+        count = self.num_envs
+        if indices is not None:
+            idx = torch.as_tensor(indices, device=self.device).to(torch.int32).reshape(-1).contiguous()
+            count = idx.numel()
+        shape = (count, height, width, 3)
+        if out is None:
+            if not (1 <= width <= 4096 and 1 <= height <= 4096):
+                raise ValueError("render_frames: width and height must be in 1..4096")
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out: expected a contiguous %s tensor of shape %s on %s" % (torch.uint8, shape, self.device))
+        if count:
+            self._before()
+            pglib.check(self.L, self.L.pgv_render_frames(self._h, c_void_p(idx.data_ptr()) if idx is not None else None,
+                                                         count, width, height, c_void_p(out.data_ptr())), "pgv_render_frames")
+            self._after()
+            self._keep_frames = (idx, out)
+        return out
+
     def save_state(self):
         """Snapshot of the whole batch (state, RNG streams, prefetched levels, outputs) as a numpy byte array."""
         import numpy as np
