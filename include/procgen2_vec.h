@@ -156,6 +156,48 @@ PGV_API int64_t pgv_snapshot_bytes(pgv_env* env);
 PGV_API int32_t pgv_save_state(pgv_env* env, void* h_buffer, int64_t capacity);
 PGV_API int32_t pgv_load_state(pgv_env* env, const void* h_buffer, int64_t size);
 
+/* Per-env state records: save, load and fork ANY envs, on the device.  (The original procgen's get_state / set_state; the
+ * reference has no counterpart.)  A record is one env's complete state as a fixed-size, opaque, position-independent
+ * block of pgv_env_record_bytes() bytes (a multiple of 16) in DEVICE memory.  Its size and its tag are functions of the
+ * engine's configuration — game, mode, game_flags, num_levels, start_level, the record layout's version — and of nothing
+ * else: not num_envs, env_offset, seed_base, the step counter or what the engine did before.  pgv_env_record_tag() is a
+ * fingerprint of that configuration, never 0.  Records are for this process and this device: the caller may copy the
+ * bytes wherever it likes, but the layout is not a file format (the tag ties a record to a layout version on purpose).
+ *
+ *   1. Saving is transparent: the engine that saved goes on exactly as one that never did.
+ *   2. A record resumes in any slot of any engine of the same configuration on the same device — another num_envs,
+ *      env_offset or seed_base, fresh or mid-rollout, at a step counter of either parity.  From the load on the slot
+ *      produces, given the actions the source env would have been given, the observations, rewards and dones the source
+ *      env would have produced, bit for bit, through any number of later auto-resets: its mt19937 stream, generator
+ *      chain, prefetched level, position in the level set and (bossfight) camera size travel.  Right after the load the
+ *      slot's rows of obs / reward / done — through the bound output pointers — are the source's at the save, and a
+ *      reset that was pending for the source is pending for the slot.
+ *   3. Envs that a load does not name are untouched, in state and in outputs.
+ *   4. Two saves of one env with nothing in between are byte-equal (padding is written), so records can be hashed.
+ *   5. What does NOT travel: the engine-wide step counter and the env's global index.  The actions pgv_step_synthetic
+ *      makes on the device hash both, so a moved env gets the actions of the SLOT it now sits in, at its new engine's
+ *      step count; a caller who wants an env's own trajectory back feeds explicit actions (pgv_step).
+ *
+ * d_records: device u8 [count][pgv_env_record_bytes], 16-byte aligned.  d_indices: device int32[count], or NULL for envs
+ * 0 .. count-1.  Both calls are enqueued on the env's stream; nothing is allocated, the host is not synchronised (the
+ * level generator's side stream is ordered by events).  count = 0 succeeds and does nothing; count < 0, or a NULL record
+ * pointer with count > 0, fails.  pgv_load_envs checks `tag` on the host before anything is enqueued: records of another
+ * configuration are refused and the engine is left as it was.
+ * An index outside the batch: save writes a record marked empty, load skips it; load also skips every record marked
+ * empty, and a zero-filled buffer is all empty records.  A save may name the same env several times.  The indices of
+ * one load must be distinct: a slot named twice ends up with one of its records or a mixture of them (nothing faults).
+ * Fork = save, then load under other indices.  Cost beside the copy itself: a save first brings home the random streams
+ * that bossfight and chaser keep in two buffers (one small launch over the batch), a load launches the level generator
+ * for the loaded slots whose next level was still queued (pgv_generator_launches counts it). */
+PGV_API int64_t pgv_env_record_bytes(pgv_env* env);
+PGV_API uint64_t pgv_env_record_tag(pgv_env* env);
+PGV_API int32_t pgv_save_envs(pgv_env* env, const int32_t* d_indices, int32_t count, void* d_records);
+PGV_API int32_t pgv_load_envs(pgv_env* env, const int32_t* d_indices, int32_t count, const void* d_records, uint64_t tag);
+/* Host-pointer conveniences (synchronous; allocate and free their device buffers), as pgv_step_host is to pgv_step. */
+PGV_API int32_t pgv_save_envs_host(pgv_env* env, const int32_t* h_indices, int32_t count, void* h_records);
+PGV_API int32_t pgv_load_envs_host(pgv_env* env, const int32_t* h_indices, int32_t count, const void* h_records,
+                                   uint64_t tag);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

@@ -1475,18 +1475,18 @@ class BossfightGame final : public Game {
     }
     // The state block, in order (state_bytes and bind).
     static void carve(Carve& c, State& s, int n) {
-        c.take(s.mt, size_t(n) * kMtWords * 4);
-        c.take(s.f, size_t(F_COUNT) * n * 4);
-        c.take(s.i, size_t(I_COUNT) * n * 4);
-        c.take(s.ashot, size_t(S_COUNT) * kAgentShots * n * 4);
-        c.take(s.abnc, size_t(kAgentShots) * n);
-        c.take(s.bshot, size_t(S_COUNT) * kBossShots * n * 4);
-        c.take(s.boom, size_t(3) * kBooms * n * 4);
-        c.take(s.rock, size_t(3) * kRocks * n * 4);
+        c.take_env(s.mt, n, 1, kMtWords * 4);
+        c.take_env(s.f, n, F_COUNT, 4);
+        c.take_env(s.i, n, I_COUNT, 4);
+        c.take_env(s.ashot, n, 1, S_COUNT * kAgentShots * 4);
+        c.take_env(s.abnc, n, 1, kAgentShots);
+        c.take_env(s.bshot, n, 1, S_COUNT * kBossShots * 4);
+        c.take_env(s.boom, n, 1, 3 * kBooms * 4);
+        c.take_env(s.rock, n, 3 * kRocks, 4);
     }
     size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        Carve::bind(carve, d_state, s_, n);
+        Carve::bind(carve, d_state, s_, n, &regions);
         s_.n = n;
         s_.stamps = stamps_at_;
         atlas_ = atlas;
@@ -1540,6 +1540,7 @@ class BossfightGame final : public Game {
     hipError_t state_loaded(hipStream_t st) override {
         return hipMemsetAsync(s_.mt_sel, 0, size_t(s_.n), st);  // the streams that were just loaded are in mt[env]; what was made ahead is not theirs
     }
+    uint8_t* stream_selectors() const override { return s_.mt_sel; }  // (per-env records: a loaded slot's stream is at home)
     // A snapshot takes the streams from mt[env]: the ones whose gang has moved on to the second buffer come home first.
     void prepare_save(hipStream_t st) override {
         hipLaunchKernelGGL(streams_home_kernel, dim3((s_.n + 63) / 64), dim3(64), 0, st, s_);

@@ -1393,6 +1393,33 @@ __global__ void __launch_bounds__(128, PG_CHASER_RENDER_WAVES) render_list_kerne
     }
 }
 
+// Behind a load of per-env records (ChaserGame::records_loaded): workgroup k takes record k's slot — none if the index is
+// outside the batch or the record is empty, as the scatter skipped it — and renders it the complete way, which leaves the
+// slot's base layer (State::base); the observation row, which that render also writes, is then put back from the record
+// (the same bytes unless the source had never been rendered: a record of a freshly made engine holds a row of zeros).
+__global__ void __launch_bounds__(128, PG_CHASER_RENDER_WAVES) record_layers_kernel(State s, AtlasView atlas, StepIO io, int flags,
+                                                                                   const int32_t* indices, const uint8_t* records,
+                                                                                   size_t record_bytes, size_t obs_offset) {
+    const int k = blockIdx.x;
+    const int env = indices ? indices[k] : k;
+    if (env < 0 || env >= s.n) return;  // (workgroup-uniform)
+    const uint8_t* rec = records + size_t(k) * record_bytes;
+    if (*reinterpret_cast<const uint32_t*>(rec) != kRecordFull) return;
+    __shared__ alignas(16) uint32_t fb[kFbWords];
+    __shared__ ComposeLdsBoxed<kGrid> L;
+    __shared__ SpriteLds S;
+    render_env<false>(s, atlas, io, flags, env, fb, L, S, false, true);
+    __syncthreads();
+    const uint4* from = reinterpret_cast<const uint4*>(rec + obs_offset);
+    uint4* to = reinterpret_cast<uint4*>(io.obs + size_t(env) * kObsBytes);
+    for (int q = threadIdx.x; q < kObsBytes / 16; q += blockDim.x) to[q] = from[q];
+}
+// … and the due list of the step with this parity, from the pending bytes (between steps a byte is 0 or 1).
+__global__ void __launch_bounds__(256) relist_due_kernel(State s, StepIO io, int parity) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < s.n && io.pending[e] == 1) s.due_list[size_t(parity) * s.n + atomicAdd(&s.due_count[parity], 1)] = e;
+}
+
 // cenv_render's frame (render_game(false)): the draw list of render_kernel, one draw at a time, for either painter of pg_frame.h.
 template <class Painter>
 __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Painter& P) {
@@ -1522,20 +1549,20 @@ class ChaserGame final : public Game {
     }
     // The state block, in order (state_bytes and bind).
     static void carve(Carve& c, State& s, int n) {
-        c.take(s.shadow, sizeof(Level));  // unused: this game never prefetches
-        c.take(s.slot, size_t(n) * 4);
-        c.take(s.mt, size_t(n) * kMtWords * 4);
-        c.take(s.tiles, size_t(n) * kTileStride);
-        c.take(s.f, size_t(F_COUNT) * n * 4);
-        c.take(s.i, size_t(I_COUNT) * n * 4);
-        c.take(s.mf, size_t(MF_COUNT) * kMobs * n * 4);
-        c.take(s.mb, size_t(2) * kMobs * n);
-        c.take(s.eb, size_t(EB_COUNT) * kMaxEnt * n);  // (same size either way round)
-        c.take(s.reset_list, size_t(n) * 4);
-        c.take(s.reset_count, 8);
-        c.take(s.due_list, size_t(2) * n * 4);
-        c.take(s.due_count, 8);
-        c.take(s.prepared, sizeof(ComposeHand));
+        c.take_shared(s.shadow, sizeof(Level));  // unused: this game never prefetches
+        c.take_env(s.slot, n, 1, 4);
+        c.take_env(s.mt, n, 1, kMtWords * 4);
+        c.take_env(s.tiles, n, 1, kTileStride);
+        c.take_env(s.f, n, F_COUNT, 4);
+        c.take_env(s.i, n, I_COUNT, 4);
+        c.take_env(s.mf, n, MF_COUNT * kMobs, 4);
+        c.take_env(s.mb, n, 2 * kMobs, 1);
+        c.take_env(s.eb, n, 1, EB_COUNT * kMaxEnt);
+        c.take_shared(s.reset_list, size_t(n) * 4);  // (the four lists and counters: the engine's, not an env's)
+        c.take_shared(s.reset_count, 8);
+        c.take_shared(s.due_list, size_t(2) * n * 4);
+        c.take_shared(s.due_count, 8);
+        c.take_shared(s.prepared, sizeof(ComposeHand));
     }
     size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     bool set_game_flags(uint32_t flags) override {  // include/procgen2_vec.h PGV_CHASER_FLOAT_ABS
@@ -1543,7 +1570,7 @@ class ChaserGame final : public Game {
         return (flags & ~PGV_CHASER_FLOAT_ABS) == 0;
     }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        Carve::bind(carve, d_state, s_, n);
+        Carve::bind(carve, d_state, s_, n, &regions);
         s_.n = n;
         s_.ranks = atlas.sort_ranks;
         atlas_ = atlas;
@@ -1613,6 +1640,21 @@ class ChaserGame final : public Game {
     hipError_t state_loaded(hipStream_t st) override {
         base_valid_ = false;
         return hipMemsetAsync(s_.mt_sel, 0, size_t(s_.n), st);  // the streams that were just loaded are in mt[env]; what was made ahead is not theirs
+    }
+    uint8_t* stream_selectors() const override { return s_.mt_sel; }  // (per-env records: a loaded slot's stream is at home)
+    // Per-env records (pg_records.h) have been scattered into some slots.  Their base layers are the previous tenants':
+    // rebuilt here, for those slots alone (base_valid_ is about the whole batch and stays as it is).  And the due list of
+    // the step that comes next is written again from the pending bytes: a slot loaded with a reset due must be on it —
+    // due_level_kernel serves listed envs only — and must not be on it twice (two workgroups would generate the same level
+    // side by side); a slot that was listed and now holds an env with nothing due is skipped by level_serve's own look at
+    // the byte, listed or not.
+    void records_loaded(hipStream_t st, const int32_t* d_indices, int count, const uint8_t* d_records, size_t record_bytes,
+                        size_t obs_offset, uint32_t next_step, StepIO io) override {
+        hipLaunchKernelGGL(record_layers_kernel, dim3(count), dim3(128), 0, st, s_, atlas_, io, debug_flags, d_indices, d_records,
+                           record_bytes, obs_offset);
+        const int parity = static_cast<int>(next_step & 1u);
+        (void)hipMemsetAsync(s_.due_count + parity, 0, 4, st);
+        hipLaunchKernelGGL(relist_due_kernel, dim3((s_.n + 255) / 256), dim3(256), 0, st, s_, io, parity);
     }
     // A snapshot takes the streams from mt[env]: the ones whose gang has moved on to the second buffer come home first.
     void prepare_save(hipStream_t st) override {

@@ -1864,22 +1864,22 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
 
     // The state block, in order (state_bytes and bind).
     static void carve(Carve& c, State& s, int n) {
-        c.take(s.shadow, size_t(n) * sizeof(Level));
-        c.take(s.slot, size_t(n) * 4);
-        c.take(s.mt, size_t(n) * kMtWords * 4);
-        c.take(s.tiles, size_t(n) * W * H);
-        c.take(s.f, size_t(F_COUNT) * n * 4);
-        c.take(s.i, size_t(I_COUNT) * n * 4);
-        c.take(s.ey, size_t(kMaxEnt) * n * 4);
-        c.take(s.eb, size_t(EB_COUNT) * kMaxEnt * n);
-        c.take(s.df, size_t(2) * DF_COUNT * kMaxEnt * n * 4);
-        c.take(s.db, size_t(2) * kMaxEnt * n);
-        c.take(s.spark, size_t(2) * 3 * kMaxEnt * kSparkRow * n * 4);
-        c.take(s.scratch, size_t(SC_COUNT) * n * 4);
+        c.take_env(s.shadow, n, 1, sizeof(Level));
+        c.take_env(s.slot, n, 1, 4);
+        c.take_env(s.mt, n, 1, kMtWords * 4);
+        c.take_env(s.tiles, n, 1, W * H);
+        c.take_env(s.f, n, F_COUNT, 4);
+        c.take_env(s.i, n, I_COUNT, 4);
+        c.take_env(s.ey, n, kMaxEnt, 4);
+        c.take_env(s.eb, n, EB_COUNT * kMaxEnt, 1);
+        c.take_env(s.df, n, 2 * DF_COUNT * kMaxEnt, 4);
+        c.take_env(s.db, n, 2 * kMaxEnt, 1);
+        c.take_env(s.spark, n, 2, 3 * kMaxEnt * kSparkRow * 4);  // (two planes of one block an env)
+        c.take_env(s.scratch, n, SC_COUNT, 4);
     }
     size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        Carve::bind(carve, d_state, s_, n);
+        Carve::bind(carve, d_state, s_, n, &regions);
         s_.n = n;
         atlas_ = atlas;
     }

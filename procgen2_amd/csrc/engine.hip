@@ -13,6 +13,7 @@
 #include "../../include/procgen2_vec.h"
 #include "pg_engine.h"
 #include "pg_order.h"
+#include "pg_records.h"
 #include "png_decode.h"
 
 #ifndef PG_DEFAULT_GAME
@@ -222,6 +223,13 @@ struct pgv_env {
     // auto-resets beside the logic kernels (pg_engine.h Game::reset_stream)
     hipStream_t reset_stream = nullptr;
     hipEvent_t reset_fork = nullptr, reset_join = nullptr;
+    // per-env records (pg_records.h): the region table as far as pgv_make knows it — the output rows' addresses are filled
+    // in per call, pgv_bind_outputs may move them — the configuration's fingerprint, and the event that orders the env's
+    // stream behind the generator's before records are read or written
+    pg::RecordTable rec{};
+    int rec_reward = 0, rec_done = 0, rec_obs = 0;
+    uint64_t rec_tag = 0;
+    hipEvent_t rec_ev = nullptr;
 
     pg::StepIO io() const { return {d_obs, d_reward, d_done, d_pending}; }
 };
@@ -286,6 +294,7 @@ void pgv_close(pgv_env* e) {
     }
     if (e->reset_fork) hipEventDestroy(e->reset_fork);
     if (e->reset_join) hipEventDestroy(e->reset_join);
+    if (e->rec_ev) hipEventDestroy(e->rec_ev);
     if (e->d_state) hipFree(e->d_state);
     if (e->d_scratch) hipFree(e->d_scratch);
     if (e->own_obs && e->d_obs) hipFree(e->d_obs);
@@ -302,6 +311,53 @@ void pgv_close(pgv_env* e) {
 // LevelPlan), so that a snapshot of the blob carries them.
 static size_t game_state_bytes(const pgv_env* e) { return (e->game->state_bytes(e->n) + 255) / 256 * 256; }
 static size_t state_blob_bytes(const pgv_env* e) { return game_state_bytes(e) + size_t(e->n) * 8; }
+
+// The record layout of this engine (pg_records.h): the game's per-env regions as its state listing describes them, then the
+// engine's own per-env data.  The listing is checked here, on the host: every byte of the state block is either an env's
+// or declared engine-wide — a region added later without saying which fails pgv_make instead of dropping out of records.
+static int32_t plan_records(pgv_env* e) {
+    const pg::EnvRegions& listed = e->game->regions;
+    const std::string who = std::string("pgv_make: ") + e->game->name() + "'s state listing ";
+    if (listed.unlisted_bytes)
+        return fail(who + "takes " + std::to_string(listed.unlisted_bytes) + " bytes with a plain take(): say take_env or take_shared (pg_engine.h Carve)");
+    size_t sum = listed.shared_bytes;
+    for (const pg::EnvRegion& r : listed.v) sum += (size_t(e->n) * r.pieces * r.piece_bytes + 255) / 256 * 256;
+    if (sum != e->game->state_bytes(e->n))
+        return fail(who + "describes " + std::to_string(sum) + " bytes of a block of " + std::to_string(e->game->state_bytes(e->n)));
+    if (listed.v.size() + 5 > size_t(pg::kMaxRecordRegions)) return fail(who + "has more per-env regions than a record table holds");
+    pg::RecordTable& t = e->rec;
+    t = pg::RecordTable{};
+    uint32_t at = pg::kRecordHeaderBytes;
+    auto add = [&](uint8_t* base, uint32_t pieces, uint32_t piece_bytes) {
+        t.r[t.regions] = pg::RecordRegion{base, pieces, piece_bytes, at};
+        at += (pieces * piece_bytes + 15u) / 16u * 16u;
+        return t.regions++;
+    };
+    for (const pg::EnvRegion& r : listed.v) add(r.base, r.pieces, r.piece_bytes);
+    add(reinterpret_cast<uint8_t*>(e->game->plan.chain_seed), 1, 4);
+    add(reinterpret_cast<uint8_t*>(e->game->plan.drawn), 1, 4);
+    e->rec_reward = add(nullptr, 1, 4);
+    e->rec_done = add(nullptr, 1, 1);
+    e->rec_obs = add(nullptr, 1, pg::kObsBytes);
+    t.n = e->n;
+    t.record_bytes = at;
+    t.selectors = e->game->stream_selectors();
+    // the fingerprint: FNV-1a over the configuration and the layout (every region's shape: they differ between variants)
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto mix = [&](uint32_t w) {
+        for (int k = 0; k < 4; k++) h = (h ^ ((w >> (8 * k)) & 0xffu)) * 0x100000001b3ull;
+    };
+    mix(pg::kRecordLayoutVersion);
+    mix(static_cast<uint32_t>(pgv_game_id(e->game->name())));
+    mix(static_cast<uint32_t>(e->mode));
+    mix(e->game_flags);
+    mix(static_cast<uint32_t>(e->game->plan.num_levels));
+    mix(static_cast<uint32_t>(e->game->plan.start_level));
+    for (int k = 0; k < t.regions; k++) mix(t.r[k].pieces), mix(t.r[k].piece_bytes);
+    mix(t.record_bytes);
+    e->rec_tag = h ? h : 1;
+    return 0;
+}
 
 int32_t pgv_make(const char* game, int32_t num_envs, int32_t device, uint32_t seed_base, int32_t env_offset,
                  void* stream, pgv_env** out) {
@@ -375,6 +431,7 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     for (auto& ev : e->ev) PG_HIP(hipEventCreate(&ev));
     PG_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));  // the level generator's stream
     for (auto& ev : e->side_ev) PG_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    PG_HIP(hipEventCreateWithFlags(&e->rec_ev, hipEventDisableTiming));
     if (e->game->resets_beside_logic()) {
         {   // the few long wavefronts of the in-step level kernel go first; the logic kernel's many short ones fill in around them
             int least = 0, greatest = 0;
@@ -415,6 +472,7 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
         uint32_t* words = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(e->d_state) + game_state_bytes(e.get()));
         e->game->plan = pg::LevelPlan{num_levels, start_level, words, words + num_envs};
     }
+    if (plan_records(e.get())) return 1;
     e->game->launch_make(e->stream, seed_base, env_offset);
     PG_HIP(hipGetLastError());
     PG_HIP(hipStreamSynchronize(e->stream));
@@ -645,6 +703,103 @@ int32_t pgv_load_state(pgv_env* e, const void* h_buffer, int64_t size) {
     PG_HIP(e->game->state_loaded(e->stream));  // (on the env's stream: ordered in front of the next step)
     pregen(e, true, true);  // queued shadow slots of the snapshot get their generator launch
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-env records (pg_records.h)
+// ------------------------------------------------------------------------------------------------
+int64_t pgv_env_record_bytes(pgv_env* e) { return e ? static_cast<int64_t>(e->rec.record_bytes) : -1; }
+uint64_t pgv_env_record_tag(pgv_env* e) { return e ? e->rec_tag : 0; }
+
+// The env's stream waits for what the generator's stream holds so far, so no prefetch slot is kSlotBusy while records are
+// read or written: a slot is then idle, queued or ready, and travels as it is (a generator launched later waits for an
+// event the env's stream records later: pregen).  Events only; the host goes on.
+static int32_t records_behind_generator(pgv_env* e) {
+    if (!e->side) return 0;
+    PG_HIP(hipEventRecord(e->rec_ev, e->side));
+    PG_HIP(hipStreamWaitEvent(e->stream, e->rec_ev, 0));
+    return 0;
+}
+static pg::RecordTable records_table(const pgv_env* e) {
+    pg::RecordTable t = e->rec;
+    t.r[e->rec_reward].base = reinterpret_cast<uint8_t*>(e->d_reward);
+    t.r[e->rec_done].base = e->d_done;
+    t.r[e->rec_obs].base = e->d_obs;
+    t.pending = e->d_pending;
+    // "a reset is due" as the pending byte says it for the step that comes next in THIS engine
+    t.due_mark = t.due_code = e->game->pending_has_parity() ? pg::reset_due_mark(e->step_index) : 1;
+    return t;
+}
+static int32_t records_arguments(const char* who, pgv_env* e, int32_t count, const void* records) {
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (count < 0) return fail(std::string(who) + ": count is negative");
+    if (count > 0 && !records) return fail(std::string(who) + ": the record buffer is NULL");
+    return 0;
+}
+
+int32_t pgv_save_envs(pgv_env* e, const int32_t* d_indices, int32_t count, void* d_records) {
+    if (records_arguments("pgv_save_envs", e, count, d_records)) return 1;
+    if (count == 0) return 0;
+    if (reinterpret_cast<uintptr_t>(d_records) & 15u) return fail("pgv_save_envs: the record buffer must be 16-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    e->game->prepare_save(e->stream);  // random streams that live in two buffers come home (a no-op elsewhere)
+    if (records_behind_generator(e)) return 1;
+    pg::launch_records(e->stream, records_table(e), false, d_indices, count, d_records);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_load_envs(pgv_env* e, const int32_t* d_indices, int32_t count, const void* d_records, uint64_t tag) {
+    if (records_arguments("pgv_load_envs", e, count, d_records)) return 1;
+    if (tag != e->rec_tag)
+        return fail("pgv_load_envs: records of another configuration (game, mode, game_flags, level set or record layout): tag " +
+                    std::to_string(tag) + ", this engine's is " + std::to_string(e->rec_tag));
+    if (count == 0) return 0;
+    if (reinterpret_cast<uintptr_t>(d_records) & 15u) return fail("pgv_load_envs: the record buffer must be 16-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    if (records_behind_generator(e)) return 1;
+    const pg::RecordTable t = records_table(e);
+    pg::launch_records(e->stream, t, true, d_indices, count, const_cast<void*>(d_records));
+    e->game->records_loaded(e->stream, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes, t.r[e->rec_obs].offset,
+                            e->step_index, e->io());
+    PG_HIP(hipGetLastError());
+    pregen(e, size_t(count) * 2 >= size_t(e->n), true);  // loaded slots that are queued get their generator launch
+    return 0;
+}
+
+// Host-pointer forms: device buffers for the call, a synchronous copy either way.
+static int32_t records_host(pgv_env* e, const int32_t* h_indices, int32_t count, void* h_records, bool load, uint64_t tag) {
+    const char* who = load ? "pgv_load_envs_host" : "pgv_save_envs_host";
+    if (records_arguments(who, e, count, h_records)) return 1;
+    if (load && tag != e->rec_tag) return pgv_load_envs(e, nullptr, count, h_records, tag);  // (refused there, before anything is touched)
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    const size_t bytes = size_t(count) * e->rec.record_bytes;
+    uint8_t* d_records = nullptr;
+    int32_t* d_indices = nullptr;
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_records), bytes);
+    if (err == hipSuccess && h_indices) {
+        err = hipMalloc(reinterpret_cast<void**>(&d_indices), size_t(count) * 4);
+        if (err == hipSuccess) err = hipMemcpyAsync(d_indices, h_indices, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
+    }
+    if (err == hipSuccess && load) err = hipMemcpyAsync(d_records, h_records, bytes, hipMemcpyHostToDevice, e->stream);
+    int32_t rc = 0;
+    if (err == hipSuccess) rc = load ? pgv_load_envs(e, d_indices, count, d_records, tag) : pgv_save_envs(e, d_indices, count, d_records);
+    if (err == hipSuccess && rc == 0) err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess && rc == 0 && !load) err = hipMemcpy(h_records, d_records, bytes, hipMemcpyDeviceToHost);
+    if (err != hipSuccess || rc != 0) (void)hipStreamSynchronize(e->stream);  // nothing may still be using what is freed next
+    if (d_indices) (void)hipFree(d_indices);
+    if (d_records) (void)hipFree(d_records);
+    if (err != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(err));
+    return rc;
+}
+int32_t pgv_save_envs_host(pgv_env* e, const int32_t* h_indices, int32_t count, void* h_records) {
+    return records_host(e, h_indices, count, h_records, false, 0);
+}
+int32_t pgv_load_envs_host(pgv_env* e, const int32_t* h_indices, int32_t count, const void* h_records, uint64_t tag) {
+    return records_host(e, h_indices, count, const_cast<void*>(h_records), true, tag);
 }
 
 uint8_t* pgv_obs(pgv_env* e) { return e ? e->d_obs : nullptr; }

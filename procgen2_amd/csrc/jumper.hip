@@ -1497,15 +1497,15 @@ class JumperGame final : public PrefetchingGame<Gen> {
     }
     // The state block, in order (state_bytes and bind).
     static void carve(Carve& c, State& s, int n) {
-        c.take(s.shadow, size_t(n) * sizeof(Level));
-        c.take(s.slot, size_t(n) * 4);
-        c.take(s.mt, size_t(n) * kMtWords * 4);
-        c.take(s.tiles, size_t(n) * kTileStride);
-        c.take(s.f, size_t(F_COUNT) * n * 4);
-        c.take(s.i, size_t(I_COUNT) * n * 4);
-        c.take(s.pf, size_t(PF_COUNT) * kPuffSlots * n * 4);
-        c.take(s.spike_cell, size_t(kSpikeSlots) * n * 2);
-        c.take(s.draw, size_t(kSpikeSlots) * n);
+        c.take_env(s.shadow, n, 1, sizeof(Level));
+        c.take_env(s.slot, n, 1, 4);
+        c.take_env(s.mt, n, 1, kMtWords * 4);
+        c.take_env(s.tiles, n, 1, kTileStride);
+        c.take_env(s.f, n, F_COUNT, 4);
+        c.take_env(s.i, n, I_COUNT, 4);
+        c.take_env(s.pf, n, 1, PF_COUNT * kPuffSlots * 4);
+        c.take_env(s.spike_cell, n, 1, kSpikeSlots * 2);
+        c.take_env(s.draw, n, 1, kSpikeSlots);
     }
     size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     // The compass ring (jumper.cpp:485-489: SDL_RenderTextureRotated(circle, NULL, &dst, 0°) at a fixed screen rectangle,
@@ -1602,7 +1602,7 @@ class JumperGame final : public PrefetchingGame<Gen> {
         return (flags & ~PGV_JUMPER_FLOAT_ABS) == 0;
     }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        Carve::bind(carve, d_state, s_, n);
+        Carve::bind(carve, d_state, s_, n, &regions);
         s_.n = n;
         atlas_ = atlas;
     }

@@ -446,17 +446,17 @@ class MazeGame final : public PrefetchingGame<Gen> {
     }
     // The state block, in order (state_bytes and bind).
     static void carve(Carve& c, State& s, int n) {
-        c.take(s.shadow, size_t(n) * sizeof(Level));
-        c.take(s.slot, size_t(n) * 4);
-        c.take(s.mt, size_t(n) * kMtWords * 4);
-        c.take(s.tiles, size_t(n) * kTileStride);
-        c.take(s.f, size_t(F_COUNT) * n * 4);
-        c.take(s.i, size_t(I_COUNT) * n * 4);
-        c.take(s.prepared, sizeof(ComposeHand));
+        c.take_env(s.shadow, n, 1, sizeof(Level));
+        c.take_env(s.slot, n, 1, 4);
+        c.take_env(s.mt, n, 1, kMtWords * 4);
+        c.take_env(s.tiles, n, 1, kTileStride);
+        c.take_env(s.f, n, F_COUNT, 4);
+        c.take_env(s.i, n, I_COUNT, 4);
+        c.take_shared(s.prepared, sizeof(ComposeHand));
     }
     size_t state_bytes(int n) const override { return Carve::size(carve, n); }
     void bind(void* d_state, int n, AtlasView atlas) override {
-        Carve::bind(carve, d_state, s_, n);
+        Carve::bind(carve, d_state, s_, n, &regions);
         s_.n = n;
         atlas_ = atlas;
     }

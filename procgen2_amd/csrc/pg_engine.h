@@ -85,6 +85,19 @@ struct LevelPlan {
     uint32_t* drawn;       // [n]  k: levels built since then
 };
 
+// The per-env regions of a game's state block, as its listing describes them (Carve, below).
+// (word 0 of a record, pg_records.h: here because a game's records_loaded looks at it too)
+constexpr uint32_t kRecordFull = 0x31524750u;  // "PGR1"
+constexpr uint32_t kRecordEmpty = 0u;
+struct EnvRegion {
+    uint8_t* base;
+    uint32_t pieces, piece_bytes;  // F, E
+};
+struct EnvRegions {
+    std::vector<EnvRegion> v;
+    size_t shared_bytes = 0, unlisted_bytes = 0;  // (rounded, as they lie in the block)
+};
+
 class Game {
    public:
     virtual ~Game() = default;
@@ -152,6 +165,26 @@ class Game {
     // blob (chaser: the base layer of every env's frame, pg chaser.hip) is stale from here on.  An error fails the load.
     virtual hipError_t state_loaded(hipStream_t st) { (void)st; return hipSuccess; }
 
+    // Per-env records (include/procgen2_vec.h pgv_save_envs / pgv_load_envs; pg_records.h).  `regions`: the per-env regions
+    // of the state block, left by bind() (Carve, describe mode).  What a game keeps per env OUTSIDE the block:
+    //   * stream_selectors(): the selector bytes of random streams that live in two buffers (bossfight, chaser: mt_sel), or
+    //     nullptr.  A save is preceded by prepare_save (every stream at home), a load zeroes the loaded slots' bytes: at
+    //     home, nothing made ahead.
+    //   * pending_has_parity(): StepIO::pending carries the parity of the step it is about (pg_prefetch.h reset_due_mark)
+    //     instead of 0 / 1.  A record holds "reset due: yes / no"; the load encodes it for the destination's next step.
+    //   * records_loaded(): called behind the scatter, on the env's stream, for whatever else is derived from the state of
+    //     the loaded slots (chaser: their base layers, the due list).  d_indices / count / d_records as given to
+    //     pgv_load_envs; obs_offset: where a record keeps the observation row; next_step: the index of the next step.
+    // The render pre-pass tables, coinrun's hazard hand-off and jumper's `fat` list are rebuilt every frame, and coinrun's
+    // `scratch` rows inside the block are a hand-off within one step (they travel, harmlessly): nothing to put right.
+    EnvRegions regions;
+    virtual uint8_t* stream_selectors() const { return nullptr; }
+    virtual bool pending_has_parity() const { return false; }
+    virtual void records_loaded(hipStream_t st, const int32_t* d_indices, int count, const uint8_t* d_records, size_t record_bytes,
+                                size_t obs_offset, uint32_t next_step, StepIO io) {
+        (void)st; (void)d_indices; (void)count; (void)d_records; (void)record_bytes; (void)obs_offset; (void)next_step; (void)io;
+    }
+
     // Device memory a game's kernels hand results to each other through within one frame (the render pre-pass,
     // pg_prepass.h): allocated by the engine beside the state, never part of a snapshot.
     virtual size_t scratch_bytes(int n) const { (void)n; return 0; }
@@ -178,13 +211,35 @@ constexpr int kDebugChaserSerialMobs = 1 << 25;  // chaser: the enemies one afte
 // its listing once, as a function list(c, s, n) that takes every region into a pointer of s; run without a base it only
 // adds up the bytes (state_bytes, scratch_bytes), with one it also hands out the addresses (bind, bind_scratch), so the
 // size and the binding cannot disagree.  A region of no bytes gets nullptr.
+//
+// A STATE listing also says which regions are per env and what an env's share of one looks like: take_env(p, n, F, E) is
+// a region of n·F·E bytes in which env i owns F pieces of E bytes at  base + f·n·E + i·E  — F = 1 for an env-major block
+// (`mt`, `tiles`, a shadow level), E = 4 or 1 and F = the field count for struct-of-arrays fields; take_shared is a
+// region the whole engine has once (a list, a counter, a prepared table).  Bound with a table (third mode: describe), the
+// listing leaves the per-env regions there: what one env's record is gathered from and scattered to (pg_records.h).  A
+// plain take() in a state listing is counted as unlisted, and pgv_make refuses an engine whose table has any: a region
+// somebody adds later must say what it is, or it would silently drop out of the records.
 struct Carve {
     uint8_t* base = nullptr;
     size_t bytes = 0;
+    EnvRegions* table = nullptr;
     template <class T>
     void take(T*& p, size_t len, size_t align = 256) {
-        p = base && len ? reinterpret_cast<T*>(base + bytes) : nullptr;
-        bytes += (len + align - 1) / align * align;
+        const size_t before = bytes;
+        place(p, len, align);
+        if (table) table->unlisted_bytes += bytes - before;
+    }
+    template <class T>
+    void take_env(T*& p, int n, size_t pieces, size_t piece_bytes) {
+        const size_t at = bytes;
+        place(p, size_t(n) * pieces * piece_bytes, 256);
+        if (table) table->v.push_back({base + at, static_cast<uint32_t>(pieces), static_cast<uint32_t>(piece_bytes)});
+    }
+    template <class T>
+    void take_shared(T*& p, size_t len) {
+        const size_t before = bytes;
+        place(p, len, 256);
+        if (table) table->shared_bytes += bytes - before;
     }
     template <class S>
     static size_t size(void (*list)(Carve&, S&, int), int n) {
@@ -194,9 +249,18 @@ struct Carve {
         return c.bytes;
     }
     template <class S>
-    static void bind(void (*list)(Carve&, S&, int), void* base, S& s, int n) {
+    static void bind(void (*list)(Carve&, S&, int), void* base, S& s, int n, EnvRegions* table = nullptr) {
         Carve c{static_cast<uint8_t*>(base)};
+        if (table) *table = EnvRegions{};
+        c.table = table;
         list(c, s, n);
+    }
+
+   private:
+    template <class T>
+    void place(T*& p, size_t len, size_t align) {
+        p = base && len ? reinterpret_cast<T*>(base + bytes) : nullptr;
+        bytes += (len + align - 1) / align * align;
     }
 };
 

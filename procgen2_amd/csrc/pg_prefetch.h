@@ -308,6 +308,7 @@ class PrefetchingGame : public Game {
     void launch_reset(hipStream_t st, const uint8_t* mask, const int32_t* seeds, StepIO io) override {
         LevelLaunch<G>::reset(st, s_, prefetch(), mask, seeds, io, plan);
     }
+    bool pending_has_parity() const override { return true; }  // (reset_due_mark, above)
     bool launch_pregen(hipStream_t side, bool bulk) override {
         if (!prefetch()) return false;
         LevelLaunch<G>::pregen(side, s_, bulk, plan);

@@ -199,6 +199,72 @@ class ProcgenVecEnv:
         buf = np.ascontiguousarray(buf, np.uint8)
         pglib.check(self.L, self.L.pgv_load_state(self._h, c_void_p(buf.ctypes.data), buf.size), "pgv_load_state")
 
+    # -- per-env records (include/procgen2_vec.h pgv_save_envs / pgv_load_envs) -------------------
+    @property
+    def env_record_bytes(self):
+        return int(self.L.pgv_env_record_bytes(self._h))
+
+    @property
+    def env_record_tag(self):
+        return int(self.L.pgv_env_record_tag(self._h))
+
+    def _indices(self, indices):
+        if indices is None:
+            return None, self.num_envs
+        idx = torch.as_tensor(indices, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        return idx, idx.numel()
+
+    def save_envs(self, indices=None, out=None):
+        """The state records of the envs `indices` (None: all of them, in order; otherwise anything torch.as_tensor takes —
+        an env may appear more than once, an index outside the batch gives an empty record) as an EnvRecords: uint8
+        [K, env_record_bytes] on this env's device plus the configuration's tag.  Gathered on the device with the same
+        stream hand-shake as step() and no host synchronisation.  out: a caller-owned contiguous uint8 tensor of that
+        shape to write into (it becomes the result's `data`)."""
+        idx, count = self._indices(indices)
+        shape = (count, self.env_record_bytes)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()
+              or out.data_ptr() % 16):
+            raise ValueError("out: expected a contiguous, 16-byte aligned %s tensor of shape %s on %s" % (torch.uint8, shape, self.device))
+        if count:
+            self._before()
+            pglib.check(self.L, self.L.pgv_save_envs(self._h, c_void_p(idx.data_ptr()) if idx is not None else None, count,
+                                                     c_void_p(out.data_ptr())), "pgv_save_envs")
+            self._after()
+            self._keep_records = (idx, out)
+        return EnvRecords(out, self.env_record_tag)
+
+    def load_envs(self, records, indices=None):
+        """Put `records` (an EnvRecords of an env of the same configuration on this device) into the slots `indices`
+        (None: record k into slot k; the indices must be distinct, one outside the batch is skipped, and so is an empty
+        record).  From here on each slot goes on as the env it was saved from; obs / reward / done show its rows at the
+        save.  Records of another configuration raise EngineError and change nothing."""
+        data = records.data
+        if data.dtype != torch.uint8 or data.dim() != 2 or data.device != self.device:
+            raise ValueError("load_envs: records.data must be a uint8 [K, record_bytes] tensor on %s" % self.device)
+        if data.shape[1] != self.env_record_bytes and records.tag == self.env_record_tag:
+            raise ValueError("load_envs: records of %d bytes, this env's are %d" % (data.shape[1], self.env_record_bytes))
+        if not data.is_contiguous() or data.data_ptr() % 16:
+            data = data.clone(memory_format=torch.contiguous_format)
+        idx, count = self._indices(indices)
+        if indices is None:
+            count = min(count, data.shape[0])
+        elif count != data.shape[0]:
+            raise ValueError("load_envs: %d indices for %d records" % (count, data.shape[0]))
+        self._before()
+        pglib.check(self.L, self.L.pgv_load_envs(self._h, c_void_p(idx.data_ptr()) if idx is not None else None, count,
+                                                 c_void_p(data.data_ptr()), records.tag), "pgv_load_envs")
+        self._after()
+        self._keep_records = (idx, data)
+
+    def fork(self, src, dst):
+        """Copy env src[k] into slot dst[k] (save, then load): dst's slots go on as copies of the src envs.  An env may be
+        a source many times; the destinations must be distinct.  Returns the records."""
+        records = self.save_envs(src)
+        self.load_envs(records, dst)
+        return records
+
     def sync(self):
         pglib.check(self.L, self.L.pgv_sync(self._h), "pgv_sync")
 
@@ -238,6 +304,26 @@ class ProcgenVecEnv:
                 self._gathers = {}
             plan = self._gathers[key] = RootGather((self.obs, self.reward, self.done), dst=dst, group=group)
         return plan()
+
+
+class EnvRecords:
+    """State records of K envs (ProcgenVecEnv.save_envs): `data`, uint8 [K, record_bytes] on the env's device, and `tag`,
+    the fingerprint of the configuration they belong to.  records[i] — an int, a slice, a tensor of indices or a mask —
+    is the EnvRecords of that selection (a view where torch gives one) and keeps the tag."""
+
+    def __init__(self, data, tag):
+        self.data, self.tag = data, int(tag)
+
+    def __len__(self):
+        return self.data.shape[0]
+
+    def __getitem__(self, item):
+        if isinstance(item, int):
+            item = slice(item, item + 1) if item != -1 else slice(item, None)
+        return EnvRecords(self.data[item], self.tag)
+
+    def clone(self):
+        return EnvRecords(self.data.clone(), self.tag)
 
 
 def step_many_synthetic(envs, steps, run_seed=0):
