@@ -848,6 +848,29 @@ __global__ void __launch_bounds__(64, PG_BOSSFIGHT_WAVES) logic_kernel(State s, 
     }
 }
 
+// The draw list of bossfight.cpp:401-424, each kind of draw stated once, for render_full_kernel, setup_kernel and
+// frame_draws: which texture, then the draw call given that texture's descriptor (x: first texel, y: width, z: height).
+// The backdrop fills the camera (bossfight.cpp:416-419).
+PG_D BgDraw space_draw(const int4& d, const Camera& cam) {
+    return BgDraw{d, -cam.sw / cam.scale * 0.5f, -cam.sh / cam.scale * 0.5f, 1.0f / d.z * cam.sh / cam.scale};
+}
+// Ships, shield, explosions and bullets are placed by their centre (cx, cy) in world units, at these sizes (the scale
+// of the draw call); a boss bullet is rotated (the wave paths carry its angle as 16.16 sine and cosine from boss_fire
+// and pass any `rot`, frame_draws the angle itself).
+constexpr float kBossSize = 0.25f, kShieldAlpha = 0.7f, kBoomSize = 0.3f, kAgentSize = 0.05f, kBossShotSize = 0.1f;
+PG_D DrawCall centred_draw(int tex, float cx, float cy, float size, float alpha, float rot, const int4& d) {
+    return DrawCall{true, false, false, tex, cx * kUnitPx - size * d.y * 0.5f, cy * kUnitPx - size * d.z * 0.5f, size, alpha, rot};
+}
+// a bullet's frame: -1 none (not drawn), 0 the laser of its side's skin, then its explosion; an explosion's: -1 none
+PG_D int shot_tex(float frame, int laser) { return (frame == 0.0f) ? kTexLaser + laser : kTexBoom + static_cast<int>(frame - 1.0f); }
+PG_D int boom_tex(float frame) { return kTexBoom + static_cast<int>(frame); }
+PG_D float shot_rotation(float rot) { return static_cast<float>(rot + kPi * 0.5f); }  // common_systems.cpp:392-450
+// the barriers, positive-z sprites (common_systems.cpp:22-48): offset (-0.15,-0.15), scale 0.3 (bossfight.cpp:479)
+PG_D DrawCall rock_draw(int tex, float x, float y, const int4& d) {
+    const float scale = 1.0f * 0.3f;
+    return DrawCall{true, false, false, tex, (x + -0.15f) * kUnitPx, (y + -0.15f) * kUnitPx, scale * kUnitPx / d.y, 1.0f, 0.0f};
+}
+
 // render_game(true) (bossfight.cpp:401-424): one workgroup of two wavefronts per env (pg_render.h).  The complete frame,
 // set-up included: every frame before the pre-pass existed; still the draw-list replay (flags bit 0), kDebugNoPrepass and
 // the timing experiments.
@@ -871,26 +894,19 @@ __global__ void __launch_bounds__(128, 4) render_full_kernel(State s, AtlasView 
     const float bx = SF(s, F_BX, env), by = SF(s, F_BY, env), ax = SF(s, F_AX, env), ay = SF(s, F_AY, env);
     Blit mine;
 
-    int4 bg_d;  // the background draw, bossfight.cpp:416-419: texture, world position, scale — each wave resolves the axis it needs (pg_render.h BgAxis)
-    float bg_px, bg_py, bg_sc;
-    {
-        const int4 d = descs.uniform(kTexSpace + backdrop);
-        bg_d = d;
-        bg_px = -kCamSize / kCamScale * 0.5f;
-        bg_py = -kCamSize / kCamScale * 0.5f;
-        bg_sc = 1.0f / d.z * kCamSize / kCamScale;
-    }
+    // the background draw, bossfight.cpp:416-419 — each wave resolves the axis it needs (pg_render.h BgAxis)
+    const BgDraw bg = space_draw(descs.uniform(kTexSpace + backdrop), cam);
     bool composed = false;
     if (PG_ABL(flags, 0x10000)) {  // (timing experiment, -DPG_ABLATE builds only: no background)
         wave_clear(fb, lane, half, halves);
         composed = true;
     } else if (!(flags & 1)) {  // no tile layer in this game: the background over black (pg_render.h)
-        compose_background(fb, atlas, bg_axis(cam, bg_d, bg_px, bg_py, bg_sc, half), lane, half, halves);
+        compose_background(fb, atlas, bg_axis(cam, bg.desc, bg.px, bg.py, bg.scale, half), lane, half, halves);
         composed = true;
     }
     if (!composed) {
         wave_clear(fb, lane, half, halves);
-        const bool has_bg = resolve_draw(cam, bg_d.y, bg_d.z, bg_d.x, bg_px, bg_py, bg_sc, 1.0f, false, false, mine);
+        const bool has_bg = resolve_draw(cam, bg.desc.y, bg.desc.z, bg.desc.x, bg.px, bg.py, bg.scale, 1.0f, false, false, mine);
         wave_replay(fb, atlas, mine, has_bg ? 1ull : 0ull, lane, half, halves);
     }
 
@@ -905,7 +921,7 @@ __global__ void __launch_bounds__(128, 4) render_full_kernel(State s, AtlasView 
             const float frame = BS(s, S_FRAME, k, env);
             if (frame != -1.0f) {
                 has = true;
-                if (frame != 0.0f) want_tex = kTexBoom + static_cast<int>(frame - 1.0f);
+                want_tex = shot_tex(frame, b_laser);
                 px = BS(s, S_X, k, env);
                 py = BS(s, S_Y, k, env);
                 rot_sn = __float_as_int(BS(s, S_SN, k, env));
@@ -914,9 +930,8 @@ __global__ void __launch_bounds__(128, 4) render_full_kernel(State s, AtlasView 
         }
         const int4 d = descs.at(want_tex);
         if (has) {
-            const float size = 0.1f;
-            has = resolve_rotated_at(cam, d.y, d.z, d.x, px * kUnitPx - size * d.y * 0.5f, py * kUnitPx - size * d.z * 0.5f,
-                                     rot_sn, rot_cs, size, 1.0f, mine);
+            const DrawCall c = centred_draw(want_tex, px, py, kBossShotSize, 1.0f, 0.0f, d);
+            has = resolve_rotated_at(cam, d.y, d.z, d.x, c.wx, c.wy, rot_sn, rot_cs, c.scale, 1.0f, mine);
         }
         if (PG_ABL(flags, 0x20000)) has = false;  // (timing experiment: no boss bullets)
         wave_replay_rows<4, true>(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
@@ -935,23 +950,23 @@ __global__ void __launch_bounds__(128, 4) render_full_kernel(State s, AtlasView 
             want_tex = kTexBoss + b_ship;
             px = bx;
             py = by;
-            size = 0.25f;
+            size = kBossSize;
         } else if (lane == 1) {
             has = (phase % 2 == 0);
             want_tex = kTexShield;
             px = bx;
             py = by;
-            size = 0.25f;
-            alpha = 0.7f;
+            size = kBossSize;
+            alpha = kShieldAlpha;
         } else if (lane < first_rock) {
             const int k = (kBooms + x_next - 1 - (lane - first_boom)) % kBooms;
             const float frame = BM(s, 2, k, env);
             if (frame != -1.0f) {
                 has = true;
-                want_tex = kTexBoom + static_cast<int>(frame);
+                want_tex = boom_tex(frame);
                 px = BM(s, 0, k, env);
                 py = BM(s, 1, k, env);
-                size = 0.3f;
+                size = kBoomSize;
             }
         } else if (lane < first_shot) {
             const int r = n_rocks - 1 - (lane - first_rock);  // sprite set order: newest barrier first
@@ -965,34 +980,22 @@ __global__ void __launch_bounds__(128, 4) render_full_kernel(State s, AtlasView 
             const float frame = AS(s, S_FRAME, k, env);
             if (frame != -1.0f) {
                 has = true;
-                want_tex = (frame == 0.0f) ? kTexLaser + a_laser : kTexBoom + static_cast<int>(frame - 1.0f);
+                want_tex = shot_tex(frame, a_laser);
                 px = AS(s, S_X, k, env);
                 py = AS(s, S_Y, k, env);
-                size = 0.05f;
+                size = kAgentSize;
             }
         } else if (lane == agent_lane) {
             has = true;
             want_tex = kTexPlayer + a_ship;
             px = ax;
             py = ay;
-            size = 0.05f;
+            size = kAgentSize;
         }
         const int4 d = descs.at(want_tex);
         if (has) {  // the two kinds of draw differ in their parameters only: pick per lane, resolve once
-            float wx, wy, sc, al;
-            if (sprite) {  // common_systems.cpp:22-48: offset (-0.15,-0.15), scale 0.3 (bossfight.cpp:479)
-                const float scale = 1.0f * 0.3f;
-                wx = (px + -0.15f) * kUnitPx;
-                wy = (py + -0.15f) * kUnitPx;
-                sc = scale * kUnitPx / d.y;
-                al = 1.0f;
-            } else {
-                wx = px * kUnitPx - size * d.y * 0.5f;
-                wy = py * kUnitPx - size * d.z * 0.5f;
-                sc = size;
-                al = alpha;
-            }
-            has = resolve_draw(cam, d.y, d.z, d.x, wx, wy, sc, al, false, false, mine);
+            const DrawCall c = sprite ? rock_draw(want_tex, px, py, d) : centred_draw(want_tex, px, py, size, alpha, 0.0f, d);
+            has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, c.alpha, false, false, mine);
         }
         if (PG_ABL(flags, 0x40000)) has = has && lane >= 2;    // (timing experiments: no boss ship and shield …
         if (PG_ABL(flags, 0x80000)) has = has && lane < 2;     //  … nothing but them)
@@ -1032,8 +1035,8 @@ __global__ void __launch_bounds__(128) backdrop_kernel(State s, AtlasView atlas)
     const int backdrop = blockIdx.x, lane = threadIdx.x & 63, axis = threadIdx.x >> 6;
     const Camera cam{0.0f, 0.0f, kCamSize, kCamSize, kCamScale};
     const int4 d = atlas.desc[kTexSpace + backdrop];
-    const float pos = -kCamSize / kCamScale * 0.5f, scale = 1.0f / d.z * kCamSize / kCamScale;
-    const uint32_t mine = bg_offset(bg_axis(cam, d, pos, pos, scale, axis), lane, axis);
+    const BgDraw bg = space_draw(d, cam);
+    const uint32_t mine = bg_offset(bg_axis(cam, d, bg.px, bg.py, bg.scale, axis), lane, axis);
     s.prep.backdrops[backdrop * 128 + axis * 64 + lane] = mine;
     __shared__ uint32_t offsets[128];
     __shared__ alignas(16) uint32_t fb[kFbWords];
@@ -1104,7 +1107,8 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             const int e = is_b ? eb : ea, env = env0 + e, slot = is_b ? q - cnt_a : q;
             const uint32_t* pe = S.env[e];
             bool has = false;
-            int want_tex = kTexLaser + static_cast<int>((pe[PE_SKINS] >> 12) & 15u);
+            const int b_laser = static_cast<int>((pe[PE_SKINS] >> 12) & 15u);
+            int want_tex = kTexLaser + b_laser;
             float px = 0.0f, py = 0.0f;
             int rot_sn = 0, rot_cs = 0;  // (boss_fire worked them out)
             if (valid) {
@@ -1112,7 +1116,7 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
                 const float frame = BS(s, S_FRAME, k, env);
                 if (frame != -1.0f) {
                     has = true;
-                    if (frame != 0.0f) want_tex = kTexBoom + static_cast<int>(frame - 1.0f);
+                    want_tex = shot_tex(frame, b_laser);
                     px = BS(s, S_X, k, env);
                     py = BS(s, S_Y, k, env);
                     rot_sn = __float_as_int(BS(s, S_SN, k, env));
@@ -1123,9 +1127,8 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             RotBox box{0, 0, 0, 0};
             if (has) {
                 const int4 d = S.desc[want_tex];
-                const float size = 0.1f;
-                has = resolve_rotated_at(cam, d.y, d.z, d.x, px * kUnitPx - size * d.y * 0.5f, py * kUnitPx - size * d.z * 0.5f,
-                                         rot_sn, rot_cs, size, 1.0f, b);
+                const DrawCall c = centred_draw(want_tex, px, py, kBossShotSize, 1.0f, 0.0f, d);
+                has = resolve_rotated_at(cam, d.y, d.z, d.x, c.wx, c.wy, rot_sn, rot_cs, c.scale, 1.0f, b);
                 if (has) {
                     // the bullet's stamp, and with it the part of the bullet that can show at all: a laser is a few opaque
                     // texels in a transparent rim, and the box is that of the core (pg_stamps.h rot_box_core) — 3 × 3 or
@@ -1191,23 +1194,23 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
                 want_tex = kTexBoss + b_ship;
                 px = bx;
                 py = by;
-                size = 0.25f;
+                size = kBossSize;
             } else if (slot == 1) {
                 has = (static_cast<int>(pe[PE_PHASE]) % 2 == 0);
                 want_tex = kTexShield;
                 px = bx;
                 py = by;
-                size = 0.25f;
-                alpha = 0.7f;
+                size = kBossSize;
+                alpha = kShieldAlpha;
             } else if (slot < first_rock) {
                 const int k = (kBooms + static_cast<int>(pe[PE_X_NEXT]) - 1 - (slot - first_boom)) % kBooms;
                 const float frame = BM(s, 2, k, env);
                 if (frame != -1.0f) {
                     has = true;
-                    want_tex = kTexBoom + static_cast<int>(frame);
+                    want_tex = boom_tex(frame);
                     px = BM(s, 0, k, env);
                     py = BM(s, 1, k, env);
-                    size = 0.3f;
+                    size = kBoomSize;
                 }
             } else if (slot < first_shot) {
                 const int r = n_rocks - 1 - (slot - first_rock);  // sprite set order: newest barrier first
@@ -1221,32 +1224,22 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
                 const float frame = AS(s, S_FRAME, k, env);
                 if (frame != -1.0f) {
                     has = true;
-                    want_tex = (frame == 0.0f) ? kTexLaser + a_laser : kTexBoom + static_cast<int>(frame - 1.0f);
+                    want_tex = shot_tex(frame, a_laser);
                     px = AS(s, S_X, k, env);
                     py = AS(s, S_Y, k, env);
-                    size = 0.05f;
+                    size = kAgentSize;
                 }
             } else {
                 has = true;
                 want_tex = kTexPlayer + a_ship;
                 px = __uint_as_float(pe[PE_AX]);
                 py = __uint_as_float(pe[PE_AY]);
-                size = 0.05f;
+                size = kAgentSize;
             }
-            PrepDraw p{has, false, false, want_tex, 0.0f, 0.0f, 1.0f, 1.0f};
+            DrawCall p = kNoDraw;
             if (has) {  // the two kinds of draw differ in their parameters only
                 const int4 d = S.desc[want_tex];
-                if (sprite) {  // common_systems.cpp:22-48: offset (-0.15,-0.15), scale 0.3 (bossfight.cpp:479)
-                    const float scale = 1.0f * 0.3f;
-                    p.wx = (px + -0.15f) * kUnitPx;
-                    p.wy = (py + -0.15f) * kUnitPx;
-                    p.scale = scale * kUnitPx / d.y;
-                } else {
-                    p.wx = px * kUnitPx - size * d.y * 0.5f;
-                    p.wy = py * kUnitPx - size * d.z * 0.5f;
-                    p.scale = size;
-                    p.alpha = alpha;
-                }
+                p = sprite ? rock_draw(want_tex, px, py, d) : centred_draw(want_tex, px, py, size, alpha, 0.0f, d);
             }
             prep_draws_pass(Q, st, S.desc, cam, cam, draws_a, draws_b, valid, is_b, p, lane, nullptr, S.stamp);
         }
@@ -1354,63 +1347,38 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     const int n_rocks = SI(s, I_NROCKS, env), phase = SI(s, I_PHASE, env);
     const float bx = SF(s, F_BX, env), by = SF(s, F_BY, env), ax = SF(s, F_AX, env), ay = SF(s, F_AY, env);
     P.clear();
-    {
-        const int tex = kTexSpace + backdrop;
-        P.draw(tex, -fw / sc * 0.5f, -fh / sc * 0.5f, 1.0f / P.desc(tex).z * fh / sc);
-    }
+    const BgDraw bg = space_draw(P.desc(kTexSpace + backdrop), P.cam);
+    P.draw(kTexSpace + backdrop, bg.px, bg.py, bg.scale);
     for (int i = 0; i < b_count; i++) {
         const int k = (kBossShots + b_next - 1 - i) % kBossShots;
         const float frame = BS(s, S_FRAME, k, env);
         if (frame == -1.0f) continue;
-        const int tex = (frame == 0.0f) ? kTexLaser + b_laser : kTexBoom + static_cast<int>(frame - 1.0f);
-        const int4 d = P.desc(tex);
-        const float size = 0.1f;
-        P.draw_rotated(tex, BS(s, S_X, k, env) * kUnitPx - size * d.y * 0.5f, BS(s, S_Y, k, env) * kUnitPx - size * d.z * 0.5f,
-                       static_cast<float>(BS(s, S_ROT, k, env) + kPi * 0.5f), size);
+        const int tex = shot_tex(frame, b_laser);
+        P.draw_rotated(centred_draw(tex, BS(s, S_X, k, env), BS(s, S_Y, k, env), kBossShotSize, 1.0f, shot_rotation(BS(s, S_ROT, k, env)), P.desc(tex)));
     }
-    {
-        const int tex = kTexBoss + b_ship;
-        const int4 d = P.desc(tex);
-        const float size = 0.25f;
-        P.draw(tex, bx * kUnitPx - size * d.y * 0.5f, by * kUnitPx - size * d.z * 0.5f, size);
-    }
-    if (phase % 2 == 0) {
-        const int4 d = P.desc(kTexShield);
-        const float size = 0.25f;
-        P.draw(kTexShield, bx * kUnitPx - size * d.y * 0.5f, by * kUnitPx - size * d.z * 0.5f, size, 0.7f);
-    }
+    P.draw(centred_draw(kTexBoss + b_ship, bx, by, kBossSize, 1.0f, 0.0f, P.desc(kTexBoss + b_ship)));
+    if (phase % 2 == 0) P.draw(centred_draw(kTexShield, bx, by, kBossSize, kShieldAlpha, 0.0f, P.desc(kTexShield)));
     for (int i = 0; i < x_count; i++) {
         const int k = (kBooms + x_next - 1 - i) % kBooms;
         const float frame = BM(s, 2, k, env);
         if (frame == -1.0f) continue;
-        const int tex = kTexBoom + static_cast<int>(frame);
-        const int4 d = P.desc(tex);
-        const float size = 0.3f;
-        P.draw(tex, BM(s, 0, k, env) * kUnitPx - size * d.y * 0.5f, BM(s, 1, k, env) * kUnitPx - size * d.z * 0.5f, size);
+        const int tex = boom_tex(frame);
+        P.draw(centred_draw(tex, BM(s, 0, k, env), BM(s, 1, k, env), kBoomSize, 1.0f, 0.0f, P.desc(tex)));
     }
     if (sflags & kFlagListed)
         for (int k = 0; k < n_rocks; k++) {
             const int r = n_rocks - 1 - k;  // sprite set order: newest barrier first
             const int tex = kTexRock + static_cast<int>(RK(s, 2, r, env));
-            const float scale = 1.0f * 0.3f;
-            P.draw(tex, (RK(s, 0, r, env) + -0.15f) * kUnitPx, (RK(s, 1, r, env) + -0.15f) * kUnitPx,
-                   scale * kUnitPx / P.desc(tex).y);
+            P.draw(rock_draw(tex, RK(s, 0, r, env), RK(s, 1, r, env), P.desc(tex)));
         }
     for (int i = 0; i < a_count; i++) {
         const int k = (kAgentShots + a_next - 1 - i) % kAgentShots;
         const float frame = AS(s, S_FRAME, k, env);
         if (frame == -1.0f) continue;
-        const int tex = (frame == 0.0f) ? kTexLaser + a_laser : kTexBoom + static_cast<int>(frame - 1.0f);
-        const int4 d = P.desc(tex);
-        const float size = 0.05f;
-        P.draw(tex, AS(s, S_X, k, env) * kUnitPx - size * d.y * 0.5f, AS(s, S_Y, k, env) * kUnitPx - size * d.z * 0.5f, size);
+        const int tex = shot_tex(frame, a_laser);
+        P.draw(centred_draw(tex, AS(s, S_X, k, env), AS(s, S_Y, k, env), kAgentSize, 1.0f, 0.0f, P.desc(tex)));
     }
-    {
-        const int tex = kTexPlayer + a_ship;
-        const int4 d = P.desc(tex);
-        const float size = 0.05f;
-        P.draw(tex, ax * kUnitPx - size * d.y * 0.5f, ay * kUnitPx - size * d.z * 0.5f, size);
-    }
+    P.draw(centred_draw(kTexPlayer + a_ship, ax, ay, kAgentSize, 1.0f, 0.0f, P.desc(kTexPlayer + a_ship)));
 }
 
 // One env, one workgroup, a W×H target in global memory: pgv_render_frame.

@@ -739,6 +739,51 @@ __global__ void __launch_bounds__(64, PG_CAVEFLYER_WAVES) logic_kernel(State s, 
 constexpr int kGrid = 16;  // 64 px / 8 px per tile → at most 10 columns/rows in view
 constexpr int kSpan = 16;  // a tile covers up to ten pixels per axis (pg_render.h compose_spans MAXSPAN)
 
+// The draw list of caveflyer.cpp:413-440, each kind of draw stated once, for render_full, setup_kernel, render_kernel and
+// frame_draws: the draw call given its texture's descriptor (x: first texel, y: width, z: height).  The rotated kinds
+// are placed by their centre (cx, cy) in world units at `size`; the wave paths carry the angle as 16.16 sine and cosine
+// from the logic kernel (store_rotation) and pass any `rot`, frame_draws the angle itself.
+PG_D DrawCall centred_draw(int tex, float cx, float cy, float size, float alpha, float rot, const int4& d) {
+    return DrawCall{true, false, false, tex, cx * kUnitPx - size * d.y * 0.5f, cy * kUnitPx - size * d.z * 0.5f, size, alpha, rot};
+}
+// System_Particles::render (common_systems.cpp:374-397): rotated, fading, drifting; d = kTexPuff's descriptor
+PG_D DrawCall puff_draw(float life, float x, float y, float dx, float dy, float rot, const int4& d) {
+    if (!(life > 0.0f)) return kNoDraw;
+    const float lifespan = 3.0f;
+    const float life_ratio = (lifespan - life) / lifespan;
+    const float alpha = 0.5f * (1.0f - life_ratio);
+    const float scale = 1.0f * (0.4f * life_ratio + 0.6f);
+    const float shift = life_ratio * 2.0f;
+    return centred_draw(kTexPuff, x + dx * shift, y + dy * shift, scale * kUnitPx / d.y, alpha, rot, d);
+}
+// the positive-z sprites (:26-48): goal, meteors, targets, enemies
+PG_D DrawCall sprite_draw(int kind, float x, float y, const int4& d) {
+    const float scale = 1.0f * 0.8f;
+    return DrawCall{true, false, false, kTexKind + kind, (x + -0.4f) * kUnitPx, (y + -0.4f) * kUnitPx, scale * kUnitPx / d.y, 1.0f, 0.0f};
+}
+// System_Agent::render (:291-327): a bullet (frame -1: none; 0: the laser; then the explosion), the ship
+PG_D int shot_tex(float frame) { return (frame == 0.0f) ? kTexLaser : kTexBoom + static_cast<int>(frame - 1.0f); }
+PG_D DrawCall shot_draw(float frame, int tex, float x, float y, float rot, const int4& d) {
+    if (frame == -1.0f) return kNoDraw;
+    return centred_draw(tex, x, y, 0.1f, 1.0f, static_cast<float>(rot + kPi * 0.5f), d);
+}
+PG_D DrawCall ship_draw(float x, float y, float rot, const int4& d) {
+    return centred_draw(kTexShip, x, y, 0.15f, 1.0f, static_cast<float>(rot + kPi * 0.5f), d);
+}
+// One lane of the wave paths' single pass — particles, sprites, bullets newest first, the ship: which texture …
+PG_D int lane_tex(bool is_puff, bool is_spr, int spr_kind, int shot_i, int s_count, float shot_frame) {
+    if (is_puff) return kTexPuff;
+    if (is_spr) return kTexKind + spr_kind;
+    return (shot_i >= 0 && shot_i < s_count && shot_frame != -1.0f) ? shot_tex(shot_frame) : kTexShip;
+}
+// … and its rotated draw, if it has one (a sprite lane's goes through resolve_draw, or comes resolved from the pre-pass)
+PG_D DrawCall lane_rotated(bool is_puff, bool is_spr, float life, float x, float y, float dx, float dy, int shot_i, int s_count,
+                           float shot_frame, float shot_x, float shot_y, int tex, const int4& d) {
+    if (is_puff) return puff_draw(life, x, y, dx, dy, 0.0f, d);
+    if (is_spr || shot_i < 0 || shot_i > s_count) return kNoDraw;
+    return shot_i == s_count ? ship_draw(shot_x, shot_y, 0.0f, d) : shot_draw(shot_frame, tex, shot_x, shot_y, 0.0f, d);
+}
+
 // The complete frame of one env by its workgroup, set-up included: the frames the pre-pass marks fat, the draw-list
 // replay (flags bit 0) and kDebugNoPrepass.
 PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, int flags, int env, uint32_t* fb,
@@ -796,28 +841,14 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     }
 
     int bg_soft = 0;  // the backdrop has texels that are not opaque (descriptor .w)
-    int4 bg_d;  // the background draw, caveflyer.cpp:427-432: texture, world position, scale — each wave resolves the axis it needs (pg_render.h BgAxis)
-    float bg_px, bg_py, bg_sc;
-    {
-        const int4 d = descs.uniform(kTexSpace + SI(s, I_BACKDROP, env));
-        bg_soft = d.w;
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        bg_d = d;
-        bg_px = -SF(s, F_BGSHIFT, env) * extra;
-        bg_py = 0.0f;
-        bg_sc = 64.0f * kUnitPx / d.z;
-    }
-    // tile window (tilemap.cpp:280-289)
-    const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
-    const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-    const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-    const int x0 = static_cast<int>(floorf(vx)), y0 = static_cast<int>(floorf(vy));
-    const int x1 = static_cast<int>(ceilf(vx + vw)), y1 = static_cast<int>(ceilf(vy + vh));
-    const int cols = x1 - x0 + 1, rows = y1 - y0 + 1, cells = cols * rows;
+    // the background draw, caveflyer.cpp:427-432 — each wave resolves the axis it needs (pg_render.h BgAxis)
+    const BgDraw bg_draw = backdrop_draw(descs.uniform(kTexSpace + SI(s, I_BACKDROP, env)), SF(s, F_BGSHIFT, env));
+    bg_soft = bg_draw.desc.w;
+    const TileWindow win = tile_window(cam);  // tilemap.cpp:280-289
+    const int x0 = win.x0, y0 = win.y0;
+    const int cols = win.x1 - x0 + 1, rows = win.y1 - y0 + 1, cells = cols * rows;
     const int4 wall_d = descs.uniform(kTexWall);
 
-    const BgDraw bg_draw{bg_d, bg_px, bg_py, bg_sc};
     BgAxis bga{};  // this wave's axis of it (wave 0: x, wave 1: y), resolved along with the tile spans
     bool composed = false;
     if (!(flags & 1) && cols <= kGrid && rows <= kGrid) {
@@ -835,7 +866,7 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     }
     if (!composed) {  // draw-list replay (tilemap.cpp:291-302)
         wave_clear(fb, lane, half, halves);
-        const bool has_bg = resolve_draw(cam, bg_d.y, bg_d.z, bg_d.x, bg_px, bg_py, bg_sc, 1.0f, false, false, mine);
+        const bool has_bg = resolve_draw(cam, bg_draw.desc.y, bg_draw.desc.z, bg_draw.desc.x, bg_draw.px, bg_draw.py, bg_draw.scale, 1.0f, false, false, mine);
         wave_replay(fb, atlas, mine, has_bg ? 1ull : 0ull, lane, half, halves);
         for (int base = 0; base < cells; base += 64) {
             const int cell = base + lane;
@@ -857,68 +888,33 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
         // per lane in that order.  The rotated kinds share one trip through resolve_rotated (its sine and cosine are
         // the expensive part), the sprites take resolve_draw.
         const bool is_puff = lane < kPuffs, is_spr = lane >= spr_lane0 && lane < shot_lane0;
-        int want_tex = kTexShip;
-        bool go = shot_i == s_count;  // the ship
-        float size = 0.15f, alpha = 1.0f, rx = 0.0f, ry = 0.0f;
-        if (is_puff) {
-            want_tex = kTexPuff;
-            go = puff_life > 0.0f;
-        } else if (is_spr) {
-            want_tex = kTexKind + spr_kind;
-            go = false;
-        } else if (shot_i >= 0 && shot_i < s_count && shot_frame != -1.0f) {
-            go = true;
-            size = 0.1f;
-            want_tex = (shot_frame == 0.0f) ? kTexLaser : kTexBoom + static_cast<int>(shot_frame - 1.0f);
-        }
+        const int want_tex = lane_tex(is_puff, is_spr, spr_kind, shot_i, s_count, shot_frame);
         const int4 d = descs.at(want_tex);
-        if (is_puff) {
-            const float lifespan = 3.0f;
-            const float life_ratio = (lifespan - puff_life) / lifespan;
-            alpha = 0.5f * (1.0f - life_ratio);
-            const float scale = 1.0f * (0.4f * life_ratio + 0.6f);
-            const float shift = life_ratio * 2.0f;
-            size = scale * kUnitPx / d.y;
-            rx = (puff_x + puff_dx * shift) * kUnitPx - size * d.y * 0.5f;
-            ry = (puff_y + puff_dy * shift) * kUnitPx - size * d.z * 0.5f;
-        } else {
-            rx = shot_x * kUnitPx - size * d.y * 0.5f;
-            ry = shot_y * kUnitPx - size * d.z * 0.5f;
-        }
+        const DrawCall c = lane_rotated(is_puff, is_spr, puff_life, puff_x, puff_y, puff_dx, puff_dy, shot_i, s_count, shot_frame,
+                                        shot_x, shot_y, want_tex, d);
         bool has = false;
-        if (go)
-            has = resolve_rotated_at(cam, d.y, d.z, d.x, rx, ry, is_puff ? puff_sn : shot_sn, is_puff ? puff_cs : shot_cs, size,
-                                     alpha, mine);
+        if (c.go)
+            has = resolve_rotated_at(cam, d.y, d.z, d.x, c.wx, c.wy, is_puff ? puff_sn : shot_sn, is_puff ? puff_cs : shot_cs, c.scale,
+                                     c.alpha, mine);
         if (is_spr) {
-            const float scale = 1.0f * 0.8f;
-            has = resolve_draw(cam, d.y, d.z, d.x, (spr_x + -0.4f) * kUnitPx, (spr_y + -0.4f) * kUnitPx,
-                               scale * kUnitPx / d.y, 1.0f, false, false, mine);
+            const DrawCall q = sprite_draw(spr_kind, spr_x, spr_y, d);
+            has = resolve_draw(cam, d.y, d.z, d.x, q.wx, q.wy, q.scale, 1.0f, false, false, mine);
         }
         wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
     } else {
         {  // System_Particles::render (common_systems.cpp:374-397): rotated, fading
             const int4 d = descs.uniform(kTexPuff);
+            const DrawCall c = lane < kPuffs ? puff_draw(puff_life, puff_x, puff_y, puff_dx, puff_dy, 0.0f, d) : kNoDraw;
             bool has = false;
-            if (lane < kPuffs && puff_life > 0.0f) {
-                const float lifespan = 3.0f;
-                const float life_ratio = (lifespan - puff_life) / lifespan;
-                const float alpha = 0.5f * (1.0f - life_ratio);
-                const float scale = 1.0f * (0.4f * life_ratio + 0.6f);
-                const float shift = life_ratio * 2.0f;
-                const float size = scale * kUnitPx / d.y;
-                has = resolve_rotated_at(cam, d.y, d.z, d.x, (puff_x + puff_dx * shift) * kUnitPx - size * d.y * 0.5f,
-                                         (puff_y + puff_dy * shift) * kUnitPx - size * d.z * 0.5f, puff_sn, puff_cs, size, alpha,
-                                         mine);
-            }
+            if (c.go) has = resolve_rotated_at(cam, d.y, d.z, d.x, c.wx, c.wy, puff_sn, puff_cs, c.scale, c.alpha, mine);
             wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
         }
         {  // positive-z sprites (common_systems.cpp:26-48): goal, meteors, targets, enemies
             const int4 d = descs.at(kTexKind + spr_kind);
             bool has = false;
             if (lane < n_draw) {
-                const float scale = 1.0f * 0.8f;
-                has = resolve_draw(cam, d.y, d.z, d.x, (spr_x + -0.4f) * kUnitPx, (spr_y + -0.4f) * kUnitPx,
-                                   scale * kUnitPx / d.y, 1.0f, false, false, mine);
+                const DrawCall c = sprite_draw(spr_kind, spr_x, spr_y, d);
+                has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, false, false, mine);
             }
             wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
             if (kMaxEnt > 64 && n_draw > 64) {  // memory_mode: up to 76 sprites, the rest in a second pass
@@ -934,26 +930,18 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
                 const int4 d2 = descs.at(kTexKind + kind2);
                 bool has2 = false;
                 if (k < n_draw) {
-                    const float scale = 1.0f * 0.8f;
-                    has2 = resolve_draw(cam, d2.y, d2.z, d2.x, (x2 + -0.4f) * kUnitPx, (y2 + -0.4f) * kUnitPx,
-                                        scale * kUnitPx / d2.y, 1.0f, false, false, mine);
+                    const DrawCall c = sprite_draw(kind2, x2, y2, d2);
+                    has2 = resolve_draw(cam, d2.y, d2.z, d2.x, c.wx, c.wy, c.scale, 1.0f, false, false, mine);
                 }
                 wave_replay_rows(fb, atlas, mine, __ballot(has2), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
             }
         }
         {  // System_Agent::render (common_systems.cpp:291-327): bullets newest first, then the ship
-            int want_tex = kTexShip;
-            bool has = lane == s_count;
-            float size = 0.15f;
-            if (lane < s_count && shot_frame != -1.0f) {
-                has = true;
-                size = 0.1f;
-                want_tex = (shot_frame == 0.0f) ? kTexLaser : kTexBoom + static_cast<int>(shot_frame - 1.0f);
-            }
+            const int want_tex = lane_tex(false, false, 0, lane, s_count, shot_frame);
             const int4 d = descs.at(want_tex);
-            if (has)
-                has = resolve_rotated_at(cam, d.y, d.z, d.x, shot_x * kUnitPx - size * d.y * 0.5f,
-                                         shot_y * kUnitPx - size * d.z * 0.5f, shot_sn, shot_cs, size, 1.0f, mine);
+            const DrawCall c = lane_rotated(false, false, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, lane, s_count, shot_frame, shot_x, shot_y, want_tex, d);
+            bool has = false;
+            if (c.go) has = resolve_rotated_at(cam, d.y, d.z, d.x, c.wx, c.wy, shot_sn, shot_cs, c.scale, 1.0f, mine);
             wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
         }
     }
@@ -1036,16 +1024,12 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
         if (active) {
             v.cam = cam;
             const int4 d = S.desc[kTexSpace + backdrop];
-            const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-            const float extra = aspect - 1.0f;
-            v.bg = BgDraw{d, -bgshift * extra, 0.0f, 64.0f * kUnitPx / d.z};  // caveflyer.cpp:427-432
-            const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;  // tilemap.cpp:280-289
-            const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-            const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-            v.x0 = static_cast<int>(floorf(vx));
-            v.y0 = static_cast<int>(floorf(vy));
-            v.cols = static_cast<int>(ceilf(vx + vw)) - v.x0 + 1;
-            v.rows = static_cast<int>(ceilf(vy + vh)) - v.y0 + 1;
+            v.bg = backdrop_draw(d, bgshift);  // caveflyer.cpp:427-432
+            const TileWindow win = tile_window(cam);  // tilemap.cpp:280-289
+            v.x0 = win.x0;
+            v.y0 = win.y0;
+            v.cols = win.x1 - win.x0 + 1;
+            v.rows = win.y1 - win.y0 + 1;
             const int4 wall_d = S.desc[kTexWall];
             v.tw = wall_d.y;
             v.th = wall_d.z;
@@ -1112,17 +1096,12 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             const int e = is_b ? eb : ea, env = env0 + e;
             const int slot = is_b ? q - cnt_a : q;
             const bool valid = q < cnt_a + cnt_b;
-            PrepDraw p{false, false, false, kTexKind, 0.0f, 0.0f, 1.0f, 1.0f};
+            DrawCall p = kNoDraw;
             if (valid) {
                 const int ent = (S.draw_order[e][slot >> 2] >> (8 * (slot & 3))) & 0xffu;
                 const int kind = EB(s, EB_INFO, ent, env) & kKindMask;
                 const float ex = EF(s, EF_X, ent, env), ey = EF(s, EF_Y, ent, env);
-                const float scale = 1.0f * 0.8f;
-                p.tex = kTexKind + kind;
-                p.wx = (ex + -0.4f) * kUnitPx;
-                p.wy = (ey + -0.4f) * kUnitPx;
-                p.scale = scale * kUnitPx / S.desc[p.tex].y;
-                p.go = true;
+                p = sprite_draw(kind, ex, ey, S.desc[kTexKind + kind]);
             }
             prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane);
         }
@@ -1201,37 +1180,14 @@ __global__ void __launch_bounds__(128, 4) render_kernel(State s, AtlasView atlas
     // one draw per lane in the reference's order: particles (common_systems.cpp:374-397: rotated, fading), the sprites the
     // pre-pass resolved, System_Agent::render (:291-327: bullets newest first, then the ship)
     const Camera cam{0.0f, 0.0f, 64.0f, 64.0f, 0.5f * 64.0f / 64.0f};  // (position: see below)
-    int want_tex = kTexShip;
-    bool go = shot_i == s_count;  // the ship
-    float size = 0.15f, alpha = 1.0f, rx = 0.0f, ry = 0.0f;
-    if (is_puff) {
-        want_tex = kTexPuff;
-        go = puff_life > 0.0f;
-    } else if (is_spr) {
-        go = false;
-    } else if (shot_i >= 0 && shot_i < s_count && shot_frame != -1.0f) {
-        go = true;
-        size = 0.1f;
-        want_tex = (shot_frame == 0.0f) ? kTexLaser : kTexBoom + static_cast<int>(shot_frame - 1.0f);
-    }
+    const int want_tex = lane_tex(is_puff, is_spr, 0, shot_i, s_count, shot_frame);  // (a sprite lane's draw comes resolved: any texture)
     const int4 d = descs.at(want_tex);
-    if (is_puff) {
-        const float lifespan = 3.0f;
-        const float life_ratio = (lifespan - puff_life) / lifespan;
-        alpha = 0.5f * (1.0f - life_ratio);
-        const float scale = 1.0f * (0.4f * life_ratio + 0.6f);
-        const float shift = life_ratio * 2.0f;
-        size = scale * kUnitPx / d.y;
-        rx = (puff_x + puff_dx * shift) * kUnitPx - size * d.y * 0.5f;
-        ry = (puff_y + puff_dy * shift) * kUnitPx - size * d.z * 0.5f;
-    } else {
-        rx = shot_x * kUnitPx - size * d.y * 0.5f;
-        ry = shot_y * kUnitPx - size * d.z * 0.5f;
-    }
+    const DrawCall c = lane_rotated(is_puff, is_spr, puff_life, puff_x, puff_y, puff_dx, puff_dy, shot_i, s_count, shot_frame, shot_x,
+                                    shot_y, want_tex, d);
     bool has = is_spr;
-    if (go) {
+    if (c.go) {
         const Camera at{__uint_as_float(M.w[PM_GAME + GW_CAM_X]), __uint_as_float(M.w[PM_GAME + GW_CAM_Y]), cam.sw, cam.sh, cam.scale};
-        has = resolve_rotated_at(at, d.y, d.z, d.x, rx, ry, is_puff ? puff_sn : shot_sn, is_puff ? puff_cs : shot_cs, size, alpha, mine);
+        has = resolve_rotated_at(at, d.y, d.z, d.x, c.wx, c.wy, is_puff ? puff_sn : shot_sn, is_puff ? puff_cs : shot_cs, c.scale, c.alpha, mine);
     }
     // The small rotated draws — exhaust particles, bullets — share their memory round trips in groups of four like the plain
     // ones (pg_render.h kRotInGroups) instead of going alone, a round trip each: 107.8 -> 118.9 M env-steps/s same-box.  (Groups of
@@ -1256,54 +1212,29 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     const int s_next = SI(s, I_SNEXT, env), s_count = SI(s, I_SCOUNT, env);
     const uint8_t* tiles = s.tiles + size_t(env) * kTileStride;
     P.clear();
-    {
-        const int4 d = P.desc(kTexSpace + SI(s, I_BACKDROP, env));
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        P.draw(kTexSpace + SI(s, I_BACKDROP, env), -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z);
-    }
-    int x0, y0, x1, y1;
-    P.window(x0, y0, x1, y1);
-    for (int y = y0; y <= y1; y++)
-        for (int x = x0; x <= x1; x++)
+    const int space = kTexSpace + SI(s, I_BACKDROP, env);
+    const BgDraw bg = backdrop_draw(P.desc(space), SF(s, F_BGSHIFT, env));
+    P.draw(space, bg.px, bg.py, bg.scale);
+    const TileWindow win = P.window();
+    for (int y = win.y0; y <= win.y1; y++)
+        for (int x = win.x0; x <= win.x1; x++)
             if (Win::direct(tiles, x, y) != kEmpty) P.draw(kTexWall, x * kUnitPx, y * kUnitPx, kUnitPx / P.desc(kTexWall).y);
-    for (int k = 0; k < kPuffs; k++) {
-        const float life = PF(s, PF_LIFE, k, env);
-        if (life <= 0.0f) continue;
-        const int4 d = P.desc(kTexPuff);
-        const float lifespan = 3.0f;
-        const float life_ratio = (lifespan - life) / lifespan;
-        const float alpha = 0.5f * (1.0f - life_ratio);
-        const float scale = 1.0f * (0.4f * life_ratio + 0.6f);
-        const float shift = life_ratio * 2.0f;
-        const float size = scale * kUnitPx / d.y;
-        P.draw_rotated(kTexPuff, (PF(s, PF_X, k, env) + PF(s, PF_DX, k, env) * shift) * kUnitPx - size * d.y * 0.5f,
-                       (PF(s, PF_Y, k, env) + PF(s, PF_DY, k, env) * shift) * kUnitPx - size * d.z * 0.5f,
-                       PF(s, PF_ROT, k, env), size, alpha);
-    }
+    for (int k = 0; k < kPuffs; k++)
+        P.draw_rotated(puff_draw(PF(s, PF_LIFE, k, env), PF(s, PF_X, k, env), PF(s, PF_Y, k, env), PF(s, PF_DX, k, env),
+                                 PF(s, PF_DY, k, env), PF(s, PF_ROT, k, env), P.desc(kTexPuff)));
     for (int k = 0; k < n_draw; k++) {
         const int e = EB(s, EB_DRAW, k, env);
-        const int tex = kTexKind + (EB(s, EB_INFO, e, env) & kKindMask);
-        const float scale = 1.0f * 0.8f;
-        P.draw(tex, (EF(s, EF_X, e, env) + -0.4f) * kUnitPx, (EF(s, EF_Y, e, env) + -0.4f) * kUnitPx,
-               scale * kUnitPx / P.desc(tex).y);
+        const int kind = EB(s, EB_INFO, e, env) & kKindMask;
+        P.draw(sprite_draw(kind, EF(s, EF_X, e, env), EF(s, EF_Y, e, env), P.desc(kTexKind + kind)));
     }
     for (int i = 0; i < s_count; i++) {
         const int k = (kShots + s_next - 1 - i) % kShots;
         const float frame = SH(s, SH_FRAME, k, env);
         if (frame == -1.0f) continue;
-        const int tex = (frame == 0.0f) ? kTexLaser : kTexBoom + static_cast<int>(frame - 1.0f);
-        const int4 d = P.desc(tex);
-        const float size = 0.1f;
-        P.draw_rotated(tex, SH(s, SH_X, k, env) * kUnitPx - size * d.y * 0.5f, SH(s, SH_Y, k, env) * kUnitPx - size * d.z * 0.5f,
-                       static_cast<float>(SH(s, SH_ROT, k, env) + kPi * 0.5f), size);
+        const int tex = shot_tex(frame);
+        P.draw_rotated(shot_draw(frame, tex, SH(s, SH_X, k, env), SH(s, SH_Y, k, env), SH(s, SH_ROT, k, env), P.desc(tex)));
     }
-    {
-        const int4 d = P.desc(kTexShip);
-        const float size = 0.15f;
-        P.draw_rotated(kTexShip, SF(s, F_AX, env) * kUnitPx - size * d.y * 0.5f, SF(s, F_AY, env) * kUnitPx - size * d.z * 0.5f,
-                       static_cast<float>(SF(s, F_ROT, env) + kPi * 0.5f), size);
-    }
+    P.draw_rotated(ship_draw(SF(s, F_AX, env), SF(s, F_AY, env), SF(s, F_ROT, env), P.desc(kTexShip)));
 }
 
 // One env, one workgroup, a W×H target in global memory: pgv_render_frame.

@@ -943,15 +943,22 @@ struct View {
 PG_HD View view_of_world() {
     const float zoom = 64.0f * kPxUnit / static_cast<float>(W);  // chaser.cpp:401
     View v{Camera{W * 0.5f * kUnitPx, H * 0.5f * kUnitPx, 64.0f, 64.0f, zoom}, 0, 0, 0, 0};
-    const Camera& cam = v.cam;
-    const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
-    const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-    const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-    v.x0 = static_cast<int>(floorf(vx));
-    v.y0 = static_cast<int>(floorf(vy));
-    v.cols = static_cast<int>(ceilf(vx + vw)) - v.x0 + 1;
-    v.rows = static_cast<int>(ceilf(vy + vh)) - v.y0 + 1;
+    const TileWindow win = tile_window(v.cam);
+    v.x0 = win.x0;
+    v.y0 = win.y0;
+    v.cols = win.x1 - win.x0 + 1;
+    v.rows = win.y1 - win.y0 + 1;
     return v;
+}
+// The draw list of chaser.cpp:396-420 after the walls, each kind of draw stated once, for render_env, prepare_kernel,
+// setup_kernel, frame_draws and the host's point stamps: orbs, points and enemies (common_systems.cpp:41-63), then the
+// agent — a sprite a cell wide around (x, y), given its texture's descriptor (y: width).
+PG_HD DrawCall sprite_draw(int tex, float x, float y, const int4& d) {
+    const float scale = 1.0f * 1.0f;
+    return DrawCall{true, false, false, tex, (x + -0.5f) * kUnitPx, (y + -0.5f) * kUnitPx, scale * kUnitPx / d.y, 1.0f, 0.0f};
+}
+PG_HD DrawCall agent_draw(float x, float y, const int4& d) {
+    return DrawCall{true, false, false, kTexAgent, (x + -0.5f) * kUnitPx, (y + -0.5f) * kUnitPx, kUnitPx / d.y * 1.0f, 1.0f, 0.0f};
 }
 // descriptor .w of what the tile layer shows, as the composer's row classes want it (a point is a candidate only
 // inside its box: if the box is solid it brings nothing that is not opaque)
@@ -1029,18 +1036,12 @@ PG_D void render_env(const State& s, const AtlasView& atlas, const StepIO& io, i
     // (the barriers of the composer, or of the replay that stands in for it, come between these writes and their readers)
 
     int bg_soft = 0;  // the backdrop has texels that are not opaque (descriptor .w)
-    int4 bg_d;  // the background draw, chaser.cpp:404-409: texture, world position, scale — each wave resolves the axis it needs (pg_render.h BgAxis)
-    float bg_px, bg_py, bg_sc;
-    {
-        const int4 d = atlas.desc[kTexFloor + __builtin_amdgcn_readfirstlane(SI(s, I_BG, env))];  // (wave-uniform: scalar loads)
-        bg_soft = d.w;
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        bg_d = d;
-        bg_px = -SF(s, F_BGSHIFT, env) * extra;
-        bg_py = 0.0f;
-        bg_sc = 64.0f * kUnitPx / d.z;
-    }
+    // the background draw, chaser.cpp:404-409 — each wave resolves the axis it needs (pg_render.h BgAxis)
+    const BgDraw bg_draw = backdrop_draw(atlas.desc[kTexFloor + __builtin_amdgcn_readfirstlane(SI(s, I_BG, env))],  // (wave-uniform: scalar loads)
+                                         SF(s, F_BGSHIFT, env));
+    const int4& bg_d = bg_draw.desc;
+    const float bg_px = bg_draw.px, bg_py = bg_draw.py, bg_sc = bg_draw.scale;
+    bg_soft = bg_d.w;
     const int x0 = view.x0, y0 = view.y0, cols = view.cols, rows = view.rows, cells = cols * rows;
     const int4 wall_d = atlas.desc[kTexWall], point_d = atlas.desc[kTexPoint];
     const bool points_in_layer = points_join_layer(point_d, flags) && !write_base;
@@ -1190,9 +1191,8 @@ PG_D void render_env(const State& s, const AtlasView& atlas, const StepIO& io, i
         if (!kPrepped) {
             const int4 d = descs.at(want_tex);
             if (has) {
-                const float scale = (k == n_draw) ? kUnitPx / d.y * 1.0f : (1.0f * 1.0f) * kUnitPx / d.y;
-                has = resolve_draw(cam, d.y, d.z, d.x, (x + -0.5f) * kUnitPx, (y + -0.5f) * kUnitPx, scale, 1.0f, false, false,
-                                   mine);
+                const DrawCall c = (k == n_draw) ? agent_draw(x, y, d) : sprite_draw(want_tex, x, y, d);
+                has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, false, false, mine);
             }
         }
         PG_MARK("t_resolved");
@@ -1256,10 +1256,9 @@ __global__ void __launch_bounds__(128) prepare_kernel(State s, AtlasView atlas) 
     for (int q = threadIdx.x; q < 2 * kCells; q += blockDim.x) {
         const int is_point = q / kCells, cell = q - is_point * kCells;
         const int4 d = atlas.desc[is_point ? kTexPoint : kTexOrb];
-        const float scale = (1.0f * 1.0f) * kUnitPx / d.y;
+        const DrawCall c = sprite_draw(is_point ? kTexPoint : kTexOrb, cell_x(cell), cell_y(cell), d);
         Blit b;
-        const bool has = resolve_draw(view.cam, d.y, d.z, d.x, (cell_x(cell) + -0.5f) * kUnitPx, (cell_y(cell) + -0.5f) * kUnitPx, scale,
-                                      1.0f, false, false, b);
+        const bool has = resolve_draw(view.cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, false, false, b);
         BlitWords w = blit_pack(b);
         if (!has) w.w[0] = w.w[1] = w.w[2] = w.w[3] = w.w[4] = w.w[5] = 0u;
         for (int k = 0; k < kBlitWords; k++) s.prep.cell_blits[size_t(q) * kBlitWords + k] = w.w[k];
@@ -1280,9 +1279,9 @@ __global__ void __launch_bounds__(256) setup_kernel(State s, AtlasView atlas) {
         const int tex = agent ? kTexAgent : kTexEnemy + MB(s, 0, item, env);
         const float x = agent ? SF(s, F_AX, env) : MF(s, MF_X, item, env), y = agent ? SF(s, F_AY, env) : MF(s, MF_Y, item, env);
         const int4 d = atlas.desc[tex];
-        const float scale = agent ? kUnitPx / d.y * 1.0f : (1.0f * 1.0f) * kUnitPx / d.y;
+        const DrawCall c = agent ? agent_draw(x, y, d) : sprite_draw(tex, x, y, d);
         Blit b;
-        const bool has = resolve_draw(view.cam, d.y, d.z, d.x, (x + -0.5f) * kUnitPx, (y + -0.5f) * kUnitPx, scale, 1.0f, false, false, b);
+        const bool has = resolve_draw(view.cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, false, false, b);
         BlitWords w = blit_pack(b);
         if (!has) w.w[0] = w.w[1] = w.w[2] = w.w[3] = w.w[4] = w.w[5] = 0u;
         uint2* at = reinterpret_cast<uint2*>(s.prep.movers + (size_t(env) * kMovers + item) * kBlitWords);
@@ -1292,9 +1291,8 @@ __global__ void __launch_bounds__(256) setup_kernel(State s, AtlasView atlas) {
     } else if (item < kMovers + 2) {
         const int axis = item - kMovers;
         const int4 d = atlas.desc[kTexFloor + SI(s, I_BG, env)];
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        const BgAxis a = bg_axis(view.cam, d, -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z, axis);
+        const BgDraw bg = backdrop_draw(d, SF(s, F_BGSHIFT, env));
+        const BgAxis a = bg_axis(view.cam, d, bg.px, bg.py, bg.scale, axis);
         uint4* at = reinterpret_cast<uint4*>(s.prep.bg + size_t(env) * 8 + axis * 4);
         *at = make_uint4(pack_halves(a.d0, a.dn), pack_halves(a.s0, a.sn), static_cast<uint32_t>(a.tex_off), static_cast<uint32_t>(a.tex_w));
     }
@@ -1430,16 +1428,12 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     const int n_draw = (sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;
     const uint8_t* tiles = s.tiles + size_t(env) * kTileStride;
     P.clear();
-    {
-        const int4 d = P.desc(kTexFloor + SI(s, I_BG, env));
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        P.draw(kTexFloor + SI(s, I_BG, env), -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z);
-    }
-    int x0, y0, x1, y1;
-    P.window(x0, y0, x1, y1);
-    for (int y = y0; y <= y1; y++)
-        for (int x = x0; x <= x1; x++)
+    const int floor_tex = kTexFloor + SI(s, I_BG, env);
+    const BgDraw bg = backdrop_draw(P.desc(floor_tex), SF(s, F_BGSHIFT, env));
+    P.draw(floor_tex, bg.px, bg.py, bg.scale);
+    const TileWindow win = P.window();
+    for (int y = win.y0; y <= win.y1; y++)
+        for (int x = win.x0; x <= win.x1; x++)
             if (tile_at(tiles, x, H - 1 - y) == kWall) P.draw(kTexWall, x * kUnitPx, y * kUnitPx, kUnitPx / P.desc(kTexWall).y);
     for (int k = 0; k < n_draw; k++) {
         const int e = EB(s, EB_DRAW, k, env);
@@ -1457,11 +1451,9 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
             x = cell_x(cell);
             y = cell_y(cell);
         }
-        const float scale = 1.0f * 1.0f;
-        P.draw(tex, (x + -0.5f) * kUnitPx, (y + -0.5f) * kUnitPx, scale * kUnitPx / P.desc(tex).y);
+        P.draw(sprite_draw(tex, x, y, P.desc(tex)));
     }
-    P.draw(kTexAgent, (SF(s, F_AX, env) + -0.5f) * kUnitPx, (SF(s, F_AY, env) + -0.5f) * kUnitPx,
-           kUnitPx / P.desc(kTexAgent).y * 1.0f);
+    P.draw(agent_draw(SF(s, F_AX, env), SF(s, F_AY, env), P.desc(kTexAgent)));
 }
 
 // One env, one workgroup, a W×H target in global memory: pgv_render_frame.
@@ -1524,9 +1516,8 @@ class ChaserGame final : public Game {
         const View view = view_of_world();
         for (int cell = 0; cell < kCells; cell++) {
             Blit b;
-            const float scale = (1.0f * 1.0f) * kUnitPx / d.y;
-            if (!resolve_draw(view.cam, d.y, d.z, 0, (cell_x(cell) + -0.5f) * kUnitPx, (cell_y(cell) + -0.5f) * kUnitPx, scale, 1.0f, false,
-                              false, b))
+            const DrawCall c = sprite_draw(kTexPoint, cell_x(cell), cell_y(cell), d);
+            if (!resolve_draw(view.cam, d.y, d.z, 0, c.wx, c.wy, c.scale, 1.0f, false, false, b))
                 continue;
             int count = 0;
             for (int j = 0; j < b.dh; j++)

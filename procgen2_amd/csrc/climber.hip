@@ -542,6 +542,29 @@ __global__ void __launch_bounds__(64, PG_CLIMBER_WAVES) logic_kernel(State s, co
 // render_game(true) (climber.cpp:431-459): one workgroup of two wavefronts per env (pg_render.h).
 constexpr int kGrid = 24;  // 64 px / 3.2 px per tile = 20 tiles → at most 22 columns/rows in view (24² = 9·64 cells; LDS: 7 envs per CU instead of 6)
 
+// The draw list of climber.cpp:431-459, each kind of draw stated once, for render_full, setup_kernel and frame_draws:
+// which texture, then the draw call given that texture's descriptor (x: first texel, y: width, z: height).
+PG_D int tile_tex(int tile, int theme) { return (tile == kWallTop ? kTexTop : kTexMid) + theme; }  // tilemap.cpp:183-198
+// positive-z sprites (common_systems.cpp:41-63): fish or gem
+PG_D int entity_tex(int info) { return (info & kMob) ? kTexFish + ((info & kFrame) ? 1 : 0) : kTexGem; }
+PG_D DrawCall entity_draw(int info, float x, float y, int tex, const int4& d) {
+    if (!(info & kTexSet)) return kNoDraw;
+    const float off = (info & kMob) ? -0.4f : -0.5f;  // tilemap.cpp:53,66
+    const float scale = 1.0f * 1.0f;
+    return DrawCall{true, (info & kFlip) != 0, false, tex, (x + off) * kUnitPx, (y + off) * kUnitPx, scale * kUnitPx / d.y, 1.0f, 0.0f};
+}
+// the agent (common_systems.cpp:272-298)
+PG_D int agent_tex(int sflags, float avx, float aphase, int suit) {
+    const bool ground = (sflags & kFlagGround) != 0;
+    if (fabsf(avx) < 0.01f && ground) return kTexStand + suit;
+    if (!ground) return kTexJump + suit;
+    return (aphase > 0.5f ? kTexWalk2 : kTexWalk1) + suit;
+}
+PG_D DrawCall agent_draw(int sflags, float ax, float ay, int tex, const int4& d) {
+    const float px = ax - 0.5f, py = ay - 1.0f;
+    return DrawCall{true, (sflags & kFlagForward) == 0, false, tex, px * kUnitPx, py * kUnitPx, 0.8f * kUnitPx / d.y, 1.0f, 0.0f};
+}
+
 // The complete frame of one env by its workgroup, set-up included: the frames the pre-pass marks fat, the draw-list
 // replay (flags bit 0) and kDebugNoPrepass.
 PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, int flags, int env, uint32_t* fb,
@@ -569,28 +592,14 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     }
 
     int bg_soft = 0;  // the backdrop has texels that are not opaque (descriptor .w)
-    int4 bg_d;  // the background draw, climber.cpp:447-452: texture, world position, scale — each wave resolves the axis it needs (pg_render.h BgAxis)
-    float bg_px, bg_py, bg_sc;
-    {
-        const int4 d = descs.uniform(kTexBackdrop + backdrop);
-        bg_soft = d.w;
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        bg_d = d;
-        bg_px = -SF(s, F_BGSHIFT, env) * extra;
-        bg_py = 0.0f;
-        bg_sc = 64.0f * kUnitPx / d.z;
-    }
-    // tile window (tilemap.cpp:172-181)
-    const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
-    const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-    const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-    const int x0 = static_cast<int>(floorf(vx)), y0 = static_cast<int>(floorf(vy));
-    const int x1 = static_cast<int>(ceilf(vx + vw)), y1 = static_cast<int>(ceilf(vy + vh));
-    const int cols = x1 - x0 + 1, rows = y1 - y0 + 1, cells = cols * rows;
+    // the background draw, climber.cpp:447-452 — each wave resolves the axis it needs (pg_render.h BgAxis)
+    const BgDraw bg_draw = backdrop_draw(descs.uniform(kTexBackdrop + backdrop), SF(s, F_BGSHIFT, env));
+    bg_soft = bg_draw.desc.w;
+    const TileWindow win = tile_window(cam);  // tilemap.cpp:172-181
+    const int x0 = win.x0, y0 = win.y0;
+    const int cols = win.x1 - x0 + 1, rows = win.y1 - y0 + 1, cells = cols * rows;
     const int4 top_d = descs.uniform(kTexTop + theme), mid_d = descs.uniform(kTexMid + theme);
 
-    const BgDraw bg_draw{bg_d, bg_px, bg_py, bg_sc};
     BgAxis bga{};  // this wave's axis of it (wave 0: x, wave 1: y), resolved along with the tile spans
     bool composed = false;
     // The brown theme's cap tile is 64×53 next to 64×64 bodies (assets/platformer/tileBrown_06.png): the composer's
@@ -613,7 +622,7 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     }
     if (!composed) {  // draw-list replay (tilemap.cpp:172-198)
         wave_clear(fb, lane, half, halves);
-        const bool has_bg = resolve_draw(cam, bg_d.y, bg_d.z, bg_d.x, bg_px, bg_py, bg_sc, 1.0f, false, false, mine);
+        const bool has_bg = resolve_draw(cam, bg_draw.desc.y, bg_draw.desc.z, bg_draw.desc.x, bg_draw.px, bg_draw.py, bg_draw.scale, 1.0f, false, false, mine);
         wave_replay(fb, atlas, mine, has_bg ? 1ull : 0ull, lane, half, halves);
         for (int base = 0; base < cells; base += 64) {
             const int cell = base + lane;
@@ -634,43 +643,20 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
 
     {  // positive-z sprites (common_systems.cpp:41-63), then the agent (:272-298): one draw per lane
         int want_tex = 0;
-        if (is_sprite) {
-            want_tex = (spr_info & kMob) ? kTexFish + ((spr_info & kFrame) ? 1 : 0) : kTexGem;
-        } else if (is_agent) {
-            const bool ground = (sflags & kFlagGround) != 0;
-            if (fabsf(SF(s, F_AVX, env)) < 0.01f && ground)
-                want_tex = kTexStand + suit;
-            else if (!ground)
-                want_tex = kTexJump + suit;
-            else if (SF(s, F_APHASE, env) > 0.5f)
-                want_tex = kTexWalk2 + suit;
-            else
-                want_tex = kTexWalk1 + suit;
-        }
+        if (is_sprite)
+            want_tex = entity_tex(spr_info);
+        else if (is_agent)
+            want_tex = agent_tex(sflags, SF(s, F_AVX, env), SF(s, F_APHASE, env), suit);
         const int4 d = descs.at(want_tex);
         // sprites and the agent differ in their parameters only: pick per lane, resolve once (a resolve_draw per kind
         // in its own branch is executed by the whole wave once per kind)
-        bool has = false, go = false, flip = false;
-        float wx = 0.0f, wy = 0.0f, scale_num = kUnitPx;
-        if (is_sprite) {
-            if (spr_info & kTexSet) {
-                const float off = (spr_info & kMob) ? -0.4f : -0.5f;  // tilemap.cpp:53,66
-                const float scale = 1.0f * 1.0f;
-                wx = (spr_x + off) * kUnitPx;
-                wy = (spr_y + off) * kUnitPx;
-                scale_num = scale * kUnitPx;
-                flip = (spr_info & kFlip) != 0;
-                go = true;
-            }
-        } else if (is_agent) {
-            const float px = SF(s, F_AX, env) - 0.5f, py = SF(s, F_AY, env) - 1.0f;
-            wx = px * kUnitPx;
-            wy = py * kUnitPx;
-            scale_num = 0.8f * kUnitPx;
-            flip = (sflags & kFlagForward) == 0;
-            go = true;
-        }
-        if (go) has = resolve_draw(cam, d.y, d.z, d.x, wx, wy, scale_num / d.y, 1.0f, flip, false, mine);
+        DrawCall c = kNoDraw;
+        if (is_sprite)
+            c = entity_draw(spr_info, spr_x, spr_y, want_tex, d);
+        else if (is_agent)
+            c = agent_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), want_tex, d);
+        bool has = false;
+        if (c.go) has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, c.flip_h, false, mine);
         wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
     }
     // each wave stores the rows it owns (pg_render.h wave_replay_rows): no barrier
@@ -748,16 +734,12 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             v.cam = cam;
             const int backdrop = themes & 0xff, theme = (themes >> 16) & 0xff;
             const int4 d = S.desc[kTexBackdrop + backdrop];
-            const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-            const float extra = aspect - 1.0f;
-            v.bg = BgDraw{d, -bgshift * extra, 0.0f, 64.0f * kUnitPx / d.z};  // climber.cpp:447-452
-            const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;  // tilemap.cpp:172-181
-            const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-            const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-            v.x0 = static_cast<int>(floorf(vx));
-            v.y0 = static_cast<int>(floorf(vy));
-            v.cols = static_cast<int>(ceilf(vx + vw)) - v.x0 + 1;
-            v.rows = static_cast<int>(ceilf(vy + vh)) - v.y0 + 1;
+            v.bg = backdrop_draw(d, bgshift);  // climber.cpp:447-452
+            const TileWindow win = tile_window(cam);  // tilemap.cpp:172-181
+            v.x0 = win.x0;
+            v.y0 = win.y0;
+            v.cols = win.x1 - win.x0 + 1;
+            v.rows = win.y1 - win.y0 + 1;
             const int4 top_d = S.desc[kTexTop + theme], mid_d = S.desc[kTexMid + theme];
             const bool two = top_d.z != mid_d.z;  // the brown theme's cap tile is 64×53 next to 64×64 bodies
             v.tw = mid_d.y;
@@ -828,40 +810,17 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             const int slot = is_b ? q - cnt_a : q;
             const bool valid = q < cnt_a + cnt_b;
             const PrepEnv& pe = S.env[e];
-            PrepDraw p{false, false, false, kTexGem, 0.0f, 0.0f, 1.0f, 1.0f};
-            float num = kUnitPx;
+            DrawCall p = kNoDraw;
             if (valid && slot < pe.n_draw) {
                 const int ent = (S.draw_order[e][slot >> 2] >> (8 * (slot & 3))) & 0xffu;
                 const int info = EB(s, EB_INFO, ent, env);
                 const float ex = EF(s, EF_X, ent, env), ey = EF(s, EF_Y, ent, env);
-                if (info & kTexSet) {
-                    p.tex = (info & kMob) ? kTexFish + ((info & kFrame) ? 1 : 0) : kTexGem;
-                    const float off = (info & kMob) ? -0.4f : -0.5f;  // tilemap.cpp:53,66
-                    const float scale = 1.0f * 1.0f;
-                    p.wx = (ex + off) * kUnitPx;
-                    p.wy = (ey + off) * kUnitPx;
-                    num = scale * kUnitPx;
-                    p.flip_h = (info & kFlip) != 0;
-                    p.go = true;
-                }
+                const int tex = entity_tex(info);
+                p = entity_draw(info, ex, ey, tex, S.desc[tex]);
             } else if (valid) {
-                const bool ground = (pe.sflags & kFlagGround) != 0;
-                if (fabsf(pe.avx) < 0.01f && ground)
-                    p.tex = kTexStand + pe.suit;
-                else if (!ground)
-                    p.tex = kTexJump + pe.suit;
-                else if (pe.aphase > 0.5f)
-                    p.tex = kTexWalk2 + pe.suit;
-                else
-                    p.tex = kTexWalk1 + pe.suit;
-                const float px = pe.ax - 0.5f, py = pe.ay - 1.0f;
-                p.wx = px * kUnitPx;
-                p.wy = py * kUnitPx;
-                num = 0.8f * kUnitPx;
-                p.flip_h = (pe.sflags & kFlagForward) == 0;
-                p.go = true;
+                const int tex = agent_tex(pe.sflags, pe.avx, pe.aphase, pe.suit);
+                p = agent_draw(pe.sflags, pe.ax, pe.ay, tex, S.desc[tex]);
             }
-            p.scale = num / S.desc[p.tex].y;
             prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane);
         }
         prep_draws_flush(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, lane);
@@ -917,45 +876,24 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     const int n_draw = (sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;
     const uint8_t* tiles = s.tiles + size_t(env) * (W * H);
     P.clear();
-    {
-        const int4 d = P.desc(kTexBackdrop + backdrop);
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        P.draw(kTexBackdrop + backdrop, -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z);
-    }
-    int x0, y0, x1, y1;
-    P.window(x0, y0, x1, y1);
-    for (int y = y0; y <= y1; y++)
-        for (int x = x0; x <= x1; x++) {
+    const BgDraw bg = backdrop_draw(P.desc(kTexBackdrop + backdrop), SF(s, F_BGSHIFT, env));
+    P.draw(kTexBackdrop + backdrop, bg.px, bg.py, bg.scale);
+    const TileWindow win = P.window();
+    for (int y = win.y0; y <= win.y1; y++)
+        for (int x = win.x0; x <= win.x1; x++) {
             const int tile = Win::direct(tiles, x, y);
             if (tile == kEmpty) continue;
-            const int tex = (tile == kWallTop ? kTexTop : kTexMid) + theme;
+            const int tex = tile_tex(tile, theme);
             P.draw(tex, x * kUnitPx, y * kUnitPx, kUnitPx / P.desc(tex).y);
         }
     for (int k = 0; k < n_draw; k++) {
         const int e = EB(s, EB_DRAW, k, env);
         const int info = EB(s, EB_INFO, e, env);
-        if (!(info & kTexSet)) continue;
-        const int tex = (info & kMob) ? kTexFish + ((info & kFrame) ? 1 : 0) : kTexGem;
-        const float off = (info & kMob) ? -0.4f : -0.5f;
-        const float scale = 1.0f * 1.0f;
-        P.draw(tex, (EF(s, EF_X, e, env) + off) * kUnitPx, (EF(s, EF_Y, e, env) + off) * kUnitPx,
-               scale * kUnitPx / P.desc(tex).y, 1.0f, (info & kFlip) != 0);
+        const int tex = entity_tex(info);
+        P.draw(entity_draw(info, EF(s, EF_X, e, env), EF(s, EF_Y, e, env), tex, P.desc(tex)));
     }
-    {
-        const bool ground = (sflags & kFlagGround) != 0;
-        int tex;
-        if (fabsf(SF(s, F_AVX, env)) < 0.01f && ground)
-            tex = kTexStand + suit;
-        else if (!ground)
-            tex = kTexJump + suit;
-        else if (SF(s, F_APHASE, env) > 0.5f)
-            tex = kTexWalk2 + suit;
-        else
-            tex = kTexWalk1 + suit;
-        const float px = SF(s, F_AX, env) - 0.5f, py = SF(s, F_AY, env) - 1.0f;
-        P.draw(tex, px * kUnitPx, py * kUnitPx, 0.8f * kUnitPx / P.desc(tex).y, 1.0f, (sflags & kFlagForward) == 0);
-    }
+    const int tex = agent_tex(sflags, SF(s, F_AVX, env), SF(s, F_APHASE, env), suit);
+    P.draw(agent_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), tex, P.desc(tex)));
 }
 
 // One env, one workgroup, a W×H target in global memory: pgv_render_frame.

@@ -1098,6 +1098,46 @@ constexpr bool kQuarters = PG_COINRUN_QUARTERS;  // the lean kernel's tiny draws
 #endif
 constexpr int kGrid = 16;  // 64 px / 4.8 px per tile = 13.3 tiles → at most 16 columns/rows in view
 
+// The draw list of coinrun.cpp:443-470, each kind of draw stated once, for render_full, setup_kernel and frame_draws:
+// which texture, then the draw call given that texture's descriptor (x: first texel, y: width, z: height).
+PG_D int tile_tex(int tile, int crate, int ground_theme) {  // tilemap.cpp:305-321
+    return tile == kWallMid   ? kTexMid + ground_theme
+           : tile == kWallTop ? kTexTop + ground_theme
+           : tile == kLavaMid ? kTexLava
+           : tile == kLavaTop ? kTexLavaTop
+                              : kTexCrate + crate;
+}
+// … of tile kind k, as the cell tables number them: 0-3 = wall_top, wall_mid, lava_top, lava_mid (tile id - 1), 4-7 = the four crates
+PG_D int kind_tex(int k, int ground_theme) { return tile_tex(k < 4 ? k + 1 : kCrate, (k - 4) & 3, ground_theme); }
+// System_Particles::render (common_systems.cpp:315-337): a spark, d = kTexSpark's descriptor
+PG_D DrawCall spark_draw(float life, float x, float y, const int4& d) {
+    if (!(life > 0.0f)) return kNoDraw;
+    const float lr = (5.0f - life) / 5.0f;
+    const float alpha = 0.5f * (1.0f - lr);
+    const float scale = 0.45f * (0.4f * lr + 0.6f);
+    const float oy = -lr * 0.17f;
+    return DrawCall{true, false, false, kTexSpark, x * kUnitPx - 0.5f * d.y * scale, (y + oy) * kUnitPx - 0.5f * d.z * scale,
+                    scale * kUnitPx / d.y, alpha, 0.0f};
+}
+// System_Sprite_Render::render (:41-63): a sprite of the draw list
+PG_D int sprite_tex(int tex0, int dyn) { return (dyn & kDynTexSet) ? tex0 + ((dyn & kDynFrame) ? 1 : 0) : 0; }  // (none yet: any valid one, never drawn)
+PG_D DrawCall sprite_draw(int dyn, float x, float y, int tex, const int4& d) {
+    if (!(dyn & kDynTexSet)) return kNoDraw;
+    const float scale = 1.0f * 1.0f;
+    return DrawCall{true, (dyn & kDynFlip) != 0, false, tex, (x + -0.5f) * kUnitPx, (y + -0.5f) * kUnitPx, scale * kUnitPx / d.y, 1.0f, 0.0f};
+}
+// the agent (:254-278)
+PG_D int agent_tex(int sflags, float avx, float aphase, int alien) {
+    const bool ground = (sflags & kFlagGround) != 0;
+    if (fabsf(avx) < 0.01f && ground) return kTexStand + alien;
+    if (!ground) return kTexJump + alien;
+    return (aphase > 0.5f ? kTexWalk2 : kTexWalk1) + alien;
+}
+PG_D DrawCall agent_draw(int sflags, float ax, float ay, int tex, const int4& d) {
+    const float px = ax - 0.5f, py = ay - 2.0f;
+    return DrawCall{true, (sflags & kFlagForward) == 0, false, tex, px * kUnitPx, py * kUnitPx, kUnitPx / d.y, 1.0f, 0.0f};
+}
+
 // The complete frame of one env by its workgroup, set-up included: every frame before the pre-pass existed, and still
 // the frames the pre-pass marks fat, the draw-list replay (flags bit 0) and kDebugNoPrepass.
 PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, int flags, int env, uint32_t* fb,
@@ -1168,92 +1208,42 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     PG_MARK("b_inputs");
 
     // background (coinrun.cpp:459-464)
-    int4 bg_d;  // the background draw: texture, world position, scale — each wave resolves the axis it needs (pg_render.h BgAxis)
-    float bg_px, bg_py, bg_sc;
-    {
-        const int4 d = descs.uniform(kTexBackdrop + backdrop);
-        bg_d = d;
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        bg_d = d;
-        bg_px = -SF(s, F_BGSHIFT, env) * extra;
-        bg_py = 0.0f;
-        bg_sc = 64.0f * kUnitPx / d.z;
-    }
+    // the background draw — each wave resolves the axis it needs (pg_render.h BgAxis)
+    const BgDraw bg_draw = backdrop_draw(descs.uniform(kTexBackdrop + backdrop), SF(s, F_BGSHIFT, env));
+    const int4& bg_d = bg_draw.desc;
     // negative-z sprites: none — every coinrun sprite has z = 1 (tilemap.cpp:63,88,283)
 
-    // tile window (tilemap.cpp:294-304)
-    const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
-    const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-    const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-    const int x0 = static_cast<int>(floorf(vx)), y0 = static_cast<int>(floorf(vy));
-    const int x1 = static_cast<int>(ceilf(vx + vw)), y1 = static_cast<int>(ceilf(vy + vh));
-    const int cols = x1 - x0 + 1, rows = y1 - y0 + 1, cells = cols * rows;
+    const TileWindow win = tile_window(cam);  // tilemap.cpp:294-304
+    const int x0 = win.x0, y0 = win.y0;
+    const int cols = win.x1 - x0 + 1, rows = win.y1 - y0 + 1, cells = cols * rows;
     const int4 tile_desc = descs.uniform(kTexMid);  // every tile texture is 128×128 (checked at make time)
 
     if (half == 1 && !PG_ABL(flags, 2)) {  // the sprite pass's draws, resolved ahead of the frame (see above)
         {
             bool has = false;
-            const int4 spark_d = descs.uniform(kTexSpark);
             // every lane asks for the descriptor it needs with a cross-lane read, so do that outside the branches
             int want_tex = 0;
-            if (is_sprite) {
-                want_tex = spr_tex + ((spr_dyn & kDynFrame) ? 1 : 0);
-            } else if (is_agent) {
-                const bool ground = (sflags & kFlagGround) != 0;
-                if (fabsf(SF(s, F_AVX, env)) < 0.01f && ground)
-                    want_tex = kTexStand + alien;
-                else if (!ground)
-                    want_tex = kTexJump + alien;
-                else if (SF(s, F_APHASE, env) > 0.5f)
-                    want_tex = kTexWalk2 + alien;
-                else
-                    want_tex = kTexWalk1 + alien;
-            }
+            if (is_part)
+                want_tex = kTexSpark;
+            else if (is_sprite)
+                want_tex = sprite_tex(spr_tex, spr_dyn);
+            else if (is_agent)
+                want_tex = agent_tex(sflags, SF(s, F_AVX, env), SF(s, F_APHASE, env), alien);
             const int4 d = descs.at(want_tex);
             // The three kinds of draw differ only in their parameters: pick them per lane, then resolve once.  (One
             // resolve_draw per kind in its own branch made every wave run its ~180 vector instructions three times.)
-            bool go = false, flip = false;
-            int tw = d.y, th = d.z, tex_at = d.x;
-            float wx = 0.0f, wy = 0.0f, scale_num = kUnitPx, alpha = 1.0f;
-            if (is_part) {  // System_Particles::render (common_systems.cpp:315-337), as `particle` above
-                if (part_life > 0.0f) {
-                    const float lr = (5.0f - part_life) / 5.0f;
-                    alpha = 0.5f * (1.0f - lr);
-                    const float scale = 0.45f * (0.4f * lr + 0.6f);
-                    const float oy = -lr * 0.17f;
-                    tw = spark_d.y;
-                    th = spark_d.z;
-                    tex_at = spark_d.x;
-                    wx = part_x * kUnitPx - 0.5f * spark_d.y * scale;
-                    wy = (part_y + oy) * kUnitPx - 0.5f * spark_d.z * scale;
-                    scale_num = scale * kUnitPx;
-                    go = true;
-                }
-            } else if (is_sprite) {
-                if (spr_dyn & kDynTexSet) {
-                    const float scale = 1.0f * 1.0f;
-                    wx = (spr_x + -0.5f) * kUnitPx;
-                    wy = (spr_y + -0.5f) * kUnitPx;
-                    scale_num = scale * kUnitPx;
-                    flip = (spr_dyn & kDynFlip) != 0;
-                    go = true;
-                }
-            } else if (is_agent) {
-                const float px = SF(s, F_AX, env) - 0.5f, py = SF(s, F_AY, env) - 2.0f;
-                wx = px * kUnitPx;
-                wy = py * kUnitPx;
-                flip = (sflags & kFlagForward) == 0;
-                go = true;
-            }
-            if (go)
-                has = resolve_draw(cam, tw, th, tex_at, wx, wy, scale_num / static_cast<float>(tw), alpha, flip, false,
-                                   mine);
+            DrawCall c = kNoDraw;
+            if (is_part)
+                c = spark_draw(part_life, part_x, part_y, d);
+            else if (is_sprite)
+                c = sprite_draw(spr_dyn, spr_x, spr_y, want_tex, d);
+            else if (is_agent)
+                c = agent_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), want_tex, d);
+            if (c.go) has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, c.alpha, c.flip_h, false, mine);
             blit_share(slots, lane, mine, has);
         }
     }
     PG_MARK("c_resolve");
-    const BgDraw bg_draw{bg_d, bg_px, bg_py, bg_sc};
     BgAxis bga{};  // this wave's axis of it (wave 0: x, wave 1: y), resolved along with the tile spans
     bool composed = false, sprites_ready = false;
     ReplayState<4> sprite_pass;
@@ -1263,12 +1253,7 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     PG_MARK("d_spans");
         // Texel offset of each tile kind's texture, one per lane (0..7), looked up with a cross-lane read:
         // lanes 0-3 = wall_top, wall_mid, lava_top, lava_mid (tile id - 1), lanes 4-7 = the four crates.
-        int kind_tex = kTexCrate + ((lane - 4) & 3);
-        if (lane == 0) kind_tex = kTexTop + ground_theme;
-        if (lane == 1) kind_tex = kTexMid + ground_theme;
-        if (lane == 2) kind_tex = kTexLavaTop;
-        if (lane == 3) kind_tex = kTexLava;
-        const int4 kind_d = descs.at(kind_tex);
+        const int4 kind_d = descs.at(kind_tex(lane & 7, ground_theme));
         const int kind_base = kind_d.x;
         // which grid rows show a texture with translucent texels (descriptor .w; crates and lava caps are the only
         // soft-edged tiles, 9 of the 49 backdrops have some): only there does the composer look at alphas
@@ -1316,7 +1301,7 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
         }
         Blit tile;  // (`mine` holds the sprite pass's draws)
         wave_clear(fb, lane, half, halves);
-        const bool has_bg = resolve_draw(cam, bg_d.y, bg_d.z, bg_d.x, bg_px, bg_py, bg_sc, 1.0f, false, false, tile);
+        const bool has_bg = resolve_draw(cam, bg_d.y, bg_d.z, bg_d.x, bg_draw.px, bg_draw.py, bg_draw.scale, 1.0f, false, false, tile);
         wave_replay(fb, atlas, tile, has_bg ? 1ull : 0ull, lane, half, halves);
         for (int base = 0; base < cells; base += 64) {
             const int cell = base + lane;
@@ -1332,18 +1317,7 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
                     crate = raw >> 4;
                 }
                 if (t != kEmpty) {
-                    int tex;
-                    if (t == kWallMid)
-                        tex = kTexMid + ground_theme;
-                    else if (t == kWallTop)
-                        tex = kTexTop + ground_theme;
-                    else if (t == kLavaMid)
-                        tex = kTexLava;
-                    else if (t == kLavaTop)
-                        tex = kTexLavaTop;
-                    else
-                        tex = kTexCrate + crate;
-                    const int4 d = atlas.desc[tex];  // fallback path: plain global lookup
+                    const int4 d = atlas.desc[tile_tex(t, crate, ground_theme)];  // fallback path: plain global lookup
                     has = resolve_draw(cam, d.y, d.z, d.x, x * kUnitPx, y * kUnitPx, kUnitPx / d.y, 1.0f, false, false,
                                        tile);
                 }
@@ -1357,16 +1331,6 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
         // common_systems.cpp:315-337), then the sprites of the draw list (positive z, :41-63; empty until the
         // first update — D2), then the agent (:254-278).
         const int4 spark_d = descs.uniform(kTexSpark);
-        auto particle = [&](float life, float px, float py, Blit& out) {
-            if (life <= 0.0f) return false;
-            const float lr = (5.0f - life) / 5.0f;
-            const float alpha = 0.5f * (1.0f - lr);
-            const float scale = 0.45f * (0.4f * lr + 0.6f);
-            const float oy = -lr * 0.17f;
-            return resolve_draw(cam, spark_d.y, spark_d.z, spark_d.x, px * kUnitPx - 0.5f * spark_d.y * scale,
-                                (py + oy) * kUnitPx - 0.5f * spark_d.z * scale, scale * kUnitPx / spark_d.y, alpha,
-                                false, false, out);
-        };
         if (!one_pass) {  // many mobs: particles in rounds of 64 first
             Blit spark;  // (`mine` holds the draws of the pass that is already under way)
             for (int base = 0; base < n_parts; base += 64) {
@@ -1374,7 +1338,8 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
                 if (base + lane < n_parts) {
                     const int idx = base + lane, m = idx / kSparks, k = idx - m * kSparks;
                     const int e = EB(s, EB_SPARK_ORDER, m, env);
-                    has = particle(SP(s, buf, 2, e, k, env), SP(s, buf, 0, e, k, env), SP(s, buf, 1, e, k, env), spark);
+                    const DrawCall c = spark_draw(SP(s, buf, 2, e, k, env), SP(s, buf, 0, e, k, env), SP(s, buf, 1, e, k, env), spark_d);
+                    has = c.go && resolve_draw(cam, spark_d.y, spark_d.z, spark_d.x, c.wx, c.wy, c.scale, c.alpha, false, false, spark);
                 }
                 wave_replay_rows(fb, atlas, spark, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
             }
@@ -1484,16 +1449,12 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             // the backdrops' texels closer to the workgroups that sample them could buy: render FETCH_SIZE 309 -> 45 MB,
             // render 0.350 -> 0.333 ms)
             const int4 d = S.desc[kTexBackdrop + (PG_ABL(flags, 16) ? 9 : (themes & 0xff))];
-            const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-            const float extra = aspect - 1.0f;
-            v.bg = BgDraw{d, -bgshift * extra, 0.0f, 64.0f * kUnitPx / d.z};  // coinrun.cpp:459-464
-            const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;  // tilemap.cpp:294-304
-            const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-            const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-            v.x0 = static_cast<int>(floorf(vx));
-            v.y0 = static_cast<int>(floorf(vy));
-            v.cols = static_cast<int>(ceilf(vx + vw)) - v.x0 + 1;
-            v.rows = static_cast<int>(ceilf(vy + vh)) - v.y0 + 1;
+            v.bg = backdrop_draw(d, bgshift);  // coinrun.cpp:459-464
+            const TileWindow win = tile_window(cam);  // tilemap.cpp:294-304
+            v.x0 = win.x0;
+            v.y0 = win.y0;
+            v.cols = win.x1 - win.x0 + 1;
+            v.rows = win.y1 - win.y0 + 1;
             const int4 tile_desc = S.desc[kTexMid];  // every tile texture is 128×128 (checked at make time)
             v.tw = tile_desc.y;
             v.th = tile_desc.z;
@@ -1510,12 +1471,7 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             int soft = 0;
 #pragma unroll
             for (int k = 0; k < 8; k++) {
-                int tex = kTexCrate + (k - kSlotCrate);
-                if (k == kSlotTop) tex = kTexTop + ground_theme;
-                if (k == kSlotMid) tex = kTexMid + ground_theme;
-                if (k == kSlotLavaTop) tex = kTexLavaTop;
-                if (k == kSlotLava) tex = kTexLava;
-                const int4 kd = S.desc[tex];
+                const int4 kd = S.desc[kind_tex(k, ground_theme)];
                 P.meta[e][PM_KINDS + k] = static_cast<uint32_t>(kd.x) * 4u;
                     if (kd.w != 0) soft |= 1 << k;
             }
@@ -1601,52 +1557,23 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             const bool valid = q < cnt_a + cnt_b;
             const PrepEnv& pe = S.env[e];
             const int n_parts = pe.n_mob * kSparks;
-            PrepDraw p{false, false, false, kTexSpark, 0.0f, 0.0f, 1.0f, 1.0f};
+            DrawCall p = kNoDraw;
             if (valid && slot < n_parts) {  // System_Particles::render (common_systems.cpp:315-337)
                 const int m = slot / kSparks, k = slot - m * kSparks;
                 const int ent = S.order[e][0][m];
                 const float life = SP(s, pe.buf, 2, ent, k, env);
                 const float px = SP(s, pe.buf, 0, ent, k, env), py = SP(s, pe.buf, 1, ent, k, env);
-                if (life > 0.0f) {
-                    const int4 spark_d = S.desc[kTexSpark];
-                    const float lr = (5.0f - life) / 5.0f;
-                    p.alpha = 0.5f * (1.0f - lr);
-                    const float scale = 0.45f * (0.4f * lr + 0.6f);
-                    const float oy = -lr * 0.17f;
-                    p.wx = px * kUnitPx - 0.5f * spark_d.y * scale;
-                    p.wy = (py + oy) * kUnitPx - 0.5f * spark_d.z * scale;
-                    p.scale = scale * kUnitPx / static_cast<float>(spark_d.y);
-                    p.go = true;
-                }
+                p = spark_draw(life, px, py, S.desc[kTexSpark]);
             } else if (valid && slot < n_parts + pe.n_sprites) {  // System_Sprite_Render::render (:41-63)
                 const int ent = S.order[e][1][slot - n_parts];
                 const int dyn = DB(s, pe.buf, ent, env);
                 const int tex0 = EB(s, EB_TEX, ent, env);
                 const float ex = DF(s, pe.buf, DF_X, ent, env), ey = EY(s, ent, env);
-                if (dyn & kDynTexSet) {
-                    p.tex = tex0 + ((dyn & kDynFrame) ? 1 : 0);
-                    const float scale = 1.0f * 1.0f;
-                    p.wx = (ex + -0.5f) * kUnitPx;
-                    p.wy = (ey + -0.5f) * kUnitPx;
-                    p.scale = scale * kUnitPx / static_cast<float>(S.desc[p.tex].y);
-                    p.flip_h = (dyn & kDynFlip) != 0;
-                    p.go = true;
-                }
+                const int tex = sprite_tex(tex0, dyn);
+                p = sprite_draw(dyn, ex, ey, tex, S.desc[tex]);
             } else if (valid) {  // the agent (:254-278)
-                const bool ground = (pe.sflags & kFlagGround) != 0;
-                if (fabsf(pe.avx) < 0.01f && ground)
-                    p.tex = kTexStand + pe.alien;
-                else if (!ground)
-                    p.tex = kTexJump + pe.alien;
-                else if (pe.aphase > 0.5f)
-                    p.tex = kTexWalk2 + pe.alien;
-                else
-                    p.tex = kTexWalk1 + pe.alien;
-                p.wx = (pe.ax - 0.5f) * kUnitPx;
-                p.wy = (pe.ay - 2.0f) * kUnitPx;
-                p.scale = kUnitPx / static_cast<float>(S.desc[p.tex].y);
-                p.flip_h = (pe.sflags & kFlagForward) == 0;
-                p.go = true;
+                const int tex = agent_tex(pe.sflags, pe.avx, pe.aphase, pe.alien);
+                p = agent_draw(pe.sflags, pe.ax, pe.ay, tex, S.desc[tex]);
             }
             prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane);
         }
@@ -1722,16 +1649,11 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     const int backdrop = themes & 0xff, alien = (themes >> 8) & 0xff, ground_theme = (themes >> 16) & 0xff;
     const uint8_t* tiles = s.tiles + size_t(env) * (W * H);
     P.clear();
-    {
-        const int4 d = P.desc(kTexBackdrop + backdrop);
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        P.draw(kTexBackdrop + backdrop, -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z);
-    }
-    int x0, y0, x1, y1;
-    P.window(x0, y0, x1, y1);
-    for (int y = y0; y <= y1; y++)
-        for (int x = x0; x <= x1; x++) {
+    const BgDraw bg = backdrop_draw(P.desc(kTexBackdrop + backdrop), SF(s, F_BGSHIFT, env));
+    P.draw(kTexBackdrop + backdrop, bg.px, bg.py, bg.scale);
+    const TileWindow win = P.window();
+    for (int y = win.y0; y <= win.y1; y++)
+        for (int x = win.x0; x <= win.x1; x++) {
             const int ty = H - 1 - y;
             int t_id = kWallMid, crate = 0;
             if (x >= 0 && ty >= 0 && x < W && ty < H) {
@@ -1740,52 +1662,24 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
                 crate = raw >> 4;
             }
             if (t_id == kEmpty) continue;
-            const int tex = t_id == kWallMid   ? kTexMid + ground_theme
-                            : t_id == kWallTop ? kTexTop + ground_theme
-                            : t_id == kLavaMid ? kTexLava
-                            : t_id == kLavaTop ? kTexLavaTop
-                                               : kTexCrate + crate;
+            const int tex = tile_tex(t_id, crate, ground_theme);
             P.draw(tex, x * kUnitPx, y * kUnitPx, kUnitPx / P.desc(tex).y);
         }
     const int n_mob = SI(s, I_NMOB, env);
     for (int m = 0; m < n_mob; m++) {  // particles, owners in the particle system's set order
         const int e = EB(s, EB_SPARK_ORDER, m, env);
-        for (int k = 0; k < kSparks; k++) {
-            const float life = SP(s, buf, 2, e, k, env);
-            if (life <= 0.0f) continue;
-            const int4 d = P.desc(kTexSpark);
-            const float lr = (5.0f - life) / 5.0f;
-            const float alpha = 0.5f * (1.0f - lr);
-            const float scale = 0.45f * (0.4f * lr + 0.6f);
-            const float oy = -lr * 0.17f;
-            P.draw(kTexSpark, SP(s, buf, 0, e, k, env) * kUnitPx - 0.5f * d.y * scale,
-                   (SP(s, buf, 1, e, k, env) + oy) * kUnitPx - 0.5f * d.z * scale, scale * kUnitPx / d.y, alpha);
-        }
+        for (int k = 0; k < kSparks; k++)
+            P.draw(spark_draw(SP(s, buf, 2, e, k, env), SP(s, buf, 0, e, k, env), SP(s, buf, 1, e, k, env), P.desc(kTexSpark)));
     }
     const int n_sprites = (sflags & kFlagListed) ? SI(s, I_NENT, env) : 0;
     for (int k = 0; k < n_sprites; k++) {
         const int e = EB(s, EB_DRAW_ORDER, k, env);
         const int dyn = DB(s, buf, e, env);
-        if (!(dyn & kDynTexSet)) continue;
-        const int tex = EB(s, EB_TEX, e, env) + ((dyn & kDynFrame) ? 1 : 0);
-        const float scale = 1.0f * 1.0f;
-        P.draw(tex, (DF(s, buf, DF_X, e, env) + -0.5f) * kUnitPx, (EY(s, e, env) + -0.5f) * kUnitPx,
-               scale * kUnitPx / P.desc(tex).y, 1.0f, (dyn & kDynFlip) != 0);
+        const int tex = sprite_tex(EB(s, EB_TEX, e, env), dyn);
+        P.draw(sprite_draw(dyn, DF(s, buf, DF_X, e, env), EY(s, e, env), tex, P.desc(tex)));
     }
-    {
-        const bool ground = (sflags & kFlagGround) != 0;
-        int tex;
-        if (fabsf(SF(s, F_AVX, env)) < 0.01f && ground)
-            tex = kTexStand + alien;
-        else if (!ground)
-            tex = kTexJump + alien;
-        else if (SF(s, F_APHASE, env) > 0.5f)
-            tex = kTexWalk2 + alien;
-        else
-            tex = kTexWalk1 + alien;
-        const float px = SF(s, F_AX, env) - 0.5f, py = SF(s, F_AY, env) - 2.0f;
-        P.draw(tex, px * kUnitPx, py * kUnitPx, kUnitPx / P.desc(tex).y, 1.0f, (sflags & kFlagForward) == 0);
-    }
+    const int tex = agent_tex(sflags, SF(s, F_AVX, env), SF(s, F_APHASE, env), alien);
+    P.draw(agent_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), tex, P.desc(tex)));
 }
 
 // One env, one workgroup, a W×H target in global memory: pgv_render_frame.

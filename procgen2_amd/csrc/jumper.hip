@@ -654,6 +654,50 @@ __global__ void __launch_bounds__(64) logic_kernel(State s, const int32_t* actio
 // render_game(true) (jumper.cpp:445-509): one workgroup of two wavefronts per env (pg_render.h).
 constexpr int kGrid = 16;  // 64 px / 4.8 px per tile → at most 16 columns/rows in view
 
+// The draw list of jumper.cpp:445-470, each kind of draw stated once, for render_full, setup_kernel and frame_draws:
+// which texture, then the draw call given that texture's descriptor (x: first texel, y: width, z: height).
+PG_D int tile_tex(int tile, int theme) { return (tile == kWallTop ? kTexTop : kTexMid) + theme; }  // tilemap.cpp:266-280
+// System_Particles::render (common_systems.cpp:285-308); d = kTexPuff's descriptor
+PG_D DrawCall puff_draw(float life, float x, float y, const int4& d) {
+    if (!(life > 0.0f)) return kNoDraw;
+    const float lifespan = 5.0f;
+    const float life_ratio = (lifespan - life) / lifespan;
+    const float alpha = 0.5f * (1.0f - life_ratio);
+    const float scale = 0.45f * (0.4f * life_ratio + 0.6f);
+    const float offset_y = -life_ratio * 0.17f;
+    return DrawCall{true, false, false, kTexPuff, x * kUnitPx - 0.5f * d.y * scale, (y + offset_y) * kUnitPx - 0.5f * d.z * scale,
+                    scale * kUnitPx / d.y, alpha, 0.0f};
+}
+// the positive-z sprites (:26-48) by their id in the draw order: 0 = the carrot, at the goal; 2 + j = spike j, in its `cell`
+PG_D int sprite_tex(int id) { return id == 0 ? kTexCarrot : kTexSpike; }
+PG_D DrawCall sprite_draw(int id, float gx, float gy, int cell, const int4& d) {
+    float scale, wx, wy;
+    if (id == 0) {
+        scale = 1.0f * 1.0f;
+        wx = (gx + -0.5f) * kUnitPx;
+        wy = (gy + -0.5f) * kUnitPx;
+    } else {
+        scale = 1.0f * 0.4f;
+        wx = (cell_x(cell) + -0.25f) * kUnitPx;
+        wy = (cell_y(cell) + -0.25f) * kUnitPx;
+    }
+    return DrawCall{true, false, false, sprite_tex(id), wx, wy, scale * kUnitPx / d.y, 1.0f, 0.0f};
+}
+// the bunny (:204-247): larger and shifted in its jump pose
+PG_D int bunny_tex(int sflags, float avx, float phase) {
+    const bool ground = (sflags & kFlagGround) != 0;
+    if (fabsf(avx) < 0.01f && ground) return kTexStand;
+    if (!ground) return kTexJump;
+    return phase > 0.5f ? kTexWalk2 : kTexWalk1;
+}
+PG_D DrawCall bunny_draw(int sflags, float ax, float ay, int tex, const int4& d) {
+    const bool jump = tex == kTexJump;
+    const float agent_scale = jump ? 0.6f : 0.5f, off_x = jump ? -0.05f : 0.0f, off_y = jump ? 0.25f : 0.2f;
+    const float px = ax - 0.25f, py = ay - 1.0f;
+    return DrawCall{true, (sflags & kFlagForward) == 0, false, tex, (px + off_x) * kUnitPx, (py + off_y) * kUnitPx,
+                    kUnitPx / d.y * agent_scale, 1.0f, 0.0f};
+}
+
 // The complete frame of one env by its workgroup, set-up included: the frames the pre-pass marks fat, the draw-list
 // replay (flags bit 0) and kDebugNoPrepass.
 PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, int flags, int env, uint32_t* fb,
@@ -678,28 +722,14 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     }
 
     int bg_soft = 0;  // the backdrop has texels that are not opaque (descriptor .w)
-    int4 bg_d;  // the background draw, jumper.cpp:459-464: texture, world position, scale — each wave resolves the axis it needs (pg_render.h BgAxis)
-    float bg_px, bg_py, bg_sc;
-    {
-        const int4 d = descs.uniform(kTexBackdrop + backdrop);
-        bg_soft = d.w;
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        bg_d = d;
-        bg_px = -SF(s, F_BGSHIFT, env) * extra;
-        bg_py = 0.0f;
-        bg_sc = 64.0f * kUnitPx / d.z;
-    }
-    // tile window (tilemap.cpp:255-264)
-    const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
-    const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-    const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-    const int x0 = static_cast<int>(floorf(vx)), y0 = static_cast<int>(floorf(vy));
-    const int x1 = static_cast<int>(ceilf(vx + vw)), y1 = static_cast<int>(ceilf(vy + vh));
-    const int cols = x1 - x0 + 1, rows = y1 - y0 + 1, cells = cols * rows;
+    // the background draw, jumper.cpp:459-464 — each wave resolves the axis it needs (pg_render.h BgAxis)
+    const BgDraw bg_draw = backdrop_draw(descs.uniform(kTexBackdrop + backdrop), SF(s, F_BGSHIFT, env));
+    bg_soft = bg_draw.desc.w;
+    const TileWindow win = tile_window(cam);  // tilemap.cpp:255-264
+    const int x0 = win.x0, y0 = win.y0;
+    const int cols = win.x1 - x0 + 1, rows = win.y1 - y0 + 1, cells = cols * rows;
     const int4 top_d = descs.uniform(kTexTop + theme), mid_d = descs.uniform(kTexMid + theme);
 
-    const BgDraw bg_draw{bg_d, bg_px, bg_py, bg_sc};
     BgAxis bga{};  // this wave's axis of it (wave 0: x, wave 1: y), resolved along with the tile spans
     bool composed = false;
     const bool two = top_d.z != mid_d.z;  // the brown cap tile is 64×53 (see climber.hip)
@@ -720,7 +750,7 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     }
     if (!composed) {  // draw-list replay (tilemap.cpp:266-280)
         wave_clear(fb, lane, half, halves);
-        const bool has_bg = resolve_draw(cam, bg_d.y, bg_d.z, bg_d.x, bg_px, bg_py, bg_sc, 1.0f, false, false, mine);
+        const bool has_bg = resolve_draw(cam, bg_draw.desc.y, bg_draw.desc.z, bg_draw.desc.x, bg_draw.px, bg_draw.py, bg_draw.scale, 1.0f, false, false, mine);
         wave_replay(fb, atlas, mine, has_bg ? 1ull : 0ull, lane, half, halves);
         for (int base = 0; base < cells; base += 64) {
             const int cell = base + lane;
@@ -749,64 +779,20 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
         const bool is_hud = hud >= 1 && hud <= 3;
         int id = 0;
         if (is_draw) id = DRW(s, lane - kPuffs, env);
-        const float avx = SF(s, F_AVX, env), phase = SF(s, F_APHASE, env);
-        const bool ground = (sflags & kFlagGround) != 0;
-        int bunny_tex;
-        float agent_scale = 0.5f, off_x = 0.0f, off_y = 0.2f;
-        if (fabsf(avx) < 0.01f && ground) {
-            bunny_tex = kTexStand;
-        } else if (!ground) {
-            bunny_tex = kTexJump;
-            agent_scale = 0.6f;
-            off_x = -0.05f;
-            off_y = 0.25f;
-        } else if (phase > 0.5f) {
-            bunny_tex = kTexWalk2;
-        } else {
-            bunny_tex = kTexWalk1;
-        }
         int want_tex = kTexPuff;
-        if (is_draw) want_tex = id == 0 ? kTexCarrot : kTexSpike;
-        if (is_bunny) want_tex = bunny_tex;
+        if (is_draw) want_tex = sprite_tex(id);
+        if (is_bunny) want_tex = bunny_tex(sflags, SF(s, F_AVX, env), SF(s, F_APHASE, env));
         if (is_hud) want_tex = kTexCircle + (hud - 1);
         const int4 d = descs.at(want_tex);
-        bool has = false, go = false, flip = false;
-        float wx = 0.0f, wy = 0.0f, scale = 1.0f, alpha = 1.0f;
-        if (is_puff) {
-            if (puff_life > 0.0f) {
-                const float lifespan = 5.0f;
-                const float life_ratio = (lifespan - puff_life) / lifespan;
-                alpha = 0.5f * (1.0f - life_ratio);
-                const float size = 0.45f * (0.4f * life_ratio + 0.6f);
-                const float offset_y = -life_ratio * 0.17f;
-                wx = puff_x * kUnitPx - 0.5f * d.y * size;
-                wy = (puff_y + offset_y) * kUnitPx - 0.5f * d.z * size;
-                scale = size * kUnitPx / d.y;
-                go = true;
-            }
-        } else if (is_draw) {
-            float sc;
-            if (id == 0) {
-                sc = 1.0f * 1.0f;
-                wx = (SF(s, F_GX, env) + -0.5f) * kUnitPx;
-                wy = (SF(s, F_GY, env) + -0.5f) * kUnitPx;
-            } else {
-                const int cell = SPK(s, id - 2, env);
-                sc = 1.0f * 0.4f;
-                wx = (cell_x(cell) + -0.25f) * kUnitPx;
-                wy = (cell_y(cell) + -0.25f) * kUnitPx;
-            }
-            scale = sc * kUnitPx / d.y;
-            go = true;
-        } else if (is_bunny) {
-            const float px = SF(s, F_AX, env) - 0.25f, py = SF(s, F_AY, env) - 1.0f;
-            wx = (px + off_x) * kUnitPx;
-            wy = (py + off_y) * kUnitPx;
-            scale = kUnitPx / d.y * agent_scale;
-            flip = (sflags & kFlagForward) == 0;
-            go = true;
-        }
-        if (go) has = resolve_draw(cam, d.y, d.z, d.x, wx, wy, scale, alpha, flip, false, mine);
+        DrawCall c = kNoDraw;
+        if (is_puff)
+            c = puff_draw(puff_life, puff_x, puff_y, d);
+        else if (is_draw)
+            c = sprite_draw(id, SF(s, F_GX, env), SF(s, F_GY, env), id == 0 ? 0 : SPK(s, id - 2, env), d);
+        else if (is_bunny)
+            c = bunny_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), want_tex, d);
+        bool has = false;
+        if (c.go) has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, c.alpha, c.flip_h, false, mine);
         if (is_hud) {  // circle, needle and bar differ in their parameters only (store_compass worked them out)
             const float width = 64.0f, compass_size = 200.0f, offset_x = -32.0f, offset_y = 32.0f;
             float sx, sy, sw, sh;
@@ -848,17 +834,9 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
     } else {  // (more spikes than a wave has lanes for: a pass per kind)
         {  // System_Particles::render (common_systems.cpp:285-308)
             const int4 d = descs.uniform(kTexPuff);
+            const DrawCall c = lane < kPuffs ? puff_draw(puff_life, puff_x, puff_y, d) : kNoDraw;
             bool has = false;
-            if (lane < kPuffs && puff_life > 0.0f) {
-                const float lifespan = 5.0f;
-                const float life_ratio = (lifespan - puff_life) / lifespan;
-                const float alpha = 0.5f * (1.0f - life_ratio);
-                const float scale = 0.45f * (0.4f * life_ratio + 0.6f);
-                const float offset_y = -life_ratio * 0.17f;
-                has = resolve_draw(cam, d.y, d.z, d.x, puff_x * kUnitPx - 0.5f * d.y * scale,
-                                   (puff_y + offset_y) * kUnitPx - 0.5f * d.z * scale, scale * kUnitPx / d.y, alpha, false,
-                                   false, mine);
-            }
+            if (c.go) has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, c.alpha, false, false, mine);
             wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
         }
         // positive-z sprites (common_systems.cpp:26-48): carrot and spikes in draw order
@@ -870,47 +848,21 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
                 id = DRW(s, k, env);
                 has = true;
             }
-            const int4 d = descs.at(id == 0 ? kTexCarrot : kTexSpike);
+            const int4 d = descs.at(sprite_tex(id));
             if (has) {  // carrot and spikes differ in their parameters only: pick per lane, resolve once
-                float wx, wy, scale;
-                if (id == 0) {
-                    scale = 1.0f * 1.0f;
-                    wx = (SF(s, F_GX, env) + -0.5f) * kUnitPx;
-                    wy = (SF(s, F_GY, env) + -0.5f) * kUnitPx;
-                } else {
-                    const int cell = SPK(s, id - 2, env);
-                    scale = 1.0f * 0.4f;
-                    wx = (cell_x(cell) + -0.25f) * kUnitPx;
-                    wy = (cell_y(cell) + -0.25f) * kUnitPx;
-                }
-                has = resolve_draw(cam, d.y, d.z, d.x, wx, wy, scale * kUnitPx / d.y, 1.0f, false, false, mine);
+                const DrawCall c = sprite_draw(id, SF(s, F_GX, env), SF(s, F_GY, env), id == 0 ? 0 : SPK(s, id - 2, env), d);
+                has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, false, false, mine);
             }
             wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
         }
         {  // lane 0: the bunny (common_systems.cpp:204-247); lanes 1-3: the compass (jumper.cpp:473-509)
-            const float avx = SF(s, F_AVX, env), phase = SF(s, F_APHASE, env);
-            const bool ground = (sflags & kFlagGround) != 0;
-            int want_tex;
-            float agent_scale = 0.5f, off_x = 0.0f, off_y = 0.2f;
-            if (fabsf(avx) < 0.01f && ground) {
-                want_tex = kTexStand;
-            } else if (!ground) {
-                want_tex = kTexJump;
-                agent_scale = 0.6f;
-                off_x = -0.05f;
-                off_y = 0.25f;
-            } else if (phase > 0.5f) {
-                want_tex = kTexWalk2;
-            } else {
-                want_tex = kTexWalk1;
-            }
+            int want_tex = bunny_tex(sflags, SF(s, F_AVX, env), SF(s, F_APHASE, env));
             if (lane >= 1 && lane <= 3) want_tex = kTexCircle + (lane - 1);
             const int4 d = descs.at(want_tex);
             bool has = false;
             if (lane == 0) {
-                const float px = SF(s, F_AX, env) - 0.25f, py = SF(s, F_AY, env) - 1.0f;
-                has = resolve_draw(cam, d.y, d.z, d.x, (px + off_x) * kUnitPx, (py + off_y) * kUnitPx,
-                                   kUnitPx / d.y * agent_scale, 1.0f, (sflags & kFlagForward) == 0, false, mine);
+                const DrawCall c = bunny_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), want_tex, d);
+                has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, c.flip_h, false, mine);
             } else if (lane <= 3) {
                 const float width = 64.0f, compass_size = 200.0f, offset_x = -32.0f, offset_y = 32.0f;
                 const float tx = SF(s, F_TOGX, env), ty = SF(s, F_TOGY, env);
@@ -1050,16 +1002,12 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             // the render kernel's FETCH_SIZE is, and what the kernel would gain if it were not there)
             const int backdrop = PG_ABL(flags, 16) ? 9 : (themes & 0xff), theme = (themes >> 8) & 0xff;
             const int4 d = S.desc[kTexBackdrop + backdrop];
-            const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-            const float extra = aspect - 1.0f;
-            v.bg = BgDraw{d, -bgshift * extra, 0.0f, 64.0f * kUnitPx / d.z};  // jumper.cpp:459-464
-            const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;  // tilemap.cpp:255-264
-            const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-            const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-            v.x0 = static_cast<int>(floorf(vx));
-            v.y0 = static_cast<int>(floorf(vy));
-            v.cols = static_cast<int>(ceilf(vx + vw)) - v.x0 + 1;
-            v.rows = static_cast<int>(ceilf(vy + vh)) - v.y0 + 1;
+            v.bg = backdrop_draw(d, bgshift);  // jumper.cpp:459-464
+            const TileWindow win = tile_window(cam);  // tilemap.cpp:255-264
+            v.x0 = win.x0;
+            v.y0 = win.y0;
+            v.cols = win.x1 - win.x0 + 1;
+            v.rows = win.y1 - win.y0 + 1;
             const int4 top_d = S.desc[kTexTop + theme], mid_d = S.desc[kTexMid + theme];
             const bool two = top_d.z != mid_d.z;  // the brown cap tile is 64×53 (see climber.hip)
             v.tw = mid_d.y;
@@ -1135,64 +1083,20 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
             const int slot = is_b ? q - cnt_a : q;
             const bool valid = q < cnt_a + cnt_b;
             const PrepEnv& pe = S.env[e];
-            PrepDraw p{false, false, false, kTexPuff, 0.0f, 0.0f, 1.0f, 1.0f};
-            float num = kUnitPx, post = 1.0f;  // scale = num / texture width * post (one division for every kind)
+            DrawCall p = kNoDraw;
             if (valid && slot < kPuffs) {
                 const float life = PF(s, PF_LIFE, slot, env), px = PF(s, PF_X, slot, env), py = PF(s, PF_Y, slot, env);
-                if (life > 0.0f) {
-                    const int4 d = S.desc[kTexPuff];
-                    const float lifespan = 5.0f;
-                    const float life_ratio = (lifespan - life) / lifespan;
-                    p.alpha = 0.5f * (1.0f - life_ratio);
-                    const float size = 0.45f * (0.4f * life_ratio + 0.6f);
-                    const float offset_y = -life_ratio * 0.17f;
-                    p.wx = px * kUnitPx - 0.5f * d.y * size;
-                    p.wy = (py + offset_y) * kUnitPx - 0.5f * d.z * size;
-                    num = size * kUnitPx;
-                    p.go = true;
-                }
+                p = puff_draw(life, px, py, S.desc[kTexPuff]);
             } else if (valid && slot < kPuffs + pe.n_draw) {
                 const int k = slot - kPuffs;
                 const int id = (S.draw_ids[e][k >> 2] >> (8 * (k & 3))) & 0xffu;
-                float sc;
-                if (id == 0) {
-                    p.tex = kTexCarrot;
-                    sc = 1.0f * 1.0f;
-                    p.wx = (pe.gx + -0.5f) * kUnitPx;
-                    p.wy = (pe.gy + -0.5f) * kUnitPx;
-                } else {
-                    const int j = id - 2;
-                    const int cell = (S.spike_cells[e][j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                    p.tex = kTexSpike;
-                    sc = 1.0f * 0.4f;
-                    p.wx = (cell_x(cell) + -0.25f) * kUnitPx;
-                    p.wy = (cell_y(cell) + -0.25f) * kUnitPx;
-                }
-                num = sc * kUnitPx;
-                p.go = true;
+                const int j = id == 0 ? 0 : id - 2;
+                const int cell = (S.spike_cells[e][j >> 1] >> (16 * (j & 1))) & 0xffffu;
+                p = sprite_draw(id, pe.gx, pe.gy, cell, S.desc[sprite_tex(id)]);
             } else if (valid) {
-                const bool ground = (pe.sflags & kFlagGround) != 0;
-                float agent_scale = 0.5f, off_x = 0.0f, off_y = 0.2f;
-                if (fabsf(pe.avx) < 0.01f && ground) {
-                    p.tex = kTexStand;
-                } else if (!ground) {
-                    p.tex = kTexJump;
-                    agent_scale = 0.6f;
-                    off_x = -0.05f;
-                    off_y = 0.25f;
-                } else if (pe.aphase > 0.5f) {
-                    p.tex = kTexWalk2;
-                } else {
-                    p.tex = kTexWalk1;
-                }
-                const float px = pe.ax - 0.25f, py = pe.ay - 1.0f;
-                p.wx = (px + off_x) * kUnitPx;
-                p.wy = (py + off_y) * kUnitPx;
-                post = agent_scale;  // kUnitPx / d.y * agent_scale
-                p.flip_h = (pe.sflags & kFlagForward) == 0;
-                p.go = true;
+                const int tex = bunny_tex(pe.sflags, pe.avx, pe.aphase);
+                p = bunny_draw(pe.sflags, pe.ax, pe.ay, tex, S.desc[tex]);
             }
-            p.scale = num / S.desc[p.tex].y * post;
             prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane, cover);
         }
         prep_draws_flush(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, lane, cover);
@@ -1368,67 +1272,23 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     const int n_draw = (sflags & kFlagListed) ? SI(s, I_NSPIKES, env) + 1 : 0;
     const uint8_t* tiles = s.tiles + size_t(env) * kTileStride;
     P.clear();
-    {
-        const int4 d = P.desc(kTexBackdrop + backdrop);
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        P.draw(kTexBackdrop + backdrop, -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z);
-    }
-    int x0, y0, x1, y1;
-    P.window(x0, y0, x1, y1);
-    for (int y = y0; y <= y1; y++)
-        for (int x = x0; x <= x1; x++) {
+    const BgDraw bg = backdrop_draw(P.desc(kTexBackdrop + backdrop), SF(s, F_BGSHIFT, env));
+    P.draw(kTexBackdrop + backdrop, bg.px, bg.py, bg.scale);
+    const TileWindow win = P.window();
+    for (int y = win.y0; y <= win.y1; y++)
+        for (int x = win.x0; x <= win.x1; x++) {
             const int tile = Win::direct(tiles, x, y);
             if (!is_wall(tile)) continue;
-            const int tex = (tile == kWallTop ? kTexTop : kTexMid) + theme;
+            const int tex = tile_tex(tile, theme);
             P.draw(tex, x * kUnitPx, y * kUnitPx, kUnitPx / P.desc(tex).y);
         }
-    for (int k = 0; k < kPuffs; k++) {
-        const float life = PF(s, PF_LIFE, k, env);
-        if (life <= 0.0f) continue;
-        const int4 d = P.desc(kTexPuff);
-        const float lifespan = 5.0f;
-        const float life_ratio = (lifespan - life) / lifespan;
-        const float alpha = 0.5f * (1.0f - life_ratio);
-        const float scale = 0.45f * (0.4f * life_ratio + 0.6f);
-        const float offset_y = -life_ratio * 0.17f;
-        P.draw(kTexPuff, PF(s, PF_X, k, env) * kUnitPx - 0.5f * d.y * scale,
-               (PF(s, PF_Y, k, env) + offset_y) * kUnitPx - 0.5f * d.z * scale, scale * kUnitPx / d.y, alpha);
-    }
+    for (int k = 0; k < kPuffs; k++) P.draw(puff_draw(PF(s, PF_LIFE, k, env), PF(s, PF_X, k, env), PF(s, PF_Y, k, env), P.desc(kTexPuff)));
     for (int k = 0; k < n_draw; k++) {
         const int id = DRW(s, k, env);
-        if (id == 0) {
-            const float scale = 1.0f * 1.0f;
-            P.draw(kTexCarrot, (SF(s, F_GX, env) + -0.5f) * kUnitPx, (SF(s, F_GY, env) + -0.5f) * kUnitPx,
-                   scale * kUnitPx / P.desc(kTexCarrot).y);
-        } else {
-            const int cell = SPK(s, id - 2, env);
-            const float scale = 1.0f * 0.4f;
-            P.draw(kTexSpike, (cell_x(cell) + -0.25f) * kUnitPx, (cell_y(cell) + -0.25f) * kUnitPx,
-                   scale * kUnitPx / P.desc(kTexSpike).y);
-        }
+        P.draw(sprite_draw(id, SF(s, F_GX, env), SF(s, F_GY, env), id == 0 ? 0 : SPK(s, id - 2, env), P.desc(sprite_tex(id))));
     }
-    {
-        const float avx = SF(s, F_AVX, env), phase = SF(s, F_APHASE, env);
-        const bool ground = (sflags & kFlagGround) != 0;
-        int tex;
-        float agent_scale = 0.5f, off_x = 0.0f, off_y = 0.2f;
-        if (fabsf(avx) < 0.01f && ground) {
-            tex = kTexStand;
-        } else if (!ground) {
-            tex = kTexJump;
-            agent_scale = 0.6f;
-            off_x = -0.05f;
-            off_y = 0.25f;
-        } else if (phase > 0.5f) {
-            tex = kTexWalk2;
-        } else {
-            tex = kTexWalk1;
-        }
-        const float px = SF(s, F_AX, env) - 0.25f, py = SF(s, F_AY, env) - 1.0f;
-        P.draw(tex, (px + off_x) * kUnitPx, (py + off_y) * kUnitPx, kUnitPx / P.desc(tex).y * agent_scale, 1.0f,
-               (sflags & kFlagForward) == 0);
-    }
+    const int tex = bunny_tex(sflags, SF(s, F_AVX, env), SF(s, F_APHASE, env));
+    P.draw(bunny_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), tex, P.desc(tex)));
     {   // compass (jumper.cpp:473-509): sized by the base zoom, not by the window
         const float width = fw, compass_size = 200.0f, offset_x = -32.0f, offset_y = 32.0f;
         const float tx = SF(s, F_TOGX, env), ty = SF(s, F_TOGY, env);

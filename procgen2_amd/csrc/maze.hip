@@ -230,12 +230,20 @@ struct Window {
     int x0, y0, cols, rows;
 };
 PG_D Window window_of(const Camera& cam) {
-    const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
-    const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-    const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-    const int x0 = static_cast<int>(floorf(vx)), y0 = static_cast<int>(floorf(vy));
-    const int x1 = static_cast<int>(ceilf(vx + vw)), y1 = static_cast<int>(ceilf(vy + vh));
-    return Window{x0, y0, x1 - x0 + 1, y1 - y0 + 1};
+    const TileWindow w = tile_window(cam);
+    return Window{w.x0, w.y0, w.x1 - w.x0 + 1, w.y1 - w.y0 + 1};
+}
+// The draw list of maze.cpp:402-420 after the walls, each kind of draw stated once, for setup_kernel, render_kernel and
+// frame_draws, given the texture's descriptor (y: width): the cheese sprite (tilemap.cpp:88: offset (-0.48,-0.5), scale
+// 0.95, z = 1), once it is listed; the mouse (common_systems.cpp:138-150), flipped when it faces forward.
+PG_D DrawCall cheese_draw(int sflags, float gx, float gy, const int4& d) {
+    const float scale = 1.0f * 0.95f;
+    return DrawCall{(sflags & kFlagListed) != 0, false, false, kTexCheese, (gx + -0.48f) * kUnitPx, (gy + -0.5f) * kUnitPx,
+                    scale * kUnitPx / d.y, 1.0f, 0.0f};
+}
+PG_D DrawCall mouse_draw(int sflags, float ax, float ay, const int4& d) {
+    return DrawCall{true, (sflags & kFlagForward) != 0, false, kTexMouse, (ax + -0.5f) * kUnitPx, (ay + -0.5f) * kUnitPx,
+                    kUnitPx / d.y * 1.0f, 1.0f, 0.0f};
 }
 PG_D float zoom_of_obs() { return 64.0f / (kUnitPx * static_cast<float>(kVisible)); }  // maze.cpp:397-400
 
@@ -267,12 +275,10 @@ __global__ void __launch_bounds__(256) setup_kernel(State s, AtlasView atlas) {
         const bool cheese = item == 0;
         const int sflags = SI(s, I_FLAGS, env);
         const int4 d = atlas.desc[cheese ? kTexCheese : kTexMouse];
-        const float wx = cheese ? (SF(s, F_GX, env) + -0.48f) * kUnitPx : (SF(s, F_AX, env) + -0.5f) * kUnitPx;
-        const float wy = cheese ? (SF(s, F_GY, env) + -0.5f) * kUnitPx : (SF(s, F_AY, env) + -0.5f) * kUnitPx;
-        const float scale = cheese ? (1.0f * 0.95f) * kUnitPx / d.y : kUnitPx / d.y * 1.0f;
-        bool has = cheese ? (sflags & kFlagListed) != 0 : true;
+        const DrawCall c = cheese ? cheese_draw(sflags, SF(s, F_GX, env), SF(s, F_GY, env), d) : mouse_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), d);
+        bool has = c.go;
         Blit b;
-        if (has) has = resolve_draw(cam, d.y, d.z, d.x, wx, wy, scale, 1.0f, !cheese && (sflags & kFlagForward) != 0, false, b);
+        if (has) has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, c.flip_h, false, b);
         BlitWords w{};
         if (has) w = blit_pack(b);
         uint2* at = reinterpret_cast<uint2*>(s.prep.draws + (size_t(env) * 2 + item) * kBlitWords);
@@ -282,9 +288,8 @@ __global__ void __launch_bounds__(256) setup_kernel(State s, AtlasView atlas) {
     } else {
         const int axis = item - 2;
         const int4 d = atlas.desc[kTexFloor + SI(s, I_BG, env)];
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        const BgAxis a = bg_axis(cam, d, -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z, axis);
+        const BgDraw bg = backdrop_draw(d, SF(s, F_BGSHIFT, env));
+        const BgAxis a = bg_axis(cam, d, bg.px, bg.py, bg.scale, axis);
         uint4* at = reinterpret_cast<uint4*>(s.prep.bg + size_t(env) * 8 + axis * 4);
         *at = make_uint4(pack_halves(a.d0, a.dn), pack_halves(a.s0, a.sn), static_cast<uint32_t>(a.tex_off), static_cast<uint32_t>(a.tex_w));
     }
@@ -310,23 +315,15 @@ __global__ void __launch_bounds__(128, 4) render_kernel(State s, AtlasView atlas
     Blit mine;
 
     int bg_soft = 0;  // the backdrop has texels that are not opaque (descriptor .w)
-    int4 bg_d;  // the background draw, background (maze.cpp:402-408): texture, world position, scale — each wave resolves the axis it needs (pg_render.h BgAxis)
-    float bg_px, bg_py, bg_sc;
-    {
-        const int4 d = atlas.desc[kTexFloor + SI(s, I_BG, env)];
-        bg_soft = d.w;
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        bg_d = d;
-        bg_px = -SF(s, F_BGSHIFT, env) * extra;
-        bg_py = 0.0f;
-        bg_sc = 64.0f * kUnitPx / d.z;
-    }
+    // the background draw (maze.cpp:402-408) — each wave resolves the axis it needs (pg_render.h BgAxis)
+    const BgDraw bg_draw = backdrop_draw(atlas.desc[kTexFloor + SI(s, I_BG, env)], SF(s, F_BGSHIFT, env));
+    const int4& bg_d = bg_draw.desc;
+    const float bg_px = bg_draw.px, bg_py = bg_draw.py, bg_sc = bg_draw.scale;
+    bg_soft = bg_d.w;
     const Window win = window_of(cam);
     const int x0 = win.x0, y0 = win.y0, cols = win.cols, rows = win.rows, cells = cols * rows;
     const int4 wall = atlas.desc[kTexWall];
 
-    const BgDraw bg_draw{bg_d, bg_px, bg_py, bg_sc};
     BgAxis bga{};  // this wave's axis of it (wave 0: x, wave 1: y), resolved along with the tile spans
     bool composed = false;
     if (!(flags & 1) && cols <= kGrid && rows <= kGrid) {
@@ -379,12 +376,9 @@ __global__ void __launch_bounds__(128, 4) render_kernel(State s, AtlasView atlas
         // only: one pass through resolve_draw, one replay, in this order.
         const bool cheese = lane == 0;
         const int4 d = atlas.desc[cheese ? kTexCheese : kTexMouse];
-        const float wx = cheese ? (SF(s, F_GX, env) + -0.48f) * kUnitPx : (SF(s, F_AX, env) + -0.5f) * kUnitPx;
-        const float wy = cheese ? (SF(s, F_GY, env) + -0.5f) * kUnitPx : (SF(s, F_AY, env) + -0.5f) * kUnitPx;
-        const float scale = cheese ? (1.0f * 0.95f) * kUnitPx / d.y : kUnitPx / d.y * 1.0f;
-        bool has = cheese ? (sflags & kFlagListed) != 0 : lane == 1;
-        if (has)
-            has = resolve_draw(cam, d.y, d.z, d.x, wx, wy, scale, 1.0f, !cheese && (sflags & kFlagForward) != 0, false, mine);
+        const DrawCall c = cheese ? cheese_draw(sflags, SF(s, F_GX, env), SF(s, F_GY, env), d) : mouse_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), d);
+        bool has = c.go && lane < 2;
+        if (has) has = resolve_draw(cam, d.y, d.z, d.x, c.wx, c.wy, c.scale, 1.0f, c.flip_h, false, mine);
         wave_replay_rows(fb, atlas, mine, __ballot(has), lane, half * (kObsH / halves), (half + 1) * (kObsH / halves));
     }
     // each wave stores the rows it owns (pg_render.h wave_replay_rows): no barrier
@@ -400,24 +394,15 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     const int sflags = SI(s, I_FLAGS, env);
     const uint8_t* tiles = s.tiles + size_t(env) * kTileStride;
     P.clear();
-    {
-        const int4 d = P.desc(kTexFloor + SI(s, I_BG, env));
-        const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
-        const float extra = aspect - 1.0f;
-        P.draw(kTexFloor + SI(s, I_BG, env), -SF(s, F_BGSHIFT, env) * extra, 0.0f, 64.0f * kUnitPx / d.z);
-    }
-    int x0, y0, x1, y1;
-    P.window(x0, y0, x1, y1);
-    for (int y = y0; y <= y1; y++)
-        for (int x = x0; x <= x1; x++)
+    const int floor_tex = kTexFloor + SI(s, I_BG, env);
+    const BgDraw bg = backdrop_draw(P.desc(floor_tex), SF(s, F_BGSHIFT, env));
+    P.draw(floor_tex, bg.px, bg.py, bg.scale);
+    const TileWindow win = P.window();
+    for (int y = win.y0; y <= win.y1; y++)
+        for (int x = win.x0; x <= win.x1; x++)
             if (tile_at(tiles, x, H - 1 - y) != kOpen) P.draw(kTexWall, x * kUnitPx, y * kUnitPx, kUnitPx / P.desc(kTexWall).y);
-    if (sflags & kFlagListed) {
-        const float scale = 1.0f * 0.95f;
-        P.draw(kTexCheese, (SF(s, F_GX, env) + -0.48f) * kUnitPx, (SF(s, F_GY, env) + -0.5f) * kUnitPx,
-               scale * kUnitPx / P.desc(kTexCheese).y);
-    }
-    P.draw(kTexMouse, (SF(s, F_AX, env) + -0.5f) * kUnitPx, (SF(s, F_AY, env) + -0.5f) * kUnitPx,
-           kUnitPx / P.desc(kTexMouse).y * 1.0f, 1.0f, (sflags & kFlagForward) != 0);
+    P.draw(cheese_draw(sflags, SF(s, F_GX, env), SF(s, F_GY, env), P.desc(kTexCheese)));
+    P.draw(mouse_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), P.desc(kTexMouse)));
 }
 
 // One env, one workgroup, a W×H target in global memory: pgv_render_frame.

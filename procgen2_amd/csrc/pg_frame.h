@@ -1,10 +1,11 @@
 // The human-size frame of cenv_render (games/*/<game>.cpp `render_game(false)`): the same draw list as
 // the observation, rasterised at W×H with camera_scale = zoom · W / 64.
 //
-// A game writes its draw list once, as `template <class Painter> frame_draws(State, AtlasView, env, Painter&)`, and
-// reaches the target only through the painter's methods (begin, clear, draw, draw_rotated, screen, window, desc, cam,
-// width / height, lead).  Two painters take it, with one statement of the raster spec between them (pg_raster.h, which
-// the host tests compile too):
+// A game walks its draw list here as `template <class Painter> frame_draws(State, AtlasView, env, Painter&)` — the draws
+// themselves are the game's own statements (pg_geom.h DrawCall), shared with its observation paths — and reaches the
+// target only through the painter's methods (begin, clear, draw, draw_rotated, screen, window, desc, cam, width /
+// height, lead).  Two painters take it, with one statement of the raster spec between them (pg_raster.h, which the
+// host tests compile too):
 //
 //   FramePainter  ONE env, one workgroup, a W×H target of 0x00BBGGRR words in global memory: pgv_render_frame, the
 //                 debugging / viewer path ("a frame per keystroke"), deliberately plain — every draw resolved by all
@@ -93,16 +94,14 @@ struct PainterCalls {
         }
         self().blit(b);
     }
-    // The tile window of System_Tilemap::render (e.g. coinrun/tilemap.cpp:294-304): inclusive cell ranges.
-    PG_D void window(int& x0, int& y0, int& x1, int& y1) const {
-        const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
-        const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
-        const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
-        x0 = static_cast<int>(floorf(vx));
-        y0 = static_cast<int>(floorf(vy));
-        x1 = static_cast<int>(ceilf(vx + vw));
-        y1 = static_cast<int>(ceilf(vy + vh));
+    // One draw of a game's draw list as the game states it (pg_geom.h DrawCall).
+    PG_D void draw(const DrawCall& c) {
+        if (c.go) draw(c.tex, c.wx, c.wy, c.scale, c.alpha, c.flip_h, c.flip_v);
     }
+    PG_D void draw_rotated(const DrawCall& c) {
+        if (c.go) draw_rotated(c.tex, c.wx, c.wy, c.rotation, c.scale, c.alpha);
+    }
+    PG_D TileWindow window() const { return tile_window(cam); }
 };
 
 struct FramePainter : PainterCalls<FramePainter> {

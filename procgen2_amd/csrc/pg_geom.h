@@ -57,6 +57,45 @@ struct Camera {
     float scale;    // gr.camera_scale
 };
 
+// One draw call as a game's draw list states it, before render_texture starts (renderer.cpp:5-7: texture, position,
+// scale, alpha, flips; `rotation` for render_texture_rotated, :84-101); `go` false = no draw call at all.  A game writes
+// each kind of draw once, as a function from loaded values to this; its complete path, its render pre-pass and its
+// frame_draws (pg_frame.h) consume it.
+struct DrawCall {
+    bool go, flip_h, flip_v;
+    int tex;
+    float wx, wy, scale, alpha;
+    float rotation;
+};
+constexpr DrawCall kNoDraw{false, false, false, 0, 0.0f, 0.0f, 1.0f, 1.0f, 0.0f};
+
+// The tile window of System_Tilemap::render (e.g. coinrun/tilemap.cpp:294-304): inclusive cell ranges.
+struct TileWindow {
+    int x0, y0, x1, y1;
+};
+PG_HD TileWindow tile_window(const Camera& cam) {
+    const float vx = (cam.px - cam.sw * 0.5f / cam.scale) * kPxUnit;
+    const float vy = (cam.py - cam.sh * 0.5f / cam.scale) * kPxUnit;
+    const float vw = cam.sw * kPxUnit / cam.scale, vh = cam.sh * kPxUnit / cam.scale;
+    return TileWindow{static_cast<int>(floorf(vx)), static_cast<int>(floorf(vy)), static_cast<int>(ceilf(vx + vw)),
+                      static_cast<int>(ceilf(vy + vh))};
+}
+
+#if defined(__HIPCC__)
+// The background's draw call: texture descriptor (x: first texel, y: width, z: height, w: opacity bits), world position
+// (pixels), scale.  Every game with a backdrop draws it the same way (e.g. coinrun.cpp:459-464): as tall as the 64-unit
+// world, shifted left by bgshift of what its aspect leaves over.
+struct BgDraw {
+    int4 desc;
+    float px, py, scale;
+};
+PG_HD BgDraw backdrop_draw(const int4& d, float bgshift) {
+    const float aspect = static_cast<float>(d.y) / static_cast<float>(d.z);
+    const float extra = aspect - 1.0f;
+    return BgDraw{d, -bgshift * extra, 0.0f, 64.0f * kUnitPx / d.z};
+}
+#endif
+
 constexpr int32_t kFlipH = 1 << 8;
 constexpr int32_t kFlipV = 1 << 9;
 constexpr int32_t kRotated = 1 << 10;

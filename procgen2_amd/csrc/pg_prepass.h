@@ -459,13 +459,6 @@ struct PrepDrawEntry {  // 24 bytes
 struct PrepDrawQueue {
     PrepDrawEntry e[kPrepQueue];
 };
-// What a game's lane knows about its draw before render_texture starts (renderer.cpp:5-7: texture, position, scale,
-// alpha, flips); `go` false = no draw call at all.
-struct PrepDraw {
-    bool go, flip_h, flip_v;
-    int tex;
-    float wx, wy, scale, alpha;
-};
 // State of a wavefront's pass over the draw lists of its two envs.
 struct PrepDrawPass {
     int queued;          // entries waiting in the worklist
@@ -559,7 +552,7 @@ PG_D void prep_draws_flush(PrepDrawQueue& Q, PrepDrawPass& st, const int4* desc,
 // One pass: this lane's draw (of env a or b of the wave) through the heads; survivors appended to the worklist in lane
 // order (= list order).  Every lane of the wave calls this, with valid = false where there is no draw.
 PG_D void prep_draws_pass(PrepDrawQueue& Q, PrepDrawPass& st, const int4* desc, const Camera& cam_a, const Camera& cam_b,
-                          uint32_t* draws_a, uint32_t* draws_b, bool valid, bool is_b, const PrepDraw& p, int lane,
+                          uint32_t* draws_a, uint32_t* draws_b, bool valid, bool is_b, const DrawCall& p, int lane,
                           const uint32_t* cover = nullptr, const uint4* stamps = nullptr) {
     const Camera& cam = is_b ? cam_b : cam_a;
     AxisHead hx{0.0f, 0.0f}, hy{0.0f, 0.0f};

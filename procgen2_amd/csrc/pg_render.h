@@ -1113,10 +1113,6 @@ struct BgAxis {
     int32_t d0, dn, s0, sn;  // destination span on the target, source span in the texture (dn = 0: nothing)
     int32_t tex_off, tex_w;
 };
-struct BgDraw {  // the background's draw call: texture descriptor, world position (pixels), scale
-    int4 desc;
-    float px, py, scale;
-};
 PG_D BgAxis bg_axis(const Camera& cam, const int4& desc, float pos_x, float pos_y, float scale, int axis) {
     Span sp;
     const bool ok = axis == 0 ? resolve_axis(cam.px, cam.sw, cam.scale, desc.y, pos_x, scale, false, false, sp)
