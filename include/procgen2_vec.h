@@ -198,6 +198,47 @@ PGV_API int32_t pgv_save_envs_host(pgv_env* env, const int32_t* h_indices, int32
 PGV_API int32_t pgv_load_envs_host(pgv_env* env, const int32_t* h_indices, int32_t count, const void* h_records,
                                    uint64_t tag);
 
+/* Assigned levels: choose, on the device, the level an env plays next, and read the level each env is in.  (The original
+ * procgen's info["level_seed"], and what level replay, curricula and "evaluate these levels" are built on; the reference
+ * has no counterpart.)
+ *
+ *   1. "Level number L" is what level-seed mode (pgv_make_levels) means by it, in ANY engine — num_levels = 0 or > 0, any
+ *      mode, any game_flags: what a fresh cenv_make(seed = L) builds as its level 0 — fresh containers and camera,
+ *      rng.seed(L).  d_levels[k] is read as its 32-bit pattern, as pgv_reset's seeds are.
+ *   2. An assignment names the next level the env BUILDS: the auto-reset after its current episode, or a pgv_reset
+ *      WITHOUT seeds that names the env, whichever comes first.
+ *   3. One pending assignment per env.  A later one overwrites an unconsumed one; it is consumed when the level is built;
+ *      a pgv_reset WITH seeds drops the pending assignment of the envs it names and behaves as it always did — also where
+ *      the level generator had already built the assigned level on a fresh chain: the container state the env's own
+ *      history left is kept until the next level is installed, and such a reset goes back to it.  There is no cancel call,
+ *      on purpose: in free mode a prefetched assigned level has already replaced the env's mt19937 stream.
+ *   4. After the assigned episode — level-seed mode: the env's own sequence goes on where it was; an assigned level takes
+ *      no place in it (k does not move, and a level of the sequence that was prefetched and is discarded is not counted).
+ *      Free mode (num_levels = 0): the env goes on as a reference env made with seed L goes on — its mt19937 stream and
+ *      containers continue from the assigned episode.
+ *   5. Timing does not show in results: an assignment made right after the env's reset (the generator's side stream has
+ *      rebuilt the shadow slot long before it is needed) and one made the step before the reset is due (the level is
+ *      generated inside the step) give the same bytes, with and without level prefetch (pgv_set_debug bit 8).
+ *   6. Envs not named are untouched.  d_indices: device int32[count], or NULL for envs 0 .. count-1; the indices of one
+ *      call must be distinct — of two entries that name one env, one wins (nothing faults); an index outside the batch is
+ *      skipped.  count = 0 succeeds and does nothing; count < 0, or NULL levels with count > 0, fails.
+ *   7. The call is enqueued on the env's stream and allocates nothing; the host is not synchronised (the level generator's
+ *      side stream is ordered by events, as for pgv_load_envs).  Cost: one small launch over the indices and one launch of
+ *      the level generator on its side stream — made by EVERY call with count > 0, however many slots it put back in the
+ *      queue, none included (pgv_generator_launches counts it; measurements: docs/OPTLOG.md).
+ *   8. pgv_level_numbers()[i] / pgv_level_known()[i] (device u32[N] / u8[N], valid from pgv_make until pgv_close, written
+ *      on the env's stream): the number of the level env i is IN, and whether it has one — 1 in level-seed mode and for an
+ *      assigned level, 0 (with number 0) for a free-mode level.  Whatever installs a level writes them: at the step that
+ *      reports `done` they still name the level that just ended — what a scorer needs — and they change in the step that
+ *      shows the new level's first frame.
+ *   9. The pending assignment, the current number and its flag, and what the shadow slot knows about the level it holds
+ *      travel in pgv_save_state and in the per-env records: a loaded slot goes on as its source would have.
+ * pgv_assign_levels_host: host pointers, synchronous (allocates and frees a device buffer), as pgv_step_host is to pgv_step. */
+PGV_API int32_t pgv_assign_levels(pgv_env* env, const int32_t* d_indices, int32_t count, const int32_t* d_levels);
+PGV_API int32_t pgv_assign_levels_host(pgv_env* env, const int32_t* h_indices, int32_t count, const int32_t* h_levels);
+PGV_API const uint32_t* pgv_level_numbers(pgv_env* env);
+PGV_API const uint8_t* pgv_level_known(pgv_env* env);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

@@ -771,27 +771,26 @@ PG_D void fresh_env(const State& s, int env) {
     }
 }
 
-// One new level for env.  restart: the env's RNG stream starts over from chain_seed.  Level-seed mode
-// (pg_engine.h LevelPlan) instead rebuilds the env as a fresh cenv_make(seed = level number) would.
-PG_D void begin_level(const State& s, const LevelPlan& plan, int env, bool restart, uint32_t chain_seed) {
+// One new level for env.  restart: the env's RNG stream starts over from chain_seed (drop: and a pending assignment is
+// dropped — a reset with seeds).  Level-seed mode and an assigned level (pg_engine.h LevelPlan) instead rebuild the env as a
+// fresh cenv_make(seed = level number) would.
+PG_D void begin_level(const State& s, const LevelPlan& plan, int env, bool restart, bool drop, uint32_t chain_seed) {
     uint32_t* mt = s.mt + size_t(env) * kMtWords;
     if (s.mt_sel[env] & 2) {  // the stream's current words are where its gang left them (State::mt_sel): home first
         const uint32_t* other = s.mt_other + size_t(env) * kMtN;
         for (int k = 0; k < kMtN; k++) mt[k] = other[k];
     }
     s.mt_sel[env] = 0;  // (… and whatever was made ahead is dropped: this lane draws, or reseeds)
-    if (restart) {
-        plan.chain_seed[env] = chain_seed;
-        plan.drawn[env] = 0;
-    }
-    if (plan.num_levels > 0) {
-        const uint32_t k = plan.drawn[env];
-        plan.drawn[env] = k + 1;
-        mt_seed(mt, level_number(plan.num_levels, plan.start_level, plan.chain_seed[env], k));
+    uint32_t number;
+    bool from_assignment;
+    const bool has = plan_next_level(plan, env, restart, drop, chain_seed, number, from_assignment);
+    if (has) {  // level-seed mode, or an assigned level (pg_engine.h LevelPlan)
+        mt_seed(mt, number);
         fresh_env(s, env);
     } else if (restart) {
         mt_seed(mt, chain_seed);
     }
+    plan_note_level(plan, env, has, number);
     LaneRng rng{mt};
     new_level(s, env, rng, true);
 }
@@ -800,7 +799,7 @@ __global__ void __launch_bounds__(64) make_kernel(State s, uint32_t seed_base, i
     const int env = blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= s.n) return;
     fresh_env(s, env);
-    begin_level(s, plan, env, true, seed_base + static_cast<uint32_t>(env_offset + env));  // level 0, never observed (D1)
+    begin_level(s, plan, env, true, false, seed_base + static_cast<uint32_t>(env_offset + env));  // level 0, never observed (D1)
 }
 
 __global__ void __launch_bounds__(64) reset_kernel(State s, const uint8_t* mask, const int32_t* seeds, StepIO io,
@@ -808,7 +807,7 @@ __global__ void __launch_bounds__(64) reset_kernel(State s, const uint8_t* mask,
     const int env = blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= s.n) return;
     if (mask && !mask[env]) return;
-    begin_level(s, plan, env, seeds != nullptr, seeds ? static_cast<uint32_t>(seeds[env]) : 0u);
+    begin_level(s, plan, env, seeds != nullptr, seeds != nullptr, seeds ? static_cast<uint32_t>(seeds[env]) : 0u);
     io.reward[env] = 0.0f;
     io.done[env] = 0;
     io.pending[env] = 0;
@@ -820,12 +819,15 @@ __global__ void __launch_bounds__(64, PG_BOSSFIGHT_WAVES) logic_kernel(State s, 
     if (env >= s.n) return;
     const Q q = Q::at(threadIdx.x);
     if (io.pending[env]) {
-        if (plan.num_levels > 0) {  // level-seed mode rebuilds the env: one lane (begin_level)
-            if (q.g == 0) begin_level(s, plan, env, false, 0u);
+        // (lane 0 of the gang reads the flag it later consumes, and hands it to the others)
+        const bool rebuild = plan.num_levels > 0 || q.any(q.g == 0 && plan.assigned_on[env] != 0);
+        if (rebuild) {  // level-seed mode and an assigned level rebuild the env: one lane (begin_level)
+            if (q.g == 0) begin_level(s, plan, env, false, false, 0u);
         } else {
             Rng rng = Rng::open(s.mt + size_t(env) * kMtWords, q, s.mt_other + size_t(env) * kMtN, s.mt_sel + env);
             new_level(s, env, rng, q.g == 0);
             rng.close();
+            if (q.g == 0) plan_note_level(plan, env, false, 0u);
         }
         if (q.g == 0) {
             io.reward[env] = 0.0f;

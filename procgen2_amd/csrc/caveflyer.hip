@@ -704,6 +704,10 @@ struct Gen {  // pg_prefetch.h level_kernel<Gen>
     }
     PG_D static void fresh_chain(const State& s, int env) { caveflyer::fresh_chain(s, env); }
     PG_D static void fresh_live(const State& s, int env) { caveflyer::fresh_live(s, env); }
+    PG_D static void chain_counts(const State& s, int env, uint32_t* w, bool put) {  // (pg_prefetch.h chain_keep: what fresh_chain empties)
+        if (put) SI(s, I_HASH_SPRITE, env) = static_cast<int>(w[0]); else w[0] = static_cast<uint32_t>(SI(s, I_HASH_SPRITE, env));
+        if (put) SI(s, I_HASH_HAZARD, env) = static_cast<int>(w[1]); else w[1] = static_cast<uint32_t>(SI(s, I_HASH_HAZARD, env));
+    }
 };
 
 __global__ void __launch_bounds__(64, PG_CAVEFLYER_WAVES) logic_kernel(State s, const int32_t* actions, uint32_t run_seed,

@@ -265,6 +265,9 @@ struct Gen {  // pg_prefetch.h level_kernel<Gen>
     PG_D static void install(const State& s, int env, const Level& lv, int lane) { climber::install(s, env, lv, lane); }
     PG_D static void fresh_chain(const State& s, int env) { climber::fresh_chain(s, env); }
     PG_D static void fresh_live(const State& s, int env) { climber::fresh_live(s, env); }
+    PG_D static void chain_counts(const State& s, int env, uint32_t* w, bool put) {  // (pg_prefetch.h chain_keep: what fresh_chain empties)
+        if (put) SI(s, I_HASH_SPRITE, env) = static_cast<int>(w[0]); else w[0] = static_cast<uint32_t>(SI(s, I_HASH_SPRITE, env));
+    }
 };
 
 PG_D bool is_wall(int t) { return t == kWallMid || t == kWallTop; }

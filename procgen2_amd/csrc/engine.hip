@@ -307,10 +307,10 @@ void pgv_close(pgv_env* e) {
     delete e;
 }
 
-// The device state blob: the game's SoA state followed by the level plan's two per-env words (pg_engine.h
-// LevelPlan), so that a snapshot of the blob carries them.
+// The device state blob: the game's SoA state followed by the level plan's per-env arrays (pg_engine.h LevelPlan: seven
+// of words, then four of bytes), so that a snapshot of the blob carries them.
 static size_t game_state_bytes(const pgv_env* e) { return (e->game->state_bytes(e->n) + 255) / 256 * 256; }
-static size_t state_blob_bytes(const pgv_env* e) { return game_state_bytes(e) + size_t(e->n) * 8; }
+static size_t state_blob_bytes(const pgv_env* e) { return game_state_bytes(e) + size_t(e->n) * pg::kPlanBytesPerEnv; }
 
 // The record layout of this engine (pg_records.h): the game's per-env regions as its state listing describes them, then the
 // engine's own per-env data.  The listing is checked here, on the host: every byte of the state block is either an env's
@@ -324,7 +324,7 @@ static int32_t plan_records(pgv_env* e) {
     for (const pg::EnvRegion& r : listed.v) sum += (size_t(e->n) * r.pieces * r.piece_bytes + 255) / 256 * 256;
     if (sum != e->game->state_bytes(e->n))
         return fail(who + "describes " + std::to_string(sum) + " bytes of a block of " + std::to_string(e->game->state_bytes(e->n)));
-    if (listed.v.size() + 5 > size_t(pg::kMaxRecordRegions)) return fail(who + "has more per-env regions than a record table holds");
+    if (listed.v.size() + 14 > size_t(pg::kMaxRecordRegions)) return fail(who + "has more per-env regions than a record table holds");
     pg::RecordTable& t = e->rec;
     t = pg::RecordTable{};
     uint32_t at = pg::kRecordHeaderBytes;
@@ -336,6 +336,16 @@ static int32_t plan_records(pgv_env* e) {
     for (const pg::EnvRegion& r : listed.v) add(r.base, r.pieces, r.piece_bytes);
     add(reinterpret_cast<uint8_t*>(e->game->plan.chain_seed), 1, 4);
     add(reinterpret_cast<uint8_t*>(e->game->plan.drawn), 1, 4);
+    // (the pending assignment, the number of the level the env is in, what its shadow slot holds: pgv_assign_levels)
+    add(reinterpret_cast<uint8_t*>(e->game->plan.assigned), 1, 4);
+    add(reinterpret_cast<uint8_t*>(e->game->plan.number), 1, 4);
+    add(reinterpret_cast<uint8_t*>(e->game->plan.slot_number), 1, 4);
+    add(e->game->plan.assigned_on, 1, 1);
+    add(e->game->plan.known, 1, 1);
+    add(e->game->plan.slot_assigned, 1, 1);
+    add(reinterpret_cast<uint8_t*>(e->game->plan.kept0), 1, 4);
+    add(reinterpret_cast<uint8_t*>(e->game->plan.kept1), 1, 4);
+    add(e->game->plan.kept_on, 1, 1);
     e->rec_reward = add(nullptr, 1, 4);
     e->rec_done = add(nullptr, 1, 1);
     e->rec_obs = add(nullptr, 1, pg::kObsBytes);
@@ -470,7 +480,11 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     }
     {
         uint32_t* words = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(e->d_state) + game_state_bytes(e.get()));
-        e->game->plan = pg::LevelPlan{num_levels, start_level, words, words + num_envs};
+        uint8_t* bytes = reinterpret_cast<uint8_t*>(words + size_t(7) * num_envs);
+        e->game->plan = pg::LevelPlan{num_levels, start_level, words, words + num_envs, words + size_t(2) * num_envs,
+                                      words + size_t(3) * num_envs, words + size_t(4) * num_envs, bytes, bytes + num_envs,
+                                      bytes + size_t(2) * num_envs, words + size_t(5) * num_envs, words + size_t(6) * num_envs,
+                                      bytes + size_t(3) * num_envs};
     }
     if (plan_records(e.get())) return 1;
     e->game->launch_make(e->stream, seed_base, env_offset);
@@ -641,7 +655,8 @@ struct SnapshotHeader {
 // 2: round 2.  3: round 3 (per-env contiguous rings and entity tables in bossfight, caveflyer, chaser, climber; caveflyer's
 // wall-bit columns and hazard places).  4: round 5/6 (the pending byte carries the parity of the step it is about —
 // pg_prefetch.h reset_due_mark / reset_served_mark — where it used to be 0 / 1; coinrun's hazard hand-off left the blob).
-static constexpr uint32_t kSnapshotMagic = 0x50474e34u;
+// 5: the level plan's assignment arrays lie behind the game's state (pg_engine.h LevelPlan; pgv_assign_levels).
+static constexpr uint32_t kSnapshotMagic = 0x50474e35u;
 
 static size_t snapshot_bytes(const pgv_env* e) {
     return sizeof(SnapshotHeader) + state_blob_bytes(e) + size_t(e->n) * (4 + 1 + 1) +
@@ -801,6 +816,77 @@ int32_t pgv_save_envs_host(pgv_env* e, const int32_t* h_indices, int32_t count, 
 int32_t pgv_load_envs_host(pgv_env* e, const int32_t* h_indices, int32_t count, const void* h_records, uint64_t tag) {
     return records_host(e, h_indices, count, const_cast<void*>(h_records), true, tag);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Assigned levels (pg_engine.h LevelPlan)
+// ------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace pg {
+// Lanes along the indices.  Runs on the env's stream behind everything the generator's stream held (records_behind_generator),
+// so no slot is kSlotBusy, and between the kernels of the env's stream, so none is kSlotSync: a slot is idle, queued or
+// ready.  A ready slot holds the level the env WOULD have built next; unless that is the very level now assigned it goes
+// back into the queue — the generator, launched behind this kernel, consumes the assignment — and where it was a level of
+// the env's own sequence, the sequence steps back to it (level-seed mode: k).  In free mode the chain has moved past the
+// discarded level; an assigned level starts the chain afresh, so nothing is lost that anything would read.
+__global__ void __launch_bounds__(256) assign_levels_kernel(LevelPlan plan, int32_t* slot, int n, const int32_t* indices, int count,
+                                                            const int32_t* levels) {
+    const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= count) return;
+    const int env = indices ? indices[k] : k;
+    if (env < 0 || env >= n) return;
+    const uint32_t number = static_cast<uint32_t>(levels[k]);
+    if (slot && slot_load(&slot[env]) == kSlotReady) {
+        const bool was_assigned = plan.slot_assigned[env] != 0;
+        if (was_assigned && plan.slot_number[env] == number) return;  // (its assignment was consumed: none is pending)
+        // (the exchange decides between two lanes that name the same env: one of them steps the sequence back)
+        if (slot_cas(&slot[env], kSlotReady, kSlotQueued) && !was_assigned && plan.num_levels > 0) plan.drawn[env] -= 1u;
+    }
+    plan.assigned[env] = number;
+    plan.assigned_on[env] = 1;
+}
+}  // namespace pg
+
+extern "C" {
+
+int32_t pgv_assign_levels(pgv_env* e, const int32_t* d_indices, int32_t count, const int32_t* d_levels) {
+    if (!e) return fail("pgv_assign_levels: env is NULL");
+    if (count < 0) return fail("pgv_assign_levels: count is negative");
+    if (count > 0 && !d_levels) return fail("pgv_assign_levels: the level buffer is NULL");
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    if (records_behind_generator(e)) return 1;
+    hipLaunchKernelGGL(pg::assign_levels_kernel, dim3((count + 255) / 256), dim3(256), 0, e->stream, e->game->plan,
+                       e->game->prefetch_slots(), e->n, d_indices, count, d_levels);
+    PG_HIP(hipGetLastError());
+    // The slots put back in the queue get their generator launch.  Not the bulk shape, whatever `count` is: a call may name
+    // every env and mean few (indices outside the batch are skipped: a caller's way to a fixed-size call), and few is the
+    // common case — the envs that just finished.
+    pregen(e, false, true);
+    return 0;
+}
+
+int32_t pgv_assign_levels_host(pgv_env* e, const int32_t* h_indices, int32_t count, const int32_t* h_levels) {
+    if (!e) return fail("pgv_assign_levels_host: env is NULL");
+    if (count < 0) return fail("pgv_assign_levels_host: count is negative");
+    if (count > 0 && !h_levels) return fail("pgv_assign_levels_host: the level buffer is NULL");
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    int32_t* d_buf = nullptr;  // (a call may name more indices than the batch has envs: not the staging buffers)
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_buf), size_t(count) * 8);
+    if (err == hipSuccess) err = hipMemcpyAsync(d_buf, h_levels, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess && h_indices) err = hipMemcpyAsync(d_buf + count, h_indices, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
+    int32_t rc = 0;
+    if (err == hipSuccess) rc = pgv_assign_levels(e, h_indices ? d_buf + count : nullptr, count, d_buf);
+    (void)hipStreamSynchronize(e->stream);  // the host buffers are the caller's, and nothing may still be using what is freed next
+    if (d_buf) (void)hipFree(d_buf);
+    if (err != hipSuccess) return fail(std::string("pgv_assign_levels_host: ") + hipGetErrorString(err));
+    return rc;
+}
+
+const uint32_t* pgv_level_numbers(pgv_env* e) { return e ? e->game->plan.number : nullptr; }
+const uint8_t* pgv_level_known(pgv_env* e) { return e ? e->game->plan.known : nullptr; }
 
 uint8_t* pgv_obs(pgv_env* e) { return e ? e->d_obs : nullptr; }
 float* pgv_reward(pgv_env* e) { return e ? e->d_reward : nullptr; }

@@ -83,7 +83,25 @@ struct LevelPlan {
     int32_t start_level;
     uint32_t* chain_seed;  // [n]  the seed the env was made / last reseeded with
     uint32_t* drawn;       // [n]  k: levels built since then
+    // Assigned levels (include/procgen2_vec.h pgv_assign_levels): the caller names the number of the level an env builds
+    // NEXT, in either mode; such a level takes no place in the env's own sequence (k stays).  One pending assignment per
+    // env, consumed by whoever builds the level — the step's reset, an explicit reset without seeds, or the side-stream
+    // generator, which then notes in the slot's two words what the shadow slot holds (pg_prefetch.h).
+    uint32_t* assigned;       // [n]  the pending assignment's level number
+    uint32_t* number;         // [n]  the number of the level the env is IN (pgv_level_numbers); 0 where it has none
+    uint32_t* slot_number;    // [n]  … of the level in the env's shadow slot, where slot_assigned says it has one
+    uint8_t* assigned_on;     // [n]  1: an assignment is pending
+    uint8_t* known;           // [n]  1: `number` holds (level-seed mode, or an assigned level) (pgv_level_known)
+    uint8_t* slot_assigned;   // [n]  1: the shadow slot's level was built from an assignment
+    // Free mode with prefetch: an assigned level that the side stream builds ahead starts the env's generator chain afresh
+    // while the env still plays its old level.  A reset WITH seeds that comes first drops the assignment and must find
+    // the chain's containers as the env's own history left them, so the generator keeps their bucket counts as they
+    // stood when the env's current level was built (pg_prefetch.h chain_keep) until the next level is installed.
+    uint32_t* kept0;          // [n]  the chain's container counts as of the level the env is in (G::chain_counts) …
+    uint32_t* kept1;          // [n]
+    uint8_t* kept_on;         // [n]  … bit 0: they are held, bit 1: an assignment built ahead has replaced the chain since
 };
+constexpr size_t kPlanBytesPerEnv = 7 * 4 + 4;  // the arrays above, words first (engine.hip: they lie behind the game's state)
 
 // The per-env regions of a game's state block, as its listing describes them (Carve, below).
 // (word 0 of a record, pg_records.h: here because a game's records_loaded looks at it too)
@@ -126,6 +144,9 @@ class Game {
     // smallest mazes are solved in a few (two: 160 -> 195 M env-steps/s; one: 191), caveflyer gains 4 % at two,
     // coinrun, climber and jumper lose 1-2 %.
     virtual int pregen_every() const { return 4; }
+    // The slot words of the game's shadow slots (pg_prefetch.h), or nullptr for a game without any: pgv_assign_levels puts
+    // a ready slot that no longer holds what the env builds next back in the queue.
+    virtual int32_t* prefetch_slots() const { return nullptr; }
     // cenv_render's human-size frame (render_game(false)) of one env into a w×h target of 0x00BBGGRR words in device
     // memory (pg_frame.h).  False = not implemented for this game.
     virtual bool launch_frame(hipStream_t s, int env, uint32_t* d_px, int w, int h) { return false; }
@@ -198,7 +219,7 @@ class Game {
     // Bit 24: coinrun — the entity lanes' hazard pre-selection assumes an agent that does not move (coinrun.hip hazard_near):
     //         the agent's own check of that assumption fails and resolve_kernel works the hazards out the long way.
     int debug_flags = 0;
-    LevelPlan plan{0, 0, nullptr, nullptr};  // set by the engine after bind()
+    LevelPlan plan{};  // set by the engine after bind()
 };
 
 constexpr int kDebugNoPrefetch = 1 << 8;
@@ -316,6 +337,40 @@ PG_HD uint32_t mix32(uint32_t x) {
 PG_HD uint32_t level_number(int32_t num_levels, int32_t start_level, uint32_t chain_seed, uint32_t k) {
     return static_cast<uint32_t>(start_level) + mix32(mix32(chain_seed) + k) % static_cast<uint32_t>(num_levels);
 }
+#if defined(__HIPCC__)
+// What env builds next, decided by ONE lane on behalf of whoever generates the level (pg_prefetch.h level_serve, bossfight's
+// begin_level).  restart: the env's own sequence starts over from chain_seed; `drop` (a reset WITH seeds) also drops a
+// pending assignment.  Returns whether the level has a number — then it is built as a fresh cenv_make(seed = number)
+// builds its level 0, in either mode — and leaves the number and whether it came from an assignment.
+PG_D bool plan_next_level(const LevelPlan& plan, int env, bool restart, bool drop, uint32_t chain_seed, uint32_t& number,
+                          bool& from_assignment) {
+    if (restart) {
+        plan.chain_seed[env] = chain_seed;
+        plan.drawn[env] = 0;
+    }
+    if (drop) plan.assigned_on[env] = 0;
+    from_assignment = false;
+    if (plan.assigned_on[env]) {
+        plan.assigned_on[env] = 0;
+        number = plan.assigned[env];
+        from_assignment = true;
+        return true;
+    }
+    if (plan.num_levels > 0) {
+        const uint32_t k = plan.drawn[env];
+        plan.drawn[env] = k + 1;
+        number = level_number(plan.num_levels, plan.start_level, plan.chain_seed[env], k);
+        return true;
+    }
+    number = 0u;
+    return false;
+}
+// … and what the lane that installs a level leaves for pgv_level_numbers / pgv_level_known.
+PG_D void plan_note_level(const LevelPlan& plan, int env, bool known, uint32_t number) {
+    plan.number[env] = known ? number : 0u;
+    plan.known[env] = known ? 1 : 0;
+}
+#endif
 PG_HD int synthetic_action(uint32_t run_seed, uint32_t step, uint32_t env) {
     uint32_t h = mix32(mix32(step * 0x9E3779B9u + run_seed) ^ (env * 0x85EBCA6Bu + 0xC2B2AE35u));
     return static_cast<int>((static_cast<uint64_t>(h) * 15u) >> 32);

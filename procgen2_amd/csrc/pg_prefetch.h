@@ -80,6 +80,38 @@ struct HasServed<G, decltype(static_cast<void>(&G::served))> {
     static constexpr bool value = true;
 };
 
+// Optional hook: G::chain_counts(s, env, w, put) — the bucket counts of the chain's containers (what fresh_chain sets to
+// "empty") read into / written from w[0..1].  A game that has it keeps them across an assigned level built ahead
+// (pg_engine.h LevelPlan::kept0): chain_keep before the side stream builds a free-mode env's next level, chain_restore when
+// a reset WITH seeds drops an assignment whose level the side stream had already built on a fresh chain.  Lane 0.
+template <class G, class = void>
+struct HasChainCounts {
+    static constexpr bool value = false;
+};
+template <class G>
+struct HasChainCounts<G, decltype(static_cast<void>(&G::chain_counts))> {
+    static constexpr bool value = true;
+};
+template <class G>
+PG_D void chain_keep(const typename G::State& s, const LevelPlan& plan, int env) {
+    if constexpr (HasChainCounts<G>::value) {
+        if (plan.kept_on[env]) return;  // (held since the env's current level was built: a second build ahead changes nothing)
+        uint32_t w[2] = {0u, 0u};
+        G::chain_counts(s, env, w, false);
+        plan.kept0[env] = w[0];
+        plan.kept1[env] = w[1];
+        plan.kept_on[env] = 1;
+    }
+}
+template <class G>
+PG_D void chain_restore(const typename G::State& s, const LevelPlan& plan, int env) {
+    if constexpr (HasChainCounts<G>::value) {
+        if (!(plan.kept_on[env] & 2)) return;
+        uint32_t w[2] = {plan.kept0[env], plan.kept1[env]};
+        G::chain_counts(s, env, w, true);
+    }
+}
+
 // `due_mark` / `served_mark`: what mode 2 looks for in StepIO::pending and what it leaves there for an env it has served —
 // 1 and 2, or reset_due_mark(step) / reset_served_mark(step) for the games whose logic kernel runs the prefetched installs
 // in its own grid (install_prefetched below).
@@ -107,21 +139,27 @@ PG_D void level_serve(const typename G::State& s, int mode, int span, int prefet
     __shared__ typename G::GenLds L;
     __shared__ Level lv;
     __shared__ int32_t verdict;
-    __shared__ uint32_t numbered;  // level-seed mode: the level number this env builds next
+    __shared__ uint32_t numbered;  // the number of the level this env builds next, where it has one …
+    __shared__ int32_t how_numbered;  // … bit 0: it has (level-seed mode, or an assigned level), bit 1: from an assignment
     const bool levels = plan.num_levels > 0;
-    // lane 0: (re)start the env's level sequence if asked, and in level-seed mode draw its next level number
-    auto next_level = [&](int env, bool restart, uint32_t chain_seed) {
+    // lane 0: (re)start the env's level sequence if asked, and settle what the env builds next — its pending assignment
+    // first, in level-seed mode otherwise its next level number (pg_engine.h plan_next_level)
+    // `ahead`: the side stream builds the level while the env plays another (mode 3); otherwise it is installed at once.
+    auto next_level = [&](int env, bool restart, bool drop, uint32_t chain_seed, bool ahead) {
         if (lane == 0) {
-            if (restart) {
-                plan.chain_seed[env] = chain_seed;
-                plan.drawn[env] = 0;
+            if (ahead) {
+                if (!levels) chain_keep<G>(s, plan, env);
+            } else {
+                if (drop) chain_restore<G>(s, plan, env);
+                plan.kept_on[env] = 0;
             }
-            if (levels) {
-                const uint32_t k = plan.drawn[env];
-                plan.drawn[env] = k + 1;
-                numbered = level_number(plan.num_levels, plan.start_level, plan.chain_seed[env], k);
-                G::fresh_chain(s, env);
-            }
+            uint32_t number;
+            bool from_assignment;
+            const bool has = plan_next_level(plan, env, restart, drop, chain_seed, number, from_assignment);
+            numbered = number;
+            how_numbered = (has ? 1 : 0) | (from_assignment ? 2 : 0);
+            if (has) G::fresh_chain(s, env);
+            if (ahead && !levels && from_assignment) plan.kept_on[env] |= 2;
         }
         __syncthreads();
     };
@@ -138,10 +176,14 @@ PG_D void level_serve(const typename G::State& s, int mode, int span, int prefet
             const bool mine = verdict != 0;
             __syncthreads();
             if (!mine) continue;
-            next_level(env, false, 0u);
-            G::generate(s, env, L, lv, levels, numbered, lane);
+            next_level(env, false, false, 0u, true);
+            G::generate(s, env, L, lv, (how_numbered & 1) != 0, numbered, lane);
             __syncthreads();
             for (int k = lane; k < kWords; k += 64) shadow[k] = local[k];
+            if (lane == 0) {  // what the slot holds, for whoever installs it
+                plan.slot_number[env] = numbered;
+                plan.slot_assigned[env] = (how_numbered & 2) ? 1 : 0;
+            }
             __threadfence();
             __syncthreads();
             if (lane == 0) slot_store(&s.slot[env], kSlotReady);
@@ -165,19 +207,27 @@ PG_D void level_serve(const typename G::State& s, int mode, int span, int prefet
         __threadfence();
         if (how == kSlotReady) {
             for (int k = lane; k < kWords; k += 64) local[k] = shadow[k];
+            if (lane == 0) {
+                const bool from_assignment = plan.slot_assigned[env] != 0;
+                numbered = plan.slot_number[env];
+                how_numbered = (levels || from_assignment ? 1 : 0) | (from_assignment ? 2 : 0);
+                plan.kept_on[env] = 0;  // (the level built ahead is the env's now: nothing to go back to)
+            }
         } else {
             const uint32_t seed = mode == 0 ? seed_base + static_cast<uint32_t>(env_offset + env)
                                             : (seeds ? static_cast<uint32_t>(seeds[env]) : 0u);
-            next_level(env, reseed, seed);
-            G::generate(s, env, L, lv, reseed || levels, levels ? numbered : seed, lane);
+            next_level(env, reseed, mode == 1 && reseed, seed, false);
+            const bool has = (how_numbered & 1) != 0;
+            G::generate(s, env, L, lv, reseed || has, has ? numbered : seed, lane);
         }
         __syncthreads();
-        if (levels && lane == 0) G::fresh_live(s, env);
+        if ((how_numbered & 1) && lane == 0) G::fresh_live(s, env);
         __syncthreads();
         G::install(s, env, lv, lane);
         __threadfence();
         __syncthreads();
         if (lane == 0) {
+            plan_note_level(plan, env, (how_numbered & 1) != 0, numbered);
             slot_store(&s.slot[env], prefetch ? kSlotQueued : kSlotIdle);
             if (mode != 0) {
                 io.reward[env] = 0.0f;
@@ -248,13 +298,16 @@ PG_D void install_prefetched(const typename G::State& s, int base, int span, int
         const uint32_t* shadow = reinterpret_cast<const uint32_t*>(&s.shadow[env]);
         uint32_t* local = reinterpret_cast<uint32_t*>(&lv);
         for (int k = lane; k < kWords; k += 64) local[k] = shadow[k];
+        const bool has = levels || plan.slot_assigned[env] != 0;  // (wave-uniform) the slot's level has a number: fresh_live
         __syncthreads();
-        if (levels && lane == 0) G::fresh_live(s, env);
+        if (has && lane == 0) G::fresh_live(s, env);
         __syncthreads();
         G::install(s, env, lv, lane);
         __threadfence();
         __syncthreads();
         if (lane == 0) {
+            plan_note_level(plan, env, has, plan.slot_number[env]);
+            plan.kept_on[env] = 0;  // (LevelPlan::kept0: the level built ahead is the env's now)
             slot_store(&s.slot[env], prefetch ? kSlotQueued : kSlotIdle);
             io.reward[env] = 0.0f;
             io.done[env] = 0;
@@ -309,6 +362,7 @@ class PrefetchingGame : public Game {
         LevelLaunch<G>::reset(st, s_, prefetch(), mask, seeds, io, plan);
     }
     bool pending_has_parity() const override { return true; }  // (reset_due_mark, above)
+    int32_t* prefetch_slots() const override { return s_.slot; }
     bool launch_pregen(hipStream_t side, bool bulk) override {
         if (!prefetch()) return false;
         LevelLaunch<G>::pregen(side, s_, bulk, plan);

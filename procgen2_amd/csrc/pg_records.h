@@ -1,6 +1,6 @@
 // Per-env state records (include/procgen2_vec.h pgv_save_envs / pgv_load_envs): one env's complete state as a fixed-size
 // block of bytes in device memory, gathered from and scattered to the per-env regions of the state block (pg_engine.h
-// Carve, describe mode) and the engine's own per-env data (the level plan's two words, reward, done, the observation row).
+// Carve, describe mode) and the engine's own per-env data (the level plan's arrays, reward, done, the observation row).
 //
 // A record:  [ 16-byte header | region 0 | region 1 | … ],  every region's share — its F pieces of E bytes one after the
 // other, piece f at f·E — rounded up to 16 bytes and the padding written as zeros, so equal states give equal bytes.
@@ -25,8 +25,8 @@
 namespace pg {
 
 constexpr int kRecordHeaderBytes = 16;
-constexpr int kMaxRecordRegions = 24;
-constexpr uint32_t kRecordLayoutVersion = 1;  // part of pgv_env_record_tag: bump with the layout above
+constexpr int kMaxRecordRegions = 40;
+constexpr uint32_t kRecordLayoutVersion = 2;  // part of pgv_env_record_tag: bump with the layout above (2: the level plan's assignment arrays travel)
 
 struct RecordRegion {
     uint8_t* base;

@@ -115,6 +115,10 @@ def load(path=None):
         "pgv_load_envs": (c_int32, [P, P, c_int32, P, c_uint64]),
         "pgv_save_envs_host": (c_int32, [P, P, c_int32, P]),
         "pgv_load_envs_host": (c_int32, [P, P, c_int32, P, c_uint64]),
+        "pgv_assign_levels": (c_int32, [P, P, c_int32, P]),
+        "pgv_assign_levels_host": (c_int32, [P, P, c_int32, P]),
+        "pgv_level_numbers": (P, [P]),
+        "pgv_level_known": (P, [P]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -143,7 +147,8 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_game_name", "pgv_game_id", "pgv_make", "pgv_make_levels", "pgv_make_config", "pgv_game_modes", "pgv_mode", "pgv_close", "pgv_reset", "pgv_step", "pgv_step_synthetic", "pgv_step_synthetic_many",
     "pgv_synthetic_action", "pgv_step_host", "pgv_reset_host", "pgv_decode_png", "pgv_sync", "pgv_generator_launches", "pgv_obs", "pgv_reward", "pgv_done", "pgv_bind_outputs", "pgv_num_envs",
     "pgv_device", "pgv_stream", "pgv_copy_out", "pgv_render_frame", "pgv_render_frames", "pgv_render_frames_host", "pgv_snapshot_bytes", "pgv_save_state", "pgv_load_state",
-    "pgv_env_record_bytes", "pgv_env_record_tag", "pgv_save_envs", "pgv_load_envs", "pgv_save_envs_host", "pgv_load_envs_host", "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
+    "pgv_env_record_bytes", "pgv_env_record_tag", "pgv_save_envs", "pgv_load_envs", "pgv_save_envs_host", "pgv_load_envs_host",
+    "pgv_assign_levels", "pgv_assign_levels_host", "pgv_level_numbers", "pgv_level_known", "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_last_error",
 ]
 EXPORTED_CENV_SYMBOLS = [

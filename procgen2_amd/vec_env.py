@@ -75,6 +75,10 @@ class ProcgenVecEnv:
         pglib.check(self.L, self.L.pgv_bind_outputs(self._h, c_void_p(self.obs.data_ptr()),
                                                     c_void_p(self.reward.data_ptr()), c_void_p(self.done.data_ptr())),
                     "pgv_bind_outputs")
+        # The engine's own per-env level words (pgv_level_numbers / pgv_level_known), exposed the way obs is: zero-copy
+        # tensors over device memory the engine writes in the step that installs a level.
+        self.level_numbers = _device_view(self.L.pgv_level_numbers(h), self.num_envs, "<u4", self.device)
+        self.level_known = _device_view(self.L.pgv_level_known(h), self.num_envs, "|u1", self.device)
         self.single_observation_shape = (64, 64, 3)
         self.num_actions = pglib.NUM_ACTIONS
 
@@ -265,6 +269,39 @@ class ProcgenVecEnv:
         self.load_envs(records, dst)
         return records
 
+    # -- assigned levels (include/procgen2_vec.h pgv_assign_levels) --------------------------------
+    def assign_levels(self, levels, indices=None):
+        """Name the level each of the envs `indices` (None: env k gets levels[k]; otherwise distinct indices, one outside
+        the batch is skipped) builds NEXT — at the auto-reset after its current episode, or at a reset() without seeds
+        that names it.  Level number L is what level-seed mode means by it, whatever num_levels this env was made with: a
+        fresh make(seed = L)'s first level.  levels / indices: anything torch.as_tensor takes (the low 32 bits of a level
+        count); tensors on this device stay there.  Same stream hand-shake as step(), no host synchronisation.  A later
+        assignment overwrites a pending one; reset(seeds=...) drops it.
+
+        `level_numbers` (torch.uint32 [N]) and `level_known` (torch.uint8 [N]) are views of the engine's own buffers, as
+        obs is: the number of the level each env is IN and whether it has one (level-seed mode or an assigned level; a
+        free-mode level has known 0 and number 0).  They still name the finished level at the step that reports done and
+        change with the new level's first frame.  uint32 because a level number is a 32-bit pattern; for the torch ops that
+        lack uint32, `.view(torch.int32)` is the same bits and `.to(torch.int64)` the same values."""
+        lv = torch.as_tensor(levels, device=self.device)
+        if lv.dtype != torch.int32:  # (the 32-bit pattern, as the C ABI reads it: 2**32 - 1 and -1 name the same level)
+            lv = lv.to(torch.int64) & 0xFFFFFFFF
+            lv = torch.where(lv >= 1 << 31, lv - (1 << 32), lv).to(torch.int32)
+        lv = lv.reshape(-1).contiguous()
+        idx = None
+        if indices is not None:
+            idx = torch.as_tensor(indices, device=self.device).to(torch.int32).reshape(-1).contiguous()
+            if idx.numel() != lv.numel():
+                raise ValueError("assign_levels: %d indices for %d levels" % (idx.numel(), lv.numel()))
+        elif lv.numel() != self.num_envs:
+            raise ValueError("assign_levels: expected %d levels, got %d" % (self.num_envs, lv.numel()))
+        if lv.numel():
+            self._before()
+            pglib.check(self.L, self.L.pgv_assign_levels(self._h, c_void_p(idx.data_ptr()) if idx is not None else None,
+                                                         lv.numel(), c_void_p(lv.data_ptr())), "pgv_assign_levels")
+            self._after()
+            self._keep_levels = (idx, lv)
+
     def sync(self):
         pglib.check(self.L, self.L.pgv_sync(self._h), "pgv_sync")
 
@@ -304,6 +341,21 @@ class ProcgenVecEnv:
                 self._gathers = {}
             plan = self._gathers[key] = RootGather((self.obs, self.reward, self.done), dst=dst, group=group)
         return plan()
+
+
+class _DeviceArray:
+    """A block of the engine's device memory as `__cuda_array_interface__` describes one (torch.as_tensor wraps it
+    without a copy)."""
+
+    def __init__(self, ptr, count, typestr):
+        self.__cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
+
+
+def _device_view(ptr, count, typestr, device):
+    if not ptr:
+        raise pglib.EngineError("the engine returned a NULL device pointer")
+    return torch.as_tensor(_DeviceArray(ptr, count, typestr), device=device)
 
 
 class EnvRecords:
