@@ -239,6 +239,72 @@ PGV_API int32_t pgv_assign_levels_host(pgv_env* env, const int32_t* h_indices, i
 PGV_API const uint32_t* pgv_level_numbers(pgv_env* env);
 PGV_API const uint8_t* pgv_level_known(pgv_env* env);
 
+/* Episodes on the device: same-step autoreset, time limits and episode results, decided without a look from the host.
+ * (Gymnasium's autoreset modes and TimeLimit, and the original procgen's episode info; the reference has no counterpart:
+ * it never truncates, coinrun.cpp:367, and leaves the reset to its caller.)  Opt-in per engine: one that never calls
+ * pgv_episodes_enable launches nothing new and gives the same bytes as before at every entry point.
+ *
+ *   1. pgv_episodes_enable allocates every buffer below, once per env; a second call fails.  It fails, with a message and
+ *      the engine left as it was, for an unknown mode, max_episode_steps < 0, final_capacity outside 0 .. num_envs, and a
+ *      step limit with PGV_AUTORESET_NEXT_STEP.  Without it pgv_step_episodes* and pgv_episode_outputs_get fail with a
+ *      message.  pgv_step_episodes* allocates nothing and does not synchronise the host; it is enqueued on the env's stream
+ *      (and the level generator on its side stream at its usual cadence).  With final_capacity > 0 the observation buffer
+ *      (pgv_bind_outputs) must be 16-byte aligned.
+ *   2. PGV_AUTORESET_NEXT_STEP: pgv_step_episodes is pgv_step for obs, the engine's own reward / done rows and all state;
+ *      the episode outputs come on top.  The step that serves an env's auto-reset (reward 0, done 0, the reset frame) — any
+ *      step that finds the env's `done` row set — is not an episode step: nothing is added to length or return.  The
+ *      terminal frame is the env's obs row itself; final_obs is filled all the same where capacity allows.
+ *   3. PGV_AUTORESET_SAME_STEP: an env that ends in this step — terminated by the game, or truncated: it played the
+ *      max_episode_steps-th step of its episode without terminating — is reset inside the same call, exactly as
+ *      pgv_reset(mask = ended, seeds = NULL) does it: the mt19937 stream continues, a pending level assignment is consumed,
+ *      the level words are written, the env's pending auto-reset is cleared.  Its obs row is then the first frame of the new
+ *      episode; its terminal frame is in final_obs, its terminal reward and flags in the episode outputs' reward /
+ *      terminated / truncated; the engine's own reward / done rows of it are what pgv_reset leaves: 0.  The call equals the
+ *      caller's loop pgv_step; read done and count steps; pgv_reset(mask) — except that the level generator keeps its
+ *      step-count cadence: the launch pgv_reset forces is not made per step.
+ *   4. ended_env lists the envs that ended in this step in ascending order; counts[0], anything from 0 to N, says how
+ *      many.  ended_return / ended_length / ended_level / ended_level_known are listed for all of them — the level words as
+ *      they stood before the reset — the frames for the first counts[1] = min(counts[0], final_capacity).  Entries past the
+ *      counts are unspecified.  Lists and ring hold one step's results until the next pgv_step_episodes*.
+ *   5. ended_return is the float32 sum of the episode's rewards in step order (ret = ret + r, one rounding a step),
+ *      ended_length the number of its steps.  running_return / running_length are those of the episode each env is IN; a
+ *      pgv_reset zeroes them for the envs it names.  pgv_load_envs and pgv_load_state leave them as they are — they travel
+ *      neither in records nor in snapshots — and the caller may write them (after a fork, with its own indexing).  A loaded
+ *      slot whose source had a reset pending has its next step recognised as the reset step: the `done` row travels.
+ *      pgv_step and pgv_step_episodes may be mixed on one engine; steps taken through pgv_step are not counted. */
+#define PGV_AUTORESET_NEXT_STEP 0
+#define PGV_AUTORESET_SAME_STEP 1
+typedef struct pgv_episode_config {
+    uint32_t struct_size;
+    int32_t autoreset;         /* PGV_AUTORESET_* */
+    int32_t max_episode_steps; /* 0: no limit.  > 0 only with PGV_AUTORESET_SAME_STEP */
+    int32_t final_capacity;    /* rows of the final-observation ring, 0 .. num_envs */
+} pgv_episode_config;
+typedef struct pgv_episode_outputs { /* device pointers, valid until pgv_close */
+    uint32_t struct_size;
+    float* reward;              /* [N]  this step's reward (same-step: the terminal step's, kept across the reset) */
+    uint8_t* terminated;        /* [N] */
+    uint8_t* truncated;         /* [N] */
+    uint8_t* ended;             /* [N]  terminated | truncated */
+    int32_t* counts;            /* [2]  episodes that ended in this step; how many of them have a row in final_obs */
+    int32_t* ended_env;         /* [N]  their env indices, ascending */
+    float* ended_return;        /* [N]  parallel to ended_env */
+    int32_t* ended_length;      /* [N] */
+    uint32_t* ended_level;      /* [N]  pgv_level_numbers / pgv_level_known of the level that just ended */
+    uint8_t* ended_level_known; /* [N] */
+    uint8_t* final_obs;         /* [final_capacity][PGV_OBS_BYTES]  terminal frame of ended_env[k], k < counts[1]; NULL at capacity 0 */
+    float* running_return;      /* [N]  of the episode each env is IN; the caller may write */
+    int32_t* running_length;    /* [N] */
+} pgv_episode_outputs;
+PGV_API int32_t pgv_episodes_enable(pgv_env* env, const pgv_episode_config* config);
+PGV_API int32_t pgv_episode_outputs_get(pgv_env* env, pgv_episode_outputs* out); /* set struct_size first */
+PGV_API int32_t pgv_step_episodes(pgv_env* env, const int32_t* d_actions);
+PGV_API int32_t pgv_step_episodes_synthetic(pgv_env* env, uint32_t run_seed); /* same action hash and step counter as pgv_step_synthetic */
+PGV_API int32_t pgv_step_episodes_host(pgv_env* env, const int32_t* h_actions); /* as pgv_step_host */
+/* Measurement: `steps` calls of pgv_step_episodes_synthetic with HIP events on the env's stream — h_step_ms[s] the whole call,
+ * h_episode_ms[s] the two episode launches behind the step alone (host arrays of `steps` floats, either may be NULL). */
+PGV_API int32_t pgv_step_episodes_times(pgv_env* env, int32_t steps, uint32_t run_seed, float* h_step_ms, float* h_episode_ms);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

@@ -12,6 +12,7 @@
 #include "../../include/procgen2_cenv.h"
 #include "../../include/procgen2_vec.h"
 #include "pg_engine.h"
+#include "pg_episodes.h"
 #include "pg_order.h"
 #include "pg_records.h"
 #include "png_decode.h"
@@ -230,6 +231,12 @@ struct pgv_env {
     int rec_reward = 0, rec_done = 0, rec_obs = 0;
     uint64_t rec_tag = 0;
     hipEvent_t rec_ev = nullptr;
+    // episode bookkeeping (pg_episodes.h; pgv_episodes_enable): off unless asked for.  One device block holds every buffer;
+    // the engine's own rows and level words are filled in per call (pgv_bind_outputs may move the rows).
+    bool episodes = false;
+    int ep_autoreset = 0;
+    void* d_episodes = nullptr;
+    pg::EpisodeBuffers ep{};
 
     pg::StepIO io() const { return {d_obs, d_reward, d_done, d_pending}; }
 };
@@ -301,6 +308,7 @@ void pgv_close(pgv_env* e) {
     if (e->own_reward && e->d_reward) hipFree(e->d_reward);
     if (e->own_done && e->d_done) hipFree(e->d_done);
     if (e->d_pending) hipFree(e->d_pending);
+    if (e->d_episodes) hipFree(e->d_episodes);
     if (e->d_host_i32) hipFree(e->d_host_i32);
     if (e->d_host_u8) hipFree(e->d_host_u8);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -503,6 +511,7 @@ int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     e->game->launch_reset(e->stream, d_mask, d_seeds, e->io());
     e->game->launch_prepass(e->stream, d_mask);
     e->game->launch_render(e->stream, d_mask, e->io());
+    if (e->episodes) pg::launch_episode_clear(e->stream, e->ep, d_mask);  // the named envs start their episodes afresh
     pregen(e, true, true);
     PG_HIP(hipGetLastError());
     return 0;
@@ -615,6 +624,144 @@ int32_t pgv_reset_host(pgv_env* e, const uint8_t* h_mask, const int32_t* h_seeds
     if (rc) return rc;
     PG_HIP(hipStreamSynchronize(e->stream));  // staging buffers are reused by the next *_host call
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Episodes on the device (pg_episodes.h): same-step autoreset, time limits, episode results
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_episodes_enable(pgv_env* e, const pgv_episode_config* cfg) {
+    if (!e) return fail("pgv_episodes_enable: env is NULL");
+    if (!cfg || cfg->struct_size < sizeof(pgv_episode_config)) return fail("pgv_episodes_enable: config is NULL or struct_size too small");
+    if (e->episodes) return fail("pgv_episodes_enable: episodes are enabled already (once per env)");
+    if (cfg->autoreset != PGV_AUTORESET_NEXT_STEP && cfg->autoreset != PGV_AUTORESET_SAME_STEP)
+        return fail("pgv_episodes_enable: unknown autoreset mode " + std::to_string(cfg->autoreset));
+    if (cfg->max_episode_steps < 0) return fail("pgv_episodes_enable: max_episode_steps must be >= 0 (0 = no limit)");
+    if (cfg->max_episode_steps > 0 && cfg->autoreset != PGV_AUTORESET_SAME_STEP)
+        return fail("pgv_episodes_enable: a step limit needs PGV_AUTORESET_SAME_STEP (a truncated env must be reset by the engine)");
+    if (cfg->final_capacity < 0 || cfg->final_capacity > e->n)
+        return fail("pgv_episodes_enable: final_capacity must be in 0 .. num_envs");
+    PG_HIP(hipSetDevice(e->device));
+    const size_t n = size_t(e->n), blocks = size_t(pg::episode_blocks(e->n));
+    size_t at = 0;
+    auto take = [&](size_t bytes) {  // offsets first, the block afterwards: every buffer 256-byte aligned
+        const size_t here = at;
+        at += (bytes + 255) / 256 * 256;
+        return here;
+    };
+    const size_t o_reward = take(n * 4), o_term = take(n), o_trunc = take(n), o_ended = take(n), o_counts = take(8), o_env = take(n * 4),
+                 o_ret = take(n * 4), o_len = take(n * 4), o_level = take(n * 4), o_known = take(n), o_rret = take(n * 4), o_rlen = take(n * 4),
+                 o_prev = take(n), o_kret = take(n * 4), o_klen = take(n * 4), o_blocks = take(blocks * 4),
+                 o_final = take(size_t(cfg->final_capacity) * pg::kObsBytes);
+    void* mem = nullptr;
+    PG_HIP(hipMalloc(&mem, at));
+    hipError_t err = hipMemsetAsync(mem, 0, at, e->stream);
+    if (err != hipSuccess) {
+        (void)hipFree(mem);
+        return fail(std::string("pgv_episodes_enable: ") + hipGetErrorString(err));
+    }
+    uint8_t* m = static_cast<uint8_t*>(mem);
+    pg::EpisodeBuffers b{};
+    b.n = e->n;
+    b.max_steps = cfg->max_episode_steps;
+    b.capacity = cfg->final_capacity;
+    b.level_number = e->game->plan.number;
+    b.level_known = e->game->plan.known;
+    b.reward = reinterpret_cast<float*>(m + o_reward);
+    b.terminated = m + o_term;
+    b.truncated = m + o_trunc;
+    b.ended = m + o_ended;
+    b.counts = reinterpret_cast<int32_t*>(m + o_counts);
+    b.ended_env = reinterpret_cast<int32_t*>(m + o_env);
+    b.ended_return = reinterpret_cast<float*>(m + o_ret);
+    b.ended_length = reinterpret_cast<int32_t*>(m + o_len);
+    b.ended_level = reinterpret_cast<uint32_t*>(m + o_level);
+    b.ended_level_known = m + o_known;
+    b.running_return = reinterpret_cast<float*>(m + o_rret);
+    b.running_length = reinterpret_cast<int32_t*>(m + o_rlen);
+    b.prev_done = m + o_prev;
+    b.kept_return = reinterpret_cast<float*>(m + o_kret);
+    b.kept_length = reinterpret_cast<int32_t*>(m + o_klen);
+    b.block_count = reinterpret_cast<int32_t*>(m + o_blocks);
+    b.final_obs = cfg->final_capacity ? m + o_final : nullptr;
+    e->d_episodes = mem;
+    e->ep = b;
+    e->ep_autoreset = cfg->autoreset;
+    e->episodes = true;
+    return 0;
+}
+
+int32_t pgv_episode_outputs_get(pgv_env* e, pgv_episode_outputs* out) {
+    if (!e) return fail("pgv_episode_outputs_get: env is NULL");
+    if (!out || out->struct_size < sizeof(pgv_episode_outputs)) return fail("pgv_episode_outputs_get: outputs is NULL or struct_size too small");
+    if (!e->episodes) return fail("pgv_episode_outputs_get: call pgv_episodes_enable first");
+    const pg::EpisodeBuffers& b = e->ep;
+    out->reward = b.reward;
+    out->terminated = b.terminated;
+    out->truncated = b.truncated;
+    out->ended = b.ended;
+    out->counts = b.counts;
+    out->ended_env = b.ended_env;
+    out->ended_return = b.ended_return;
+    out->ended_length = b.ended_length;
+    out->ended_level = b.ended_level;
+    out->ended_level_known = b.ended_level_known;
+    out->final_obs = b.final_obs;
+    out->running_return = b.running_return;
+    out->running_length = b.running_length;
+    return 0;
+}
+
+// step_impl, then the episode launches and — same-step — the masked reset of the envs that ended: pgv_reset(ended, NULL)
+// without its forced generator launch (the generator keeps the cadence of pregen(e, false, false) inside the step).
+// `before_episodes` / `after_episodes`: optional events (measurement only) round the two launches behind the step.
+static int32_t step_episodes_impl(const char* who, pgv_env* e, const int32_t* d_actions, uint32_t run_seed, hipEvent_t before_episodes = nullptr,
+                                  hipEvent_t after_episodes = nullptr) {
+    if (!e->episodes) return fail(std::string(who) + ": call pgv_episodes_enable first");
+    if (e->ep.capacity > 0 && (reinterpret_cast<uintptr_t>(e->d_obs) & 15u))
+        return fail(std::string(who) + ": the observation buffer must be 16-byte aligned for the final-observation ring");
+    pg::EpisodeBuffers& b = e->ep;
+    b.obs = e->d_obs;
+    b.step_reward = e->d_reward;
+    b.done = e->d_done;
+    (void)hipGetLastError();
+    pg::launch_episode_before(e->stream, b);
+    PG_HIP(hipGetLastError());
+    if (step_impl(e, d_actions, run_seed)) return 1;
+    if (before_episodes) PG_HIP(hipEventRecord(before_episodes, e->stream));
+    pg::launch_episode_after(e->stream, b);
+    PG_HIP(hipGetLastError());
+    if (after_episodes) PG_HIP(hipEventRecord(after_episodes, e->stream));
+    if (e->ep_autoreset == PGV_AUTORESET_SAME_STEP) {
+        e->game->launch_reset(e->stream, b.ended, nullptr, e->io());
+        e->game->launch_prepass(e->stream, b.ended);
+        e->game->launch_render(e->stream, b.ended, e->io());
+        PG_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int32_t pgv_step_episodes(pgv_env* e, const int32_t* d_actions) {
+    if (!e) return fail("pgv_step_episodes: env is NULL");
+    if (!d_actions) return fail("pgv_step_episodes: actions is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    return step_episodes_impl("pgv_step_episodes", e, d_actions, 0);
+}
+
+int32_t pgv_step_episodes_synthetic(pgv_env* e, uint32_t run_seed) {
+    if (!e) return fail("pgv_step_episodes_synthetic: env is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    return step_episodes_impl("pgv_step_episodes_synthetic", e, nullptr, run_seed);
+}
+
+int32_t pgv_step_episodes_host(pgv_env* e, const int32_t* h_actions) {
+    if (!e) return fail("pgv_step_episodes_host: env is NULL");
+    if (!h_actions) return fail("pgv_step_episodes_host: actions is NULL");
+    if (!e->episodes) return fail("pgv_step_episodes_host: call pgv_episodes_enable first");
+    PG_HIP(hipSetDevice(e->device));
+    if (ensure_staging(e)) return 1;
+    PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
+    PG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is the caller's: do not keep reading it
+    return step_episodes_impl("pgv_step_episodes_host", e, e->d_host_i32, 0);
 }
 
 int32_t pgv_decode_png(const char* path, int32_t* w, int32_t* h, uint8_t* h_rgba, int64_t cap) {
@@ -1029,6 +1176,26 @@ int32_t pgv_step_phases_many(pgv_env* const* envs, int32_t count, int32_t steps,
     std::vector<float*> out(size_t(count) * 5);
     for (size_t k = 0; k < out.size(); k++) out[k] = h_ms + k * size_t(steps > 0 ? steps : 0);
     return pg::step_phases_many(envs, count, steps, run_seed, out.data());
+}
+
+int32_t pgv_step_episodes_times(pgv_env* e, int32_t steps, uint32_t run_seed, float* h_step_ms, float* h_episode_ms) {
+    if (!e) return fail("pgv_step_episodes_times: env is NULL");
+    if (steps < 1 || steps > (1 << 20)) return fail("pgv_step_episodes_times: steps must be in 1..1048576");
+    PG_HIP(hipSetDevice(e->device));
+    StepEvents ev;  // per step: start, before the episode launches, behind them; one more at the end
+    ev.v.assign(size_t(steps) * 3 + 1, nullptr);
+    for (auto& p : ev.v) PG_HIP(hipEventCreate(&p));
+    for (int s = 0; s < steps; s++) {
+        PG_HIP(hipEventRecord(ev.v[3 * s], e->stream));
+        if (step_episodes_impl("pgv_step_episodes_times", e, nullptr, run_seed, ev.v[3 * s + 1], ev.v[3 * s + 2])) return 1;
+    }
+    PG_HIP(hipEventRecord(ev.v[size_t(steps) * 3], e->stream));
+    PG_HIP(hipEventSynchronize(ev.v[size_t(steps) * 3]));
+    for (int s = 0; s < steps; s++) {
+        if (h_step_ms) PG_HIP(hipEventElapsedTime(&h_step_ms[s], ev.v[3 * s], ev.v[3 * s + 3]));
+        if (h_episode_ms) PG_HIP(hipEventElapsedTime(&h_episode_ms[s], ev.v[3 * s + 1], ev.v[3 * s + 2]));
+    }
+    return 0;
 }
 
 int32_t pgv_render_frame(pgv_env* e, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb) {

@@ -22,6 +22,18 @@ Boxes; what RL code imports is a vector env with real spaces.  This class gives 
 * Outputs are views of the engine's buffers: torch tensors on the device by default (zero copy), numpy arrays with
   `output="numpy"` (one device→host copy per step).
 
+* `episodes="device"` (opt-in) moves the episode boundary into the engine (include/procgen2_vec.h pgv_step_episodes):
+  `step()` is ONE engine call and no host synchronisation in either autoreset mode, `terminated` and `truncated` are
+  real (`max_episode_steps`, same_step only), and `info` carries, every step,
+      `_final_obs`         bool-like [N]: which envs ended (terminated | truncated);
+      `final_obs_compact`  uint8 [capacity, 64, 64, 3]: the ring of terminal frames, `final_obs_env` int32 [N] the envs
+                           they belong to (ascending), `final_count` int32 [2]: how many ended, how many have a frame;
+      `episode`            {"r": returns, "l": lengths, "level": level numbers, "level_known": flags}, parallel to
+                           `final_obs_env`, meaningful up to final_count[0].
+  With output="torch" these are VIEWS of the engine's buffers, overwritten by the next step — that is the price of the
+  missing round trip and the reason the mode is opt-in: the default path keeps handing out fresh tensors.  With
+  output="numpy" the lists are cut to the counts (copies; the host synchronisation is inherent there).
+
 The class only talks to an *engine* object with `reset(mask, seeds) -> obs`, `step(actions) -> (obs, reward, done)`,
 `close()`, `num_envs`; `ProcgenVecEnv` is the real one.  The CPU tests drive the same code with an oracle-backed
 stand-in, so the wrapper logic is covered without a GPU.
@@ -124,9 +136,18 @@ class GymVectorAdapter(_VectorBase):
 
     metadata = {"render_modes": ["rgb_array"], "autoreset_mode": "next_step"}
 
-    def __init__(self, engine, output="torch", render_mode=None, render_size=(512, 512), autoreset_mode="next_step"):
+    def __init__(self, engine, output="torch", render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None):
         if output not in ("torch", "numpy"):
             raise ValueError("output must be 'torch' or 'numpy'")
+        if episodes not in (None, "device"):
+            raise ValueError("episodes must be None or 'device'")
+        if episodes == "device":
+            if not hasattr(engine, "step_episodes"):
+                raise ValueError("episodes='device' needs an engine with step_episodes (ProcgenVecEnv made with autoreset_mode=...)")
+            if getattr(engine, "autoreset_mode", None) != autoreset_mode:
+                raise ValueError("episodes='device': the engine was made with autoreset_mode=%r, the adapter with %r"
+                                 % (getattr(engine, "autoreset_mode", None), autoreset_mode))
+        self.episodes = episodes
         if autoreset_mode not in ("next_step", "same_step"):
             raise ValueError("autoreset_mode must be 'next_step' or 'same_step'")
         self.autoreset_mode = autoreset_mode
@@ -186,6 +207,8 @@ class GymVectorAdapter(_VectorBase):
         n = actions.numel() if hasattr(actions, "numel") else np.asarray(actions).size
         if n != self.num_envs:
             raise ValueError("expected %d actions, got %d" % (self.num_envs, n))
+        if self.episodes == "device":
+            return self._step_device(actions)
         obs, reward, done = self.engine.step(actions)
         terminated = done != 0
         truncated = np.zeros(self.num_envs, dtype=bool) if self.output == "numpy" else (done != done)
@@ -222,6 +245,23 @@ class GymVectorAdapter(_VectorBase):
             info = {"final_obs": by_env, "_final_obs": self._out(mask, bool), "final_obs_compact": self._out(final),
                     "final_obs_env": self._out(where)}
         return self._out(obs), self._out(reward), self._out(terminated, bool), truncated, info
+
+    def _step_device(self, actions):
+        """episodes="device": one engine call; everything returned is a view of the engine's buffers (torch) or cut to the
+        step's counts (numpy).  See the module docstring for the info keys."""
+        obs, ep = self.engine.step_episodes(actions)
+        if self.output == "numpy":
+            counts = self._out(ep.counts)
+            c, k = int(counts[0]), int(counts[1])
+            cut = lambda x, m: self._out(x)[:m].copy()
+            info = {"_final_obs": self._out(ep.ended, bool), "final_obs_compact": cut(ep.final_obs, k), "final_obs_env": cut(ep.ended_env, c),
+                    "final_count": counts.copy(),
+                    "episode": {"r": cut(ep.ended_return, c), "l": cut(ep.ended_length, c), "level": cut(ep.ended_level, c),
+                                "level_known": cut(ep.ended_level_known, c)}}
+            return (self._out(obs), self._out(ep.reward), self._out(ep.terminated, bool), self._out(ep.truncated, bool), info)
+        info = {"_final_obs": ep.ended != 0, "final_obs_compact": ep.final_obs, "final_obs_env": ep.ended_env, "final_count": ep.counts,
+                "episode": {"r": ep.ended_return, "l": ep.ended_length, "level": ep.ended_level, "level_known": ep.ended_level_known}}
+        return obs, ep.reward, ep.terminated != 0, ep.truncated != 0, info
 
     def render(self, index=0):
         """The human-size frame of one env (the reference's `cenv_render`, coinrun.cpp:393-411; default 512×512 as its
@@ -270,10 +310,17 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
     """`GymVectorAdapter` over the HIP engine.  Raises if there is no HIP device (no CPU fallback)."""
 
     def __init__(self, game, num_envs, device=0, seed=1, env_offset=0, output="torch", num_levels=0, start_level=0,
-                 distribution_mode=None, render_mode=None, render_size=(512, 512), autoreset_mode="next_step"):
+                 distribution_mode=None, render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None,
+                 max_episode_steps=0, final_obs_capacity=0):
         from .vec_env import ProcgenVecEnv
+        if episodes not in (None, "device"):
+            raise ValueError("episodes must be None or 'device'")
+        if episodes is None and (max_episode_steps or final_obs_capacity):
+            raise ValueError("max_episode_steps / final_obs_capacity need episodes='device'")
+        more = {} if episodes is None else {"autoreset_mode": autoreset_mode, "max_episode_steps": max_episode_steps,
+                                            "final_obs_capacity": final_obs_capacity}
         super().__init__(ProcgenVecEnv(game, num_envs, device=device, seed_base=seed, env_offset=env_offset,
                                        num_levels=num_levels, start_level=start_level,
-                                       distribution_mode=distribution_mode), output=output, render_mode=render_mode,
-                         render_size=render_size, autoreset_mode=autoreset_mode)
+                                       distribution_mode=distribution_mode, **more), output=output, render_mode=render_mode,
+                         render_size=render_size, autoreset_mode=autoreset_mode, episodes=episodes)
         self.game = game

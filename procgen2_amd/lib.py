@@ -26,6 +26,32 @@ class Config(ctypes.Structure):
                 ("start_level", c_int32), ("mode", c_int32), ("game_flags", c_uint32)]
 
 
+class EpisodeConfig(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_episode_config`."""
+    _fields_ = [("struct_size", c_uint32), ("autoreset", c_int32), ("max_episode_steps", c_int32), ("final_capacity", c_int32)]
+
+
+class EpisodeOutputs(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_episode_outputs` (device pointers)."""
+    _fields_ = [("struct_size", c_uint32)] + [(name, c_void_p) for name in (
+        "reward", "terminated", "truncated", "ended", "counts", "ended_env", "ended_return", "ended_length", "ended_level",
+        "ended_level_known", "final_obs", "running_return", "running_length")]
+
+
+# include/procgen2_vec.h PGV_AUTORESET_*
+AUTORESET_MODES = {"next_step": 0, "same_step": 1}
+
+
+def episodes_enable(lib, h, autoreset_mode, max_episode_steps=0, final_capacity=0):
+    """pgv_episodes_enable + pgv_episode_outputs_get → EpisodeOutputs.  autoreset_mode: a name of AUTORESET_MODES or the number."""
+    mode = AUTORESET_MODES[autoreset_mode] if autoreset_mode in AUTORESET_MODES else int(autoreset_mode)
+    cfg = EpisodeConfig(ctypes.sizeof(EpisodeConfig), mode, int(max_episode_steps), int(final_capacity))
+    check(lib, lib.pgv_episodes_enable(h, ctypes.byref(cfg)), "pgv_episodes_enable")
+    out = EpisodeOutputs(ctypes.sizeof(EpisodeOutputs))
+    check(lib, lib.pgv_episode_outputs_get(h, ctypes.byref(out)), "pgv_episode_outputs_get")
+    return out
+
+
 def mode_id(mode):
     if mode is None:
         return 0
@@ -119,6 +145,12 @@ def load(path=None):
         "pgv_assign_levels_host": (c_int32, [P, P, c_int32, P]),
         "pgv_level_numbers": (P, [P]),
         "pgv_level_known": (P, [P]),
+        "pgv_episodes_enable": (c_int32, [P, POINTER(EpisodeConfig)]),
+        "pgv_episode_outputs_get": (c_int32, [P, POINTER(EpisodeOutputs)]),
+        "pgv_step_episodes": (c_int32, [P, P]),
+        "pgv_step_episodes_synthetic": (c_int32, [P, c_uint32]),
+        "pgv_step_episodes_host": (c_int32, [P, P]),
+        "pgv_step_episodes_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -148,7 +180,9 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_synthetic_action", "pgv_step_host", "pgv_reset_host", "pgv_decode_png", "pgv_sync", "pgv_generator_launches", "pgv_obs", "pgv_reward", "pgv_done", "pgv_bind_outputs", "pgv_num_envs",
     "pgv_device", "pgv_stream", "pgv_copy_out", "pgv_render_frame", "pgv_render_frames", "pgv_render_frames_host", "pgv_snapshot_bytes", "pgv_save_state", "pgv_load_state",
     "pgv_env_record_bytes", "pgv_env_record_tag", "pgv_save_envs", "pgv_load_envs", "pgv_save_envs_host", "pgv_load_envs_host",
-    "pgv_assign_levels", "pgv_assign_levels_host", "pgv_level_numbers", "pgv_level_known", "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
+    "pgv_assign_levels", "pgv_assign_levels_host", "pgv_level_numbers", "pgv_level_known",
+    "pgv_episodes_enable", "pgv_episode_outputs_get", "pgv_step_episodes", "pgv_step_episodes_synthetic", "pgv_step_episodes_host", "pgv_step_episodes_times",
+    "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_last_error",
 ]
 EXPORTED_CENV_SYMBOLS = [

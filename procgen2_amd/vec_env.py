@@ -29,8 +29,13 @@ def shard_range(total_envs, world_size, rank):
 
 class ProcgenVecEnv:
     def __init__(self, game, num_envs, device=0, seed_base=1, env_offset=0, lib_path=None, num_levels=0,
-                 start_level=0, distribution_mode=None, game_flags=0, out=None):
-        """out = (obs, reward, done): caller-owned result tensors on `device` — uint8 [N,64,64,3], float32 [N],
+                 start_level=0, distribution_mode=None, game_flags=0, out=None, autoreset_mode=None, max_episode_steps=0,
+                 final_obs_capacity=0):
+        """autoreset_mode = None | "next_step" | "same_step": episodes on the device (include/procgen2_vec.h
+        pgv_episodes_enable) — step_episodes() and the `episode` tensors; None changes nothing at all.  max_episode_steps
+        (0: no limit; same_step only) truncates, final_obs_capacity (0 .. num_envs) is the rows of the terminal-frame ring.
+
+        out = (obs, reward, done): caller-owned result tensors on `device` — uint8 [N,64,64,3], float32 [N],
         uint8 [N], contiguous — e.g. slices of one slab that several envs (the games of a mixed workload) fill side by
         side ("one contiguous [N_local,64,64,3] slab regardless of game").  Default: own tensors."""
         if not torch.cuda.is_available():
@@ -81,6 +86,20 @@ class ProcgenVecEnv:
         self.level_known = _device_view(self.L.pgv_level_known(h), self.num_envs, "|u1", self.device)
         self.single_observation_shape = (64, 64, 3)
         self.num_actions = pglib.NUM_ACTIONS
+        self.autoreset_mode, self.episode = autoreset_mode, None
+        if autoreset_mode is None:
+            if max_episode_steps or final_obs_capacity:
+                self.close()
+                raise ValueError("max_episode_steps / final_obs_capacity need autoreset_mode='next_step' or 'same_step'")
+        else:
+            try:
+                if autoreset_mode not in pglib.AUTORESET_MODES:
+                    raise ValueError("autoreset_mode must be None, 'next_step' or 'same_step'")
+                self.episode = EpisodeTensors(pglib.episodes_enable(self.L, h, autoreset_mode, max_episode_steps, final_obs_capacity),
+                                              self.num_envs, int(final_obs_capacity), self.device)
+            except Exception:
+                self.close()
+                raise
 
     # -- life cycle ------------------------------------------------------------------------------
     def reset(self, mask=None, seeds=None):
@@ -120,6 +139,46 @@ class ProcgenVecEnv:
         if ordered:
             self._after()
         return self.obs, self.reward, self.done
+
+    def _needs_episodes(self):
+        if self.episode is None:
+            raise pglib.EngineError("step_episodes needs an env made with autoreset_mode='next_step' or 'same_step'")
+
+    def step_episodes(self, actions):
+        """step() with the episode bookkeeping of the mode this env was made with (pgv_step_episodes): one engine call, no
+        host synchronisation.  Returns (obs, episode): in same_step mode the obs rows of the envs that ended already show
+        their next episode's first frame; `episode` (also self.episode) holds this step's reward / terminated / truncated /
+        ended, the list of ended envs with their returns, lengths and levels, and the ring of terminal frames — views of
+        the engine's buffers, reused by the next step_episodes."""
+        self._needs_episodes()
+        a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+        if a.numel() != self.num_envs:
+            raise ValueError("expected %d actions, got %d" % (self.num_envs, a.numel()))
+        self._before()
+        pglib.check(self.L, self.L.pgv_step_episodes(self._h, c_void_p(a.data_ptr())), "pgv_step_episodes")
+        self._after()
+        self._keep = (a,)
+        return self.obs, self.episode
+
+    def step_episodes_synthetic(self, run_seed=0, ordered=True):
+        """step_synthetic() with the episode bookkeeping (pgv_step_episodes_synthetic); ordered as there."""
+        self._needs_episodes()
+        if ordered:
+            self._before()
+        pglib.check(self.L, self.L.pgv_step_episodes_synthetic(self._h, run_seed), "pgv_step_episodes_synthetic")
+        if ordered:
+            self._after()
+        return self.obs, self.episode
+
+    def step_episodes_times(self, steps, run_seed=0):
+        """`steps` step_episodes_synthetic calls timed by HIP events on the engine's stream (pgv_step_episodes_times):
+        (step_ms[steps], episode_ms[steps]) — the whole call, and the two episode launches behind the step alone."""
+        import numpy as np
+        self._needs_episodes()
+        step_ms, episode_ms = np.zeros(steps, np.float32), np.zeros(steps, np.float32)
+        pglib.check(self.L, self.L.pgv_step_episodes_times(self._h, steps, run_seed, c_void_p(step_ms.ctypes.data),
+                                                           c_void_p(episode_ms.ctypes.data)), "pgv_step_episodes_times")
+        return step_ms, episode_ms
 
     def _before(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -356,6 +415,27 @@ def _device_view(ptr, count, typestr, device):
     if not ptr:
         raise pglib.EngineError("the engine returned a NULL device pointer")
     return torch.as_tensor(_DeviceArray(ptr, count, typestr), device=device)
+
+
+class EpisodeTensors:
+    """Zero-copy tensors over the engine's episode outputs (include/procgen2_vec.h pgv_episode_outputs), written by every
+    step_episodes and valid until the next: reward f32[N], terminated / truncated / ended u8[N], counts int32[2] (episodes
+    that ended in the step; how many of them have a row in final_obs), ended_env int32[N] (ascending), ended_return f32[N],
+    ended_length int32[N], ended_level uint32[N], ended_level_known u8[N] (all parallel to ended_env, meaningful up to
+    counts[0]), final_obs u8[capacity, 64, 64, 3] (rows up to counts[1]), and the writable running_return f32[N] /
+    running_length int32[N] of the episode each env is in."""
+
+    def __init__(self, out, n, capacity, device):
+        for name, typestr in (("reward", "<f4"), ("terminated", "|u1"), ("truncated", "|u1"), ("ended", "|u1"), ("ended_env", "<i4"),
+                              ("ended_return", "<f4"), ("ended_length", "<i4"), ("ended_level", "<u4"), ("ended_level_known", "|u1"),
+                              ("running_return", "<f4"), ("running_length", "<i4")):
+            setattr(self, name, _device_view(getattr(out, name), n, typestr, device))
+        self.counts = _device_view(out.counts, 2, "<i4", device)
+        self.capacity = capacity
+        if capacity:
+            self.final_obs = _device_view(out.final_obs, capacity * pglib.OBS_BYTES, "|u1", device).view(capacity, 64, 64, 3)
+        else:
+            self.final_obs = torch.zeros((0, 64, 64, 3), dtype=torch.uint8, device=device)
 
 
 class EnvRecords:
