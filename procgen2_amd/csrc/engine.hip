@@ -5,6 +5,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <array>
 #include <atomic>
 #include <cstring>
 #include <mutex>
@@ -192,6 +193,34 @@ static const Variant* find_variant(int game, int mode) {
     return nullptr;
 }
 
+// Device buffers for one call of a host-pointer entry point, filled from and read back to host memory on the env's stream.
+// The first error is kept and what follows it skipped; on every way out the stream is drained before the buffers are freed.
+struct Staged {
+    hipStream_t stream;
+    hipError_t err = hipSuccess;
+    std::vector<void*> held;
+    ~Staged() {
+        (void)hipStreamSynchronize(stream);
+        for (void* p : held) (void)hipFree(p);
+    }
+    template <class T>
+    T* alloc(size_t count, const T* h_from = nullptr) {  // device T[count], with a copy of h_from[count] where given
+        void* p = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T));
+        if (p) held.push_back(p);
+        if (h_from) upload(p, h_from, count * sizeof(T));
+        return static_cast<T*>(p);
+    }
+    void upload(void* d_to, const void* h_from, size_t bytes) {
+        if (err == hipSuccess) err = hipMemcpyAsync(d_to, h_from, bytes, hipMemcpyHostToDevice, stream);
+    }
+    void finish() { err = err == hipSuccess ? hipStreamSynchronize(stream) : err; }
+    void fetch(void* h_to, const void* d_from, size_t bytes) {  // behind everything the stream holds
+        finish();
+        if (err == hipSuccess) err = hipMemcpy(h_to, d_from, bytes, hipMemcpyDeviceToHost);
+    }
+};
+
 }  // namespace pg
 
 // ------------------------------------------------------------------------------------------------
@@ -239,6 +268,13 @@ struct pgv_env {
     pg::EpisodeBuffers ep{};
 
     pg::StepIO io() const { return {d_obs, d_reward, d_done, d_pending}; }
+    // The per-env output rows, in the order a snapshot holds them behind the state blob.  Separate allocations:
+    // pgv_bind_outputs replaces them one at a time.
+    struct Row { void** d; size_t bytes_per_env; };
+    std::array<Row, 4> rows() {
+        return {{{reinterpret_cast<void**>(&d_reward), 4}, {reinterpret_cast<void**>(&d_done), 1},
+                 {reinterpret_cast<void**>(&d_pending), 1}, {reinterpret_cast<void**>(&d_obs), size_t(pg::kObsBytes)}}};
+    }
 };
 
 // Queue one generator launch behind everything the main stream holds so far.  In the step loop: every
@@ -315,15 +351,16 @@ void pgv_close(pgv_env* e) {
     delete e;
 }
 
-// The device state blob: the game's SoA state followed by the level plan's per-env arrays (pg_engine.h LevelPlan: seven
-// of words, then four of bytes), so that a snapshot of the blob carries them.
+// The device state blob: the game's SoA state followed by the level plan's per-env arrays (pg_carve.h list_plan), so that
+// a snapshot of the blob carries them.
 static size_t game_state_bytes(const pgv_env* e) { return (e->game->state_bytes(e->n) + 255) / 256 * 256; }
-static size_t state_blob_bytes(const pgv_env* e) { return game_state_bytes(e) + size_t(e->n) * pg::kPlanBytesPerEnv; }
+static size_t state_blob_bytes(const pgv_env* e) { return game_state_bytes(e) + pg::Carve::size(pg::list_plan, e->n); }
 
 // The record layout of this engine (pg_records.h): the game's per-env regions as its state listing describes them, then the
-// engine's own per-env data.  The listing is checked here, on the host: every byte of the state block is either an env's
-// or declared engine-wide — a region added later without saying which fails pgv_make instead of dropping out of records.
-static int32_t plan_records(pgv_env* e) {
+// level plan's as list_plan describes them (`planned`), then the engine's output rows.  The game's listing is checked
+// here, on the host: every byte of the state block is either an env's or declared engine-wide — a region added later
+// without saying which fails pgv_make instead of dropping out of records.
+static int32_t plan_records(pgv_env* e, const pg::EnvRegions& planned) {
     const pg::EnvRegions& listed = e->game->regions;
     const std::string who = std::string("pgv_make: ") + e->game->name() + "'s state listing ";
     if (listed.unlisted_bytes)
@@ -332,31 +369,20 @@ static int32_t plan_records(pgv_env* e) {
     for (const pg::EnvRegion& r : listed.v) sum += (size_t(e->n) * r.pieces * r.piece_bytes + 255) / 256 * 256;
     if (sum != e->game->state_bytes(e->n))
         return fail(who + "describes " + std::to_string(sum) + " bytes of a block of " + std::to_string(e->game->state_bytes(e->n)));
-    if (listed.v.size() + 14 > size_t(pg::kMaxRecordRegions)) return fail(who + "has more per-env regions than a record table holds");
+    std::vector<pg::EnvRegion> all = listed.v;
+    all.insert(all.end(), planned.v.begin(), planned.v.end());
+    for (auto [index, bytes] : {std::pair<int*, uint32_t>{&e->rec_reward, 4}, {&e->rec_done, 1}, {&e->rec_obs, pg::kObsBytes}}) {
+        *index = static_cast<int>(all.size());  // (the rows' bases: records_table, per call)
+        all.push_back({nullptr, 1, bytes});
+    }
+    if (all.size() > size_t(pg::kMaxRecordRegions)) return fail(who + "has more per-env regions than a record table holds");
     pg::RecordTable& t = e->rec;
     t = pg::RecordTable{};
     uint32_t at = pg::kRecordHeaderBytes;
-    auto add = [&](uint8_t* base, uint32_t pieces, uint32_t piece_bytes) {
-        t.r[t.regions] = pg::RecordRegion{base, pieces, piece_bytes, at};
-        at += (pieces * piece_bytes + 15u) / 16u * 16u;
-        return t.regions++;
-    };
-    for (const pg::EnvRegion& r : listed.v) add(r.base, r.pieces, r.piece_bytes);
-    add(reinterpret_cast<uint8_t*>(e->game->plan.chain_seed), 1, 4);
-    add(reinterpret_cast<uint8_t*>(e->game->plan.drawn), 1, 4);
-    // (the pending assignment, the number of the level the env is in, what its shadow slot holds: pgv_assign_levels)
-    add(reinterpret_cast<uint8_t*>(e->game->plan.assigned), 1, 4);
-    add(reinterpret_cast<uint8_t*>(e->game->plan.number), 1, 4);
-    add(reinterpret_cast<uint8_t*>(e->game->plan.slot_number), 1, 4);
-    add(e->game->plan.assigned_on, 1, 1);
-    add(e->game->plan.known, 1, 1);
-    add(e->game->plan.slot_assigned, 1, 1);
-    add(reinterpret_cast<uint8_t*>(e->game->plan.kept0), 1, 4);
-    add(reinterpret_cast<uint8_t*>(e->game->plan.kept1), 1, 4);
-    add(e->game->plan.kept_on, 1, 1);
-    e->rec_reward = add(nullptr, 1, 4);
-    e->rec_done = add(nullptr, 1, 1);
-    e->rec_obs = add(nullptr, 1, pg::kObsBytes);
+    for (const pg::EnvRegion& r : all) {
+        t.r[t.regions++] = pg::RecordRegion{r.base, r.pieces, r.piece_bytes, at};
+        at += (r.pieces * r.piece_bytes + 15u) / 16u * 16u;
+    }
     t.n = e->n;
     t.record_bytes = at;
     t.selectors = e->game->stream_selectors();
@@ -470,15 +496,11 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     const size_t sb = state_blob_bytes(e.get());
     PG_HIP(hipMalloc(&e->d_state, sb));
     PG_HIP(hipMemsetAsync(e->d_state, 0, sb, e->stream));
-    PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_obs), size_t(num_envs) * pg::kObsBytes));
-    PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_reward), size_t(num_envs) * 4));
-    PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_done), size_t(num_envs)));
-    PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_pending), size_t(num_envs)));
     e->own_obs = e->own_reward = e->own_done = true;
-    PG_HIP(hipMemsetAsync(e->d_obs, 0, size_t(num_envs) * pg::kObsBytes, e->stream));
-    PG_HIP(hipMemsetAsync(e->d_reward, 0, size_t(num_envs) * 4, e->stream));
-    PG_HIP(hipMemsetAsync(e->d_done, 0, size_t(num_envs), e->stream));
-    PG_HIP(hipMemsetAsync(e->d_pending, 0, size_t(num_envs), e->stream));
+    for (const pgv_env::Row& row : e->rows()) {
+        PG_HIP(hipMalloc(row.d, size_t(num_envs) * row.bytes_per_env));
+        PG_HIP(hipMemsetAsync(*row.d, 0, size_t(num_envs) * row.bytes_per_env, e->stream));
+    }
 
     e->game->bind(e->d_state, num_envs, e->atlas.view());
     if (const size_t scratch = e->game->scratch_bytes(num_envs)) {
@@ -486,15 +508,10 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
         PG_HIP(hipMemsetAsync(e->d_scratch, 0, scratch, e->stream));
         e->game->bind_scratch(e->d_scratch, num_envs);
     }
-    {
-        uint32_t* words = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(e->d_state) + game_state_bytes(e.get()));
-        uint8_t* bytes = reinterpret_cast<uint8_t*>(words + size_t(7) * num_envs);
-        e->game->plan = pg::LevelPlan{num_levels, start_level, words, words + num_envs, words + size_t(2) * num_envs,
-                                      words + size_t(3) * num_envs, words + size_t(4) * num_envs, bytes, bytes + num_envs,
-                                      bytes + size_t(2) * num_envs, words + size_t(5) * num_envs, words + size_t(6) * num_envs,
-                                      bytes + size_t(3) * num_envs};
-    }
-    if (plan_records(e.get())) return 1;
+    pg::EnvRegions planned;
+    e->game->plan = pg::LevelPlan{num_levels, start_level};
+    pg::Carve::bind(pg::list_plan, static_cast<uint8_t*>(e->d_state) + game_state_bytes(e.get()), e->game->plan, num_envs, &planned);
+    if (plan_records(e.get(), planned)) return 1;
     e->game->launch_make(e->stream, seed_base, env_offset);
     PG_HIP(hipGetLastError());
     PG_HIP(hipStreamSynchronize(e->stream));
@@ -641,48 +658,21 @@ int32_t pgv_episodes_enable(pgv_env* e, const pgv_episode_config* cfg) {
     if (cfg->final_capacity < 0 || cfg->final_capacity > e->n)
         return fail("pgv_episodes_enable: final_capacity must be in 0 .. num_envs");
     PG_HIP(hipSetDevice(e->device));
-    const size_t n = size_t(e->n), blocks = size_t(pg::episode_blocks(e->n));
-    size_t at = 0;
-    auto take = [&](size_t bytes) {  // offsets first, the block afterwards: every buffer 256-byte aligned
-        const size_t here = at;
-        at += (bytes + 255) / 256 * 256;
-        return here;
-    };
-    const size_t o_reward = take(n * 4), o_term = take(n), o_trunc = take(n), o_ended = take(n), o_counts = take(8), o_env = take(n * 4),
-                 o_ret = take(n * 4), o_len = take(n * 4), o_level = take(n * 4), o_known = take(n), o_rret = take(n * 4), o_rlen = take(n * 4),
-                 o_prev = take(n), o_kret = take(n * 4), o_klen = take(n * 4), o_blocks = take(blocks * 4),
-                 o_final = take(size_t(cfg->final_capacity) * pg::kObsBytes);
-    void* mem = nullptr;
-    PG_HIP(hipMalloc(&mem, at));
-    hipError_t err = hipMemsetAsync(mem, 0, at, e->stream);
-    if (err != hipSuccess) {
-        (void)hipFree(mem);
-        return fail(std::string("pgv_episodes_enable: ") + hipGetErrorString(err));
-    }
-    uint8_t* m = static_cast<uint8_t*>(mem);
     pg::EpisodeBuffers b{};
     b.n = e->n;
     b.max_steps = cfg->max_episode_steps;
     b.capacity = cfg->final_capacity;
     b.level_number = e->game->plan.number;
     b.level_known = e->game->plan.known;
-    b.reward = reinterpret_cast<float*>(m + o_reward);
-    b.terminated = m + o_term;
-    b.truncated = m + o_trunc;
-    b.ended = m + o_ended;
-    b.counts = reinterpret_cast<int32_t*>(m + o_counts);
-    b.ended_env = reinterpret_cast<int32_t*>(m + o_env);
-    b.ended_return = reinterpret_cast<float*>(m + o_ret);
-    b.ended_length = reinterpret_cast<int32_t*>(m + o_len);
-    b.ended_level = reinterpret_cast<uint32_t*>(m + o_level);
-    b.ended_level_known = m + o_known;
-    b.running_return = reinterpret_cast<float*>(m + o_rret);
-    b.running_length = reinterpret_cast<int32_t*>(m + o_rlen);
-    b.prev_done = m + o_prev;
-    b.kept_return = reinterpret_cast<float*>(m + o_kret);
-    b.kept_length = reinterpret_cast<int32_t*>(m + o_klen);
-    b.block_count = reinterpret_cast<int32_t*>(m + o_blocks);
-    b.final_obs = cfg->final_capacity ? m + o_final : nullptr;
+    const size_t bytes = pg::Carve::size(pg::list_episodes, e->n, b);
+    void* mem = nullptr;
+    PG_HIP(hipMalloc(&mem, bytes));
+    hipError_t err = hipMemsetAsync(mem, 0, bytes, e->stream);
+    if (err != hipSuccess) {
+        (void)hipFree(mem);
+        return fail(std::string("pgv_episodes_enable: ") + hipGetErrorString(err));
+    }
+    pg::Carve::bind(pg::list_episodes, mem, b, e->n);
     e->d_episodes = mem;
     e->ep = b;
     e->ep_autoreset = cfg->autoreset;
@@ -802,12 +792,23 @@ struct SnapshotHeader {
 // 2: round 2.  3: round 3 (per-env contiguous rings and entity tables in bossfight, caveflyer, chaser, climber; caveflyer's
 // wall-bit columns and hazard places).  4: round 5/6 (the pending byte carries the parity of the step it is about —
 // pg_prefetch.h reset_due_mark / reset_served_mark — where it used to be 0 / 1; coinrun's hazard hand-off left the blob).
-// 5: the level plan's assignment arrays lie behind the game's state (pg_engine.h LevelPlan; pgv_assign_levels).
+// 5: the level plan's assignment arrays lie behind the game's state (pg_carve.h LevelPlan; pgv_assign_levels).
 static constexpr uint32_t kSnapshotMagic = 0x50474e35u;
 
-static size_t snapshot_bytes(const pgv_env* e) {
-    return sizeof(SnapshotHeader) + state_blob_bytes(e) + size_t(e->n) * (4 + 1 + 1) +
-           size_t(e->n) * pg::kObsBytes;
+static size_t snapshot_bytes(pgv_env* e) {
+    size_t bytes = sizeof(SnapshotHeader) + state_blob_bytes(e);
+    for (const pgv_env::Row& row : e->rows()) bytes += size_t(e->n) * row.bytes_per_env;
+    return bytes;
+}
+// What follows the header: the state blob, then the output rows — device to host (save) or back (load).
+static int32_t snapshot_copy(pgv_env* e, uint8_t* h_body, size_t blob_bytes, bool load) {
+    std::vector<std::pair<void*, size_t>> parts{{e->d_state, blob_bytes}};
+    for (const pgv_env::Row& row : e->rows()) parts.push_back({*row.d, size_t(e->n) * row.bytes_per_env});
+    for (const auto& [d, bytes] : parts) {
+        PG_HIP(load ? hipMemcpy(d, h_body, bytes, hipMemcpyHostToDevice) : hipMemcpy(h_body, d, bytes, hipMemcpyDeviceToHost));
+        h_body += bytes;
+    }
+    return 0;
 }
 
 int64_t pgv_snapshot_bytes(pgv_env* e) { return e ? static_cast<int64_t>(snapshot_bytes(e)) : -1; }
@@ -824,17 +825,7 @@ int32_t pgv_save_state(pgv_env* e, void* h_buffer, int64_t capacity) {
     SnapshotHeader hd{kSnapshotMagic, static_cast<uint32_t>(pgv_game_id(e->game->name())), e->n, e->env_offset,
                       state_blob_bytes(e), e->step_index, e->game->plan.num_levels, e->game->plan.start_level, e->mode, e->game_flags, 0};
     std::memcpy(out, &hd, sizeof(hd));
-    out += sizeof(hd);
-    PG_HIP(hipMemcpy(out, e->d_state, hd.state_bytes, hipMemcpyDeviceToHost));
-    out += hd.state_bytes;
-    PG_HIP(hipMemcpy(out, e->d_reward, size_t(e->n) * 4, hipMemcpyDeviceToHost));
-    out += size_t(e->n) * 4;
-    PG_HIP(hipMemcpy(out, e->d_done, size_t(e->n), hipMemcpyDeviceToHost));
-    out += size_t(e->n);
-    PG_HIP(hipMemcpy(out, e->d_pending, size_t(e->n), hipMemcpyDeviceToHost));
-    out += size_t(e->n);
-    PG_HIP(hipMemcpy(out, e->d_obs, size_t(e->n) * pg::kObsBytes, hipMemcpyDeviceToHost));
-    return 0;
+    return snapshot_copy(e, out + sizeof(hd), hd.state_bytes, false);
 }
 
 int32_t pgv_load_state(pgv_env* e, const void* h_buffer, int64_t size) {
@@ -851,16 +842,7 @@ int32_t pgv_load_state(pgv_env* e, const void* h_buffer, int64_t size) {
     PG_HIP(hipSetDevice(e->device));
     PG_HIP(hipStreamSynchronize(e->stream));
     if (e->side) PG_HIP(hipStreamSynchronize(e->side));
-    in += sizeof(hd);
-    PG_HIP(hipMemcpy(e->d_state, in, hd.state_bytes, hipMemcpyHostToDevice));
-    in += hd.state_bytes;
-    PG_HIP(hipMemcpy(e->d_reward, in, size_t(e->n) * 4, hipMemcpyHostToDevice));
-    in += size_t(e->n) * 4;
-    PG_HIP(hipMemcpy(e->d_done, in, size_t(e->n), hipMemcpyHostToDevice));
-    in += size_t(e->n);
-    PG_HIP(hipMemcpy(e->d_pending, in, size_t(e->n), hipMemcpyHostToDevice));
-    in += size_t(e->n);
-    PG_HIP(hipMemcpy(e->d_obs, in, size_t(e->n) * pg::kObsBytes, hipMemcpyHostToDevice));
+    if (snapshot_copy(e, const_cast<uint8_t*>(in) + sizeof(hd), hd.state_bytes, true)) return 1;
     e->step_index = hd.step_index;
     PG_HIP(e->game->state_loaded(e->stream));  // (on the env's stream: ordered in front of the next step)
     pregen(e, true, true);  // queued shadow slots of the snapshot get their generator launch
@@ -939,23 +921,16 @@ static int32_t records_host(pgv_env* e, const int32_t* h_indices, int32_t count,
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
     const size_t bytes = size_t(count) * e->rec.record_bytes;
-    uint8_t* d_records = nullptr;
-    int32_t* d_indices = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_records), bytes);
-    if (err == hipSuccess && h_indices) {
-        err = hipMalloc(reinterpret_cast<void**>(&d_indices), size_t(count) * 4);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_indices, h_indices, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
+    pg::Staged dev{e->stream};
+    uint8_t* d_records = dev.alloc<uint8_t>(bytes);
+    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
+    if (load) dev.upload(d_records, h_records, bytes);
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = load ? pgv_load_envs(e, d_indices, count, d_records, tag) : pgv_save_envs(e, d_indices, count, d_records)) return rc;
+        if (load) dev.finish(); else dev.fetch(h_records, d_records, bytes);
     }
-    if (err == hipSuccess && load) err = hipMemcpyAsync(d_records, h_records, bytes, hipMemcpyHostToDevice, e->stream);
-    int32_t rc = 0;
-    if (err == hipSuccess) rc = load ? pgv_load_envs(e, d_indices, count, d_records, tag) : pgv_save_envs(e, d_indices, count, d_records);
-    if (err == hipSuccess && rc == 0) err = hipStreamSynchronize(e->stream);
-    if (err == hipSuccess && rc == 0 && !load) err = hipMemcpy(h_records, d_records, bytes, hipMemcpyDeviceToHost);
-    if (err != hipSuccess || rc != 0) (void)hipStreamSynchronize(e->stream);  // nothing may still be using what is freed next
-    if (d_indices) (void)hipFree(d_indices);
-    if (d_records) (void)hipFree(d_records);
-    if (err != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(err));
-    return rc;
+    if (dev.err != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(dev.err));
+    return 0;
 }
 int32_t pgv_save_envs_host(pgv_env* e, const int32_t* h_indices, int32_t count, void* h_records) {
     return records_host(e, h_indices, count, h_records, false, 0);
@@ -965,7 +940,7 @@ int32_t pgv_load_envs_host(pgv_env* e, const int32_t* h_indices, int32_t count, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Assigned levels (pg_engine.h LevelPlan)
+// Assigned levels (pg_carve.h LevelPlan)
 // ------------------------------------------------------------------------------------------------
 }  // extern "C"
 
@@ -1020,16 +995,11 @@ int32_t pgv_assign_levels_host(pgv_env* e, const int32_t* h_indices, int32_t cou
     if (count > 0 && !h_levels) return fail("pgv_assign_levels_host: the level buffer is NULL");
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
-    int32_t* d_buf = nullptr;  // (a call may name more indices than the batch has envs: not the staging buffers)
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_buf), size_t(count) * 8);
-    if (err == hipSuccess) err = hipMemcpyAsync(d_buf, h_levels, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
-    if (err == hipSuccess && h_indices) err = hipMemcpyAsync(d_buf + count, h_indices, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
-    int32_t rc = 0;
-    if (err == hipSuccess) rc = pgv_assign_levels(e, h_indices ? d_buf + count : nullptr, count, d_buf);
-    (void)hipStreamSynchronize(e->stream);  // the host buffers are the caller's, and nothing may still be using what is freed next
-    if (d_buf) (void)hipFree(d_buf);
-    if (err != hipSuccess) return fail(std::string("pgv_assign_levels_host: ") + hipGetErrorString(err));
-    return rc;
+    pg::Staged dev{e->stream};  // (a call may name more indices than the batch has envs: not the staging buffers)
+    const int32_t* d_levels = dev.alloc(size_t(count), h_levels);
+    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
+    if (dev.err != hipSuccess) return fail(std::string("pgv_assign_levels_host: ") + hipGetErrorString(dev.err));
+    return pgv_assign_levels(e, d_indices, count, d_levels);  // (the host buffers are the caller's: drained on the way out)
 }
 
 const uint32_t* pgv_level_numbers(pgv_env* e) { return e ? e->game->plan.number : nullptr; }
@@ -1205,18 +1175,14 @@ int32_t pgv_render_frame(pgv_env* e, int32_t index, int32_t width, int32_t heigh
         return fail("pgv_render_frame: bad frame size or NULL buffer");
     PG_HIP(hipSetDevice(e->device));
     const size_t px = size_t(width) * height;
-    uint32_t* d_px = nullptr;
-    PG_HIP(hipMalloc(reinterpret_cast<void**>(&d_px), px * 4));
-    if (!e->game->launch_frame(e->stream, index, d_px, width, height)) {
-        hipFree(d_px);
+    pg::Staged dev{e->stream};
+    uint32_t* d_px = dev.alloc<uint32_t>(px);
+    if (dev.err == hipSuccess && !e->game->launch_frame(e->stream, index, d_px, width, height))
         return fail(std::string("pgv_render_frame: not implemented for ") + e->game->name());
-    }
     std::vector<uint32_t> host(px);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err == hipSuccess) err = hipMemcpy(host.data(), d_px, px * 4, hipMemcpyDeviceToHost);
-    hipFree(d_px);
-    if (err != hipSuccess) return fail(std::string("pgv_render_frame: ") + hipGetErrorString(err));
+    if (dev.err == hipSuccess) dev.err = hipGetLastError();
+    dev.fetch(host.data(), d_px, px * 4);
+    if (dev.err != hipSuccess) return fail(std::string("pgv_render_frame: ") + hipGetErrorString(dev.err));
     for (size_t k = 0; k < px; k++) {  // RGBA → RGB, row-major (coinrun.cpp:401-407)
         h_rgb[3 * k + 0] = static_cast<uint8_t>(host[k]);
         h_rgb[3 * k + 1] = static_cast<uint8_t>(host[k] >> 8);
@@ -1246,22 +1212,15 @@ int32_t pgv_render_frames_host(pgv_env* e, const int32_t* h_indices, int32_t cou
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
     const size_t bytes = size_t(count) * size_t(height) * size_t(width) * 3;
-    uint8_t* d_rgb = nullptr;
-    int32_t* d_indices = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_rgb), bytes);
-    if (err == hipSuccess && h_indices) {
-        err = hipMalloc(reinterpret_cast<void**>(&d_indices), size_t(count) * 4);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_indices, h_indices, size_t(count) * 4, hipMemcpyHostToDevice, e->stream);
+    pg::Staged dev{e->stream};
+    uint8_t* d_rgb = dev.alloc<uint8_t>(bytes);
+    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_render_frames(e, d_indices, count, width, height, d_rgb)) return rc;
+        dev.fetch(h_rgb, d_rgb, bytes);
     }
-    int32_t rc = 0;
-    if (err == hipSuccess) rc = pgv_render_frames(e, d_indices, count, width, height, d_rgb);
-    if (err == hipSuccess && rc == 0) err = hipStreamSynchronize(e->stream);
-    if (err == hipSuccess && rc == 0) err = hipMemcpy(h_rgb, d_rgb, bytes, hipMemcpyDeviceToHost);
-    if (err != hipSuccess || rc != 0) (void)hipStreamSynchronize(e->stream);  // nothing may still be using what is freed next
-    if (d_indices) (void)hipFree(d_indices);
-    if (d_rgb) (void)hipFree(d_rgb);
-    if (err != hipSuccess) return fail(std::string("pgv_render_frames_host: ") + hipGetErrorString(err));
-    return rc;
+    if (dev.err != hipSuccess) return fail(std::string("pgv_render_frames_host: ") + hipGetErrorString(dev.err));
+    return 0;
 }
 
 int32_t pgv_set_debug(pgv_env* e, int32_t flags) {

@@ -15,6 +15,7 @@
 // Bounds: every list index is below the number of ended envs <= n; a ring row is written only where place < capacity.
 #pragma once
 
+#include "pg_carve.h"
 #include "pg_defs.h"
 
 namespace pg {
@@ -84,6 +85,28 @@ struct EpisodeBuffers {
     int32_t* kept_length;    // [n]
     int32_t* block_count;    // [ceil(n / 256)]
 };
+inline int episode_blocks(int n) { return (n + kEpisodeBlock - 1) / kEpisodeBlock; }
+// The one device block behind the seventeen buffers (pg_carve.h): n and b.capacity say how big they are.
+inline void list_episodes(Carve& c, EpisodeBuffers& b, int n) {
+    const size_t envs = size_t(n);
+    c.take(b.reward, envs * 4);
+    c.take(b.terminated, envs);
+    c.take(b.truncated, envs);
+    c.take(b.ended, envs);
+    c.take(b.counts, 8);  // [0] ended envs, [1] ring rows written
+    c.take(b.ended_env, envs * 4);
+    c.take(b.ended_return, envs * 4);
+    c.take(b.ended_length, envs * 4);
+    c.take(b.ended_level, envs * 4);
+    c.take(b.ended_level_known, envs);
+    c.take(b.running_return, envs * 4);
+    c.take(b.running_length, envs * 4);
+    c.take(b.prev_done, envs);
+    c.take(b.kept_return, envs * 4);
+    c.take(b.kept_length, envs * 4);
+    c.take(b.block_count, size_t(episode_blocks(n)) * 4);
+    c.take(b.final_obs, size_t(b.capacity) * kObsBytes);  // (no ring: nullptr)
+}
 
 #if defined(__HIPCC__)
 __global__ void __launch_bounds__(kEpisodeBlock) episode_before_kernel(EpisodeBuffers b) {
@@ -181,7 +204,6 @@ __global__ void __launch_bounds__(kEpisodeBlock) episode_list_kernel(EpisodeBuff
     }
 }
 
-inline int episode_blocks(int n) { return (n + kEpisodeBlock - 1) / kEpisodeBlock; }
 inline void launch_episode_before(hipStream_t st, const EpisodeBuffers& b) {
     hipLaunchKernelGGL(episode_before_kernel, dim3(episode_blocks(b.n)), dim3(kEpisodeBlock), 0, st, b);
 }

@@ -26,7 +26,7 @@ namespace pg {
 
 constexpr int kRecordHeaderBytes = 16;
 constexpr int kMaxRecordRegions = 40;
-constexpr uint32_t kRecordLayoutVersion = 2;  // part of pgv_env_record_tag: bump with the layout above (2: the level plan's assignment arrays travel)
+constexpr uint32_t kRecordLayoutVersion = 3;  // part of pgv_env_record_tag: bump with the layout above (2: the level plan's assignment arrays travel; 3: the plan's regions in list_plan's order)
 
 struct RecordRegion {
     uint8_t* base;

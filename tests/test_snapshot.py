@@ -279,6 +279,32 @@ def test_snapshot_at_full_size(game, saves, capsys):
         v.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("game", ["maze", "chaser"])  # with prefetch slots, and without
+def test_the_level_plan_lies_in_the_snapshot_where_its_listing_says(game):
+    """The last 32·n bytes of a snapshot's state blob are the level plan's arrays at the offsets that
+    tests/cpp/test_engine_layout.cpp pins for the listing (pg_carve.h list_plan) — the engine binds its kernels' pointers with
+    that listing, so what they wrote is found there: word array 0 the seeds the envs were made with, word array 3 what
+    pgv_level_numbers shows, byte array 1 what pgv_level_known shows.  And the snapshot's size is its parts'."""
+    import torch
+    from procgen2_amd.vec_env import ProcgenVecEnv
+    n, seed_base, env_offset = 65, 4242, 7
+    v = ProcgenVecEnv(game, n, seed_base=seed_base, env_offset=env_offset, num_levels=5, start_level=100)
+    for _ in range(20):
+        v.step_synthetic(RUN_SEED)
+    snap = v.save_state()
+    numbers = v.level_numbers.view(torch.int32).cpu().numpy().view(np.uint32)
+    known = v.level_known.cpu().numpy()
+    v.close()
+    state_bytes = int(snap[16:24].view(np.uint64)[0])  # the header: magic, game, n, env_offset, then the blob's length
+    assert snap.size == 48 + state_bytes + n * (4 + 1 + 1 + 12288)
+    plan = snap[48 + state_bytes - 32 * n:48 + state_bytes]
+    assert np.array_equal(plan[12 * n:16 * n].view(np.uint32), numbers)
+    assert np.array_equal(plan[28 * n + n:28 * n + 2 * n], known)
+    assert np.array_equal(plan[0:4 * n].view(np.uint32), (seed_base + env_offset + np.arange(n)).astype(np.uint32))
+    assert known.all() and ((numbers >= 100) & (numbers < 105)).all()  # (level-seed mode: the words compared are not blank)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # human-size frames and the camera (D15)
 # ---------------------------------------------------------------------------------------------------------------------
