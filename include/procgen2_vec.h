@@ -305,6 +305,54 @@ PGV_API int32_t pgv_step_episodes_host(pgv_env* env, const int32_t* h_actions); 
  * h_episode_ms[s] the two episode launches behind the step alone (host arrays of `steps` floats, either may be NULL). */
 PGV_API int32_t pgv_step_episodes_times(pgv_env* env, int32_t steps, uint32_t run_seed, float* h_step_ms, float* h_episode_ms);
 
+/* Steps without frames: play a sequence of T sub-steps in one call and render only the last of them, or none.  (Look-ahead
+ * over forked envs, fast-forwarding a batch, open-loop evaluation, action repeat, any consumer of rewards and dones that
+ * does not look at pixels; the reference and the original procgen draw every step.)
+ *
+ *   1. pgv_step_sequence with T sub-steps leaves the engine as T calls of pgv_step would — of pgv_step_synthetic when
+ *      `actions` is NULL — with the same rows, bit for bit, through any number of auto-resets inside the sequence: the game
+ *      state, the random streams, the prefetched levels and pending resets, the level words and pending assignments, the
+ *      step counter, the engine's own reward / done rows (the last sub-step's), pgv_generator_launches and, with
+ *      PGV_FRAMES_LAST, the whole observation slab.
+ *   2. rewards[t][i] / dones[t][i] are what pgv_reward()[i] / pgv_done()[i] would have held after sub-step t.  An env that
+ *      reports done in sub-step t serves its reset in sub-step t + 1 (reward 0, done 0) and plays on: the engine's own
+ *      next-step policy.  The call is NOT a frame-skip wrapper that freezes ended envs; the caller cuts at the first done,
+ *      and seq_* does that cutting on the device.
+ *   3. seq_length[i] is the index of env i's first sub-step with done set, plus 1, or T if there is none; seq_done[i] says
+ *      whether there is one; seq_return[i] is the float32 sum of rewards[0 .. seq_length - 1][i] in step order from 0.0f, one
+ *      rounding a step (ret = ret + r, the rule of ended_return).  Pure functions of the rows, available with rewards / dones
+ *      NULL; a sub-step that serves a reset counts like any other.
+ *   4. PGV_FRAMES_NONE: nothing is drawn for the envs that play.  Where a game needs frames of its own inside a frameless
+ *      step (chaser's late pass over the envs just reset) it makes them, which is why obs is unspecified and not untouched.
+ *      pgv_render_obs(NULL) afterwards leaves exactly the slab PGV_FRAMES_LAST would have left; pgv_render_obs(mask) does so
+ *      for the rows whose mask byte is non-zero and leaves the others' bytes alone.  pgv_render_obs changes no state, at any
+ *      time between steps: an engine that called it goes on exactly as one that did not, and twice gives the same bytes.
+ *   5. Everything is enqueued on the env's stream; nothing is allocated per call and the host is not synchronised.  The
+ *      _host forms take HOST pointers for every pointer of the struct, allocate and free their staging and synchronise.
+ *   6. Every check is made on the host before anything is enqueued; a refusal leaves a message and the engine as it was:
+ *      steps < 0, an unknown `frames`, a struct_size too small, with actions a stride that is neither 0 nor >= N.
+ *      steps = 0 succeeds and does nothing (no output is written).
+ *   7. On an engine with episodes enabled the call behaves as pgv_step does: its steps are not counted. */
+#define PGV_FRAMES_LAST 0 /* the last sub-step is a complete pgv_step: its frame is rendered */
+#define PGV_FRAMES_NONE 1 /* no sub-step renders; obs is unspecified until pgv_render_obs or the next rendering call */
+typedef struct pgv_sequence {
+    uint32_t struct_size;
+    int32_t steps;          /* T >= 0; 0 succeeds and does nothing */
+    const int32_t* actions; /* device int32; sub-step t reads row actions + t*action_stride; NULL: synthetic */
+    int64_t action_stride;  /* elements; 0 = the same row every sub-step (action repeat), else >= N */
+    uint32_t run_seed;      /* synthetic actions only: same hash, same step counter as pgv_step_synthetic */
+    int32_t frames;         /* PGV_FRAMES_* */
+    float* rewards;         /* device f32[T][N] or NULL */
+    uint8_t* dones;         /* device u8 [T][N] or NULL */
+    float* seq_return;      /* device f32[N] or NULL */
+    int32_t* seq_length;    /* device i32[N] or NULL */
+    uint8_t* seq_done;      /* device u8 [N] or NULL */
+} pgv_sequence;
+PGV_API int32_t pgv_step_sequence(pgv_env* env, const pgv_sequence* seq);
+PGV_API int32_t pgv_step_sequence_host(pgv_env* env, const pgv_sequence* seq); /* every pointer a HOST pointer; synchronous, as pgv_step_host */
+PGV_API int32_t pgv_render_obs(pgv_env* env, const uint8_t* d_mask);           /* device u8[N] or NULL = all */
+PGV_API int32_t pgv_render_obs_host(pgv_env* env, const uint8_t* h_mask);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

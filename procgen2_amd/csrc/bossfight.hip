@@ -1489,6 +1489,14 @@ class BossfightGame final : public Game {
             hipLaunchKernelGGL(setup_kernel, dim3(groups + (s_.n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, st, s_, atlas_, mask, groups);
         }
     }
+    // A step without a frame (pgv_step_sequence): of the pre-pass only the workgroups that make the random streams' next
+    // blocks ahead (n_groups = 0: every workgroup is one of those).  Without them a gang regenerates its block in place
+    // (pg_gang.h GangRng::refill) — the same words, later: a frameless sub-step of 135 µs against 99 (docs/OPTLOG.md).
+    void launch_no_frame(hipStream_t st, StepIO io) override {
+        (void)io;
+        if (lean())
+            hipLaunchKernelGGL(setup_kernel, dim3((s_.n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, st, s_, atlas_, nullptr, 0);
+    }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         if (lean())
             hipLaunchKernelGGL(render_kernel, dim3(kRenderParts * s_.n), dim3(64), 0, st, s_, atlas_, mask, io);

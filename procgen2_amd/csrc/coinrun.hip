@@ -1704,6 +1704,28 @@ __global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasVie
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// A step without a frame (pgv_step_sequence) still owes the env the one thing its render wavefront does beside drawing: the
+// entity table of an env whose step ended after fewer than four sub-steps is brought to that sub-step (resolve_kernel,
+// SC_REDO) and the flag cleared.  Left set, the flag would be applied to whatever table the env holds when it is next
+// drawn — after the reset the env's ending brings, the next level's.  A wavefront looks at the flags of 64 envs; the few
+// that are set (envs that ended an episode in this step) are served one after the other, a lane per entity.
+__global__ void __launch_bounds__(64) redo_kernel(State s) {
+    const int lane = threadIdx.x, env0 = blockIdx.x * 64, mine = env0 + lane;
+    unsigned long long todo = __ballot(mine < s.n && SCI(s, SC_REDO, mine) != 0);
+    while (todo) {  // (wave-uniform)
+        const int env = env0 + __builtin_ctzll(todo);  // < n: only such lanes vote
+        todo &= todo - 1;
+        const int redo = SCI(s, SC_REDO, env);
+        const int buf = (SI(s, I_FLAGS, env) & kFlagBuf) ? 1 : 0;
+        if (lane < SI(s, I_NENT, env)) {  // <= kMaxEnt < 64
+            float hb[6];
+            entity_step(s, env, lane, 1 - buf, redo, hb);
+        }
+        if (lane == 0) SCI(s, SC_REDO, env) = 0;
+    }
+}
+static_assert(kMaxEnt <= 64, "a lane per entity");
+
 class CoinrunGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "coinrun"; }
@@ -1820,6 +1842,10 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(64 * kRenderWaves), 0, st, s_, atlas_, mask, io,
                            debug_flags);
+    }
+    void launch_no_frame(hipStream_t st, StepIO io) override {
+        (void)io;
+        hipLaunchKernelGGL(redo_kernel, dim3(blocks()), dim3(64), 0, st, s_);
     }
     // Scratch (not state, not in snapshots): the pre-pass's hand-over, then the hazards' boxes — written by logic_kernel's
     // entity lanes and read by resolve_kernel of the same step, only where a candidate bit of that step says so.

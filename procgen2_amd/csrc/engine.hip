@@ -16,6 +16,7 @@
 #include "pg_episodes.h"
 #include "pg_order.h"
 #include "pg_records.h"
+#include "pg_sequence.h"
 #include "png_decode.h"
 
 #ifndef PG_DEFAULT_GAME
@@ -266,6 +267,9 @@ struct pgv_env {
     int ep_autoreset = 0;
     void* d_episodes = nullptr;
     pg::EpisodeBuffers ep{};
+    // steps without frames (pg_sequence.h; pgv_step_sequence): the running values of the summary, one block
+    void* d_sequence = nullptr;
+    pg::SequenceBuffers seq{};
 
     pg::StepIO io() const { return {d_obs, d_reward, d_done, d_pending}; }
     // The per-env output rows, in the order a snapshot holds them behind the state blob.  Separate allocations:
@@ -345,6 +349,7 @@ void pgv_close(pgv_env* e) {
     if (e->own_done && e->d_done) hipFree(e->d_done);
     if (e->d_pending) hipFree(e->d_pending);
     if (e->d_episodes) hipFree(e->d_episodes);
+    if (e->d_sequence) hipFree(e->d_sequence);
     if (e->d_host_i32) hipFree(e->d_host_i32);
     if (e->d_host_u8) hipFree(e->d_host_u8);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -502,6 +507,9 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
         PG_HIP(hipMemsetAsync(*row.d, 0, size_t(num_envs) * row.bytes_per_env, e->stream));
     }
 
+    PG_HIP(hipMalloc(&e->d_sequence, pg::Carve::size(pg::list_sequence, num_envs)));  // (written before it is read: pg_sequence.h)
+    pg::Carve::bind(pg::list_sequence, e->d_sequence, e->seq, num_envs);
+
     e->game->bind(e->d_state, num_envs, e->atlas.view());
     if (const size_t scratch = e->game->scratch_bytes(num_envs)) {
         PG_HIP(hipMalloc(&e->d_scratch, scratch));
@@ -540,8 +548,11 @@ int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
 // level generator's launch on the side stream), behind the render pre-pass = in front of the render kernel, behind the
 // render launch (jumper: its list kernel included).  What follows after_render inside a step is the late pass of a game
 // that resets beside its render kernel (chaser).
+// `frame` = false: a step without a frame (pgv_step_sequence) — neither the pre-pass nor the render launch; the game's
+// launch_no_frame in their place, and the late pass all the same (chaser: the pending bytes, the due list and the reset
+// envs' base layers depend on it).
 static int32_t step_impl(pgv_env* e, const int32_t* d_actions, uint32_t run_seed, hipEvent_t before_render = nullptr,
-                         hipEvent_t after_render = nullptr, hipEvent_t after_logic = nullptr) {
+                         hipEvent_t after_render = nullptr, hipEvent_t after_logic = nullptr, bool frame = true) {
     // hipGetLastError is sticky and per thread: whatever the embedding application left behind (a stream query's
     // NotReady, say) is not this step's; start clean.
     (void)hipGetLastError();
@@ -564,13 +575,16 @@ static int32_t step_impl(pgv_env* e, const int32_t* d_actions, uint32_t run_seed
     pregen(e, false, false);  // before the render launch: the generator overlaps it
     launched();
     if (after_logic && status == hipSuccess) status = hipEventRecord(after_logic, e->stream);
-    if (status == hipSuccess) {
+    if (frame && status == hipSuccess) {
         e->game->launch_prepass(e->stream, nullptr);
         launched();
     }
     if (before_render && status == hipSuccess) status = hipEventRecord(before_render, e->stream);
     if (status == hipSuccess) {
-        e->game->launch_render_step(e->stream, e->io());
+        if (frame)
+            e->game->launch_render_step(e->stream, e->io());
+        else
+            e->game->launch_no_frame(e->stream, e->io());
         launched();
     }
     if (after_render && status == hipSuccess) status = hipEventRecord(after_render, e->stream);
@@ -585,6 +599,11 @@ static int32_t step_impl(pgv_env* e, const int32_t* d_actions, uint32_t run_seed
     }
     if (status != hipSuccess) return fail(std::string("step: ") + hipGetErrorString(status));
     return 0;
+}
+
+// A step without a frame, by name: the flag sits behind three event pointers.
+static int32_t step_no_frame(pgv_env* e, const int32_t* d_actions, uint32_t run_seed) {
+    return step_impl(e, d_actions, run_seed, nullptr, nullptr, nullptr, /*frame=*/false);
 }
 
 int32_t pgv_step(pgv_env* e, const int32_t* d_actions) {
@@ -752,6 +771,106 @@ int32_t pgv_step_episodes_host(pgv_env* e, const int32_t* h_actions) {
     PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
     PG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is the caller's: do not keep reading it
     return step_episodes_impl("pgv_step_episodes_host", e, e->d_host_i32, 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Steps without frames (pg_sequence.h)
+// ------------------------------------------------------------------------------------------------
+static int32_t sequence_arguments(const char* who, pgv_env* e, const pgv_sequence* q) {
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!q || q->struct_size < sizeof(pgv_sequence)) return fail(std::string(who) + ": sequence is NULL or struct_size too small");
+    if (q->steps < 0) return fail(std::string(who) + ": steps is negative");
+    if (q->frames != PGV_FRAMES_LAST && q->frames != PGV_FRAMES_NONE) return fail(std::string(who) + ": unknown frames mode " + std::to_string(q->frames));
+    if (q->actions && q->action_stride != 0 && q->action_stride < e->n)
+        return fail(std::string(who) + ": action_stride must be 0 (the same row every sub-step) or >= num_envs");
+    return 0;
+}
+
+int32_t pgv_step_sequence(pgv_env* e, const pgv_sequence* q) {
+    if (sequence_arguments("pgv_step_sequence", e, q)) return 1;
+    if (q->steps == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    pg::SequenceRow row{};
+    row.n = e->n;
+    row.fold = (q->seq_return || q->seq_length || q->seq_done) ? 1 : 0;
+    row.acc = e->seq;
+    row.seq_return = q->seq_return;
+    row.seq_length = q->seq_length;
+    row.seq_done = q->seq_done;
+    const bool rows = q->rewards || q->dones;
+    for (int32_t t = 0; t < q->steps; t++) {
+        const bool last = t == q->steps - 1;
+        const int32_t* actions = q->actions ? q->actions + int64_t(t) * q->action_stride : nullptr;
+        const bool frame = last && q->frames == PGV_FRAMES_LAST;
+        if (frame ? step_impl(e, actions, q->run_seed) : step_no_frame(e, actions, q->run_seed))
+            return fail(pg::g_error + " (pgv_step_sequence: sub-step " + std::to_string(t) + " of " + std::to_string(q->steps) + "; the ones before it were taken)");
+        if (!row.fold && !rows) continue;
+        row.first = t == 0;
+        row.last = last;
+        row.reward = e->d_reward;
+        row.done = e->d_done;
+        row.row_reward = q->rewards ? q->rewards + size_t(t) * e->n : nullptr;
+        row.row_done = q->dones ? q->dones + size_t(t) * e->n : nullptr;
+        pg::launch_sequence_row(e->stream, row);
+        PG_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int32_t pgv_step_sequence_host(pgv_env* e, const pgv_sequence* q) {
+    if (sequence_arguments("pgv_step_sequence_host", e, q)) return 1;
+    if (q->steps == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    const size_t n = size_t(e->n), rows = size_t(q->steps) * n;
+    pg::Staged dev{e->stream};
+    pgv_sequence d = *q;
+    if (q->actions) d.actions = dev.alloc(q->action_stride ? size_t(q->steps - 1) * size_t(q->action_stride) + n : n, q->actions);
+    if (q->rewards) d.rewards = dev.alloc<float>(rows);
+    if (q->dones) d.dones = dev.alloc<uint8_t>(rows);
+    if (q->seq_return) d.seq_return = dev.alloc<float>(n);
+    if (q->seq_length) d.seq_length = dev.alloc<int32_t>(n);
+    if (q->seq_done) d.seq_done = dev.alloc<uint8_t>(n);
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_step_sequence(e, &d)) return rc;
+        if (q->rewards) dev.fetch(q->rewards, d.rewards, rows * 4);
+        if (q->dones) dev.fetch(q->dones, d.dones, rows);
+        if (q->seq_return) dev.fetch(q->seq_return, d.seq_return, n * 4);
+        if (q->seq_length) dev.fetch(q->seq_length, d.seq_length, n * 4);
+        if (q->seq_done) dev.fetch(q->seq_done, d.seq_done, n);
+        dev.finish();
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_step_sequence_host: ") + hipGetErrorString(dev.err));
+    return 0;
+}
+
+// The frames of the state as it stands, by the launches pgv_reset draws its frames with: the pre-pass and the render launch
+// under the mask.  Between steps a pending byte is 0 or 1 (or carries a parity), which no render launch touches.
+// "Changes no state" means everything a result, a record or a snapshot can see.  Two things outside that do move, and are
+// harmless only because of what they are: bossfight's pre-pass also makes the random streams' next blocks ahead (mt_other /
+// mt_sel: the same words a gang would make in place), and chaser's complete path rewrites the base layers of the envs it
+// draws and, with a NULL mask, sets base_valid_ (the layers depend on the level alone).  Nothing a step's outcome depends on
+// may be hung on launch_prepass or launch_render.
+int32_t pgv_render_obs(pgv_env* e, const uint8_t* d_mask) {
+    if (!e) return fail("pgv_render_obs: env is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    e->game->launch_prepass(e->stream, d_mask);
+    e->game->launch_render(e->stream, d_mask, e->io());
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_render_obs_host(pgv_env* e, const uint8_t* h_mask) {
+    if (!e) return fail("pgv_render_obs_host: env is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    pg::Staged dev{e->stream};
+    const uint8_t* d_mask = h_mask ? dev.alloc(size_t(e->n), h_mask) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_render_obs(e, d_mask)) return rc;
+        dev.finish();
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_render_obs_host: ") + hipGetErrorString(dev.err));
+    return 0;
 }
 
 int32_t pgv_decode_png(const char* path, int32_t* w, int32_t* h, uint8_t* h_rgba, int64_t cap) {

@@ -142,6 +142,12 @@ class Game {
     // launch_render_late() — called once the reset stream has joined — the few that were.  Default: one launch.
     virtual void launch_render_step(hipStream_t s, StepIO io) { launch_render(s, nullptr, io); }
     virtual bool launch_render_late(hipStream_t s, StepIO io) { return false; }
+    // A step that has no frame (pgv_step_sequence: every sub-step but a rendered last one): called where launch_prepass and
+    // launch_render_step would have been, for whatever those launches do beside drawing that later steps or frames need:
+    // coinrun's render wavefront finishes the entity table of a step that ended early (its redo_kernel does that here),
+    // bossfight's pre-pass makes the random streams' next blocks ahead.  The pending bytes are not its business — the logic
+    // kernels settle them, or the late pass, which a frameless step keeps (launch_render_late).  Default: nothing.
+    virtual void launch_no_frame(hipStream_t s, StepIO io) { (void)s; (void)io; }
 
     // Called after pgv_load_state has replaced the state blob: whatever a game derives from its state and keeps OUTSIDE the
     // blob (chaser: the base layer of every env's frame, pg chaser.hip) is stale from here on.  An error fails the load.

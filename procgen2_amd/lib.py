@@ -38,6 +38,24 @@ class EpisodeOutputs(ctypes.Structure):
         "ended_level_known", "final_obs", "running_return", "running_length")]
 
 
+class Sequence(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_sequence` (device pointers; host pointers for pgv_step_sequence_host)."""
+    _fields_ = [("struct_size", c_uint32), ("steps", c_int32), ("actions", c_void_p), ("action_stride", c_int64),
+                ("run_seed", c_uint32), ("frames", c_int32), ("rewards", c_void_p), ("dones", c_void_p),
+                ("seq_return", c_void_p), ("seq_length", c_void_p), ("seq_done", c_void_p)]
+
+
+# include/procgen2_vec.h PGV_FRAMES_*
+FRAMES = {"last": 0, "none": 1}
+
+
+def sequence(steps, actions=None, action_stride=0, run_seed=0, frames="last", rewards=None, dones=None, seq_return=None,
+             seq_length=None, seq_done=None):
+    """A filled-in Sequence; the pointers are integers (data_ptr(), ctypes.data) or None.  frames: a name of FRAMES or the number."""
+    return Sequence(ctypes.sizeof(Sequence), int(steps), actions, int(action_stride), int(run_seed) & 0xFFFFFFFF,
+                    FRAMES[frames] if frames in FRAMES else int(frames), rewards, dones, seq_return, seq_length, seq_done)
+
+
 # include/procgen2_vec.h PGV_AUTORESET_*
 AUTORESET_MODES = {"next_step": 0, "same_step": 1}
 
@@ -151,6 +169,10 @@ def load(path=None):
         "pgv_step_episodes_synthetic": (c_int32, [P, c_uint32]),
         "pgv_step_episodes_host": (c_int32, [P, P]),
         "pgv_step_episodes_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
+        "pgv_step_sequence": (c_int32, [P, POINTER(Sequence)]),
+        "pgv_step_sequence_host": (c_int32, [P, POINTER(Sequence)]),
+        "pgv_render_obs": (c_int32, [P, P]),
+        "pgv_render_obs_host": (c_int32, [P, P]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -182,6 +204,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_env_record_bytes", "pgv_env_record_tag", "pgv_save_envs", "pgv_load_envs", "pgv_save_envs_host", "pgv_load_envs_host",
     "pgv_assign_levels", "pgv_assign_levels_host", "pgv_level_numbers", "pgv_level_known",
     "pgv_episodes_enable", "pgv_episode_outputs_get", "pgv_step_episodes", "pgv_step_episodes_synthetic", "pgv_step_episodes_host", "pgv_step_episodes_times",
+    "pgv_step_sequence", "pgv_step_sequence_host", "pgv_render_obs", "pgv_render_obs_host",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_last_error",
 ]

@@ -18,6 +18,7 @@ import torch
 from . import lib as pglib
 
 GAMES = ("coinrun", "maze", "bossfight", "climber", "caveflyer", "chaser", "jumper")
+_SEQUENCES_KEPT = 4  # ProcgenVecEnv.step_sequence: result sets kept, by T
 
 
 def shard_range(total_envs, world_size, rank):
@@ -63,6 +64,7 @@ class ProcgenVecEnv:
         self.num_levels, self.start_level = int(num_levels), int(start_level)
         self.distribution_mode = {v: k for k, v in pglib.MODES.items()}[self.L.pgv_mode(h)]
         self._h = h
+        self._sequences = {}  # step_sequence's result tensors, by T: the _SEQUENCES_KEPT most recently used
         # torch owns the result buffers; the engine writes straight into them.
         if out is not None:
             self.obs, self.reward, self.done = out
@@ -179,6 +181,76 @@ class ProcgenVecEnv:
         pglib.check(self.L, self.L.pgv_step_episodes_times(self._h, steps, run_seed, c_void_p(step_ms.ctypes.data),
                                                            c_void_p(episode_ms.ctypes.data)), "pgv_step_episodes_times")
         return step_ms, episode_ms
+
+    # -- steps without frames (include/procgen2_vec.h pgv_step_sequence) ---------------------------
+    def step_sequence(self, actions=None, steps=None, *, frames="last", run_seed=0, rewards=True, dones=True, summary=True,
+                      out=None):
+        """T sub-steps in one engine call, of which only the last is drawn (frames="last") or none (frames="none").
+        actions: int32 [T, N] — sub-step t plays row t — or int32 [N] with steps=T, the same row every sub-step (action
+        repeat), or None with steps=T for device-generated actions (run_seed; the hash and step counter of step_synthetic).
+        The engine is left as T step() calls would leave it; an env that reports done inside the sequence serves its reset
+        in the next sub-step and plays on.
+
+        Returns a SequenceResult: obs (the engine's obs view; None with frames="none" — render_obs() draws it when wanted),
+        rewards f32 [T, N] and dones u8 [T, N] (what reward / done held after each sub-step), seq_length i32 [N] (sub-steps
+        up to and including the env's first done, T without one), seq_done u8 [N] (whether there was one) and seq_return
+        f32 [N] (the float32 sum of the env's rewards over those sub-steps, in order).  rewards / dones / summary = False
+        leave the respective parts out (None).  The tensors live on this env's device, are allocated once per T and written
+        again by the next call with the same T; the sets of the four most recently used T are kept (5·T·N + 9·N bytes each),
+        an older one is dropped and allocated afresh when its T comes again.  A caller whose T varies widely passes out = a
+        SequenceResult of caller-owned contiguous tensors of those shapes to write instead.  Same stream hand-shake as step(), no host synchronisation."""
+        if frames not in pglib.FRAMES:
+            raise ValueError("frames must be 'last' or 'none'")
+        n, a, stride = self.num_envs, None, 0
+        if actions is not None:
+            a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+            if a.dim() == 2 and a.shape[1] == n and steps in (None, a.shape[0]):
+                steps, stride = a.shape[0], n
+            elif not (a.dim() == 1 and a.numel() == n and steps is not None):
+                raise ValueError("step_sequence: actions must be [T, %d], or [%d] with steps=T" % (n, n))
+        elif steps is None:
+            raise ValueError("step_sequence: steps is needed without [T, N] actions")
+        T = int(steps)
+        if T < 0:
+            raise ValueError("step_sequence: steps must be >= 0")
+        want = SequenceResult.layout(T, n)
+        if out is None:
+            out = self._sequences.pop(T, None)
+            if out is None:
+                out = SequenceResult(**{k: torch.zeros(shape, dtype=dtype, device=self.device) for k, (shape, dtype) in want.items()})
+            self._sequences[T] = out  # (most recent last)
+            while len(self._sequences) > _SEQUENCES_KEPT:
+                del self._sequences[next(iter(self._sequences))]
+        else:
+            for k, (shape, dtype) in want.items():
+                t = getattr(out, k)
+                if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
+                    raise ValueError("out.%s: expected a contiguous %s tensor of shape %s on %s" % (k, dtype, shape, self.device))
+        given = {"rewards": rewards, "dones": dones, "seq_return": summary, "seq_length": summary, "seq_done": summary}
+        res = SequenceResult(**{k: getattr(out, k) if given[k] else None for k in want})
+        ptr = {k: c_void_p(getattr(res, k).data_ptr()) if getattr(res, k) is not None and T else None for k in want}
+        seq = pglib.sequence(T, c_void_p(a.data_ptr()) if a is not None else None, stride, run_seed, frames, **ptr)
+        self._before()
+        pglib.check(self.L, self.L.pgv_step_sequence(self._h, ctypes.byref(seq)), "pgv_step_sequence")
+        self._after()
+        self._keep = (a, res)
+        res.obs = self.obs if frames == "last" else None
+        return res
+
+    def render_obs(self, mask=None):
+        """Draw the observations of the state as it stands (pgv_render_obs) — after step_sequence(frames="none"), or at any
+        time between steps: no state changes.  mask (uint8 [N], non-zero = draw): the other rows keep their bytes.  Returns
+        the obs view."""
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+            if m.numel() != self.num_envs:
+                raise ValueError("expected a mask of %d envs, got %d" % (self.num_envs, m.numel()))
+        self._before()
+        pglib.check(self.L, self.L.pgv_render_obs(self._h, c_void_p(m.data_ptr()) if m is not None else None), "pgv_render_obs")
+        self._after()
+        self._keep = (m,)
+        return self.obs
 
     def _before(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -436,6 +508,20 @@ class EpisodeTensors:
             self.final_obs = _device_view(out.final_obs, capacity * pglib.OBS_BYTES, "|u1", device).view(capacity, 64, 64, 3)
         else:
             self.final_obs = torch.zeros((0, 64, 64, 3), dtype=torch.uint8, device=device)
+
+
+class SequenceResult:
+    """What ProcgenVecEnv.step_sequence returns (and takes as `out`): obs, rewards f32 [T, N], dones u8 [T, N], seq_return
+    f32 [N], seq_length i32 [N], seq_done u8 [N]; a part that was not asked for is None."""
+
+    def __init__(self, rewards=None, dones=None, seq_return=None, seq_length=None, seq_done=None, obs=None):
+        self.obs, self.rewards, self.dones = obs, rewards, dones
+        self.seq_return, self.seq_length, self.seq_done = seq_return, seq_length, seq_done
+
+    @staticmethod
+    def layout(T, n):
+        return {"rewards": ((T, n), torch.float32), "dones": ((T, n), torch.uint8), "seq_return": ((n,), torch.float32),
+                "seq_length": ((n,), torch.int32), "seq_done": ((n,), torch.uint8)}
 
 
 class EnvRecords:

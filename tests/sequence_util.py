@@ -1,0 +1,79 @@
+"""The model of pgv_step_sequence (include/procgen2_vec.h): an OracleVec stepped T times, drawing switched off
+(OracleVec.set_render(False): logic is unaffected) on the sub-steps that draw nothing, plus the summary folded in numpy.
+The GPU tests trust this model, not the engine; tests/test_sequence.py holds the model itself to T drawn oracle steps.
+
+The protocol every GPU test runs: PROTOCOL_N envs, seed_base 1, one full reset, pgo_synthetic_action with run seed
+PROTOCOL_SEED as explicit actions, PROTOCOL_STEPS steps cut into sequences of PROTOCOL_LENGTHS.
+"""
+import numpy as np
+
+from episodes_util import synthetic_actions
+from oracle_util import OracleVec
+
+GAMES = ("coinrun", "maze", "bossfight", "climber", "caveflyer", "chaser", "jumper")
+PROTOCOL_N, PROTOCOL_SEED = 300, 7
+PROTOCOL_LENGTHS = (1, 2, 3, 5, 8, 13) * 5
+PROTOCOL_STEPS = sum(PROTOCOL_LENGTHS)  # 160
+
+
+def fold(rewards, dones):
+    """(seq_return, seq_length, seq_done) of rows [T, N]: the sub-steps up to and including the env's first done — all T
+    without one — and the float32 sum of their rewards in step order from 0.0f, one rounding a step."""
+    T, n = dones.shape
+    ret, length, done = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    for t in range(T):
+        live = done == 0
+        ret = np.where(live, (ret + rewards[t]).astype(np.float32), ret).astype(np.float32)
+        length = length + live.astype(np.int32)
+        done = np.where(live, (dones[t] != 0).astype(np.uint8), done).astype(np.uint8)
+    return ret, length, done
+
+
+def protocol_calls(n=PROTOCOL_N, lengths=PROTOCOL_LENGTHS, run_seed=PROTOCOL_SEED, first_step=0):
+    """The protocol's calls in order: (index of the call's first step, actions int32 [T, n])."""
+    t = first_step
+    for T in lengths:
+        yield t, np.stack([synthetic_actions(run_seed, t + k, n) for k in range(T)])
+        t += T
+
+
+class SequenceModel:
+    def __init__(self, game, n, seed_base=1, render=True):
+        self.o = OracleVec(game, n, seed_base=seed_base, render=render)
+        self.n, self.can_draw = n, render
+
+    obs = property(lambda self: self.o.obs)
+    engine_reward = property(lambda self: self.o.reward)
+    engine_done = property(lambda self: self.o.done)
+
+    def first_reset(self):
+        """The engine's first pgv_reset after make: an OracleVec had it when it was made."""
+        return self.o.reset_obs()
+
+    def reset(self):
+        """pgv_reset(NULL, NULL) — the protocol's one full reset: what it leaves in the engine's rows included."""
+        self.o.reset()
+        self.o.reward[:] = 0.0
+        self.o.done[:] = 0
+        return self.o.obs
+
+    def sequence(self, actions, draw_last=True):
+        """T sub-steps, actions [T, N]; only the last is drawn, and that one only if draw_last.  With draw_last, `obs` is then
+        what PGV_FRAMES_LAST leaves — and what pgv_render_obs(NULL) leaves after PGV_FRAMES_NONE."""
+        actions = np.asarray(actions, np.int32)
+        T = actions.shape[0]
+        self.rewards, self.dones = np.zeros((T, self.n), np.float32), np.zeros((T, self.n), np.uint8)
+        for t in range(T):
+            if self.can_draw:
+                self.o.set_render(draw_last and t == T - 1)
+            _, self.rewards[t], self.dones[t] = self.o.step(actions[t])
+        if self.can_draw:
+            self.o.set_render(True)
+        self.seq_return, self.seq_length, self.seq_done = fold(self.rewards, self.dones)
+        return self.rewards, self.dones
+
+    def plain_step(self, actions):
+        return self.o.step(actions)
+
+    def close(self):
+        self.o.close()
