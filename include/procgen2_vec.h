@@ -353,6 +353,66 @@ PGV_API int32_t pgv_step_sequence_host(pgv_env* env, const pgv_sequence* seq); /
 PGV_API int32_t pgv_render_obs(pgv_env* env, const uint8_t* d_mask);           /* device u8[N] or NULL = all */
 PGV_API int32_t pgv_render_obs_host(pgv_env* env, const uint8_t* h_mask);
 
+/* Policy-ready observations on the device: the frame a policy network reads — channel-first, scaled, frame-stacked,
+ * optionally gray — made by the engine behind the render launch, where the facts it needs are known: which envs served a
+ * reset, resets inside a frameless sequence included.  (Gymnasium's FrameStackObservation / GrayscaleObservation and the
+ * permute-convert-divide every consumer of the u8 [N][64][64][3] slab writes; the reference has no counterpart.)  Opt-in
+ * per engine: one that never calls pgv_policy_obs_enable launches nothing new and gives the same bytes as before at every
+ * entry point.
+ *
+ * The tensor: [N][K*C][64][64], contiguous, C = 3 (planes R, G, B) or 1 (gray); slot 0 is the oldest frame, slot K-1 the
+ * newest, channel slot*C + c.  The value of byte v: PGV_POLICY_U8 v; PGV_POLICY_F32 the float32 float(v) / 255.0f (one
+ * correctly rounded division); PGV_POLICY_F16 / PGV_POLICY_BF16 that float32 rounded to nearest-even binary16 / bfloat16.
+ * Gray: y = (77*R + 150*G + 29*B + 128) >> 8 in integers (white stays 255), then the value rule on y.
+ *
+ *   1. pgv_policy_obs_enable may be called once per env, at any time.  Everything is checked on the host before anything is
+ *      enqueued; a refusal leaves a message and the engine as it was: a second call, stack outside 1 .. 8, gray outside
+ *      0 .. 1, an unknown dtype, an `out` that is not 16-byte aligned, a struct_size too small.  It sets every env's restart
+ *      flag and pushes nothing: the first push after it fills every stack with that env's frame.  Until then the engine's
+ *      own tensor is zero and a caller's is as the caller left it.
+ *   2. A PUSH converts the obs slab as it stands at that point of the env's stream: an env whose restart flag is set gets
+ *      the new frame into all K slots and its flag cleared; any other env has slots 1 .. K-1 moved to 0 .. K-2 and the new
+ *      frame put into slot K-1.  With a mask, an env whose mask byte is 0 is not touched: no move, no flag change.  A push
+ *      is enqueued on the env's stream, allocates nothing and does not synchronise the host.  It needs the obs slab 16-byte
+ *      aligned (pgv_bind_outputs may move the slab): pgv_policy_obs_push and every call of point 4 that ends with a push
+ *      check that on the host before they enqueue anything, and fail with a message and the engine as it was — no step
+ *      taken, no flag set, the step counter where it stood.  The calls that do not push do not check.
+ *   3. An env's restart flag is set by: every step, however taken — the measurement entry points and the sub-steps of
+ *      pgv_step_sequence included — that finds the env's `done` row set (that step serves its reset); pgv_reset, for the
+ *      envs it names; a same-step auto-reset, for the envs that ended; pgv_load_envs, for the slots it actually wrote (an
+ *      index outside the batch and an empty record set nothing); pgv_load_state, for all envs.  Only a push that touches
+ *      the env clears it.  The stack travels neither in records nor in snapshots: pgv_snapshot_bytes and
+ *      pgv_env_record_bytes are what they were.
+ *   4. Who pushes, once per call and behind everything else the call enqueues: pgv_step, pgv_step_synthetic and
+ *      pgv_step_host, all envs; pgv_step_episodes, pgv_step_episodes_synthetic and pgv_step_episodes_host, all envs, after
+ *      the same-step reset has redrawn the ended envs — an ended env's stack is then K copies of its new episode's first
+ *      frame, its terminal frame is in final_obs as before, and the stacked view of the terminal step is not kept;
+ *      pgv_reset and pgv_reset_host, under their mask (envs not named keep their bytes); pgv_step_sequence and
+ *      pgv_step_sequence_host with PGV_FRAMES_LAST, all envs, once, behind the last sub-step: an env that served a reset in
+ *      any sub-step has its stack restarted with the drawn frame, so the call is a frame-skip whose stack never mixes
+ *      episodes.  Who does not push: PGV_FRAMES_NONE, pgv_render_obs and pgv_render_obs_host, pgv_step_synthetic_many,
+ *      pgv_timed_steps, pgv_step_times, pgv_step_phases, pgv_step_phases_many, pgv_step_episodes_times.  Flags still
+ *      accumulate there, so a later push is right.
+ *   5. PGV_FRAMES_NONE, then pgv_render_obs(NULL), then pgv_policy_obs_push(NULL) leaves exactly what PGV_FRAMES_LAST would
+ *      have left: the obs slab, the policy tensor and the flags. */
+#define PGV_POLICY_U8 0
+#define PGV_POLICY_F16 1
+#define PGV_POLICY_BF16 2
+#define PGV_POLICY_F32 3
+typedef struct pgv_policy_obs_config {
+    uint32_t struct_size;
+    int32_t stack; /* K, 1 .. 8 */
+    int32_t gray;  /* 0: three planes R, G, B; 1: one plane, the gray rule */
+    int32_t dtype; /* PGV_POLICY_* */
+    void* out;     /* device, 16-byte aligned, N * pgv_policy_obs_bytes_per_env bytes; NULL: the engine allocates (zeroed) */
+} pgv_policy_obs_config;
+PGV_API int32_t pgv_policy_obs_enable(pgv_env* env, const pgv_policy_obs_config* config);
+PGV_API void* pgv_policy_obs(pgv_env* env);                       /* the tensor; NULL before enable */
+PGV_API int64_t pgv_policy_obs_bytes_per_env(pgv_env* env);       /* K*C*4096*element size; 0 before enable */
+PGV_API const uint8_t* pgv_policy_obs_restart(pgv_env* env);      /* device u8[N]: the pending restart flags; NULL before enable */
+PGV_API int32_t pgv_policy_obs_push(pgv_env* env, const uint8_t* d_mask); /* device u8[N] or NULL = all */
+PGV_API int32_t pgv_policy_obs_push_host(pgv_env* env, const uint8_t* h_mask);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);
@@ -406,7 +466,9 @@ PGV_API int32_t pgv_step_phases_many(pgv_env* const* envs, int32_t count, int32_
  * hand-back path of games that never take it in a normal run).  Bit 24: coinrun works every hazard's boxes out behind
  * the agent instead of the few its entity lanes pre-selected (the fallback a normal run never takes).  Bit 25: chaser's
  * enemies take their turns one after the other on the env's random stream itself instead of side by side on outputs
- * peeked from it (what the last few words of a 624-word block take in a normal run).  Any other bit is refused. */
+ * peeked from it (what the last few words of a 624-word block take in a normal run).  Bit 26: a push of the policy
+ * observations stores each lane's own 16 values per plane as they lie (lanes 32 or 64 bytes apart for 2- and 4-byte elements)
+ * instead of exchanging them inside the wave for dense stores.  Any other bit is refused. */
 PGV_API int32_t pgv_set_debug(pgv_env* env, int32_t flags);
 
 /* Parity taps (host pointers): game-defined state vector / tile ids of one env; return the full

@@ -15,6 +15,7 @@
 #include "pg_engine.h"
 #include "pg_episodes.h"
 #include "pg_order.h"
+#include "pg_policy_obs.h"
 #include "pg_records.h"
 #include "pg_sequence.h"
 #include "png_decode.h"
@@ -270,6 +271,14 @@ struct pgv_env {
     // steps without frames (pg_sequence.h; pgv_step_sequence): the running values of the summary, one block
     void* d_sequence = nullptr;
     pg::SequenceBuffers seq{};
+    // policy-ready observations (pg_policy_obs.h; pgv_policy_obs_enable): off unless asked for.  One device block holds the
+    // restart flags and the value table; the tensor is the caller's, or the engine's own.
+    bool policy = false, own_policy_out = false;
+    int policy_stack = 0, policy_planes = 0, policy_es = 0;
+    void* d_policy = nullptr;
+    uint8_t* d_policy_out = nullptr;
+    pg::PolicyObsBuffers pol{};
+    uint32_t policy_table[256] = {};  // (the upload's source: lives as long as the env)
 
     pg::StepIO io() const { return {d_obs, d_reward, d_done, d_pending}; }
     // The per-env output rows, in the order a snapshot holds them behind the state blob.  Separate allocations:
@@ -350,6 +359,8 @@ void pgv_close(pgv_env* e) {
     if (e->d_pending) hipFree(e->d_pending);
     if (e->d_episodes) hipFree(e->d_episodes);
     if (e->d_sequence) hipFree(e->d_sequence);
+    if (e->d_policy) hipFree(e->d_policy);
+    if (e->own_policy_out && e->d_policy_out) hipFree(e->d_policy_out);
     if (e->d_host_i32) hipFree(e->d_host_i32);
     if (e->d_host_u8) hipFree(e->d_host_u8);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -530,8 +541,35 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     return 0;
 }
 
+// What a call that ends with a push of the policy observations asks of the host, BEFORE it enqueues anything: a slab the
+// push kernel's 16-byte loads can read (pgv_bind_outputs may have moved it).  A refusal leaves the engine as it was — no
+// step taken, no flag set, the step counter where it stood.  An engine without the feature passes.
+static int32_t policy_ready(const char* who, const pgv_env* e) {
+    if (e->policy && (reinterpret_cast<uintptr_t>(e->d_obs) & 15u))
+        return fail(std::string(who) + ": the observation buffer must be 16-byte aligned for the policy observations");
+    return 0;
+}
+
+// A push of the policy observations (pg_policy_obs.h) on the env's stream, for the calls that end with one: the obs slab as
+// it stands there.  Its callers have asked policy_ready() first.
+static int32_t policy_push(const char* who, pgv_env* e, const uint8_t* d_mask) {
+    pg::PolicyPush q{};
+    q.n = e->n;
+    q.stack = e->policy_stack;
+    q.planes = e->policy_planes;
+    q.dense = (e->game->debug_flags & pg::kDebugPolicyStrided) ? 0 : 1;
+    q.obs = e->d_obs;
+    q.out = e->d_policy_out;
+    q.mask = d_mask;
+    q.b = e->pol;
+    pg::launch_policy_push(e->stream, q, e->policy_es);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
 int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     if (!e) return fail("pgv_reset: env is NULL");
+    if (policy_ready("pgv_reset", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     e->game->launch_reset(e->stream, d_mask, d_seeds, e->io());
     e->game->launch_prepass(e->stream, d_mask);
@@ -539,6 +577,10 @@ int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     if (e->episodes) pg::launch_episode_clear(e->stream, e->ep, d_mask);  // the named envs start their episodes afresh
     pregen(e, true, true);
     PG_HIP(hipGetLastError());
+    if (e->policy) {  // the named envs' stacks restart with the frame just drawn
+        pg::launch_policy_flag_mask(e->stream, e->pol, e->n, d_mask);
+        return policy_push("pgv_reset", e, d_mask);
+    }
     return 0;
 }
 
@@ -556,6 +598,8 @@ static int32_t step_impl(pgv_env* e, const int32_t* d_actions, uint32_t run_seed
     // hipGetLastError is sticky and per thread: whatever the embedding application left behind (a stream query's
     // NotReady, say) is not this step's; start clean.
     (void)hipGetLastError();
+    // (policy observations: the done row as this step finds it — in front of the fork, so no reset kernel is at the row yet)
+    if (e->policy) pg::launch_policy_flag_done(e->stream, e->pol, e->n, e->d_done);
     const bool forked = e->reset_stream != nullptr;
     if (forked) {  // fork: the auto-resets of this step go beside its logic and render kernels
         PG_HIP(hipEventRecord(e->reset_fork, e->stream));
@@ -609,14 +653,18 @@ static int32_t step_no_frame(pgv_env* e, const int32_t* d_actions, uint32_t run_
 int32_t pgv_step(pgv_env* e, const int32_t* d_actions) {
     if (!e) return fail("pgv_step: env is NULL");
     if (!d_actions) return fail("pgv_step: actions is NULL");
+    if (policy_ready("pgv_step", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
-    return step_impl(e, d_actions, 0);
+    if (step_impl(e, d_actions, 0)) return 1;
+    return e->policy ? policy_push("pgv_step", e, nullptr) : 0;
 }
 
 int32_t pgv_step_synthetic(pgv_env* e, uint32_t run_seed) {
     if (!e) return fail("pgv_step_synthetic: env is NULL");
+    if (policy_ready("pgv_step_synthetic", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
-    return step_impl(e, nullptr, run_seed);
+    if (step_impl(e, nullptr, run_seed)) return 1;
+    return e->policy ? policy_push("pgv_step_synthetic", e, nullptr) : 0;
 }
 
 int32_t pgv_step_synthetic_many(pgv_env* const* envs, int32_t count, int32_t steps, uint32_t run_seed) {
@@ -642,6 +690,7 @@ static int32_t ensure_staging(pgv_env* e) {
 int32_t pgv_step_host(pgv_env* e, const int32_t* h_actions) {
     if (!e) return fail("pgv_step_host: env is NULL");
     if (!h_actions) return fail("pgv_step_host: actions is NULL");
+    if (policy_ready("pgv_step_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (ensure_staging(e)) return 1;
     PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
@@ -651,6 +700,7 @@ int32_t pgv_step_host(pgv_env* e, const int32_t* h_actions) {
 
 int32_t pgv_reset_host(pgv_env* e, const uint8_t* h_mask, const int32_t* h_seeds) {
     if (!e) return fail("pgv_reset_host: env is NULL");
+    if (policy_ready("pgv_reset_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (ensure_staging(e)) return 1;
     if (h_mask) PG_HIP(hipMemcpyAsync(e->d_host_u8, h_mask, size_t(e->n), hipMemcpyHostToDevice, e->stream));
@@ -744,33 +794,41 @@ static int32_t step_episodes_impl(const char* who, pgv_env* e, const int32_t* d_
         e->game->launch_reset(e->stream, b.ended, nullptr, e->io());
         e->game->launch_prepass(e->stream, b.ended);
         e->game->launch_render(e->stream, b.ended, e->io());
+        if (e->policy) pg::launch_policy_flag_mask(e->stream, e->pol, e->n, b.ended);  // their stacks restart with the new first frame
         PG_HIP(hipGetLastError());
     }
     return 0;
+}
+// … and, for the entry points that are not measurements, the push behind everything.
+static int32_t step_episodes_push(const char* who, pgv_env* e, const int32_t* d_actions, uint32_t run_seed) {
+    if (policy_ready(who, e)) return 1;
+    if (step_episodes_impl(who, e, d_actions, run_seed)) return 1;
+    return e->policy ? policy_push(who, e, nullptr) : 0;
 }
 
 int32_t pgv_step_episodes(pgv_env* e, const int32_t* d_actions) {
     if (!e) return fail("pgv_step_episodes: env is NULL");
     if (!d_actions) return fail("pgv_step_episodes: actions is NULL");
     PG_HIP(hipSetDevice(e->device));
-    return step_episodes_impl("pgv_step_episodes", e, d_actions, 0);
+    return step_episodes_push("pgv_step_episodes", e, d_actions, 0);
 }
 
 int32_t pgv_step_episodes_synthetic(pgv_env* e, uint32_t run_seed) {
     if (!e) return fail("pgv_step_episodes_synthetic: env is NULL");
     PG_HIP(hipSetDevice(e->device));
-    return step_episodes_impl("pgv_step_episodes_synthetic", e, nullptr, run_seed);
+    return step_episodes_push("pgv_step_episodes_synthetic", e, nullptr, run_seed);
 }
 
 int32_t pgv_step_episodes_host(pgv_env* e, const int32_t* h_actions) {
     if (!e) return fail("pgv_step_episodes_host: env is NULL");
     if (!h_actions) return fail("pgv_step_episodes_host: actions is NULL");
     if (!e->episodes) return fail("pgv_step_episodes_host: call pgv_episodes_enable first");
+    if (policy_ready("pgv_step_episodes_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (ensure_staging(e)) return 1;
     PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
     PG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is the caller's: do not keep reading it
-    return step_episodes_impl("pgv_step_episodes_host", e, e->d_host_i32, 0);
+    return step_episodes_push("pgv_step_episodes_host", e, e->d_host_i32, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -789,6 +847,7 @@ static int32_t sequence_arguments(const char* who, pgv_env* e, const pgv_sequenc
 int32_t pgv_step_sequence(pgv_env* e, const pgv_sequence* q) {
     if (sequence_arguments("pgv_step_sequence", e, q)) return 1;
     if (q->steps == 0) return 0;
+    if (q->frames == PGV_FRAMES_LAST && policy_ready("pgv_step_sequence", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     pg::SequenceRow row{};
     row.n = e->n;
@@ -814,12 +873,14 @@ int32_t pgv_step_sequence(pgv_env* e, const pgv_sequence* q) {
         pg::launch_sequence_row(e->stream, row);
         PG_HIP(hipGetLastError());
     }
+    if (e->policy && q->frames == PGV_FRAMES_LAST) return policy_push("pgv_step_sequence", e, nullptr);  // once, behind the drawn sub-step
     return 0;
 }
 
 int32_t pgv_step_sequence_host(pgv_env* e, const pgv_sequence* q) {
     if (sequence_arguments("pgv_step_sequence_host", e, q)) return 1;
     if (q->steps == 0) return 0;
+    if (q->frames == PGV_FRAMES_LAST && policy_ready("pgv_step_sequence_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     const size_t n = size_t(e->n), rows = size_t(q->steps) * n;
     pg::Staged dev{e->stream};
@@ -870,6 +931,79 @@ int32_t pgv_render_obs_host(pgv_env* e, const uint8_t* h_mask) {
         dev.finish();
     }
     if (dev.err != hipSuccess) return fail(std::string("pgv_render_obs_host: ") + hipGetErrorString(dev.err));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Policy-ready observations (pg_policy_obs.h)
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_policy_obs_enable(pgv_env* e, const pgv_policy_obs_config* cfg) {
+    if (!e) return fail("pgv_policy_obs_enable: env is NULL");
+    if (!cfg || cfg->struct_size < sizeof(pgv_policy_obs_config)) return fail("pgv_policy_obs_enable: config is NULL or struct_size too small");
+    if (e->policy) return fail("pgv_policy_obs_enable: policy observations are enabled already (once per env)");
+    if (cfg->stack < 1 || cfg->stack > pg::kPolicyMaxStack) return fail("pgv_policy_obs_enable: stack must be in 1 .. 8");
+    if (cfg->gray != 0 && cfg->gray != 1) return fail("pgv_policy_obs_enable: gray must be 0 or 1");
+    if (cfg->dtype != PGV_POLICY_U8 && cfg->dtype != PGV_POLICY_F16 && cfg->dtype != PGV_POLICY_BF16 && cfg->dtype != PGV_POLICY_F32)
+        return fail("pgv_policy_obs_enable: unknown dtype " + std::to_string(cfg->dtype));
+    if (reinterpret_cast<uintptr_t>(cfg->out) & 15u) return fail("pgv_policy_obs_enable: out must be 16-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    const int planes = cfg->gray ? 1 : 3, es = pg::policy_element_bytes(cfg->dtype);
+    const size_t out_bytes = size_t(e->n) * pg::policy_bytes_per_env(cfg->stack, planes, es);
+    for (uint32_t v = 0; v < 256; v++) e->policy_table[v] = pg::policy_table_entry(cfg->dtype, v);
+    void* mem = nullptr;
+    void* out = cfg->out;
+    pg::PolicyObsBuffers b{};
+    hipError_t err = hipMalloc(&mem, pg::Carve::size(pg::list_policy_obs, e->n));
+    if (err == hipSuccess && !out) err = hipMalloc(&out, out_bytes);
+    if (err == hipSuccess && !cfg->out) err = hipMemsetAsync(out, 0, out_bytes, e->stream);
+    if (err == hipSuccess) {
+        pg::Carve::bind(pg::list_policy_obs, mem, b, e->n);
+        err = hipMemsetAsync(b.restart, 1, size_t(e->n), e->stream);  // the first push fills every stack
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->policy_table, sizeof(e->policy_table), hipMemcpyHostToDevice, e->stream);
+    if (err != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        if (mem) (void)hipFree(mem);
+        if (out && !cfg->out) (void)hipFree(out);
+        return fail(std::string("pgv_policy_obs_enable: ") + hipGetErrorString(err));
+    }
+    e->d_policy = mem;
+    e->pol = b;
+    e->d_policy_out = static_cast<uint8_t*>(out);
+    e->own_policy_out = !cfg->out;
+    e->policy_stack = cfg->stack;
+    e->policy_planes = planes;
+    e->policy_es = es;
+    e->policy = true;
+    return 0;
+}
+
+void* pgv_policy_obs(pgv_env* e) { return e && e->policy ? e->d_policy_out : nullptr; }
+int64_t pgv_policy_obs_bytes_per_env(pgv_env* e) {
+    return e && e->policy ? static_cast<int64_t>(pg::policy_bytes_per_env(e->policy_stack, e->policy_planes, e->policy_es)) : 0;
+}
+const uint8_t* pgv_policy_obs_restart(pgv_env* e) { return e && e->policy ? e->pol.restart : nullptr; }
+
+int32_t pgv_policy_obs_push(pgv_env* e, const uint8_t* d_mask) {
+    if (!e) return fail("pgv_policy_obs_push: env is NULL");
+    if (!e->policy) return fail("pgv_policy_obs_push: call pgv_policy_obs_enable first");
+    PG_HIP(hipSetDevice(e->device));
+    if (policy_ready("pgv_policy_obs_push", e)) return 1;
+    (void)hipGetLastError();
+    return policy_push("pgv_policy_obs_push", e, d_mask);
+}
+
+int32_t pgv_policy_obs_push_host(pgv_env* e, const uint8_t* h_mask) {
+    if (!e) return fail("pgv_policy_obs_push_host: env is NULL");
+    if (!e->policy) return fail("pgv_policy_obs_push_host: call pgv_policy_obs_enable first");
+    PG_HIP(hipSetDevice(e->device));
+    pg::Staged dev{e->stream};
+    const uint8_t* d_mask = h_mask ? dev.alloc(size_t(e->n), h_mask) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_policy_obs_push(e, d_mask)) return rc;
+        dev.finish();
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_policy_obs_push_host: ") + hipGetErrorString(dev.err));
     return 0;
 }
 
@@ -964,6 +1098,7 @@ int32_t pgv_load_state(pgv_env* e, const void* h_buffer, int64_t size) {
     if (snapshot_copy(e, const_cast<uint8_t*>(in) + sizeof(hd), hd.state_bytes, true)) return 1;
     e->step_index = hd.step_index;
     PG_HIP(e->game->state_loaded(e->stream));  // (on the env's stream: ordered in front of the next step)
+    if (e->policy) pg::launch_policy_flag_mask(e->stream, e->pol, e->n, nullptr);  // the stacks do not travel: every env restarts
     pregen(e, true, true);  // queued shadow slots of the snapshot get their generator launch
     return 0;
 }
@@ -1027,6 +1162,8 @@ int32_t pgv_load_envs(pgv_env* e, const int32_t* d_indices, int32_t count, const
     pg::launch_records(e->stream, t, true, d_indices, count, const_cast<void*>(d_records));
     e->game->records_loaded(e->stream, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes, t.r[e->rec_obs].offset,
                             e->step_index, e->io());
+    if (e->policy)  // the slots actually written restart their stacks
+        pg::launch_policy_flag_list(e->stream, e->pol, e->n, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes, pg::kRecordFull);
     PG_HIP(hipGetLastError());
     pregen(e, size_t(count) * 2 >= size_t(e->n), true);  // loaded slots that are queued get their generator launch
     return 0;
@@ -1345,8 +1482,8 @@ int32_t pgv_render_frames_host(pgv_env* e, const int32_t* h_indices, int32_t cou
 int32_t pgv_set_debug(pgv_env* e, int32_t flags) {
     if (!e) return fail("pgv_set_debug: env is NULL");
 #ifndef PG_ABLATE
-    if (flags & ~(1 | pg::kDebugNoPrefetch | pg::kDebugNoPrepass | pg::kDebugFatThirds | pg::kDebugCoinrunNoReach | pg::kDebugChaserSerialMobs))
-        return fail("pgv_set_debug: only bit 0 (draw-list replay), bit 8 (no level prefetch), bit 21 (no render pre-pass), bit 23 (every third frame by the complete path), bit 24 (coinrun: hazards the long way) and bit 25 (chaser: enemies the long way) exist in this build");
+    if (flags & ~(1 | pg::kDebugNoPrefetch | pg::kDebugNoPrepass | pg::kDebugFatThirds | pg::kDebugCoinrunNoReach | pg::kDebugChaserSerialMobs | pg::kDebugPolicyStrided))
+        return fail("pgv_set_debug: only bit 0 (draw-list replay), bit 8 (no level prefetch), bit 21 (no render pre-pass), bit 23 (every third frame by the complete path), bit 24 (coinrun: hazards the long way), bit 25 (chaser: enemies the long way) and bit 26 (policy observations: lane-strided stores) exist in this build");
 #endif
     if (e->side) hipStreamSynchronize(e->side);
     e->game->debug_flags = flags;

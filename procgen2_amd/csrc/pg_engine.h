@@ -194,6 +194,7 @@ constexpr int kDebugNoPrepass = 1 << 21;  // (clear of the -DPG_ABLATE experimen
 constexpr int kDebugFatThirds = 1 << 23;
 constexpr int kDebugCoinrunNoReach = 1 << 24;
 constexpr int kDebugChaserSerialMobs = 1 << 25;  // chaser: the enemies one after the other on the stream itself (chaser.hip advance)
+constexpr int kDebugPolicyStrided = 1 << 26;     // policy observations: each lane stores its own units (pg_policy_obs.h), no exchange
 
 // The debug dumps (Game::dump_state, dump_tiles): one element of device memory; a dump's values copied out as far as cap
 // allows, returning how many there are; one env's tile bytes (each masked with `mask`).

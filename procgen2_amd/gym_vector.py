@@ -34,6 +34,13 @@ Boxes; what RL code imports is a vector env with real spaces.  This class gives 
   missing round trip and the reason the mode is opt-in: the default path keeps handing out fresh tensors.  With
   output="numpy" the lists are cut to the counts (copies; the host synchronisation is inherent there).
 
+* `policy_obs=dict(stack=4, gray=True, dtype="float16")` (opt-in): `reset` and `step` return the engine's policy-ready
+  tensor (include/procgen2_vec.h pgv_policy_obs_enable) — [N, K*C, 64, 64], channel-first, scaled to 0 .. 1 unless uint8,
+  frame-stacked with slot 0 the oldest, every stack restarted where its episode began — in place of the HWC frame, in all
+  three step paths, and the spaces become `Box(0, 255 or 1.0, (K*C, 64, 64), dtype)` (bfloat16, which numpy lacks, is
+  described as float32 and handed out as float32 with output="numpy").  `info["final_obs*"]` stays the HWC terminal
+  frame; the stacked view of a terminal step is not kept.  Without it the adapter is byte for byte what it was.
+
 The class only talks to an *engine* object with `reset(mask, seeds) -> obs`, `step(actions) -> (obs, reward, done)`,
 `close()`, `num_envs`; `ProcgenVecEnv` is the real one.  The CPU tests drive the same code with an oracle-backed
 stand-in, so the wrapper logic is covered without a GPU.
@@ -66,6 +73,8 @@ class _Box:
         return x.shape == self.shape and x.dtype == self.dtype
 
     def sample(self):
+        if self.dtype.kind == "f":
+            return (self._rng.random(self.shape) * float(self.high.flat[0])).astype(self.dtype)
         return self._rng.integers(0, 256, self.shape, dtype=np.int64).astype(self.dtype)
 
     def seed(self, seed=None):
@@ -116,17 +125,18 @@ class _MultiDiscrete:
         return "MultiDiscrete(%d x %d)" % (self.nvec.size, int(self.nvec.flat[0]) if self.nvec.size else 0)
 
 
-def make_spaces(num_envs):
+def make_spaces(num_envs, shape=OBS_SHAPE, dtype=np.uint8, high=255):
     """(single_observation, single_action, observation, action) spaces."""
+    shape = tuple(shape)
     if _spaces is not None:
-        single_obs = _spaces.Box(0, 255, OBS_SHAPE, np.uint8)
+        single_obs = _spaces.Box(0, high, shape, dtype)
         single_act = _spaces.Discrete(NUM_ACTIONS)
-        obs = _spaces.Box(0, 255, (num_envs,) + OBS_SHAPE, np.uint8)
+        obs = _spaces.Box(0, high, (num_envs,) + shape, dtype)
         act = _spaces.MultiDiscrete(np.full(num_envs, NUM_ACTIONS, dtype=np.int64))
     else:
-        single_obs = _Box(0, 255, OBS_SHAPE, np.uint8)
+        single_obs = _Box(0, high, shape, dtype)
         single_act = _Discrete(NUM_ACTIONS)
-        obs = _Box(0, 255, (num_envs,) + OBS_SHAPE, np.uint8)
+        obs = _Box(0, high, (num_envs,) + shape, dtype)
         act = _MultiDiscrete(np.full(num_envs, NUM_ACTIONS, dtype=np.int64))
     return single_obs, single_act, obs, act
 
@@ -136,7 +146,7 @@ class GymVectorAdapter(_VectorBase):
 
     metadata = {"render_modes": ["rgb_array"], "autoreset_mode": "next_step"}
 
-    def __init__(self, engine, output="torch", render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None):
+    def __init__(self, engine, output="torch", render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None, policy_obs=None):
         if output not in ("torch", "numpy"):
             raise ValueError("output must be 'torch' or 'numpy'")
         if episodes not in (None, "device"):
@@ -157,8 +167,18 @@ class GymVectorAdapter(_VectorBase):
         self.num_envs = int(engine.num_envs)
         self.output = output
         self.render_size = (int(render_size[0]), int(render_size[1]))
-        (self.single_observation_space, self.single_action_space, self.observation_space,
-         self.action_space) = make_spaces(self.num_envs)
+        self.policy = bool(policy_obs)
+        if self.policy:
+            tensor = getattr(engine, "policy_obs", None)
+            if tensor is None:
+                raise ValueError("policy_obs= needs an engine with a policy_obs tensor (ProcgenVecEnv made with policy_obs=dict(...))")
+            name = str(tensor.dtype).replace("torch.", "")
+            (self.single_observation_space, self.single_action_space, self.observation_space,
+             self.action_space) = make_spaces(self.num_envs, tuple(tensor.shape[1:]), np.dtype("float32" if name == "bfloat16" else name),
+                                              255 if name == "uint8" else 1.0)
+        else:
+            (self.single_observation_space, self.single_action_space, self.observation_space,
+             self.action_space) = make_spaces(self.num_envs)
         self.render_mode = render_mode
         self.closed = False
         self.metadata = dict(self.metadata, autoreset_mode=autoreset_mode)
@@ -172,9 +192,18 @@ class GymVectorAdapter(_VectorBase):
     # -- helpers ---------------------------------------------------------------------------------
     def _out(self, x, dtype=None):
         if self.output == "numpy":
-            x = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+            if hasattr(x, "detach"):
+                x = x.detach().cpu()
+                x = (x.float() if str(x.dtype) == "torch.bfloat16" else x).numpy()  # (numpy has no bfloat16)
+            else:
+                x = np.asarray(x)
             return x.astype(dtype, copy=False) if dtype is not None else x
         return x
+
+    def _observation(self, obs):
+        """What reset and step hand out: the engine's policy tensor where the adapter was made with policy_obs=, which every
+        engine call that drew `obs` has pushed into; `obs` itself otherwise."""
+        return self.engine.policy_obs if self.policy else obs
 
     def _seeds(self, seed):
         if seed is None:
@@ -201,7 +230,7 @@ class GymVectorAdapter(_VectorBase):
                 if mask.shape != (self.num_envs,):
                     raise ValueError("reset_mask must have shape (%d,)" % self.num_envs)
         obs = self.engine.reset(mask=mask, seeds=self._seeds(seed))
-        return self._out(obs), {}
+        return self._out(self._observation(obs)), {}
 
     def step(self, actions):
         n = actions.numel() if hasattr(actions, "numel") else np.asarray(actions).size
@@ -244,7 +273,7 @@ class GymVectorAdapter(_VectorBase):
             reward, terminated = rew, mask
             info = {"final_obs": by_env, "_final_obs": self._out(mask, bool), "final_obs_compact": self._out(final),
                     "final_obs_env": self._out(where)}
-        return self._out(obs), self._out(reward), self._out(terminated, bool), truncated, info
+        return self._out(self._observation(obs)), self._out(reward), self._out(terminated, bool), truncated, info
 
     def _step_device(self, actions):
         """episodes="device": one engine call; everything returned is a view of the engine's buffers (torch) or cut to the
@@ -258,10 +287,10 @@ class GymVectorAdapter(_VectorBase):
                     "final_count": counts.copy(),
                     "episode": {"r": cut(ep.ended_return, c), "l": cut(ep.ended_length, c), "level": cut(ep.ended_level, c),
                                 "level_known": cut(ep.ended_level_known, c)}}
-            return (self._out(obs), self._out(ep.reward), self._out(ep.terminated, bool), self._out(ep.truncated, bool), info)
+            return (self._out(self._observation(obs)), self._out(ep.reward), self._out(ep.terminated, bool), self._out(ep.truncated, bool), info)
         info = {"_final_obs": ep.ended != 0, "final_obs_compact": ep.final_obs, "final_obs_env": ep.ended_env, "final_count": ep.counts,
                 "episode": {"r": ep.ended_return, "l": ep.ended_length, "level": ep.ended_level, "level_known": ep.ended_level_known}}
-        return obs, ep.reward, ep.terminated != 0, ep.truncated != 0, info
+        return self._observation(obs), ep.reward, ep.terminated != 0, ep.truncated != 0, info
 
     def render(self, index=0):
         """The human-size frame of one env (the reference's `cenv_render`, coinrun.cpp:393-411; default 512×512 as its
@@ -311,7 +340,7 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
 
     def __init__(self, game, num_envs, device=0, seed=1, env_offset=0, output="torch", num_levels=0, start_level=0,
                  distribution_mode=None, render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None,
-                 max_episode_steps=0, final_obs_capacity=0):
+                 max_episode_steps=0, final_obs_capacity=0, policy_obs=None):
         from .vec_env import ProcgenVecEnv
         if episodes not in (None, "device"):
             raise ValueError("episodes must be None or 'device'")
@@ -319,8 +348,10 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
             raise ValueError("max_episode_steps / final_obs_capacity need episodes='device'")
         more = {} if episodes is None else {"autoreset_mode": autoreset_mode, "max_episode_steps": max_episode_steps,
                                             "final_obs_capacity": final_obs_capacity}
+        if policy_obs is not None:
+            more["policy_obs"] = policy_obs
         super().__init__(ProcgenVecEnv(game, num_envs, device=device, seed_base=seed, env_offset=env_offset,
                                        num_levels=num_levels, start_level=start_level,
                                        distribution_mode=distribution_mode, **more), output=output, render_mode=render_mode,
-                         render_size=render_size, autoreset_mode=autoreset_mode, episodes=episodes)
+                         render_size=render_size, autoreset_mode=autoreset_mode, episodes=episodes, policy_obs=policy_obs)
         self.game = game

@@ -45,6 +45,23 @@ class Sequence(ctypes.Structure):
                 ("seq_return", c_void_p), ("seq_length", c_void_p), ("seq_done", c_void_p)]
 
 
+class PolicyObsConfig(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_policy_obs_config`."""
+    _fields_ = [("struct_size", c_uint32), ("stack", c_int32), ("gray", c_int32), ("dtype", c_int32), ("out", c_void_p)]
+
+
+# include/procgen2_vec.h PGV_POLICY_*: name → (number, element bytes)
+POLICY_DTYPES = {"uint8": (0, 1), "float16": (1, 2), "bfloat16": (2, 2), "float32": (3, 4)}
+
+
+def policy_obs_enable(lib, h, stack=4, gray=True, dtype="float16", out=None):
+    """pgv_policy_obs_enable.  dtype: a name of POLICY_DTYPES or the number; out: a device pointer (integer) or None for a
+    tensor of the engine's own (pgv_policy_obs)."""
+    number = POLICY_DTYPES[dtype][0] if dtype in POLICY_DTYPES else int(dtype)
+    cfg = PolicyObsConfig(ctypes.sizeof(PolicyObsConfig), int(stack), int(gray), number, out)
+    check(lib, lib.pgv_policy_obs_enable(h, ctypes.byref(cfg)), "pgv_policy_obs_enable")
+
+
 # include/procgen2_vec.h PGV_FRAMES_*
 FRAMES = {"last": 0, "none": 1}
 
@@ -173,6 +190,12 @@ def load(path=None):
         "pgv_step_sequence_host": (c_int32, [P, POINTER(Sequence)]),
         "pgv_render_obs": (c_int32, [P, P]),
         "pgv_render_obs_host": (c_int32, [P, P]),
+        "pgv_policy_obs_enable": (c_int32, [P, POINTER(PolicyObsConfig)]),
+        "pgv_policy_obs": (P, [P]),
+        "pgv_policy_obs_bytes_per_env": (c_int64, [P]),
+        "pgv_policy_obs_restart": (P, [P]),
+        "pgv_policy_obs_push": (c_int32, [P, P]),
+        "pgv_policy_obs_push_host": (c_int32, [P, P]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -205,6 +228,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_assign_levels", "pgv_assign_levels_host", "pgv_level_numbers", "pgv_level_known",
     "pgv_episodes_enable", "pgv_episode_outputs_get", "pgv_step_episodes", "pgv_step_episodes_synthetic", "pgv_step_episodes_host", "pgv_step_episodes_times",
     "pgv_step_sequence", "pgv_step_sequence_host", "pgv_render_obs", "pgv_render_obs_host",
+    "pgv_policy_obs_enable", "pgv_policy_obs", "pgv_policy_obs_bytes_per_env", "pgv_policy_obs_restart", "pgv_policy_obs_push", "pgv_policy_obs_push_host",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_last_error",
 ]

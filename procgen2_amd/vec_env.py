@@ -31,8 +31,15 @@ def shard_range(total_envs, world_size, rank):
 class ProcgenVecEnv:
     def __init__(self, game, num_envs, device=0, seed_base=1, env_offset=0, lib_path=None, num_levels=0,
                  start_level=0, distribution_mode=None, game_flags=0, out=None, autoreset_mode=None, max_episode_steps=0,
-                 final_obs_capacity=0):
-        """autoreset_mode = None | "next_step" | "same_step": episodes on the device (include/procgen2_vec.h
+                 final_obs_capacity=0, policy_obs=None):
+        """policy_obs = None | dict(stack=4, gray=True, dtype="float16"): policy-ready observations on the device
+        (include/procgen2_vec.h pgv_policy_obs_enable) — `policy_obs`, a [N, K*C, 64, 64] tensor of that dtype ("uint8",
+        "float16", "bfloat16", "float32"; C = 1 gray, 3 RGB; slot 0 the oldest frame) that every step, reset and drawn
+        sequence keeps current, stacks restarted where an episode began; `policy_restart`, the pending restart flags;
+        push_policy_obs() by hand.  Every return value stays as it is: the tensor is read from the attribute.  None changes
+        nothing at all.
+
+        autoreset_mode = None | "next_step" | "same_step": episodes on the device (include/procgen2_vec.h
         pgv_episodes_enable) — step_episodes() and the `episode` tensors; None changes nothing at all.  max_episode_steps
         (0: no limit; same_step only) truncates, final_obs_capacity (0 .. num_envs) is the rows of the terminal-frame ring.
 
@@ -46,6 +53,7 @@ class ProcgenVecEnv:
         self.game = game
         self.num_envs = int(num_envs)
         self.env_offset = int(env_offset)
+        policy = _policy_obs_config(policy_obs)  # (ValueError before anything is made)
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         # The engine gets a stream of its own (a torch stream, so torch can order against it): torch's default stream
@@ -99,6 +107,19 @@ class ProcgenVecEnv:
                     raise ValueError("autoreset_mode must be None, 'next_step' or 'same_step'")
                 self.episode = EpisodeTensors(pglib.episodes_enable(self.L, h, autoreset_mode, max_episode_steps, final_obs_capacity),
                                               self.num_envs, int(final_obs_capacity), self.device)
+            except Exception:
+                self.close()
+                raise
+        self.policy_obs = self.policy_restart = None
+        if policy is not None:
+            # torch owns the tensor, as it owns obs; the engine writes straight into it.
+            stack, gray, dtype = policy
+            self.policy_obs = torch.zeros((self.num_envs, stack * (1 if gray else 3), 64, 64), dtype=getattr(torch, dtype), device=self.device)
+            try:
+                self._before()
+                pglib.policy_obs_enable(self.L, h, stack, gray, dtype, c_void_p(self.policy_obs.data_ptr()))
+                self._after()
+                self.policy_restart = _device_view(self.L.pgv_policy_obs_restart(h), self.num_envs, "|u1", self.device)
             except Exception:
                 self.close()
                 raise
@@ -252,6 +273,23 @@ class ProcgenVecEnv:
         self._keep = (m,)
         return self.obs
 
+    def push_policy_obs(self, mask=None):
+        """Push the obs slab as it stands into the policy tensor by hand (pgv_policy_obs_push) — after
+        step_sequence(frames="none") and render_obs(), say; step(), reset() and the drawn sequences push on their own.
+        mask (uint8 [N], non-zero = push): the other envs keep their stacks and their restart flags.  Returns policy_obs."""
+        if self.policy_obs is None:
+            raise pglib.EngineError("push_policy_obs needs an env made with policy_obs=dict(...)")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+            if m.numel() != self.num_envs:
+                raise ValueError("expected a mask of %d envs, got %d" % (self.num_envs, m.numel()))
+        self._before()
+        pglib.check(self.L, self.L.pgv_policy_obs_push(self._h, c_void_p(m.data_ptr()) if m is not None else None), "pgv_policy_obs_push")
+        self._after()
+        self._keep = (m,)
+        return self.policy_obs
+
     def _before(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
 
@@ -333,6 +371,8 @@ class ProcgenVecEnv:
         import numpy as np
         buf = np.ascontiguousarray(buf, np.uint8)
         pglib.check(self.L, self.L.pgv_load_state(self._h, c_void_p(buf.ctypes.data), buf.size), "pgv_load_state")
+        if self.policy_obs is not None:  # (the restart flags the load sets on the engine's stream, ordered for the caller)
+            self._after()
 
     # -- per-env records (include/procgen2_vec.h pgv_save_envs / pgv_load_envs) -------------------
     @property
@@ -472,6 +512,27 @@ class ProcgenVecEnv:
                 self._gathers = {}
             plan = self._gathers[key] = RootGather((self.obs, self.reward, self.done), dst=dst, group=group)
         return plan()
+
+
+def _policy_obs_config(policy_obs):
+    """(stack, gray, dtype name) of ProcgenVecEnv's policy_obs= argument, or None; ValueError for anything else."""
+    if policy_obs is None:
+        return None
+    if not isinstance(policy_obs, dict):
+        raise ValueError("policy_obs must be None or a dict with the keys stack, gray, dtype")
+    unknown = set(policy_obs) - {"stack", "gray", "dtype"}
+    if unknown:
+        raise ValueError("policy_obs: unknown key(s) %s" % ", ".join(sorted(unknown)))
+    stack, gray, dtype = policy_obs.get("stack", 4), policy_obs.get("gray", True), policy_obs.get("dtype", "float16")
+    if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= 8:
+        raise ValueError("policy_obs: stack must be an integer in 1 .. 8")
+    if gray not in (True, False, 0, 1):
+        raise ValueError("policy_obs: gray must be True or False")
+    if isinstance(dtype, torch.dtype):
+        dtype = str(dtype).replace("torch.", "")
+    if dtype not in pglib.POLICY_DTYPES:
+        raise ValueError("policy_obs: dtype must be one of %s" % ", ".join(pglib.POLICY_DTYPES))
+    return int(stack), bool(gray), dtype
 
 
 class _DeviceArray:
