@@ -37,9 +37,42 @@ def protocol_calls(n=PROTOCOL_N, lengths=PROTOCOL_LENGTHS, run_seed=PROTOCOL_SEE
         t += T
 
 
+def count_protocol(game, mode=0):
+    """The ground the protocol covers in one (game, mode), counted on the oracle without drawing: dones inside a sequence, and
+    chaser's late-pass rows — envs reset in a call's last sub-step (test_sequence_gpu.run_frames_none) — summed over every
+    third call and over every call."""
+    m = SequenceModel(game, PROTOCOL_N, render=False, mode=mode)
+    m.reset()
+    inside = third = every = 0
+    due = np.zeros(PROTOCOL_N, bool)
+    for k, (_, actions) in enumerate(protocol_calls()):
+        _, dones = m.sequence(actions)
+        inside += int((dones[:-1] != 0).sum())
+        reset_last = dones[-2] != 0 if len(actions) >= 2 else due
+        due = dones[-1] != 0
+        every += int(reset_last.sum())
+        third += int(reset_last.sum()) if k % 3 == 2 else 0
+    m.close()
+    return inside, third, every
+
+
+# chaser's late-pass rows per distribution mode (0: the default, easy), on the oracle: (in every third call, in every call);
+# tests/test_variant_paths.py holds the table to count_protocol
+CHASER_LATE_ROWS = {0: (8, 27), 2: (17, 33), 4: (15, 35)}
+
+
+def chaser_late_rows(mode):
+    """(rows the GPU test will see, whether it looks at every call, its floor).  Every third call where that gives six
+    rows or more, else every call; the floor is half the oracle's count (the default mode keeps the 5 of 8 it always had)."""
+    third, every = CHASER_LATE_ROWS[mode]
+    every_call = third < 6
+    count = every if every_call else third
+    return count, every_call, 5 if mode == 0 else (count + 1) // 2
+
+
 class SequenceModel:
-    def __init__(self, game, n, seed_base=1, render=True):
-        self.o = OracleVec(game, n, seed_base=seed_base, render=render)
+    def __init__(self, game, n, seed_base=1, render=True, mode=0):
+        self.o = OracleVec(game, n, seed_base=seed_base, render=render, mode=mode)
         self.n, self.can_draw = n, render
 
     obs = property(lambda self: self.o.obs)

@@ -15,6 +15,8 @@ from engine_util import EngineVec
 from episodes_util import NEXT_STEP, SAME_STEP, EpisodeModel, synthetic_actions
 from oracle_util import OBS_BYTES
 from procgen2_amd import lib as pglib
+from test_modes import NON_DEFAULT
+from variant_paths_util import (EPISODE_LIMIT, EPISODE_N, EPISODE_RING, assert_limit_case_covers, run_limit_case)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +34,12 @@ LIMIT_CASES = [(g, 23) for g in GAMES] + [("chaser", 60)]
 class Engine:
     """ProcgenVecEnv with episodes, driven with host arrays and read back as numpy, as the model is."""
 
-    def __init__(self, game, n, mode, max_episode_steps=0, final_capacity=0):
+    def __init__(self, game, n, mode, max_episode_steps=0, final_capacity=0, distribution_mode=0):
         import torch
         from procgen2_amd.vec_env import ProcgenVecEnv
         self.torch = torch
         self.v = ProcgenVecEnv(game, n, seed_base=1, autoreset_mode=mode, max_episode_steps=max_episode_steps,
-                               final_obs_capacity=final_capacity)
+                               final_obs_capacity=final_capacity, distribution_mode=distribution_mode)
         self.n = n
 
     def rows(self):
@@ -168,6 +170,21 @@ def test_same_step_with_a_limit_and_staggered_episodes(game, T):
     assert truncated > 0 and overflows >= 1, (terminated, truncated, overflows)
     if (game, T) != ("chaser", 23):  # (see LIMIT_CASES: the oracle's chaser cannot end a game in 23 steps; it does in 60)
         assert terminated > 0 and mixed >= 1, (terminated, truncated, overflows, mixed)
+    eng.close(), model.close()
+
+
+@pytest.mark.parametrize("game,mode", NON_DEFAULT)
+def test_same_step_with_a_limit_in_every_variant(game, mode):
+    """Case 3 in every non-default distribution mode, 131 envs, 70 steps, everything checked after every step: the
+    masked-reset level install that same-step episodes make (pg_prefetch.h level_serve mode 1) runs on the mode's own Level
+    and GenLds.  With a limit of 23 every env ends at least twice, so every env's level comes from that install at least
+    twice, in jumper-memory and caveflyer-memory too (variant_paths_util.py; tests/test_variant_paths.py asserts the same on
+    the oracle alone)."""
+    eng = Engine(game, EPISODE_N, SAME_STEP, EPISODE_LIMIT, EPISODE_RING, distribution_mode=mode)
+    model = EpisodeModel(game, EPISODE_N, SAME_STEP, EPISODE_LIMIT, EPISODE_RING, distribution_mode=mode)
+    assert pglib.MODES[eng.v.distribution_mode] == mode
+    assert np.array_equal(eng.reset(), model.first_reset()) and np.array_equal(eng.reset(), model.reset())
+    assert_limit_case_covers(*run_limit_case(model, eng, check_step))
     eng.close(), model.close()
 
 

@@ -13,9 +13,11 @@ pytestmark = pytest.mark.gpu
 
 from procgen2_amd import lib as pglib  # noqa: E402
 
-# tests/test_parity_gpu.py FRAME_GAMES: every game, and the distribution modes with a camera / world size of their own
+from test_modes import NON_DEFAULT  # noqa: E402
+
+# tests/test_parity_gpu.py FRAME_GAMES: every game, and every distribution mode that is not its game's default
 FRAME_GAMES = [("coinrun", 0), ("maze", 0), ("bossfight", 0), ("climber", 0), ("caveflyer", 0), ("chaser", 0),
-               ("jumper", 0), ("maze", 3), ("chaser", 4), ("jumper", 3), ("caveflyer", 1)]
+               ("jumper", 0)] + NON_DEFAULT
 GAMES = ("coinrun", "maze", "bossfight", "climber", "caveflyer", "chaser", "jumper")
 SIZES = ((512, 512), (160, 160), (200, 120), (64, 64), (131, 77))  # the last: both edges ragged, W·3 odd
 

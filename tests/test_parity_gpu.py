@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 from procgen2_amd import cenv as pgcenv  # noqa: E402
 from procgen2_amd import lib as pglib  # noqa: E402
+from test_modes import NON_DEFAULT  # noqa: E402
 
 
 def _actions(L, run_seed, step, n, offset=0):
@@ -343,9 +344,7 @@ def test_snapshot_restore_replays_the_same_rollout(game):
 
 
 FRAME_GAMES = [("coinrun", 0), ("maze", 0), ("bossfight", 0), ("climber", 0), ("caveflyer", 0), ("chaser", 0),
-               ("jumper", 0),
-               # non-default distribution modes with their own camera / world size (include/procgen2_vec.h PGV_MODE_*)
-               ("maze", 3), ("chaser", 4), ("jumper", 3), ("caveflyer", 1)]
+               ("jumper", 0)] + NON_DEFAULT  # and every non-default distribution mode (include/procgen2_vec.h PGV_MODE_*)
 
 
 @pytest.mark.parametrize("game,mode", FRAME_GAMES)

@@ -16,7 +16,9 @@ from engine_util import EngineVec
 from episodes_util import synthetic_actions
 from oracle_util import OBS_BYTES
 from procgen2_amd import lib as pglib
-from sequence_util import GAMES, PROTOCOL_N as N, PROTOCOL_SEED as RUN_SEED, PROTOCOL_STEPS, SequenceModel, fold, protocol_calls
+from sequence_util import (GAMES, PROTOCOL_N as N, PROTOCOL_SEED as RUN_SEED, PROTOCOL_STEPS, SequenceModel, chaser_late_rows, fold,
+                           protocol_calls)
+from test_modes import NON_DEFAULT
 
 pytestmark = pytest.mark.gpu
 
@@ -68,17 +70,19 @@ def check_rows(eng, model, got, t):
         assert same_bits(got[name], getattr(model, name)), "%s, call at step %d" % (name, t)
 
 
-def run_frames_last(game, debug=0):
-    eng, twin, model = SeqEngine(game, N), SeqEngine(game, N), SequenceModel(game, N)
+def run_frames_last(game, debug=0, mode=0):
+    eng, twin, model = SeqEngine(game, N, mode=mode), SeqEngine(game, N, mode=mode), SequenceModel(game, N, mode=mode)
+    assert eng.L.pgv_mode(eng.h) == mode or mode == 0
     if debug:
         eng.set_debug(debug), twin.set_debug(debug)
     assert np.array_equal(eng.reset(), model.first_reset()) and np.array_equal(twin.reset(), model.obs)
     assert np.array_equal(eng.reset(), model.reset()) and np.array_equal(twin.reset(), model.obs)
-    steps = 0
+    steps = inside = 0
     for t, actions in protocol_calls():
         got = eng.sequence(actions, frames=LAST)
         model.sequence(actions)
         check_rows(eng, model, got, t)
+        inside += int((model.dones[:-1] != 0).sum())
         assert np.array_equal(eng._fetch()[0], model.obs), "obs, call at step %d" % t
         for a in actions:
             obs, reward, done = twin.step(a)
@@ -87,6 +91,7 @@ def run_frames_last(game, debug=0):
         steps += len(actions)
     assert steps == PROTOCOL_STEPS  # (bossfight and chaser have no level prefetch: their launch count is 0 on both sides)
     eng.close(), twin.close(), model.close()
+    return inside
 
 
 @pytest.mark.parametrize("game", GAMES)
@@ -103,29 +108,30 @@ def test_frames_last_with_debug_paths(game, debug):
     run_frames_last(game, debug)
 
 
-@pytest.mark.parametrize("game", GAMES)
-def test_frames_none_then_render_obs(game):
-    """Test 2: PGV_FRAMES_NONE: rows and summary after every call; after every third, pgv_render_obs(NULL) is the frame
-    PGV_FRAMES_LAST would have left — the first time behind a masked pgv_render_obs of every other env, which leaves the
-    other rows' bytes alone.  Then 20 plain steps: nothing was left stale.  chaser: "unspecified" still means the late
-    pass has drawn the envs reset in the call's last sub-step (their base layers come from that) — those rows are the
-    model's before any pgv_render_obs."""
-    eng, model = SeqEngine(game, N), SequenceModel(game, N)
+def run_frames_none(game, mode=0):
+    """The body of test_frames_none_then_render_obs (see there), in any distribution mode.  Returns the resets that fell
+    inside a sequence.  chaser: the late-pass rows are looked at after every third call, or after every call in a mode where
+    every third gives fewer than six (sequence_util.chaser_late_rows); the model then draws every call's last sub-step,
+    which changes nothing it computes, and the engine is asked for no frame it would not be asked for otherwise."""
+    eng, model = SeqEngine(game, N, mode=mode), SequenceModel(game, N, mode=mode)
+    assert eng.L.pgv_mode(eng.h) == mode or mode == 0
     assert np.array_equal(eng.reset(), model.first_reset()) and np.array_equal(eng.reset(), model.reset())
-    masked, late_rows = False, 0
+    every_call, late_floor = chaser_late_rows(mode)[1:] if game == "chaser" else (False, 0)
+    masked, late_rows, inside = False, 0, 0
     due = np.zeros(N, bool)  # envs whose reset the next sub-step serves
     for k, (t, actions) in enumerate(protocol_calls()):
         draw = k % 3 == 2
         got = eng.sequence(actions, frames=NONE)
-        model.sequence(actions, draw_last=draw)
+        model.sequence(actions, draw_last=draw or every_call)
         check_rows(eng, model, got, t)
+        inside += int((model.dones[:-1] != 0).sum())
         reset_last = model.dones[-2] != 0 if len(actions) >= 2 else due
         due = model.dones[-1] != 0
-        if not draw:
-            continue
-        if game == "chaser":
+        if game == "chaser" and (draw or every_call):
             assert np.array_equal(eng._fetch()[0][reset_last], model.obs[reset_last]), "the late pass's frames, call at step %d" % t
             late_rows += int(reset_last.sum())
+        if not draw:
+            continue
         if not masked:
             masked = True
             before = eng._fetch()[0].copy()
@@ -135,13 +141,39 @@ def test_frames_none_then_render_obs(game):
             assert np.array_equal(after[0::2], model.obs[0::2]), "the rows a masked pgv_render_obs names"
         assert np.array_equal(eng.render_obs(), model.obs), "pgv_render_obs, call at step %d" % t
         assert np.array_equal(eng.render_obs(), model.obs), "pgv_render_obs twice"
-    assert masked and (game != "chaser" or late_rows >= 5), late_rows  # (on the oracle: 8 such rows in the calls looked at)
+    assert masked and (game != "chaser" or late_rows >= late_floor), late_rows  # (mode 0, on the oracle: 8 such rows in the calls looked at)
     for t in range(PROTOCOL_STEPS, PROTOCOL_STEPS + 20):
         a = synthetic_actions(RUN_SEED, t, N)
         obs, reward, done = eng.step(a)
         want = model.plain_step(a)
         assert np.array_equal(obs, want[0]) and same_bits(reward, want[1]) and same_bits(done, want[2]), "plain step %d" % t
     eng.close(), model.close()
+    return inside
+
+
+@pytest.mark.parametrize("game", GAMES)
+def test_frames_none_then_render_obs(game):
+    """Test 2: PGV_FRAMES_NONE: rows and summary after every call; after every third, pgv_render_obs(NULL) is the frame
+    PGV_FRAMES_LAST would have left — the first time behind a masked pgv_render_obs of every other env, which leaves the
+    other rows' bytes alone.  Then 20 plain steps: nothing was left stale.  chaser: "unspecified" still means the late
+    pass has drawn the envs reset in the call's last sub-step (their base layers come from that) — those rows are the
+    model's before any pgv_render_obs."""
+    run_frames_none(game)
+
+
+@pytest.mark.parametrize("game,mode", NON_DEFAULT)
+def test_frames_last_in_every_variant(game, mode):
+    """Test 1 in every non-default distribution mode: launch_no_frame and the late pass a frameless step keeps are game
+    code, compiled per mode.  At least 10 resets fall inside a sequence (tests/test_variant_paths.py has each pair's count)."""
+    inside = run_frames_last(game, mode=mode)
+    assert inside >= 10, inside
+
+
+@pytest.mark.parametrize("game,mode", NON_DEFAULT)
+def test_frames_none_then_render_obs_in_every_variant(game, mode):
+    """Test 2 in every non-default distribution mode, pgv_render_obs and chaser's late-pass rows included."""
+    inside = run_frames_none(game, mode=mode)
+    assert inside >= 10, inside
 
 
 def test_synthetic_sequences_share_the_action_hash_and_the_step_counter():
