@@ -413,6 +413,69 @@ PGV_API const uint8_t* pgv_policy_obs_restart(pgv_env* env);      /* device u8[N
 PGV_API int32_t pgv_policy_obs_push(pgv_env* env, const uint8_t* d_mask); /* device u8[N] or NULL = all */
 PGV_API int32_t pgv_policy_obs_push_host(pgv_env* env, const uint8_t* h_mask);
 
+/* Frame history on the device: the last T frames of every env, each stored once as planar u8 with one `began` byte, and a
+ * gather that builds stacked, scaled, channel-first rows — what the policy observations keep for "now" — for any list of
+ * (push number, env) pairs, only when somebody reads them: the acting batch, or a training minibatch over T x N.  A push
+ * writes one frame per env instead of moving K; a rollout's observations cost C*4096 bytes per (step, env) instead of
+ * K*C*4096*element size.  Opt-in per engine: one that never calls pgv_history_enable launches nothing new and gives the same
+ * bytes as before at every entry point.  Independent of the policy observations: either may be enabled without the other.
+ *
+ *   1. Slots.  Push number p (0, 1, 2, ...) lives in slot p % T of `frames`, u8 [T][N][C][64][64], C = 3 (planes R, G, B) or
+ *      1 (gray: (77*R + 150*G + 29*B + 128) >> 8, the policy observations' rule), and of `began`, u8 [T][N].  Push p is HELD
+ *      while head - T <= p < head, head being the number of pushes so far (pgv_history_head: a host counter that moves when a
+ *      push is enqueued, read without synchronisation).
+ *   2. A PUSH converts the obs slab as it stands at that point of the env's stream into slot head % T, all envs, writes
+ *      began[slot][i] = env i's pending flag, clears the flag, and head moves.  It is enqueued on the env's stream, allocates
+ *      nothing and does not synchronise the host.  It needs the obs slab 16-byte aligned (pgv_bind_outputs may move the
+ *      slab): pgv_history_push and every call of point 4 or 5 check that on the host before they enqueue anything, and fail
+ *      with a message and the engine as it was — no step taken, no flag set, head and the step counter where they stood.
+ *   3. An env's pending flag is set by exactly the events of point 3 of the policy observations: any step, however taken,
+ *      that finds the env's `done` row set; pgv_reset, for the envs it names; a same-step auto-reset, for the envs that
+ *      ended; pgv_load_envs, for the slots it actually wrote; pgv_load_state, for all envs; and pgv_history_enable itself,
+ *      for all envs.  The flags are the feature's own array (pgv_history_pending).  The ring travels neither in records nor
+ *      in snapshots: pgv_snapshot_bytes and pgv_env_record_bytes are what they were.
+ *   4. Who pushes a new slot, once per call and behind everything else the call enqueues: the callers of point 4 of the
+ *      policy observations — pgv_step, pgv_step_synthetic, pgv_step_host; pgv_step_episodes, pgv_step_episodes_synthetic,
+ *      pgv_step_episodes_host, after the same-step reset has redrawn the ended envs; pgv_step_sequence and
+ *      pgv_step_sequence_host with PGV_FRAMES_LAST.  Who does not push: the same list as there.  After PGV_FRAMES_NONE and
+ *      pgv_render_obs(NULL), pgv_history_push leaves what PGV_FRAMES_LAST would have left.
+ *   5. pgv_reset (and pgv_reset_host) opens no slot of its own: the newest slot is "what pgv_obs showed when the caller next
+ *      acts", and after a reset that is the reset frame.  It rewrites, in slot (head - 1) % T, the rows of the envs it names
+ *      with the frame it drew, began = 1, and clears their pending flags; rows and flags of envs it does not name keep their
+ *      bytes.  At head == 0 it opens slot 0 first (head becomes 1): the rows of envs it does not name are then what `frames`
+ *      held — zeros in the engine's own — and their flags stay set, so their first pushed frame begins their history.
+ *   6. pgv_history_gather writes `count` rows of [K*C][64][64] elements of `dtype`, K = stack in 1 .. 8, slot K-1 the newest
+ *      frame, values by the policy observations' value rule.  For an entry (p, i): f_0 = p; for j = 1 .. K-1, f_j = f_(j-1)
+ *      if began[f_(j-1)][i] is set or push f_(j-1) - 1 is not held, else f_(j-1) - 1; row slot K-1-j is frame f_j.  So a stack
+ *      never mixes episodes, an env that just began holds K copies of its first frame, and a walk that reaches the oldest
+ *      held push repeats that push.  An entry whose p is not held, or whose env is outside 0 .. N-1, gives a row of zero
+ *      bytes; nothing faults for any index values, and an entry may appear more than once.  "Held" is judged by head as
+ *      it stands when the call is made.  count = 0 succeeds and does nothing.  Checked on the host before anything is
+ *      enqueued: stack, dtype, count < 0, d_out 16-byte aligned, NULL pointers with count > 0.
+ *   7. pgv_history_enable may be called once per env, at any time.  Each refusal leaves a message and the engine as it was:
+ *      a second call, capacity < 1, gray outside 0 .. 1, a `frames` that is not 16-byte aligned, a struct_size too small, a
+ *      failed allocation.  It sets every pending flag and pushes nothing.  The engine's own `frames` start as zeros; a
+ *      caller's are as the caller left them.
+ *
+ * The law that ties the two features: on an engine with both enabled at the same moment, the same `gray`, and T >= K,
+ * gather(p = head - 1, envs 0 .. N-1, K, dtype) equals pgv_policy_obs bit for bit after every call of point 4 and after
+ * every pgv_reset.  (pgv_policy_obs_push under a mask by hand has no counterpart here.) */
+typedef struct pgv_history_config {
+    uint32_t struct_size;
+    int32_t capacity; /* T >= 1 time slots */
+    int32_t gray;     /* 0: planes R, G, B; 1: one plane, the gray rule of the policy observations */
+    void* frames;     /* device, 16-byte aligned, T*N*C*4096 bytes; NULL: the engine allocates (zeroed) */
+} pgv_history_config;
+PGV_API int32_t pgv_history_enable(pgv_env* env, const pgv_history_config* config);
+PGV_API uint8_t* pgv_history_frames(pgv_env* env);        /* device u8 [T][N][C][64][64]; NULL before enable */
+PGV_API const uint8_t* pgv_history_began(pgv_env* env);   /* device u8 [T][N]; NULL before enable */
+PGV_API const uint8_t* pgv_history_pending(pgv_env* env); /* device u8 [N]: the pending "began" flags; NULL before enable */
+PGV_API int64_t pgv_history_head(pgv_env* env);           /* pushes so far (host counter, no synchronisation); 0 before enable, -1 for NULL */
+PGV_API int32_t pgv_history_capacity(pgv_env* env);       /* T; 0 before enable */
+PGV_API int32_t pgv_history_push(pgv_env* env);           /* by hand: all envs, a new slot */
+PGV_API int32_t pgv_history_gather(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack,
+                                   int32_t dtype /* PGV_POLICY_* */, void* d_out);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

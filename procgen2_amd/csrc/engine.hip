@@ -15,6 +15,7 @@
 #include "pg_engine.h"
 #include "pg_episodes.h"
 #include "pg_order.h"
+#include "pg_history.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
 #include "pg_sequence.h"
@@ -279,6 +280,13 @@ struct pgv_env {
     uint8_t* d_policy_out = nullptr;
     pg::PolicyObsBuffers pol{};
     uint32_t policy_table[256] = {};  // (the upload's source: lives as long as the env)
+    // frame history (pg_history.h; pgv_history_enable): off unless asked for.  One device block holds the pending flags, the
+    // began bytes, the value tables and — unless the caller brought them — the frames.  `history_head` counts the pushes.
+    bool history = false;
+    int64_t history_head = 0;
+    void* d_history = nullptr;
+    pg::HistoryBuffers hist{};
+    uint32_t history_table[pg::kHistoryTables * 256] = {};  // (the upload's source: lives as long as the env)
 
     pg::StepIO io() const { return {d_obs, d_reward, d_done, d_pending}; }
     // The per-env output rows, in the order a snapshot holds them behind the state blob.  Separate allocations:
@@ -361,6 +369,7 @@ void pgv_close(pgv_env* e) {
     if (e->d_sequence) hipFree(e->d_sequence);
     if (e->d_policy) hipFree(e->d_policy);
     if (e->own_policy_out && e->d_policy_out) hipFree(e->d_policy_out);
+    if (e->d_history) hipFree(e->d_history);
     if (e->d_host_i32) hipFree(e->d_host_i32);
     if (e->d_host_u8) hipFree(e->d_host_u8);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -541,12 +550,14 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     return 0;
 }
 
-// What a call that ends with a push of the policy observations asks of the host, BEFORE it enqueues anything: a slab the
-// push kernel's 16-byte loads can read (pgv_bind_outputs may have moved it).  A refusal leaves the engine as it was — no
-// step taken, no flag set, the step counter where it stood.  An engine without the feature passes.
+// What a call that ends with a push of the policy observations or of the frame history asks of the host, BEFORE it enqueues
+// anything: a slab the push kernels' 16-byte loads can read (pgv_bind_outputs may have moved it).  A refusal leaves the
+// engine as it was — no step taken, no flag set, the step counter and the ring's head where they stood.  An engine with
+// neither feature passes.
 static int32_t policy_ready(const char* who, const pgv_env* e) {
-    if (e->policy && (reinterpret_cast<uintptr_t>(e->d_obs) & 15u))
-        return fail(std::string(who) + ": the observation buffer must be 16-byte aligned for the policy observations");
+    if ((e->policy || e->history) && (reinterpret_cast<uintptr_t>(e->d_obs) & 15u))
+        return fail(std::string(who) + ": the observation buffer must be 16-byte aligned for the " +
+                    (e->policy ? "policy observations" : "frame history"));
     return 0;
 }
 
@@ -567,6 +578,31 @@ static int32_t policy_push(const char* who, pgv_env* e, const uint8_t* d_mask) {
     return 0;
 }
 
+// A push of the frame history (pg_history.h) on the env's stream: the obs slab as it stands there into a new slot, all envs
+// — or, for pgv_reset (`reset`), into the newest slot under the mask (slot 0, opened, where there is none yet).  Its callers
+// have asked policy_ready() first.
+static int32_t history_push(pgv_env* e, bool reset, const uint8_t* d_mask) {
+    const bool open = !reset || e->history_head == 0;
+    pg::HistoryPush q{};
+    q.n = e->n;
+    q.planes = e->hist.planes;
+    q.slot = pg::history_slot(open ? e->history_head : e->history_head - 1, e->hist.capacity);
+    q.reset = reset ? 1 : 0;
+    q.obs = e->d_obs;
+    q.mask = d_mask;
+    q.b = e->hist;
+    pg::launch_history_push(e->stream, q);
+    PG_HIP(hipGetLastError());
+    if (open) e->history_head++;
+    return 0;
+}
+
+// The pushes that end a call of point 4: the policy observations, then the frame history, whichever is enabled.
+static int32_t end_with_pushes(const char* who, pgv_env* e) {
+    if (e->policy && policy_push(who, e, nullptr)) return 1;
+    return e->history ? history_push(e, false, nullptr) : 0;
+}
+
 int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     if (!e) return fail("pgv_reset: env is NULL");
     if (policy_ready("pgv_reset", e)) return 1;
@@ -579,8 +615,9 @@ int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     PG_HIP(hipGetLastError());
     if (e->policy) {  // the named envs' stacks restart with the frame just drawn
         pg::launch_policy_flag_mask(e->stream, e->pol, e->n, d_mask);
-        return policy_push("pgv_reset", e, d_mask);
+        if (policy_push("pgv_reset", e, d_mask)) return 1;
     }
+    if (e->history) return history_push(e, true, d_mask);  // … and their rows of the newest slot are that frame, began = 1
     return 0;
 }
 
@@ -600,6 +637,7 @@ static int32_t step_impl(pgv_env* e, const int32_t* d_actions, uint32_t run_seed
     (void)hipGetLastError();
     // (policy observations: the done row as this step finds it — in front of the fork, so no reset kernel is at the row yet)
     if (e->policy) pg::launch_policy_flag_done(e->stream, e->pol, e->n, e->d_done);
+    if (e->history) pg::launch_policy_flag_done(e->stream, pg::history_flags(e->hist), e->n, e->d_done);
     const bool forked = e->reset_stream != nullptr;
     if (forked) {  // fork: the auto-resets of this step go beside its logic and render kernels
         PG_HIP(hipEventRecord(e->reset_fork, e->stream));
@@ -656,7 +694,7 @@ int32_t pgv_step(pgv_env* e, const int32_t* d_actions) {
     if (policy_ready("pgv_step", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (step_impl(e, d_actions, 0)) return 1;
-    return e->policy ? policy_push("pgv_step", e, nullptr) : 0;
+    return end_with_pushes("pgv_step", e);
 }
 
 int32_t pgv_step_synthetic(pgv_env* e, uint32_t run_seed) {
@@ -664,7 +702,7 @@ int32_t pgv_step_synthetic(pgv_env* e, uint32_t run_seed) {
     if (policy_ready("pgv_step_synthetic", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (step_impl(e, nullptr, run_seed)) return 1;
-    return e->policy ? policy_push("pgv_step_synthetic", e, nullptr) : 0;
+    return end_with_pushes("pgv_step_synthetic", e);
 }
 
 int32_t pgv_step_synthetic_many(pgv_env* const* envs, int32_t count, int32_t steps, uint32_t run_seed) {
@@ -795,6 +833,7 @@ static int32_t step_episodes_impl(const char* who, pgv_env* e, const int32_t* d_
         e->game->launch_prepass(e->stream, b.ended);
         e->game->launch_render(e->stream, b.ended, e->io());
         if (e->policy) pg::launch_policy_flag_mask(e->stream, e->pol, e->n, b.ended);  // their stacks restart with the new first frame
+        if (e->history) pg::launch_policy_flag_mask(e->stream, pg::history_flags(e->hist), e->n, b.ended);
         PG_HIP(hipGetLastError());
     }
     return 0;
@@ -803,7 +842,7 @@ static int32_t step_episodes_impl(const char* who, pgv_env* e, const int32_t* d_
 static int32_t step_episodes_push(const char* who, pgv_env* e, const int32_t* d_actions, uint32_t run_seed) {
     if (policy_ready(who, e)) return 1;
     if (step_episodes_impl(who, e, d_actions, run_seed)) return 1;
-    return e->policy ? policy_push(who, e, nullptr) : 0;
+    return end_with_pushes(who, e);
 }
 
 int32_t pgv_step_episodes(pgv_env* e, const int32_t* d_actions) {
@@ -873,8 +912,7 @@ int32_t pgv_step_sequence(pgv_env* e, const pgv_sequence* q) {
         pg::launch_sequence_row(e->stream, row);
         PG_HIP(hipGetLastError());
     }
-    if (e->policy && q->frames == PGV_FRAMES_LAST) return policy_push("pgv_step_sequence", e, nullptr);  // once, behind the drawn sub-step
-    return 0;
+    return q->frames == PGV_FRAMES_LAST ? end_with_pushes("pgv_step_sequence", e) : 0;  // once, behind the drawn sub-step
 }
 
 int32_t pgv_step_sequence_host(pgv_env* e, const pgv_sequence* q) {
@@ -1007,6 +1045,88 @@ int32_t pgv_policy_obs_push_host(pgv_env* e, const uint8_t* h_mask) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Frame history (pg_history.h)
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_history_enable(pgv_env* e, const pgv_history_config* cfg) {
+    if (!e) return fail("pgv_history_enable: env is NULL");
+    if (!cfg || cfg->struct_size < sizeof(pgv_history_config)) return fail("pgv_history_enable: config is NULL or struct_size too small");
+    if (e->history) return fail("pgv_history_enable: the frame history is enabled already (once per env)");
+    if (cfg->capacity < 1) return fail("pgv_history_enable: capacity must be >= 1");
+    if (cfg->gray != 0 && cfg->gray != 1) return fail("pgv_history_enable: gray must be 0 or 1");
+    if (reinterpret_cast<uintptr_t>(cfg->frames) & 15u) return fail("pgv_history_enable: frames must be 16-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    pg::HistoryBuffers b{};
+    b.capacity = cfg->capacity;
+    b.planes = cfg->gray ? 1 : 3;
+    b.own_frames = cfg->frames ? 0 : 1;
+    for (int dtype = 0; dtype < pg::kHistoryTables; dtype++)
+        for (uint32_t v = 0; v < 256; v++) e->history_table[dtype * 256 + v] = pg::policy_table_entry(dtype, v);
+    const size_t bytes = pg::Carve::size(pg::list_history, e->n, b);
+    void* mem = nullptr;
+    hipError_t err = hipMalloc(&mem, bytes);
+    if (err == hipSuccess) {
+        pg::Carve::bind(pg::list_history, mem, b, e->n);
+        err = hipMemsetAsync(mem, 0, bytes, e->stream);  // began, and the engine's own frames
+    }
+    if (err == hipSuccess) err = hipMemsetAsync(b.pending, 1, size_t(e->n), e->stream);  // every env's first frame begins its history
+    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->history_table, sizeof(e->history_table), hipMemcpyHostToDevice, e->stream);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(e->stream);
+        if (mem) (void)hipFree(mem);
+        return fail(std::string("pgv_history_enable: ") + hipGetErrorString(err));
+    }
+    if (cfg->frames) b.frames = static_cast<uint8_t*>(cfg->frames);
+    e->d_history = mem;
+    e->hist = b;
+    e->history_head = 0;
+    e->history = true;
+    return 0;
+}
+
+uint8_t* pgv_history_frames(pgv_env* e) { return e && e->history ? e->hist.frames : nullptr; }
+const uint8_t* pgv_history_began(pgv_env* e) { return e && e->history ? e->hist.began : nullptr; }
+const uint8_t* pgv_history_pending(pgv_env* e) { return e && e->history ? e->hist.pending : nullptr; }
+int64_t pgv_history_head(pgv_env* e) { return e ? e->history_head : -1; }
+int32_t pgv_history_capacity(pgv_env* e) { return e && e->history ? e->hist.capacity : 0; }
+
+int32_t pgv_history_push(pgv_env* e) {
+    if (!e) return fail("pgv_history_push: env is NULL");
+    if (!e->history) return fail("pgv_history_push: call pgv_history_enable first");
+    if (policy_ready("pgv_history_push", e)) return 1;
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    return history_push(e, false, nullptr);
+}
+
+int32_t pgv_history_gather(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype, void* d_out) {
+    if (!e) return fail("pgv_history_gather: env is NULL");
+    if (!e->history) return fail("pgv_history_gather: call pgv_history_enable first");
+    if (stack < 1 || stack > pg::kPolicyMaxStack) return fail("pgv_history_gather: stack must be in 1 .. 8");
+    if (dtype != PGV_POLICY_U8 && dtype != PGV_POLICY_F16 && dtype != PGV_POLICY_BF16 && dtype != PGV_POLICY_F32)
+        return fail("pgv_history_gather: unknown dtype " + std::to_string(dtype));
+    if (count < 0) return fail("pgv_history_gather: count is negative");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail("pgv_history_gather: out must be 16-byte aligned");
+    if (count == 0) return 0;
+    if (!d_pushes || !d_envs || !d_out) return fail("pgv_history_gather: pushes, envs or out is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::HistoryGather q{};
+    q.n = e->n;
+    q.stack = stack;
+    q.count = count;
+    q.head = e->history_head;
+    q.pushes = d_pushes;
+    q.envs = d_envs;
+    q.table = e->hist.table + dtype * 256;
+    q.out = static_cast<uint8_t*>(d_out);
+    q.b = e->hist;
+    pg::launch_history_gather(e->stream, q, pg::policy_element_bytes(dtype));
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
 int32_t pgv_decode_png(const char* path, int32_t* w, int32_t* h, uint8_t* h_rgba, int64_t cap) {
     pg::Image img;
     std::string err;
@@ -1099,6 +1219,7 @@ int32_t pgv_load_state(pgv_env* e, const void* h_buffer, int64_t size) {
     e->step_index = hd.step_index;
     PG_HIP(e->game->state_loaded(e->stream));  // (on the env's stream: ordered in front of the next step)
     if (e->policy) pg::launch_policy_flag_mask(e->stream, e->pol, e->n, nullptr);  // the stacks do not travel: every env restarts
+    if (e->history) pg::launch_policy_flag_mask(e->stream, pg::history_flags(e->hist), e->n, nullptr);  // nor does the ring
     pregen(e, true, true);  // queued shadow slots of the snapshot get their generator launch
     return 0;
 }
@@ -1164,6 +1285,9 @@ int32_t pgv_load_envs(pgv_env* e, const int32_t* d_indices, int32_t count, const
                             e->step_index, e->io());
     if (e->policy)  // the slots actually written restart their stacks
         pg::launch_policy_flag_list(e->stream, e->pol, e->n, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes, pg::kRecordFull);
+    if (e->history)  // … and begin their history afresh
+        pg::launch_policy_flag_list(e->stream, pg::history_flags(e->hist), e->n, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes,
+                                    pg::kRecordFull);
     PG_HIP(hipGetLastError());
     pregen(e, size_t(count) * 2 >= size_t(e->n), true);  // loaded slots that are queued get their generator launch
     return 0;

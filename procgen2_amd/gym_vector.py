@@ -41,6 +41,10 @@ Boxes; what RL code imports is a vector env with real spaces.  This class gives 
   described as float32 and handed out as float32 with output="numpy").  `info["final_obs*"]` stays the HWC terminal
   frame; the stacked view of a terminal step is not kept.  Without it the adapter is byte for byte what it was.
 
+* `history=dict(capacity=T, gray=False)` (opt-in, `ProcgenGymVectorEnv`): the engine keeps the last T frames of every env
+  (include/procgen2_vec.h pgv_history_enable); `.history` is the engine's HistoryTensors and `engine.history_gather()`
+  builds stacked rows for a minibatch.  Every return value stays as it is.
+
 The class only talks to an *engine* object with `reset(mask, seeds) -> obs`, `step(actions) -> (obs, reward, done)`,
 `close()`, `num_envs`; `ProcgenVecEnv` is the real one.  The CPU tests drive the same code with an oracle-backed
 stand-in, so the wrapper logic is covered without a GPU.
@@ -340,7 +344,7 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
 
     def __init__(self, game, num_envs, device=0, seed=1, env_offset=0, output="torch", num_levels=0, start_level=0,
                  distribution_mode=None, render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None,
-                 max_episode_steps=0, final_obs_capacity=0, policy_obs=None):
+                 max_episode_steps=0, final_obs_capacity=0, policy_obs=None, history=None):
         from .vec_env import ProcgenVecEnv
         if episodes not in (None, "device"):
             raise ValueError("episodes must be None or 'device'")
@@ -350,8 +354,11 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
                                             "final_obs_capacity": final_obs_capacity}
         if policy_obs is not None:
             more["policy_obs"] = policy_obs
+        if history is not None:
+            more["history"] = history
         super().__init__(ProcgenVecEnv(game, num_envs, device=device, seed_base=seed, env_offset=env_offset,
                                        num_levels=num_levels, start_level=start_level,
                                        distribution_mode=distribution_mode, **more), output=output, render_mode=render_mode,
                          render_size=render_size, autoreset_mode=autoreset_mode, episodes=episodes, policy_obs=policy_obs)
         self.game = game
+        self.history = self.engine.history

@@ -62,6 +62,17 @@ def policy_obs_enable(lib, h, stack=4, gray=True, dtype="float16", out=None):
     check(lib, lib.pgv_policy_obs_enable(h, ctypes.byref(cfg)), "pgv_policy_obs_enable")
 
 
+class HistoryConfig(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_history_config`."""
+    _fields_ = [("struct_size", c_uint32), ("capacity", c_int32), ("gray", c_int32), ("frames", c_void_p)]
+
+
+def history_enable(lib, h, capacity, gray=False, frames=None):
+    """pgv_history_enable.  frames: a device pointer (integer) or None for a ring of the engine's own (pgv_history_frames)."""
+    cfg = HistoryConfig(ctypes.sizeof(HistoryConfig), int(capacity), int(gray), frames)
+    check(lib, lib.pgv_history_enable(h, ctypes.byref(cfg)), "pgv_history_enable")
+
+
 # include/procgen2_vec.h PGV_FRAMES_*
 FRAMES = {"last": 0, "none": 1}
 
@@ -196,6 +207,14 @@ def load(path=None):
         "pgv_policy_obs_restart": (P, [P]),
         "pgv_policy_obs_push": (c_int32, [P, P]),
         "pgv_policy_obs_push_host": (c_int32, [P, P]),
+        "pgv_history_enable": (c_int32, [P, POINTER(HistoryConfig)]),
+        "pgv_history_frames": (P, [P]),
+        "pgv_history_began": (P, [P]),
+        "pgv_history_pending": (P, [P]),
+        "pgv_history_head": (c_int64, [P]),
+        "pgv_history_capacity": (c_int32, [P]),
+        "pgv_history_push": (c_int32, [P]),
+        "pgv_history_gather": (c_int32, [P, P, P, c_int32, c_int32, c_int32, P]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -229,6 +248,8 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_episodes_enable", "pgv_episode_outputs_get", "pgv_step_episodes", "pgv_step_episodes_synthetic", "pgv_step_episodes_host", "pgv_step_episodes_times",
     "pgv_step_sequence", "pgv_step_sequence_host", "pgv_render_obs", "pgv_render_obs_host",
     "pgv_policy_obs_enable", "pgv_policy_obs", "pgv_policy_obs_bytes_per_env", "pgv_policy_obs_restart", "pgv_policy_obs_push", "pgv_policy_obs_push_host",
+    "pgv_history_enable", "pgv_history_frames", "pgv_history_began", "pgv_history_pending", "pgv_history_head", "pgv_history_capacity", "pgv_history_push",
+    "pgv_history_gather",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_last_error",
 ]

@@ -31,8 +31,14 @@ def shard_range(total_envs, world_size, rank):
 class ProcgenVecEnv:
     def __init__(self, game, num_envs, device=0, seed_base=1, env_offset=0, lib_path=None, num_levels=0,
                  start_level=0, distribution_mode=None, game_flags=0, out=None, autoreset_mode=None, max_episode_steps=0,
-                 final_obs_capacity=0, policy_obs=None):
-        """policy_obs = None | dict(stack=4, gray=True, dtype="float16"): policy-ready observations on the device
+                 final_obs_capacity=0, policy_obs=None, history=None):
+        """history = None | dict(capacity=T, gray=False): frame history on the device (include/procgen2_vec.h
+        pgv_history_enable) — `history`, a HistoryTensors: `frames` u8 [T, N, C, 64, 64] (C = 1 gray, 3 RGB), one frame per env
+        and push in slot push % T, `began` u8 [T, N], `pending` u8 [N], `head` (the pushes so far) and `capacity`; every step,
+        step_episodes and drawn sequence pushes a slot, reset() rewrites the newest; history_push() by hand and
+        history_gather() for stacked, scaled rows of any (push, env) pairs.  None changes nothing at all.
+
+        policy_obs = None | dict(stack=4, gray=True, dtype="float16"): policy-ready observations on the device
         (include/procgen2_vec.h pgv_policy_obs_enable) — `policy_obs`, a [N, K*C, 64, 64] tensor of that dtype ("uint8",
         "float16", "bfloat16", "float32"; C = 1 gray, 3 RGB; slot 0 the oldest frame) that every step, reset and drawn
         sequence keeps current, stacks restarted where an episode began; `policy_restart`, the pending restart flags;
@@ -54,6 +60,7 @@ class ProcgenVecEnv:
         self.num_envs = int(num_envs)
         self.env_offset = int(env_offset)
         policy = _policy_obs_config(policy_obs)  # (ValueError before anything is made)
+        ring = _history_config(history)
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         # The engine gets a stream of its own (a torch stream, so torch can order against it): torch's default stream
@@ -120,6 +127,20 @@ class ProcgenVecEnv:
                 pglib.policy_obs_enable(self.L, h, stack, gray, dtype, c_void_p(self.policy_obs.data_ptr()))
                 self._after()
                 self.policy_restart = _device_view(self.L.pgv_policy_obs_restart(h), self.num_envs, "|u1", self.device)
+            except Exception:
+                self.close()
+                raise
+
+        self.history = None
+        if ring is not None:
+            # torch owns the ring, as it owns obs; the engine writes straight into it.
+            capacity, gray = ring
+            try:
+                frames = torch.zeros((capacity, self.num_envs, 1 if gray else 3, 64, 64), dtype=torch.uint8, device=self.device)
+                self._before()
+                pglib.history_enable(self.L, h, capacity, gray, c_void_p(frames.data_ptr()))
+                self._after()
+                self.history = HistoryTensors(self, frames)
             except Exception:
                 self.close()
                 raise
@@ -290,6 +311,50 @@ class ProcgenVecEnv:
         self._keep = (m,)
         return self.policy_obs
 
+    def _needs_history(self, who):
+        if self.history is None:
+            raise pglib.EngineError(who + " needs an env made with history=dict(capacity=T, ...)")
+
+    def history_push(self):
+        """Push the obs slab as it stands into a new slot of the frame history by hand (pgv_history_push), all envs — after
+        step_sequence(frames="none") and render_obs(), say; step(), step_episodes() and the drawn sequences push on their
+        own.  Returns the push number of the slot it wrote."""
+        self._needs_history("history_push")
+        self._before()
+        pglib.check(self.L, self.L.pgv_history_push(self._h), "pgv_history_push")
+        self._after()
+        return self.history.head - 1
+
+    def history_gather(self, pushes, envs, stack=4, dtype="float16", out=None):
+        """Rows [B, K*C, 64, 64] of `dtype` ("uint8", "float16", "bfloat16", "float32") for the B pairs (pushes[b], envs[b])
+        — int64 and int32 device tensors, or anything torch.as_tensor takes: row slot K-1 is the frame of that push, the
+        slots in front of it the env's frames before it, never across the start of an episode nor past the oldest push held
+        (pgv_history_gather).  A pair whose push is not held (head - T <= p < head) or whose env is outside the batch gives a
+        row of zeros.  out: a caller-owned contiguous tensor of that shape and dtype to write into (and return).  Same stream
+        hand-shake as step(), no host synchronisation."""
+        self._needs_history("history_gather")
+        if dtype not in pglib.POLICY_DTYPES:
+            raise ValueError("history_gather: dtype must be one of %s" % ", ".join(pglib.POLICY_DTYPES))
+        if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= 8:
+            raise ValueError("history_gather: stack must be an integer in 1 .. 8")
+        p = torch.as_tensor(pushes, device=self.device).to(torch.int64).reshape(-1).contiguous()
+        i = torch.as_tensor(envs, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        if p.numel() != i.numel():
+            raise ValueError("history_gather: %d pushes but %d envs" % (p.numel(), i.numel()))
+        shape = (p.numel(), stack * self.history.frames.shape[2], 64, 64)
+        tdtype = getattr(torch, dtype)
+        if out is None:
+            out = torch.empty(shape, dtype=tdtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != tdtype or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out: expected a contiguous %s tensor of shape %s on %s" % (tdtype, shape, self.device))
+        if p.numel():
+            self._before()
+            pglib.check(self.L, self.L.pgv_history_gather(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
+                                                          pglib.POLICY_DTYPES[dtype][0], c_void_p(out.data_ptr())), "pgv_history_gather")
+            self._after()
+            self._keep_gather = (p, i, out)
+        return out
+
     def _before(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
 
@@ -371,7 +436,7 @@ class ProcgenVecEnv:
         import numpy as np
         buf = np.ascontiguousarray(buf, np.uint8)
         pglib.check(self.L, self.L.pgv_load_state(self._h, c_void_p(buf.ctypes.data), buf.size), "pgv_load_state")
-        if self.policy_obs is not None:  # (the restart flags the load sets on the engine's stream, ordered for the caller)
+        if self.policy_obs is not None or self.history is not None:  # (the flags the load sets on the engine's stream, ordered for the caller)
             self._after()
 
     # -- per-env records (include/procgen2_vec.h pgv_save_envs / pgv_load_envs) -------------------
@@ -512,6 +577,44 @@ class ProcgenVecEnv:
                 self._gathers = {}
             plan = self._gathers[key] = RootGather((self.obs, self.reward, self.done), dst=dst, group=group)
         return plan()
+
+
+class HistoryTensors:
+    """The frame history of a ProcgenVecEnv made with history=dict(...): zero-copy tensors over the ring and its flags."""
+
+    def __init__(self, env, frames=None, gray=False):
+        """frames: the tensor the engine was given, or None for a view of the engine's own ring (of 1 plane if `gray`)."""
+        L, h, n = env.L, env._h, env.num_envs
+        self._env = env
+        self.capacity = int(L.pgv_history_capacity(h))
+        if frames is None:
+            shape = (self.capacity, n, 1 if gray else 3, 64, 64)
+            frames = _device_view(L.pgv_history_frames(h), shape[0] * n * shape[2] * 4096, "|u1", env.device).view(shape)
+        self.frames = frames  # u8 [T, N, C, 64, 64]
+        self.began = _device_view(L.pgv_history_began(h), self.capacity * n, "|u1", env.device).view(self.capacity, n)
+        self.pending = _device_view(L.pgv_history_pending(h), n, "|u1", env.device)
+
+    @property
+    def head(self):
+        """The pushes so far: push p is held while head - capacity <= p < head."""
+        return int(self._env.L.pgv_history_head(self._env._h))
+
+
+def _history_config(history):
+    """(capacity, gray) of ProcgenVecEnv's history= argument, or None; ValueError for anything else."""
+    if history is None:
+        return None
+    if not isinstance(history, dict):
+        raise ValueError("history must be None or a dict with the keys capacity, gray")
+    unknown = set(history) - {"capacity", "gray"}
+    if unknown:
+        raise ValueError("history: unknown key(s) %s" % ", ".join(sorted(unknown)))
+    capacity, gray = history.get("capacity"), history.get("gray", False)
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
+        raise ValueError("history: capacity must be an integer >= 1")
+    if gray not in (True, False, 0, 1):
+        raise ValueError("history: gray must be True or False")
+    return capacity, bool(gray)
 
 
 def _policy_obs_config(policy_obs):
