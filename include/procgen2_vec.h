@@ -476,6 +476,61 @@ PGV_API int32_t pgv_history_push(pgv_env* env);           /* by hand: all envs, 
 PGV_API int32_t pgv_history_gather(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack,
                                    int32_t dtype /* PGV_POLICY_* */, void* d_out);
 
+/* Augmented gathers: pgv_history_gather with a random shift or crop (RAD, DrAC, DrQ's pad-and-shift) and a cutout (RAD's
+ * cutout and cutout-color) worked into the same pass — on the stored u8 bytes, in front of the value rule, so the result is
+ * exact and can be held bit for bit to a model.  The gather reads the stored bytes once and writes the row once either way:
+ * a window only changes which stored byte an element reads, a cutout replaces some bytes.
+ *
+ *   1. Output.  `count` rows of [K*C][H'][W'] elements of `dtype`, contiguous, H' = out_height, W' = out_width; slot K-1 the
+ *      newest frame.  The frames f_0 .. f_(K-1) of an entry are those of point 6 of the frame history: the same walk, the
+ *      same began bytes, "held" judged by head at the call.
+ *   2. The draws of entry e (its position in the call), all arithmetic uint32 and wrapping, mix32 the engine's hash
+ *      (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16):
+ *          word(j)   = mix32( mix32(seed + 0x9E3779B9*(e+1)) ^ (j*0x85EBCA6B + 0xC2B2AE35) )
+ *          draw(m,j) = (uint64(word(j)) * m) >> 32                                  (pgv_synthetic_action's rule)
+ *          oy = -pad + draw(64 + 2*pad - H' + 1, 0)      ox = -pad + draw(64 + 2*pad - W' + 1, 1)
+ *      and with cutout_max > 0
+ *          ch = min(H', cutout_min + draw(max-min+1, 2))    cw = min(W', cutout_min + draw(max-min+1, 3))
+ *          cy = draw(H' - ch + 1, 4)    cx = draw(W' - cw + 1, 5)    colour = word(6), 0 with PGV_AUG_CUTOUT_BLACK;
+ *      without, ch = cw = cy = cx = colour = 0.  Plane c of an RGB ring uses byte c of colour, the gray plane byte 0.  They
+ *      are a function of (aug, e) and of nothing else: not of count, of the other entries, or of whether the entry is held.
+ *   3. The element at (slot s, plane c, y, x): where cy <= y < cy+ch and cx <= x < cx+cw the byte is the plane's colour byte;
+ *      else, with sy = oy+y and sx = ox+x both in 0 .. 63, the stored byte of frame f_(K-1-s), plane c, at (sy, sx); outside
+ *      the frame that byte at the coordinates clamped to 0 .. 63 (PGV_AUG_EDGE_REPLICATE) or byte 0 (PGV_AUG_EDGE_ZERO).  The
+ *      element is the policy observations' value of that byte.  One window and one rectangle per entry, shared by its K
+ *      frames and all planes.  An entry that is not held, or whose env is outside the batch, gives a row of zero bytes,
+ *      cutout or not.
+ *   4. `params`, where not NULL, receives {oy, ox, cy, cx, ch, cw, colour & 0xFFFFFF, 0} per entry, held or not; on a gray
+ *      ring the seventh word is colour & 0xFF, the one byte it used.  pgv_gather_aug_params gives the same row on the host,
+ *      in the RGB form (it knows no ring).
+ *   5. Laws.  With H' = W' = 64, pad = 0 and cutout_max = 0 the output equals pgv_history_gather's bit for bit, for any seed
+ *      and edge.  The call changes nothing — ring, began bytes, pending flags, head, engine state — and a second call gives
+ *      the same bytes.
+ *   6. Checked on the host before anything is enqueued, each refusal leaving a message and the engine as it was: everything
+ *      pgv_history_gather refuses; aug NULL or its struct_size too small; H' outside 1 .. 64; W' outside 8 .. 64 or no
+ *      multiple of 8; pad outside 0 .. 16; an unknown edge or colour mode; cutout sides outside 0 .. 64, min > max, min = 0
+ *      with max > 0; d_out not 16-byte aligned; params not 4-byte aligned.  count = 0 succeeds and does nothing.  The call
+ *      is enqueued on the env's stream, allocates nothing and does not synchronise.  pgv_gather_aug_params makes the same
+ *      checks of `aug` and refuses entry < 0. */
+#define PGV_AUG_EDGE_REPLICATE 0 /* a source pixel outside the frame is the nearest pixel of the frame (DrQ's replicate pad) */
+#define PGV_AUG_EDGE_ZERO 1      /* ... is byte 0 */
+#define PGV_AUG_CUTOUT_BLACK 0   /* the rectangle is byte 0 in every plane (RAD cutout) */
+#define PGV_AUG_CUTOUT_RANDOM 1  /* one drawn byte per plane (RAD cutout-color) */
+typedef struct pgv_gather_aug {
+    uint32_t struct_size;
+    int32_t out_height, out_width;  /* H' in 1 .. 64; W' in 8 .. 64 and a multiple of 8 */
+    int32_t pad;                    /* 0 .. 16: how far the window may hang over each edge of the frame */
+    int32_t edge;                   /* PGV_AUG_EDGE_* */
+    int32_t cutout_min, cutout_max; /* side lengths; max = 0 (then min = 0): no cutout; else 1 <= min <= max <= 64 */
+    int32_t cutout_color;           /* PGV_AUG_CUTOUT_* */
+    uint32_t seed;
+    int32_t* params;                /* device int32 [count][8] or NULL: what was drawn for each entry */
+} pgv_gather_aug;
+PGV_API int32_t pgv_history_gather_aug(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count,
+                                       int32_t stack, int32_t dtype, const pgv_gather_aug* aug, void* d_out);
+/* The draws of entry `entry` under `aug` (host, pure, no GPU, env not needed): h_params8[0..7] as `params` rows are. */
+PGV_API int32_t pgv_gather_aug_params(const pgv_gather_aug* aug, int32_t entry, int32_t* h_params8);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

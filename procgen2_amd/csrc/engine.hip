@@ -16,6 +16,7 @@
 #include "pg_episodes.h"
 #include "pg_order.h"
 #include "pg_history.h"
+#include "pg_history_aug.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
 #include "pg_sequence.h"
@@ -1123,6 +1124,54 @@ int32_t pgv_history_gather(pgv_env* e, const int64_t* d_pushes, const int32_t* d
     q.out = static_cast<uint8_t*>(d_out);
     q.b = e->hist;
     pg::launch_history_gather(e->stream, q, pg::policy_element_bytes(dtype));
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// What both augmented calls check of `aug`, the same way; `who` heads the message.
+static int32_t gather_aug_config(const char* who, const pgv_gather_aug* aug, pg::AugConfig& cfg) {
+    if (!aug || aug->struct_size < sizeof(pgv_gather_aug)) return fail(std::string(who) + ": aug is NULL or struct_size too small");
+    cfg = pg::AugConfig{aug->out_height, aug->out_width, aug->pad, aug->edge, aug->cutout_min, aug->cutout_max, aug->cutout_color, aug->seed};
+    if (const char* why = pg::aug_config_error(cfg)) return fail(std::string(who) + ": " + why);
+    if (reinterpret_cast<uintptr_t>(aug->params) & 3u) return fail(std::string(who) + ": params must be 4-byte aligned");
+    return 0;
+}
+
+int32_t pgv_gather_aug_params(const pgv_gather_aug* aug, int32_t entry, int32_t* h_params8) {
+    pg::AugConfig cfg{};
+    if (gather_aug_config("pgv_gather_aug_params", aug, cfg)) return 1;
+    if (entry < 0) return fail("pgv_gather_aug_params: entry is negative");
+    if (!h_params8) return fail("pgv_gather_aug_params: params8 is NULL");
+    pg::aug_params_row(pg::aug_params(cfg, static_cast<uint32_t>(entry)), 3, h_params8);
+    return 0;
+}
+
+int32_t pgv_history_gather_aug(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype,
+                               const pgv_gather_aug* aug, void* d_out) {
+    if (!e) return fail("pgv_history_gather_aug: env is NULL");
+    if (!e->history) return fail("pgv_history_gather_aug: call pgv_history_enable first");
+    if (stack < 1 || stack > pg::kPolicyMaxStack) return fail("pgv_history_gather_aug: stack must be in 1 .. 8");
+    if (dtype != PGV_POLICY_U8 && dtype != PGV_POLICY_F16 && dtype != PGV_POLICY_BF16 && dtype != PGV_POLICY_F32)
+        return fail("pgv_history_gather_aug: unknown dtype " + std::to_string(dtype));
+    if (count < 0) return fail("pgv_history_gather_aug: count is negative");
+    pg::HistoryGatherAug q{};
+    if (gather_aug_config("pgv_history_gather_aug", aug, q.cfg)) return 1;
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail("pgv_history_gather_aug: out must be 16-byte aligned");
+    if (count == 0) return 0;
+    if (!d_pushes || !d_envs || !d_out) return fail("pgv_history_gather_aug: pushes, envs or out is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    q.g.n = e->n;
+    q.g.stack = stack;
+    q.g.count = count;
+    q.g.head = e->history_head;
+    q.g.pushes = d_pushes;
+    q.g.envs = d_envs;
+    q.g.table = e->hist.table + dtype * 256;
+    q.g.out = static_cast<uint8_t*>(d_out);
+    q.g.b = e->hist;
+    q.params = aug->params;
+    pg::launch_history_gather_aug(e->stream, q, pg::policy_element_bytes(dtype));
     PG_HIP(hipGetLastError());
     return 0;
 }

@@ -73,6 +73,24 @@ def history_enable(lib, h, capacity, gray=False, frames=None):
     check(lib, lib.pgv_history_enable(h, ctypes.byref(cfg)), "pgv_history_enable")
 
 
+class GatherAug(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_gather_aug`."""
+    _fields_ = [("struct_size", c_uint32), ("out_height", c_int32), ("out_width", c_int32), ("pad", c_int32), ("edge", c_int32),
+                ("cutout_min", c_int32), ("cutout_max", c_int32), ("cutout_color", c_int32), ("seed", c_uint32), ("params", c_void_p)]
+
+
+# include/procgen2_vec.h PGV_AUG_EDGE_*, PGV_AUG_CUTOUT_*
+AUG_EDGES = {"replicate": 0, "zero": 1}
+AUG_CUTOUT_COLORS = {"black": 0, "random": 1}
+
+
+def gather_aug(out_height, out_width, pad=0, edge="replicate", cutout_min=0, cutout_max=0, cutout_color="black", seed=0, params=None):
+    """A filled-in GatherAug.  edge, cutout_color: a name or the number; params: a device pointer (integer) or None."""
+    return GatherAug(ctypes.sizeof(GatherAug), int(out_height), int(out_width), int(pad), AUG_EDGES[edge] if edge in AUG_EDGES else int(edge),
+                     int(cutout_min), int(cutout_max), AUG_CUTOUT_COLORS[cutout_color] if cutout_color in AUG_CUTOUT_COLORS else int(cutout_color),
+                     int(seed) & 0xFFFFFFFF, params)
+
+
 # include/procgen2_vec.h PGV_FRAMES_*
 FRAMES = {"last": 0, "none": 1}
 
@@ -215,6 +233,8 @@ def load(path=None):
         "pgv_history_capacity": (c_int32, [P]),
         "pgv_history_push": (c_int32, [P]),
         "pgv_history_gather": (c_int32, [P, P, P, c_int32, c_int32, c_int32, P]),
+        "pgv_history_gather_aug": (c_int32, [P, P, P, c_int32, c_int32, c_int32, POINTER(GatherAug), P]),
+        "pgv_gather_aug_params": (c_int32, [POINTER(GatherAug), c_int32, POINTER(c_int32)]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -249,7 +269,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_step_sequence", "pgv_step_sequence_host", "pgv_render_obs", "pgv_render_obs_host",
     "pgv_policy_obs_enable", "pgv_policy_obs", "pgv_policy_obs_bytes_per_env", "pgv_policy_obs_restart", "pgv_policy_obs_push", "pgv_policy_obs_push_host",
     "pgv_history_enable", "pgv_history_frames", "pgv_history_began", "pgv_history_pending", "pgv_history_head", "pgv_history_capacity", "pgv_history_push",
-    "pgv_history_gather",
+    "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_last_error",
 ]

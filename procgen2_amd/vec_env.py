@@ -325,13 +325,23 @@ class ProcgenVecEnv:
         self._after()
         return self.history.head - 1
 
-    def history_gather(self, pushes, envs, stack=4, dtype="float16", out=None):
+    def history_gather(self, pushes, envs, stack=4, dtype="float16", out=None, augment=None, return_params=False):
         """Rows [B, K*C, 64, 64] of `dtype` ("uint8", "float16", "bfloat16", "float32") for the B pairs (pushes[b], envs[b])
         — int64 and int32 device tensors, or anything torch.as_tensor takes: row slot K-1 is the frame of that push, the
         slots in front of it the env's frames before it, never across the start of an episode nor past the oldest push held
         (pgv_history_gather).  A pair whose push is not held (head - T <= p < head) or whose env is outside the batch gives a
         row of zeros.  out: a caller-owned contiguous tensor of that shape and dtype to write into (and return).  Same stream
-        hand-shake as step(), no host synchronisation."""
+        hand-shake as step(), no host synchronisation.
+
+        augment = None | dict(size=int | (H, W), pad=0, edge="replicate" | "zero", cutout=None | (lo, hi),
+        cutout_color="black" | "random", seed=int): the rows through a random window and a cutout, drawn per row from `seed`
+        and the row's position, on the stored bytes (pgv_history_gather_aug): [B, K*C, H', W'].  size: H' in 1 .. 64, W' in
+        8 .. 64 and a multiple of 8; pad 0 .. 16: how far a window may hang over the frame, where `edge` fills in; cutout:
+        the range of the rectangle's sides, 1 <= lo <= hi <= 64.  seed is required: the same seed gives the same rows.
+        return_params=True: (rows, params int32 [B, 8]) — oy, ox, cy, cx, ch, cw, colour, 0 of every row."""
+        aug = None if augment is None else _augment_config(augment)
+        if return_params and aug is None:
+            raise ValueError("history_gather: return_params needs augment=dict(...)")
         self._needs_history("history_gather")
         if dtype not in pglib.POLICY_DTYPES:
             raise ValueError("history_gather: dtype must be one of %s" % ", ".join(pglib.POLICY_DTYPES))
@@ -341,19 +351,26 @@ class ProcgenVecEnv:
         i = torch.as_tensor(envs, device=self.device).to(torch.int32).reshape(-1).contiguous()
         if p.numel() != i.numel():
             raise ValueError("history_gather: %d pushes but %d envs" % (p.numel(), i.numel()))
-        shape = (p.numel(), stack * self.history.frames.shape[2], 64, 64)
+        shape = (p.numel(), stack * self.history.frames.shape[2]) + ((64, 64) if aug is None else (aug.out_height, aug.out_width))
         tdtype = getattr(torch, dtype)
         if out is None:
             out = torch.empty(shape, dtype=tdtype, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != tdtype or out.device != self.device or not out.is_contiguous():
             raise ValueError("out: expected a contiguous %s tensor of shape %s on %s" % (tdtype, shape, self.device))
+        params = torch.empty((p.numel(), 8), dtype=torch.int32, device=self.device) if return_params else None
         if p.numel():
             self._before()
-            pglib.check(self.L, self.L.pgv_history_gather(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
-                                                          pglib.POLICY_DTYPES[dtype][0], c_void_p(out.data_ptr())), "pgv_history_gather")
+            if aug is None:
+                pglib.check(self.L, self.L.pgv_history_gather(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
+                                                              pglib.POLICY_DTYPES[dtype][0], c_void_p(out.data_ptr())), "pgv_history_gather")
+            else:
+                aug.params = params.data_ptr() if return_params else None
+                pglib.check(self.L, self.L.pgv_history_gather_aug(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
+                                                                  pglib.POLICY_DTYPES[dtype][0], ctypes.byref(aug), c_void_p(out.data_ptr())),
+                            "pgv_history_gather_aug")
             self._after()
-            self._keep_gather = (p, i, out)
-        return out
+            self._keep_gather = (p, i, out, params)
+        return (out, params) if return_params else out
 
     def _before(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -598,6 +615,52 @@ class HistoryTensors:
     def head(self):
         """The pushes so far: push p is held while head - capacity <= p < head."""
         return int(self._env.L.pgv_history_head(self._env._h))
+
+
+def _augment_config(augment):
+    """The pglib.GatherAug of history_gather's augment= dict; ValueError for anything the engine would refuse, and for more:
+    keys it does not know, a missing seed, values of the wrong type."""
+    def integer(x):
+        return isinstance(x, int) and not isinstance(x, bool)
+
+    if not isinstance(augment, dict):
+        raise ValueError("augment must be None or a dict with the keys size, pad, edge, cutout, cutout_color, seed")
+    unknown = set(augment) - {"size", "pad", "edge", "cutout", "cutout_color", "seed"}
+    if unknown:
+        raise ValueError("augment: unknown key(s) %s" % ", ".join(sorted(unknown)))
+    if "size" not in augment or "seed" not in augment:
+        raise ValueError("augment: size and seed are required")
+    size = augment["size"]
+    if integer(size):
+        size = (size, size)
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(integer(x) for x in size):
+        raise ValueError("augment: size must be an integer or a pair (H, W) of integers")
+    height, width = size
+    if not 1 <= height <= 64:
+        raise ValueError("augment: the height must be in 1 .. 64")
+    if not 8 <= width <= 64 or width % 8:
+        raise ValueError("augment: the width must be in 8 .. 64 and a multiple of 8")
+    pad = augment.get("pad", 0)
+    if not integer(pad) or not 0 <= pad <= 16:
+        raise ValueError("augment: pad must be an integer in 0 .. 16")
+    edge = augment.get("edge", "replicate")
+    if not isinstance(edge, str) or edge not in pglib.AUG_EDGES:
+        raise ValueError("augment: edge must be one of %s" % ", ".join(pglib.AUG_EDGES))
+    cutout = augment.get("cutout")
+    lo = hi = 0
+    if cutout is not None:
+        if not isinstance(cutout, (tuple, list)) or len(cutout) != 2 or not all(integer(x) for x in cutout):
+            raise ValueError("augment: cutout must be None or a pair (lo, hi) of integers")
+        lo, hi = cutout
+        if not 1 <= lo <= hi <= 64:
+            raise ValueError("augment: cutout needs 1 <= lo <= hi <= 64")
+    color = augment.get("cutout_color", "black")
+    if not isinstance(color, str) or color not in pglib.AUG_CUTOUT_COLORS:
+        raise ValueError("augment: cutout_color must be one of %s" % ", ".join(pglib.AUG_CUTOUT_COLORS))
+    seed = augment["seed"]
+    if not integer(seed) or not 0 <= seed <= 0xFFFFFFFF:
+        raise ValueError("augment: seed must be an integer in 0 .. 2^32 - 1")
+    return pglib.gather_aug(height, width, pad, edge, lo, hi, color, seed)
 
 
 def _history_config(history):
