@@ -280,14 +280,14 @@ struct pgv_env {
     void* d_policy = nullptr;
     uint8_t* d_policy_out = nullptr;
     pg::PolicyObsBuffers pol{};
-    uint32_t policy_table[256] = {};  // (the upload's source: lives as long as the env)
     // frame history (pg_history.h; pgv_history_enable): off unless asked for.  One device block holds the pending flags, the
     // began bytes, the value tables and — unless the caller brought them — the frames.  `history_head` counts the pushes.
     bool history = false;
     int64_t history_head = 0;
     void* d_history = nullptr;
     pg::HistoryBuffers hist{};
-    uint32_t history_table[pg::kHistoryTables * 256] = {};  // (the upload's source: lives as long as the env)
+    // both features' value tables, dtype by dtype (pg_planes.h): the uploads' source, so they live as long as the env
+    uint32_t value_tables[pg::kPolicyTables][256];  // (filled where the env is made)
 
     pg::StepIO io() const { return {d_obs, d_reward, d_done, d_pending}; }
     // The per-env output rows, in the order a snapshot holds them behind the state blob.  Separate allocations:
@@ -490,6 +490,8 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     e->game = variant->make();
     e->mode = variant->mode;
     e->game_flags = cfg->game_flags;
+    for (int dtype = 0; dtype < pg::kPolicyTables; dtype++)
+        for (uint32_t v = 0; v < 256; v++) e->value_tables[dtype][v] = pg::policy_table_entry(dtype, v);
     if (!e->game->set_game_flags(cfg->game_flags))
         return fail(std::string("pgv_make: game '") + game + "' does not take game_flags " + std::to_string(cfg->game_flags));
     if (stream) {
@@ -555,15 +557,21 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
 // anything: a slab the push kernels' 16-byte loads can read (pgv_bind_outputs may have moved it).  A refusal leaves the
 // engine as it was — no step taken, no flag set, the step counter and the ring's head where they stood.  An engine with
 // neither feature passes.
-static int32_t policy_ready(const char* who, const pgv_env* e) {
+static int32_t slab_ready(const char* who, const pgv_env* e) {
     if ((e->policy || e->history) && (reinterpret_cast<uintptr_t>(e->d_obs) & 15u))
         return fail(std::string(who) + ": the observation buffer must be 16-byte aligned for the " +
                     (e->policy ? "policy observations" : "frame history"));
     return 0;
 }
 
+// The flag array of every enabled feature — the policy observations' restart flags, then the frame history's pending flags;
+// nullptr for one that is off: the stacks and the ring begin afresh at the same events, told by the same flag kernels.
+static std::array<uint8_t*, 2> flag_arrays(const pgv_env* e) {
+    return {{e->policy ? e->pol.restart : nullptr, e->history ? e->hist.pending : nullptr}};
+}
+
 // A push of the policy observations (pg_policy_obs.h) on the env's stream, for the calls that end with one: the obs slab as
-// it stands there.  Its callers have asked policy_ready() first.
+// it stands there.  Its callers have asked slab_ready() first.
 static int32_t policy_push(const char* who, pgv_env* e, const uint8_t* d_mask) {
     pg::PolicyPush q{};
     q.n = e->n;
@@ -581,7 +589,7 @@ static int32_t policy_push(const char* who, pgv_env* e, const uint8_t* d_mask) {
 
 // A push of the frame history (pg_history.h) on the env's stream: the obs slab as it stands there into a new slot, all envs
 // — or, for pgv_reset (`reset`), into the newest slot under the mask (slot 0, opened, where there is none yet).  Its callers
-// have asked policy_ready() first.
+// have asked slab_ready() first.
 static int32_t history_push(pgv_env* e, bool reset, const uint8_t* d_mask) {
     const bool open = !reset || e->history_head == 0;
     pg::HistoryPush q{};
@@ -606,7 +614,7 @@ static int32_t end_with_pushes(const char* who, pgv_env* e) {
 
 int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     if (!e) return fail("pgv_reset: env is NULL");
-    if (policy_ready("pgv_reset", e)) return 1;
+    if (slab_ready("pgv_reset", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     e->game->launch_reset(e->stream, d_mask, d_seeds, e->io());
     e->game->launch_prepass(e->stream, d_mask);
@@ -615,7 +623,7 @@ int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     pregen(e, true, true);
     PG_HIP(hipGetLastError());
     if (e->policy) {  // the named envs' stacks restart with the frame just drawn
-        pg::launch_policy_flag_mask(e->stream, e->pol, e->n, d_mask);
+        pg::launch_policy_flag_mask(e->stream, e->pol.restart, e->n, d_mask);
         if (policy_push("pgv_reset", e, d_mask)) return 1;
     }
     if (e->history) return history_push(e, true, d_mask);  // … and their rows of the newest slot are that frame, began = 1
@@ -636,9 +644,9 @@ static int32_t step_impl(pgv_env* e, const int32_t* d_actions, uint32_t run_seed
     // hipGetLastError is sticky and per thread: whatever the embedding application left behind (a stream query's
     // NotReady, say) is not this step's; start clean.
     (void)hipGetLastError();
-    // (policy observations: the done row as this step finds it — in front of the fork, so no reset kernel is at the row yet)
-    if (e->policy) pg::launch_policy_flag_done(e->stream, e->pol, e->n, e->d_done);
-    if (e->history) pg::launch_policy_flag_done(e->stream, pg::history_flags(e->hist), e->n, e->d_done);
+    // (policy observations, frame history: the done row as this step finds it — in front of the fork, so no reset kernel is at the row yet)
+    for (uint8_t* flags : flag_arrays(e))
+        if (flags) pg::launch_policy_flag_done(e->stream, flags, e->n, e->d_done);
     const bool forked = e->reset_stream != nullptr;
     if (forked) {  // fork: the auto-resets of this step go beside its logic and render kernels
         PG_HIP(hipEventRecord(e->reset_fork, e->stream));
@@ -692,7 +700,7 @@ static int32_t step_no_frame(pgv_env* e, const int32_t* d_actions, uint32_t run_
 int32_t pgv_step(pgv_env* e, const int32_t* d_actions) {
     if (!e) return fail("pgv_step: env is NULL");
     if (!d_actions) return fail("pgv_step: actions is NULL");
-    if (policy_ready("pgv_step", e)) return 1;
+    if (slab_ready("pgv_step", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (step_impl(e, d_actions, 0)) return 1;
     return end_with_pushes("pgv_step", e);
@@ -700,7 +708,7 @@ int32_t pgv_step(pgv_env* e, const int32_t* d_actions) {
 
 int32_t pgv_step_synthetic(pgv_env* e, uint32_t run_seed) {
     if (!e) return fail("pgv_step_synthetic: env is NULL");
-    if (policy_ready("pgv_step_synthetic", e)) return 1;
+    if (slab_ready("pgv_step_synthetic", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (step_impl(e, nullptr, run_seed)) return 1;
     return end_with_pushes("pgv_step_synthetic", e);
@@ -729,7 +737,7 @@ static int32_t ensure_staging(pgv_env* e) {
 int32_t pgv_step_host(pgv_env* e, const int32_t* h_actions) {
     if (!e) return fail("pgv_step_host: env is NULL");
     if (!h_actions) return fail("pgv_step_host: actions is NULL");
-    if (policy_ready("pgv_step_host", e)) return 1;
+    if (slab_ready("pgv_step_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (ensure_staging(e)) return 1;
     PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
@@ -739,7 +747,7 @@ int32_t pgv_step_host(pgv_env* e, const int32_t* h_actions) {
 
 int32_t pgv_reset_host(pgv_env* e, const uint8_t* h_mask, const int32_t* h_seeds) {
     if (!e) return fail("pgv_reset_host: env is NULL");
-    if (policy_ready("pgv_reset_host", e)) return 1;
+    if (slab_ready("pgv_reset_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (ensure_staging(e)) return 1;
     if (h_mask) PG_HIP(hipMemcpyAsync(e->d_host_u8, h_mask, size_t(e->n), hipMemcpyHostToDevice, e->stream));
@@ -833,15 +841,16 @@ static int32_t step_episodes_impl(const char* who, pgv_env* e, const int32_t* d_
         e->game->launch_reset(e->stream, b.ended, nullptr, e->io());
         e->game->launch_prepass(e->stream, b.ended);
         e->game->launch_render(e->stream, b.ended, e->io());
-        if (e->policy) pg::launch_policy_flag_mask(e->stream, e->pol, e->n, b.ended);  // their stacks restart with the new first frame
-        if (e->history) pg::launch_policy_flag_mask(e->stream, pg::history_flags(e->hist), e->n, b.ended);
+        // their stacks restart, and their history begins afresh, with the new first frame
+        for (uint8_t* flags : flag_arrays(e))
+            if (flags) pg::launch_policy_flag_mask(e->stream, flags, e->n, b.ended);
         PG_HIP(hipGetLastError());
     }
     return 0;
 }
 // … and, for the entry points that are not measurements, the push behind everything.
 static int32_t step_episodes_push(const char* who, pgv_env* e, const int32_t* d_actions, uint32_t run_seed) {
-    if (policy_ready(who, e)) return 1;
+    if (slab_ready(who, e)) return 1;
     if (step_episodes_impl(who, e, d_actions, run_seed)) return 1;
     return end_with_pushes(who, e);
 }
@@ -863,7 +872,7 @@ int32_t pgv_step_episodes_host(pgv_env* e, const int32_t* h_actions) {
     if (!e) return fail("pgv_step_episodes_host: env is NULL");
     if (!h_actions) return fail("pgv_step_episodes_host: actions is NULL");
     if (!e->episodes) return fail("pgv_step_episodes_host: call pgv_episodes_enable first");
-    if (policy_ready("pgv_step_episodes_host", e)) return 1;
+    if (slab_ready("pgv_step_episodes_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (ensure_staging(e)) return 1;
     PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
@@ -887,7 +896,7 @@ static int32_t sequence_arguments(const char* who, pgv_env* e, const pgv_sequenc
 int32_t pgv_step_sequence(pgv_env* e, const pgv_sequence* q) {
     if (sequence_arguments("pgv_step_sequence", e, q)) return 1;
     if (q->steps == 0) return 0;
-    if (q->frames == PGV_FRAMES_LAST && policy_ready("pgv_step_sequence", e)) return 1;
+    if (q->frames == PGV_FRAMES_LAST && slab_ready("pgv_step_sequence", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     pg::SequenceRow row{};
     row.n = e->n;
@@ -919,7 +928,7 @@ int32_t pgv_step_sequence(pgv_env* e, const pgv_sequence* q) {
 int32_t pgv_step_sequence_host(pgv_env* e, const pgv_sequence* q) {
     if (sequence_arguments("pgv_step_sequence_host", e, q)) return 1;
     if (q->steps == 0) return 0;
-    if (q->frames == PGV_FRAMES_LAST && policy_ready("pgv_step_sequence_host", e)) return 1;
+    if (q->frames == PGV_FRAMES_LAST && slab_ready("pgv_step_sequence_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     const size_t n = size_t(e->n), rows = size_t(q->steps) * n;
     pg::Staged dev{e->stream};
@@ -982,13 +991,11 @@ int32_t pgv_policy_obs_enable(pgv_env* e, const pgv_policy_obs_config* cfg) {
     if (e->policy) return fail("pgv_policy_obs_enable: policy observations are enabled already (once per env)");
     if (cfg->stack < 1 || cfg->stack > pg::kPolicyMaxStack) return fail("pgv_policy_obs_enable: stack must be in 1 .. 8");
     if (cfg->gray != 0 && cfg->gray != 1) return fail("pgv_policy_obs_enable: gray must be 0 or 1");
-    if (cfg->dtype != PGV_POLICY_U8 && cfg->dtype != PGV_POLICY_F16 && cfg->dtype != PGV_POLICY_BF16 && cfg->dtype != PGV_POLICY_F32)
-        return fail("pgv_policy_obs_enable: unknown dtype " + std::to_string(cfg->dtype));
+    if (!pg::policy_dtype_known(cfg->dtype)) return fail("pgv_policy_obs_enable: unknown dtype " + std::to_string(cfg->dtype));
     if (reinterpret_cast<uintptr_t>(cfg->out) & 15u) return fail("pgv_policy_obs_enable: out must be 16-byte aligned");
     PG_HIP(hipSetDevice(e->device));
     const int planes = cfg->gray ? 1 : 3, es = pg::policy_element_bytes(cfg->dtype);
     const size_t out_bytes = size_t(e->n) * pg::policy_bytes_per_env(cfg->stack, planes, es);
-    for (uint32_t v = 0; v < 256; v++) e->policy_table[v] = pg::policy_table_entry(cfg->dtype, v);
     void* mem = nullptr;
     void* out = cfg->out;
     pg::PolicyObsBuffers b{};
@@ -999,7 +1006,7 @@ int32_t pgv_policy_obs_enable(pgv_env* e, const pgv_policy_obs_config* cfg) {
         pg::Carve::bind(pg::list_policy_obs, mem, b, e->n);
         err = hipMemsetAsync(b.restart, 1, size_t(e->n), e->stream);  // the first push fills every stack
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->policy_table, sizeof(e->policy_table), hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->value_tables[cfg->dtype], sizeof(e->value_tables[0]), hipMemcpyHostToDevice, e->stream);
     if (err != hipSuccess) {
         (void)hipStreamSynchronize(e->stream);
         if (mem) (void)hipFree(mem);
@@ -1027,7 +1034,7 @@ int32_t pgv_policy_obs_push(pgv_env* e, const uint8_t* d_mask) {
     if (!e) return fail("pgv_policy_obs_push: env is NULL");
     if (!e->policy) return fail("pgv_policy_obs_push: call pgv_policy_obs_enable first");
     PG_HIP(hipSetDevice(e->device));
-    if (policy_ready("pgv_policy_obs_push", e)) return 1;
+    if (slab_ready("pgv_policy_obs_push", e)) return 1;
     (void)hipGetLastError();
     return policy_push("pgv_policy_obs_push", e, d_mask);
 }
@@ -1061,8 +1068,6 @@ int32_t pgv_history_enable(pgv_env* e, const pgv_history_config* cfg) {
     b.capacity = cfg->capacity;
     b.planes = cfg->gray ? 1 : 3;
     b.own_frames = cfg->frames ? 0 : 1;
-    for (int dtype = 0; dtype < pg::kHistoryTables; dtype++)
-        for (uint32_t v = 0; v < 256; v++) e->history_table[dtype * 256 + v] = pg::policy_table_entry(dtype, v);
     const size_t bytes = pg::Carve::size(pg::list_history, e->n, b);
     void* mem = nullptr;
     hipError_t err = hipMalloc(&mem, bytes);
@@ -1071,7 +1076,7 @@ int32_t pgv_history_enable(pgv_env* e, const pgv_history_config* cfg) {
         err = hipMemsetAsync(mem, 0, bytes, e->stream);  // began, and the engine's own frames
     }
     if (err == hipSuccess) err = hipMemsetAsync(b.pending, 1, size_t(e->n), e->stream);  // every env's first frame begins its history
-    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->history_table, sizeof(e->history_table), hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->value_tables, sizeof(e->value_tables), hipMemcpyHostToDevice, e->stream);
     if (err != hipSuccess) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(e->stream);
@@ -1095,37 +1100,10 @@ int32_t pgv_history_capacity(pgv_env* e) { return e && e->history ? e->hist.capa
 int32_t pgv_history_push(pgv_env* e) {
     if (!e) return fail("pgv_history_push: env is NULL");
     if (!e->history) return fail("pgv_history_push: call pgv_history_enable first");
-    if (policy_ready("pgv_history_push", e)) return 1;
+    if (slab_ready("pgv_history_push", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     (void)hipGetLastError();
     return history_push(e, false, nullptr);
-}
-
-int32_t pgv_history_gather(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype, void* d_out) {
-    if (!e) return fail("pgv_history_gather: env is NULL");
-    if (!e->history) return fail("pgv_history_gather: call pgv_history_enable first");
-    if (stack < 1 || stack > pg::kPolicyMaxStack) return fail("pgv_history_gather: stack must be in 1 .. 8");
-    if (dtype != PGV_POLICY_U8 && dtype != PGV_POLICY_F16 && dtype != PGV_POLICY_BF16 && dtype != PGV_POLICY_F32)
-        return fail("pgv_history_gather: unknown dtype " + std::to_string(dtype));
-    if (count < 0) return fail("pgv_history_gather: count is negative");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail("pgv_history_gather: out must be 16-byte aligned");
-    if (count == 0) return 0;
-    if (!d_pushes || !d_envs || !d_out) return fail("pgv_history_gather: pushes, envs or out is NULL");
-    PG_HIP(hipSetDevice(e->device));
-    (void)hipGetLastError();
-    pg::HistoryGather q{};
-    q.n = e->n;
-    q.stack = stack;
-    q.count = count;
-    q.head = e->history_head;
-    q.pushes = d_pushes;
-    q.envs = d_envs;
-    q.table = e->hist.table + dtype * 256;
-    q.out = static_cast<uint8_t*>(d_out);
-    q.b = e->hist;
-    pg::launch_history_gather(e->stream, q, pg::policy_element_bytes(dtype));
-    PG_HIP(hipGetLastError());
-    return 0;
 }
 
 // What both augmented calls check of `aug`, the same way; `who` heads the message.
@@ -1134,6 +1112,36 @@ static int32_t gather_aug_config(const char* who, const pgv_gather_aug* aug, pg:
     cfg = pg::AugConfig{aug->out_height, aug->out_width, aug->pad, aug->edge, aug->cutout_min, aug->cutout_max, aug->cutout_color, aug->seed};
     if (const char* why = pg::aug_config_error(cfg)) return fail(std::string(who) + ": " + why);
     if (reinterpret_cast<uintptr_t>(aug->params) & 3u) return fail(std::string(who) + ": params must be 4-byte aligned");
+    return 0;
+}
+
+// What both gathers check of their arguments, in the order they check it, and the entry list they hand their kernel.  `cfg`
+// (the augmented gather): its config is checked between the count and the tensor.  Leaves q.count = 0 where nothing is asked for.
+static int32_t gather_arguments(const char* who, pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack,
+                                int32_t dtype, void* d_out, pg::HistoryGather& q, const pgv_gather_aug* aug = nullptr, pg::AugConfig* cfg = nullptr) {
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!e->history) return fail(std::string(who) + ": call pgv_history_enable first");
+    if (stack < 1 || stack > pg::kPolicyMaxStack) return fail(std::string(who) + ": stack must be in 1 .. 8");
+    if (!pg::policy_dtype_known(dtype)) return fail(std::string(who) + ": unknown dtype " + std::to_string(dtype));
+    if (count < 0) return fail(std::string(who) + ": count is negative");
+    if (cfg && gather_aug_config(who, aug, *cfg)) return 1;
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail(std::string(who) + ": out must be 16-byte aligned");
+    if (count == 0) return 0;
+    if (!d_pushes || !d_envs || !d_out) return fail(std::string(who) + ": pushes, envs or out is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    q.n = e->n, q.stack = stack, q.count = count, q.head = e->history_head;
+    q.pushes = d_pushes, q.envs = d_envs, q.table = e->hist.table + dtype * 256, q.out = static_cast<uint8_t*>(d_out);
+    q.b = e->hist;
+    return 0;
+}
+
+int32_t pgv_history_gather(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype, void* d_out) {
+    pg::HistoryGather q{};
+    if (gather_arguments("pgv_history_gather", e, d_pushes, d_envs, count, stack, dtype, d_out, q)) return 1;
+    if (q.count == 0) return 0;
+    pg::launch_history_gather(e->stream, q, pg::policy_element_bytes(dtype));
+    PG_HIP(hipGetLastError());
     return 0;
 }
 
@@ -1148,28 +1156,9 @@ int32_t pgv_gather_aug_params(const pgv_gather_aug* aug, int32_t entry, int32_t*
 
 int32_t pgv_history_gather_aug(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype,
                                const pgv_gather_aug* aug, void* d_out) {
-    if (!e) return fail("pgv_history_gather_aug: env is NULL");
-    if (!e->history) return fail("pgv_history_gather_aug: call pgv_history_enable first");
-    if (stack < 1 || stack > pg::kPolicyMaxStack) return fail("pgv_history_gather_aug: stack must be in 1 .. 8");
-    if (dtype != PGV_POLICY_U8 && dtype != PGV_POLICY_F16 && dtype != PGV_POLICY_BF16 && dtype != PGV_POLICY_F32)
-        return fail("pgv_history_gather_aug: unknown dtype " + std::to_string(dtype));
-    if (count < 0) return fail("pgv_history_gather_aug: count is negative");
     pg::HistoryGatherAug q{};
-    if (gather_aug_config("pgv_history_gather_aug", aug, q.cfg)) return 1;
-    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail("pgv_history_gather_aug: out must be 16-byte aligned");
-    if (count == 0) return 0;
-    if (!d_pushes || !d_envs || !d_out) return fail("pgv_history_gather_aug: pushes, envs or out is NULL");
-    PG_HIP(hipSetDevice(e->device));
-    (void)hipGetLastError();
-    q.g.n = e->n;
-    q.g.stack = stack;
-    q.g.count = count;
-    q.g.head = e->history_head;
-    q.g.pushes = d_pushes;
-    q.g.envs = d_envs;
-    q.g.table = e->hist.table + dtype * 256;
-    q.g.out = static_cast<uint8_t*>(d_out);
-    q.g.b = e->hist;
+    if (gather_arguments("pgv_history_gather_aug", e, d_pushes, d_envs, count, stack, dtype, d_out, q.g, aug, &q.cfg)) return 1;
+    if (q.g.count == 0) return 0;
     q.params = aug->params;
     pg::launch_history_gather_aug(e->stream, q, pg::policy_element_bytes(dtype));
     PG_HIP(hipGetLastError());
@@ -1267,8 +1256,9 @@ int32_t pgv_load_state(pgv_env* e, const void* h_buffer, int64_t size) {
     if (snapshot_copy(e, const_cast<uint8_t*>(in) + sizeof(hd), hd.state_bytes, true)) return 1;
     e->step_index = hd.step_index;
     PG_HIP(e->game->state_loaded(e->stream));  // (on the env's stream: ordered in front of the next step)
-    if (e->policy) pg::launch_policy_flag_mask(e->stream, e->pol, e->n, nullptr);  // the stacks do not travel: every env restarts
-    if (e->history) pg::launch_policy_flag_mask(e->stream, pg::history_flags(e->hist), e->n, nullptr);  // nor does the ring
+    // neither the stacks nor the ring travel: every env restarts
+    for (uint8_t* flags : flag_arrays(e))
+        if (flags) pg::launch_policy_flag_mask(e->stream, flags, e->n, nullptr);
     pregen(e, true, true);  // queued shadow slots of the snapshot get their generator launch
     return 0;
 }
@@ -1332,11 +1322,8 @@ int32_t pgv_load_envs(pgv_env* e, const int32_t* d_indices, int32_t count, const
     pg::launch_records(e->stream, t, true, d_indices, count, const_cast<void*>(d_records));
     e->game->records_loaded(e->stream, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes, t.r[e->rec_obs].offset,
                             e->step_index, e->io());
-    if (e->policy)  // the slots actually written restart their stacks
-        pg::launch_policy_flag_list(e->stream, e->pol, e->n, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes, pg::kRecordFull);
-    if (e->history)  // … and begin their history afresh
-        pg::launch_policy_flag_list(e->stream, pg::history_flags(e->hist), e->n, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes,
-                                    pg::kRecordFull);
+    for (uint8_t* flags : flag_arrays(e))  // the slots actually written restart their stacks and begin their history afresh
+        if (flags) pg::launch_policy_flag_list(e->stream, flags, e->n, d_indices, count, static_cast<const uint8_t*>(d_records), t.record_bytes, pg::kRecordFull);
     PG_HIP(hipGetLastError());
     pregen(e, size_t(count) * 2 >= size_t(e->n), true);  // loaded slots that are queued get their generator launch
     return 0;

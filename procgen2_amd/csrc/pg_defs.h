@@ -39,6 +39,17 @@ constexpr int kNumActions = 15;               // coinrun.cpp:26
 constexpr float kUnitPx = 16.0f;
 constexpr float kPxUnit = 1.0f / 16.0f;
 
+// The counter-based hash behind everything that is a function of a seed and a counter alone: level numbers and synthetic
+// actions (pg_engine.h), the draws of the augmented gathers (pg_history_aug.h).
+PG_HD uint32_t mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
 enum GameId : int32_t { kGameCoinrun = 0, kGameMaze = 1, kGameBossfight = 2, kGameClimber = 3, kGameCaveflyer = 4, kGameChaser = 5, kGameJumper = 6, kNumGames = 7 };
 
 }  // namespace pg

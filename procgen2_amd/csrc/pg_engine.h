@@ -236,15 +236,7 @@ std::unique_ptr<Game> make_jumper_v0();
 std::unique_ptr<Game> make_jumper_v1();
 std::unique_ptr<Game> make_jumper_v2();
 
-// Counter-based synthetic action shared with the oracle (oracle/pgo_api.cpp pgo_synthetic_action).
-PG_HD uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
+// Level numbers, and the counter-based synthetic action shared with the oracle (oracle/pgo_api.cpp pgo_synthetic_action).
 PG_HD uint32_t level_number(int32_t num_levels, int32_t start_level, uint32_t chain_seed, uint32_t k) {
     return static_cast<uint32_t>(start_level) + mix32(mix32(chain_seed) + k) % static_cast<uint32_t>(num_levels);
 }

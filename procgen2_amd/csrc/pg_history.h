@@ -6,27 +6,26 @@
 //     a gathered row [K*C][64][64] elements; slot K-1 the newest frame; values by policy_table_entry.
 // Push p is HELD while head - T <= p < head (head: the pushes so far, a host counter handed to every launch by value).
 //
-// The push kernel: one workgroup of 256 lanes per env.  Lane t owns the 16 consecutive pixels 16t .. 16t+15, reads their 48
-// bytes of the HWC row as three 16-byte loads (as policy_push_kernel does) and stores 16 bytes per plane: at one byte per
-// element the lanes of a plane lie 16 bytes apart as they are, so nothing is exchanged.  Lane 0 files the env's pending flag
-// as the slot's began byte and clears it; no other lane touches either byte.  An env whose mask byte is 0 is left before
-// anything is read or written.  The form pgv_reset uses (`reset` set) writes into the newest slot and files began = 1.
+// Values, the lane's share of a frame, units, the wave's exchange and the row of zero bytes are pg_planes.h's.
 //
-// The gather kernel: one workgroup of 256 lanes per entry.  Lane 0 validates the entry and walks back from p (history_walk:
-// at most K-1 dependent byte loads of began) while all lanes copy the dtype's 256 table words into LDS; one barrier shares
-// both.  Per frame and plane a lane loads the 16 stored bytes of its pixels and looks them up: 16·ES bytes, which at ES = 2
-// and 4 the wave exchanges through LDS as policy_push_kernel does, so that store instruction k of lane l writes unit 64k + l
-// — lanes 16 bytes apart (policy_unit's dense form; measured against each lane storing its own units as they lie: -7 % at
-// 2 bytes, -36 % at 4, docs/OPTLOG.md).  The exchange sits under a workgroup-uniform condition, so its barriers are met by
-// all lanes or none.  Where the walk repeats a frame the values already in registers are stored again.  An entry that is not
-// held, or whose env is outside the batch, gets a row of zero bytes.
+// The push kernel: one workgroup of 256 lanes per env.  A lane reads its 48 bytes of the slab and stores 16 bytes per plane: at
+// one byte per element the lanes of a plane lie 16 bytes apart as they are, so nothing is exchanged.  Lane 0 files the env's
+// pending flag as the slot's began byte and clears it; no other lane touches either byte.  An env whose mask byte is 0 is left
+// before anything is read or written.  The form pgv_reset uses (`reset` set) writes into the newest slot and files began = 1.
+//
+// The gather kernel: one workgroup of 256 lanes per entry, begun by gather_entry and fed by history_fetch (both shared with
+// pg_history_aug.h).  Per frame and plane a lane looks its 16 stored bytes up: 16·ES bytes, which at ES = 2 and 4 the wave
+// exchanges (measured against each lane storing its own units as they lie: -7 % at 2 bytes, -36 % at 4, docs/OPTLOG.md).
+// Where the walk repeats a frame the values already in registers are stored again.  An entry that is not held, or whose env
+// is outside the batch, gets a row of zero bytes.
 // Plain vector loads and stores, no atomics.
 // Bounds.  Push: the grid is n workgroups, env = blockIdx.x < n, slot < T by the host; a lane reads obs[env·12 288 + 48t ..
 // + 47] and writes frames[((slot·n + env)·C + c)·4096 + 16t .. + 15], c < C, t < 256  <  T·n·C·4096; began[slot·n + env],
 // pending[env].  Gather: the grid is `count` workgroups, entry = blockIdx.x < count; pushes[entry], envs[entry]; nothing of
 // the ring is read unless 0 <= env < n and max(0, head - T) <= p < head, and the walk only ever moves to a held push, so
 // every slot is f % T < T with f >= 0; a lane writes channel ch < K·C, wave w < 4, unit u < 64·ES at
-// entry·K·C·4096·ES + policy_unit_offset(ES, ch, w, u) .. + 15  <  (entry + 1)·K·C·4096·ES.  The table is indexed by a byte.
+// entry·K·C·4096·ES + policy_unit_offset(ES, ch, w, u) .. + 15  <  (entry + 1)·K·C·4096·ES; the zero row writes units
+// u < 256·ES of 16 bytes of every channel, the same bytes.  The table is indexed by a byte.
 // Offsets are size_t: 65 536 envs, T = 32, RGB are 25.8 GB.
 #pragma once
 
@@ -37,7 +36,6 @@
 namespace pg {
 
 constexpr int kHistoryBlock = kPolicyBlock;  // lanes a workgroup, 16 pixels a lane
-constexpr int kHistoryTables = 4;            // PGV_POLICY_U8, _F16, _BF16, _F32
 
 PG_HD int history_slot(int64_t push, int capacity) { return static_cast<int>(push % capacity); }  // (push >= 0)
 PG_HD bool history_held(int64_t push, int64_t head, int capacity) { return push >= 0 && push < head && push >= head - capacity; }
@@ -71,11 +69,9 @@ struct HistoryBuffers {
 inline void list_history(Carve& c, HistoryBuffers& b, int n) {
     c.take(b.pending, size_t(n));
     c.take(b.began, size_t(b.capacity) * size_t(n));
-    c.take(b.table, kHistoryTables * 256 * 4);
+    c.take(b.table, kPolicyTables * 256 * 4);
     if (b.own_frames) c.take(b.frames, history_frames_bytes(b.capacity, n, b.planes));
 }
-// The pending flags are set by the policy observations' flag kernels, which know one array of flags and nothing else.
-inline PolicyObsBuffers history_flags(const HistoryBuffers& b) { return PolicyObsBuffers{b.pending, nullptr}; }
 
 struct HistoryPush {
     int n, planes, slot, reset;  // reset: pgv_reset's form — began = 1 whatever the flag
@@ -100,28 +96,44 @@ __global__ void __launch_bounds__(kHistoryBlock) history_push_kernel(HistoryPush
     const int env = static_cast<int>(blockIdx.x);
     if (q.mask && !q.mask[env]) return;  // (workgroup-uniform)
     const int tid = static_cast<int>(threadIdx.x);
-    const PolicyVec16* from = reinterpret_cast<const PolicyVec16*>(q.obs + size_t(env) * kObsBytes + size_t(tid) * 48);
-    const PolicyVec16 in0 = from[0], in1 = from[1], in2 = from[2];
+    const SlabWords slab = slab_load(q.obs, env, tid);
     if (tid == 0) {
         q.b.began[history_began_offset(q.slot, q.n, env)] = q.reset ? uint8_t(1) : q.b.pending[env];
         q.b.pending[env] = 0;
     }
     uint8_t* const to = q.b.frames + history_frame_offset(q.slot, q.n, env, C) + size_t(tid) * kPolicyLanePixels;
-    const uint32_t word[12] = {in0.x, in0.y, in0.z, in0.w, in1.x, in1.y, in1.z, in1.w, in2.x, in2.y, in2.z, in2.w};
 #pragma unroll
-    for (int p = 0; p < C; p++) {  // (unrolled: every byte position is a constant)
+    for (int p = 0; p < C; p++) {
         uint32_t v[kPolicyLanePixels];
-#pragma unroll
-        for (int j = 0; j < kPolicyLanePixels; j++) {
-            const int at = 3 * j;
-            const uint32_t r = (word[at >> 2] >> (8 * (at & 3))) & 0xFFu, g = (word[(at + 1) >> 2] >> (8 * ((at + 1) & 3))) & 0xFFu,
-                           b = (word[(at + 2) >> 2] >> (8 * ((at + 2) & 3))) & 0xFFu;
-            v[j] = C == 1 ? policy_gray(r, g, b) : p == 0 ? r : p == 1 ? g : b;
-        }
+        slab_plane_bytes<C>(slab, p, v);
         PolicyVec16 mine[1];
         policy_pack<1>(v, mine);
         *reinterpret_cast<PolicyVec16*>(to + size_t(p) * kPolicyPlane) = mine[0];
     }
+}
+
+// The head of a gather kernel: all lanes copy the dtype's 256 table words into `table` while lane 0 validates the entry and,
+// where it is valid, walks back from its push (history_walk: at most K-1 dependent byte loads of began) into `frame`; one
+// barrier shares both (all three in LDS).  Returns the verdict (workgroup-uniform) and the entry's `env`.
+PG_D bool gather_entry(const HistoryGather& q, size_t entry, int tid, uint32_t* table, int64_t* frame, int* valid, int& env) {
+    table[tid] = q.table[tid];
+    if (tid == 0) {
+        const int64_t push = q.pushes[entry];
+        env = q.envs[entry];
+        const int ok = env >= 0 && env < q.n && history_held(push, q.head, q.b.capacity);
+        *valid = ok;
+        if (ok) history_walk(q.b.began, q.n, q.b.capacity, q.head, push, env, q.stack, frame);
+    }
+    __syncthreads();  // the table is whole; the walk is shared
+    env = q.envs[entry];
+    return *valid != 0;
+}
+// Lane tid's 16 stored bytes of each of the C planes of env's frame f (a held push).
+template <int C>
+PG_D void history_fetch(const HistoryGather& q, int64_t f, int env, int tid, PolicyVec16 (&in)[C]) {
+    const uint8_t* from = q.b.frames + history_frame_offset(history_slot(f, q.b.capacity), q.n, env, C) + size_t(tid) * kPolicyLanePixels;
+#pragma unroll
+    for (int p = 0; p < C; p++) in[p] = *reinterpret_cast<const PolicyVec16*>(from + size_t(p) * kPolicyPlane);
 }
 
 template <int ES, int C>  // element bytes; planes
@@ -132,55 +144,31 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_kernel(HistoryGa
     __shared__ PolicyVec16 exchange[ES > 1 ? kHistoryBlock * ES : 1];  // a wave's units of one plane, in the wave's own quarter
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
     const size_t entry = blockIdx.x;
-    const int T = q.b.capacity, K = q.stack;
-    table[tid] = q.table[tid];
+    const int K = q.stack;
     int env = 0;
-    if (tid == 0) {
-        const int64_t push = q.pushes[entry];
-        env = q.envs[entry];
-        const int ok = env >= 0 && env < q.n && history_held(push, q.head, T);
-        valid = ok;
-        if (ok) history_walk(q.b.began, q.n, T, q.head, push, env, K, frame);
-    }
-    __syncthreads();  // the table is whole; the walk is shared
-    env = q.envs[entry];
+    const bool ok = gather_entry(q, entry, tid, table, frame, &valid, env);
     uint8_t* const out = q.out + entry * policy_bytes_per_env(K, C, ES);
+    const size_t channel = size_t(kPolicyPlane) * ES;
+    if (!ok) {  // (workgroup-uniform)
+        zero_row<PolicyVec16>(out, K * C, channel, kHistoryBlock * ES, tid);
+        return;
+    }
     size_t unit[ES];  // byte offset, inside a channel of this wave, of the units this lane stores
 #pragma unroll
     for (int k = 0; k < ES; k++) unit[k] = policy_unit_offset(ES, 0, wave, policy_unit(true, ES, lane, k));
-    const size_t channel = size_t(kPolicyPlane) * ES;
-    if (!valid) {  // (workgroup-uniform)
-        const PolicyVec16 zero{0u, 0u, 0u, 0u};
-        for (int ch = 0; ch < K * C; ch++)
-#pragma unroll
-            for (int k = 0; k < ES; k++) *reinterpret_cast<PolicyVec16*>(out + ch * channel + unit[k]) = zero;
-        return;
-    }
     PolicyVec16 held[C * ES];
     for (int j = 0; j < K; j++) {
         const int64_t f = frame[j];
         if (j == 0 || f != frame[j - 1]) {  // (workgroup-uniform)
-            const uint8_t* from = q.b.frames + history_frame_offset(history_slot(f, T), q.n, env, C) + size_t(tid) * kPolicyLanePixels;
             PolicyVec16 in[C];
-#pragma unroll
-            for (int p = 0; p < C; p++) in[p] = *reinterpret_cast<const PolicyVec16*>(from + size_t(p) * kPolicyPlane);
+            history_fetch<C>(q, f, env, tid, in);
 #pragma unroll
             for (int p = 0; p < C; p++) {
-                const uint32_t word[4] = {in[p].x, in[p].y, in[p].z, in[p].w};
                 uint32_t v[kPolicyLanePixels];
-#pragma unroll
-                for (int i = 0; i < kPolicyLanePixels; i++) v[i] = table[(word[i >> 2] >> (8 * (i & 3))) & 0xFFu];
+                plane_values(table, in[p], v);
                 PolicyVec16 mine[ES];
                 policy_pack<ES>(v, mine);
-                if (ES > 1) {  // lane l's units l·ES + k out, units 64k + l in
-                    PolicyVec16* share = exchange + wave * 64 * ES;
-#pragma unroll
-                    for (int k = 0; k < ES; k++) share[lane * ES + k] = mine[k];
-                    __syncthreads();
-#pragma unroll
-                    for (int k = 0; k < ES; k++) mine[k] = share[64 * k + lane];
-                    __syncthreads();  // before the next plane overwrites the share
-                }
+                if (ES > 1) wave_exchange<ES>(exchange, wave, lane, mine);
 #pragma unroll
                 for (int k = 0; k < ES; k++) held[p * ES + k] = mine[k];
             }
@@ -197,12 +185,9 @@ inline void launch_history_push(hipStream_t st, const HistoryPush& q) {
     hipLaunchKernelGGL(q.planes == 1 ? history_push_kernel<1> : history_push_kernel<3>, dim3(q.n), dim3(kHistoryBlock), 0, st, q);
 }
 inline void launch_history_gather(hipStream_t st, const HistoryGather& q, int es) {
-    void (*kernel)(HistoryGather) = nullptr;
-    if (q.b.planes == 1)
-        kernel = es == 1 ? history_gather_kernel<1, 1> : es == 2 ? history_gather_kernel<2, 1> : history_gather_kernel<4, 1>;
-    else
-        kernel = es == 1 ? history_gather_kernel<1, 3> : es == 2 ? history_gather_kernel<2, 3> : history_gather_kernel<4, 3>;
-    hipLaunchKernelGGL(kernel, dim3(q.count), dim3(kHistoryBlock), 0, st, q);
+    for_es_planes(es, q.b.planes, [&](auto es_c, auto planes_c) {
+        hipLaunchKernelGGL((history_gather_kernel<decltype(es_c)::value, decltype(planes_c)::value>), dim3(q.count), dim3(kHistoryBlock), 0, st, q);
+    });
 }
 #endif
 

@@ -6,19 +6,18 @@
 //     element (slot, plane, y, x) = table[byte], byte by aug_source_byte_index: the plane's colour byte inside the rectangle,
 //     else the stored byte at (oy + y, ox + x), outside the frame the nearest pixel's (REPLICATE) or 0 (ZERO).
 //
-// The kernel: one workgroup of 256 lanes per entry.  Lane 0 validates the entry and walks (history_walk) and writes the
-// params row while all lanes copy the dtype's 256 table words into LDS; one barrier shares both.  Every lane works the
-// entry's draws out for itself (they are workgroup-uniform).  Per DISTINCT frame of the walk a lane loads the 16 stored bytes
-// of its pixels of each plane, as the plain gather does, and the workgroup stages the C planes in LDS (C·4096 bytes) between
-// two barriers under a workgroup-uniform condition; a frame the walk repeats is neither fetched nor staged again.  The lanes
-// then write the output plane in dense order: unit u (U bytes, U/ES elements) of a plane is written by lane u % 256 in its
-// store number u / 256, so the lanes of one store instruction lie U bytes apart.  A lane reads its source bytes from the
-// staged planes one byte at a time (neighbouring lanes read neighbouring bytes: the same or the next LDS word), through
-// aug_source_byte_index, then through the table, and packs them.
+// The kernel: one workgroup of 256 lanes per entry, begun as the plain gather's is (pg_history.h gather_entry); lane 0 writes
+// the params row behind it.  Every lane works the entry's draws out for itself (they are workgroup-uniform).  Per DISTINCT
+// frame of the walk a lane fetches its stored bytes of each plane (history_fetch) and the workgroup stages the C planes in LDS
+// (C·4096 bytes) between two barriers under a workgroup-uniform condition; a frame the walk repeats is neither fetched nor
+// staged again.  The lanes then write the output plane in dense order: unit u (U bytes, U/ES elements) of a plane is written
+// by lane u % 256 in its store number u / 256, so the lanes of one store instruction lie U bytes apart.  A lane reads its
+// source bytes from the staged planes one byte at a time (neighbouring lanes read neighbouring bytes: the same or the next LDS
+// word), through aug_source_byte_index, then through the table, and packs them.
 // U is 16 where a plane's H'·W'·ES bytes are a multiple of 16 — then every row and plane starts 16-byte aligned — and 8
 // otherwise: W' is a multiple of 8, so a plane is always a whole number of 8-byte units, starts 8-byte aligned, and no store
 // is ever narrower than a unit or reaches past its plane.  An entry that is not held, or whose env is outside the batch,
-// gets a row of zero bytes by the same units.  Plain vector loads and stores, no atomics.
+// gets a row of zero bytes by the same units (pg_planes.h zero_row).  Plain vector loads and stores, no atomics.
 // Bounds.  The grid is `count` workgroups, entry = blockIdx.x < count; pushes[entry], envs[entry], params[entry·8 .. + 7];
 // nothing of the ring is read unless 0 <= env < n and the push is held, and the walk only moves to held pushes (pg_history.h):
 // a lane reads frames[frame offset + p·4096 + 16t .. + 15], p < C, t < 256.  The staged planes are indexed by
@@ -60,18 +59,9 @@ PG_HD const char* aug_config_error(const AugConfig& a) {
     return nullptr;
 }
 
-// The counter-based hash of pg_engine.h (mix32), restated so that this header compiles without the HIP runtime.
-PG_HD uint32_t aug_mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
 // Word j of entry e, and a draw in 0 .. m-1 from it (synthetic_action's rule).
 PG_HD uint32_t aug_word(uint32_t seed, uint32_t entry, uint32_t j) {
-    return aug_mix32(aug_mix32(seed + 0x9E3779B9u * (entry + 1u)) ^ (j * 0x85EBCA6Bu + 0xC2B2AE35u));
+    return mix32(mix32(seed + 0x9E3779B9u * (entry + 1u)) ^ (j * 0x85EBCA6Bu + 0xC2B2AE35u));
 }
 PG_HD int aug_draw(uint32_t seed, uint32_t entry, uint32_t m, uint32_t j) {
     return static_cast<int>((static_cast<uint64_t>(aug_word(seed, entry, j)) * m) >> 32);
@@ -129,20 +119,11 @@ struct HistoryGatherAug {
 
 #if defined(__HIPCC__)
 typedef uint32_t AugVec8 __attribute__((ext_vector_type(2)));  // 8 bytes a lane
-template <int U> struct AugUnit;
-template <> struct AugUnit<16> {
-    typedef PolicyVec16 type;
-    static PG_D type make(const uint32_t (&w)[4]) { return type{w[0], w[1], w[2], w[3]}; }
-};
-template <> struct AugUnit<8> {
-    typedef AugVec8 type;
-    static PG_D type make(const uint32_t (&w)[2]) { return type{w[0], w[1]}; }
-};
 
 template <int ES, int C, int U>  // element bytes; planes; bytes a store unit
 __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(HistoryGatherAug q) {
-    typedef typename AugUnit<U>::type Unit;
-    constexpr int kWords = U / 4, kPerWord = 4 / ES, kPerUnit = U / ES;  // words a unit; pixels a word; pixels a unit
+    typedef std::conditional_t<U == 16, PolicyVec16, AugVec8> Unit;
+    constexpr int kPerWord = 4 / ES, kPerUnit = U / ES;  // pixels a word; pixels a unit
     constexpr int kRun = kPerUnit < 8 ? kPerUnit : 8;                    // pixels in a row of the output for certain: W' % 8 == 0
     __shared__ uint32_t table[256];
     __shared__ int64_t frame[kPolicyMaxStack];
@@ -150,46 +131,30 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(Histo
     __shared__ PolicyVec16 staged[C * kPolicyPlane / 16];  // the C planes of one frame, as stored
     const int tid = static_cast<int>(threadIdx.x);
     const size_t entry = blockIdx.x;
-    const int T = q.g.b.capacity, K = q.g.stack;
+    const int K = q.g.stack;
     const AugParams ap = aug_params(q.cfg, static_cast<uint32_t>(entry));
-    table[tid] = q.g.table[tid];
     int env = 0;
-    if (tid == 0) {
-        const int64_t push = q.g.pushes[entry];
-        env = q.g.envs[entry];
-        const int ok = env >= 0 && env < q.g.n && history_held(push, q.g.head, T);
-        valid = ok;
-        if (ok) history_walk(q.g.b.began, q.g.n, T, q.g.head, push, env, K, frame);
-        if (q.params) {
-            int32_t row[kAugParamWords];
-            aug_params_row(ap, C, row);
+    const bool ok = gather_entry(q.g, entry, tid, table, frame, &valid, env);
+    if (tid == 0 && q.params) {
+        int32_t row[kAugParamWords];
+        aug_params_row(ap, C, row);
 #pragma unroll
-            for (int k = 0; k < kAugParamWords; k++) q.params[entry * kAugParamWords + k] = row[k];
-        }
+        for (int k = 0; k < kAugParamWords; k++) q.params[entry * kAugParamWords + k] = row[k];
     }
-    __syncthreads();  // the table is whole; the walk is shared
-    env = q.g.envs[entry];
     const int W = q.cfg.out_w, edge = q.cfg.edge;
     const int units = q.cfg.out_h * W / kPerUnit;  // (exact: aug_unit_bytes)
     const size_t channel = aug_plane_bytes(q.cfg.out_h, W, ES);
     uint8_t* const out = q.g.out + entry * (size_t(K) * C * channel);
-    if (!valid) {  // (workgroup-uniform)
-        uint32_t none[kWords];
-#pragma unroll
-        for (int k = 0; k < kWords; k++) none[k] = 0u;
-        const Unit zero = AugUnit<U>::make(none);
-        for (int ch = 0; ch < K * C; ch++)
-            for (int u = tid; u < units; u += kHistoryBlock) *reinterpret_cast<Unit*>(out + ch * channel + size_t(u) * U) = zero;
+    if (!ok) {  // (workgroup-uniform)
+        zero_row<Unit>(out, K * C, channel, units, tid);
         return;
     }
     const uint8_t* const bytes = reinterpret_cast<const uint8_t*>(staged);
     for (int j = 0; j < K; j++) {
         const int64_t f = frame[j];
         if (j == 0 || f != frame[j - 1]) {  // (workgroup-uniform)
-            const uint8_t* from = q.g.b.frames + history_frame_offset(history_slot(f, T), q.g.n, env, C) + size_t(tid) * kPolicyLanePixels;
             PolicyVec16 in[C];
-#pragma unroll
-            for (int p = 0; p < C; p++) in[p] = *reinterpret_cast<const PolicyVec16*>(from + size_t(p) * kPolicyPlane);
+            history_fetch<C>(q.g, f, env, tid, in);
             __syncthreads();  // every lane has done with the frame staged before
 #pragma unroll
             for (int p = 0; p < C; p++) staged[p * (kPolicyPlane / 16) + tid] = in[p];
@@ -201,9 +166,7 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(Histo
             const uint8_t* const plane = bytes + p * kPolicyPlane;
             const uint32_t colour = (ap.colour >> (8 * p)) & 0xFFu;
             for (int u = tid; u < units; u += kHistoryBlock) {
-                uint32_t w[kWords];
-#pragma unroll
-                for (int k = 0; k < kWords; k++) w[k] = 0u;
+                Unit w{};
 #pragma unroll
                 for (int r = 0; r < kPerUnit / kRun; r++) {
                     const int first = u * kPerUnit + r * kRun, y = first / W, x0 = first - y * W;
@@ -215,23 +178,19 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(Histo
                         w[px / kPerWord] |= table[byte] << (8 * ES * (px % kPerWord));
                     }
                 }
-                *reinterpret_cast<Unit*>(to + p * channel + size_t(u) * U) = AugUnit<U>::make(w);
+                *reinterpret_cast<Unit*>(to + p * channel + size_t(u) * U) = w;
             }
         }
     }
 }
 
-template <int ES, int C>
-inline void launch_history_gather_aug_units(hipStream_t st, const HistoryGatherAug& q) {
-    void (*kernel)(HistoryGatherAug) = history_gather_aug_kernel<ES, C, 8>;
-    if (aug_unit_bytes(q.cfg.out_h, q.cfg.out_w, ES) == 16) kernel = history_gather_aug_kernel<ES, C, 16>;
-    hipLaunchKernelGGL(kernel, dim3(q.g.count), dim3(kHistoryBlock), 0, st, q);
-}
 inline void launch_history_gather_aug(hipStream_t st, const HistoryGatherAug& q, int es) {
-    if (q.g.b.planes == 1)
-        es == 1 ? launch_history_gather_aug_units<1, 1>(st, q) : es == 2 ? launch_history_gather_aug_units<2, 1>(st, q) : launch_history_gather_aug_units<4, 1>(st, q);
-    else
-        es == 1 ? launch_history_gather_aug_units<1, 3>(st, q) : es == 2 ? launch_history_gather_aug_units<2, 3>(st, q) : launch_history_gather_aug_units<4, 3>(st, q);
+    for_es_planes(es, q.g.b.planes, [&](auto es_c, auto planes_c) {
+        constexpr int ES = decltype(es_c)::value, C = decltype(planes_c)::value;
+        void (*kernel)(HistoryGatherAug) = history_gather_aug_kernel<ES, C, 8>;
+        if (aug_unit_bytes(q.cfg.out_h, q.cfg.out_w, ES) == 16) kernel = history_gather_aug_kernel<ES, C, 16>;
+        hipLaunchKernelGGL(kernel, dim3(q.g.count), dim3(kHistoryBlock), 0, st, q);
+    });
 }
 #endif
 

@@ -32,7 +32,7 @@ static int t_draw(uint32_t seed, uint32_t e, int m, uint32_t j) { return int((ui
 
 static int test_draws() {
     using namespace pg;
-    CHECK(aug_mix32(0u) == 0u && aug_mix32(1u) == t_mix(1u) && aug_mix32(0xFFFFFFFFu) == t_mix(0xFFFFFFFFu));
+    CHECK(mix32(0u) == 0u && mix32(1u) == t_mix(1u) && mix32(0xFFFFFFFFu) == t_mix(0xFFFFFFFFu));
     const uint32_t seeds[3] = {0u, 1u, 0xFFFFFFFFu};
     long rows = 0;
     for (int k = 0; k < 7; k++)
