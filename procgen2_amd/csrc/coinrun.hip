@@ -514,14 +514,17 @@ struct Hit {
 };
 
 // (box_overlap_flat — get_collision_overlap without its early return — is pg_tiles.h's)
-template <class Pred>
+// kNine = false (entity_redo): the loops only, never the nine fixed steps — the same cells in the same order with the same
+// arithmetic, in fewer registers (redo_kernel: 128 with the fixed steps, 96 with the loops; docs/OPTLOG.md, "The step's
+// private memory").
+template <bool kNine = true, class Pred>
 PG_D Hit collide(const TileWin& win, Box r, Pred solid, bool fallthrough, float step_y) {
     bool any = false;
     const int x0 = static_cast<int>(floorf(r.x)), y0 = static_cast<int>(floorf(r.y));
     const int x1 = static_cast<int>(ceilf(r.x + r.w)), y1 = static_cast<int>(ceilf(r.y + r.h));
     const float mid_x = r.x + r.w * 0.5f, mid_y = r.y + r.h * 0.5f;
     Box cell{0.0f, 0.0f, 1.0f, 1.0f};
-    if ((x1 - x0 <= 2) & (y1 - y0 <= 2) & (x0 >= win.ax) & (y0 >= win.ay) & (x1 < win.ax + 4) & (y1 < win.ay + 4)) {
+    if (kNine && ((x1 - x0 <= 2) & (y1 - y0 <= 2) & (x0 >= win.ax) & (y0 >= win.ay) & (x1 < win.ax + 4) & (y1 < win.ay + 4))) {
         // The boxes of this game are at most a tile wide and high: three by three cells at most, and the callers keep
         // them inside the window.  Walked as nine fixed steps with every decision a select (bitwise, so that nothing
         // short-circuits into a branch) — same cells, same order, same arithmetic as the loops below — because this
@@ -686,6 +689,8 @@ PG_D void entity_step(const State& s, int env, int e, int src, int limit, float 
     }
     // both sensors of all sub-steps live inside this window (x drifts by at most 0.15 per step)
     const TileWin win = TileWin::fetch(tiles, static_cast<int>(floorf(x - 0.66f)), static_cast<int>(floorf(y - 0.6f)));
+    // (entity_redo below holds a SECOND COPY of this sub-step, for the redo of an early-ended step: a change to the loop's
+    // body must be made there too — tests/test_coinrun_lean_gpu.py holds the copy to the oracle through real early ends.)
 #pragma unroll
     for (int ss = 0; ss < 4; ss++) {
         if (ss >= limit) break;
@@ -752,6 +757,91 @@ PG_D void entity_step(const State& s, int env, int e, int src, int limit, float 
     }
     hb[4] = y + -0.48f;
     hb[5] = 0.98f;
+}
+
+// entity_step for the REDO of a step that ended early (SC_REDO: render_full, redo_kernel), light on
+// registers, because it sits in the render kernel, whose register budget every frame pays: no hazard boxes (the step
+// has been decided), the sub-steps a loop, not four copies, and of a mob's thirty spark floats only the ten lives are held —
+// the loop never reads a spark's x or y, it writes them once, where the spark respawns.  So the untouched ones are copied
+// from the source half to the destination half and a respawned one is stored where it happens: the same arithmetic, the
+// same last store to every location, the same results (docs/OPTLOG.md, "The step's private memory": render_kernel 127
+// spilled registers and 200 B of scratch a lane -> 3 and 16 B, redo_kernel 142 registers -> 96).
+PG_D void entity_redo(const State& s, int env, int e, int src, int limit) {
+    const uint8_t* tiles = s.tiles + size_t(env) * (W * H);
+    const int dst = 1 - src;
+    const float dt = 1.0f / 4;
+    const int kind = EB(s, EB_KIND, e, env);
+    float hb[6];  // (static_step's; nobody reads it)
+    if (kind == kCoin) {
+        static_step(s, env, e, kind, dst, limit, DF(s, src, DF_X, e, env), 0.0f, 0.0f, DB(s, src, e, env), hb);
+        return;
+    }
+    float x = DF(s, src, DF_X, e, env);
+    const float y = EY(s, e, env);
+    float anim_t = DF(s, src, DF_ANIM_T, e, env);
+    int dyn = DB(s, src, e, env);
+    if (kind == kSaw) {
+        static_step(s, env, e, kind, dst, limit, x, y, anim_t, dyn, hb);
+        return;
+    }
+    float vx = DF(s, src, DF_VX, e, env);
+    float timer = DF(s, src, DF_SPAWN_T, e, env);
+    float sl[kSparks];
+#pragma unroll
+    for (int k = 0; k < kSparks; k++) {
+        sl[k] = SP(s, src, 2, e, k, env);
+        SP(s, dst, 0, e, k, env) = SP(s, src, 0, e, k, env);
+        SP(s, dst, 1, e, k, env) = SP(s, src, 1, e, k, env);
+    }
+    const TileWin win = TileWin::fetch(tiles, static_cast<int>(floorf(x - 0.66f)), static_cast<int>(floorf(y - 0.6f)));
+#pragma unroll 1
+    for (int ss = 0; ss < limit; ss++) {  // (entity_step's sub-step, line for line)
+        x += vx * dt;
+        const Box wall_probe{x - 0.5f, y - 0.6f, 1.0f, 0.5f};
+        const Box floor_probe{x - 0.5f, y + 0.6f, 1.0f, 0.5f};
+        const bool wall_maybe = !win.holds(wall_probe) ||
+                                pg::collide_any(win, wall_probe, [](int t) { return t == kWallMid || t == kWallTop; });
+        const bool gap_maybe = !win.holds(floor_probe) || pg::collide_any(win, floor_probe, [](int t) { return t == kEmpty; });
+        Hit wall{wall_probe.x, wall_probe.y, false}, gap{floor_probe.x, floor_probe.y, false};
+        if (__ballot(wall_maybe))  // (wave-uniform)
+            wall = collide<false>(
+                win, wall_probe, [](int t) { return (t == kWallMid || t == kWallTop) ? kFull : kPass; }, false, 0.0f);
+        if (__ballot(gap_maybe))
+            gap = collide<false>(
+                win, floor_probe, [](int t) { return t == kEmpty ? kFull : kPass; }, false, 0.0f);
+        float nx = wall.x + 0.5f;
+        if (gap.any) nx = gap.x + 0.5f;
+        x = nx;
+        if (wall.any || gap.any) vx *= -1.0f;
+        dyn = (dyn & ~kDynFlip) | (vx > 0.0f ? kDynFlip : 0);
+
+        int dead = -1;
+#pragma unroll
+        for (int k = 0; k < kSparks; k++) {
+            sl[k] -= dt;
+            if (sl[k] <= 0.0f) dead = k;
+        }
+        timer += dt;
+        if (dead != -1 && timer >= 0.5f) {
+            timer = fmodf(timer, 0.5f);
+#pragma unroll
+            for (int k = 0; k < kSparks; k++)
+                if (k == dead) sl[k] = 5.0f;
+            SP(s, dst, 0, e, dead, env) = x + 0.0f;
+            SP(s, dst, 1, e, dead, env) = y + 0.34f;
+        }
+        anim_t += dt;
+        const int adv = static_cast<int>(anim_t * 0.2f);
+        anim_t -= adv / 0.2f;
+        dyn = ((dyn & ~kDynFrame) | ((((dyn & kDynFrame) ? 1 : 0) + adv) % 2 ? kDynFrame : 0)) | kDynTexSet;
+    }
+    DF(s, dst, DF_X, e, env) = x;
+    DF(s, dst, DF_VX, e, env) = vx;
+    DF(s, dst, DF_ANIM_T, e, env) = anim_t;
+    DF(s, dst, DF_SPAWN_T, e, env) = timer;
+    DB(s, dst, e, env) = static_cast<uint8_t>(dyn);
+#pragma unroll
+    for (int k = 0; k < kSparks; k++) SP(s, dst, 2, e, k, env) = sl[k];
 }
 
 // Which hazards can touch the agent at all is decided before anyone knows where the agent goes: an entity lane compares
@@ -1172,10 +1262,7 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
         const int redo = SCI(s, SC_REDO, env);
         __syncthreads();  // every wave has read the flag before it is cleared
         if (redo) {
-            if (half == 0 && lane < n_ent) {
-                float hb[6];
-                entity_step(s, env, lane, 1 - buf, redo, hb);
-            }
+            if (half == 0 && lane < n_ent) entity_redo(s, env, lane, 1 - buf, redo);
             if (threadIdx.x == 0) SCI(s, SC_REDO, env) = 0;
             __threadfence();
             __syncthreads();
@@ -1717,10 +1804,7 @@ __global__ void __launch_bounds__(64) redo_kernel(State s) {
         todo &= todo - 1;
         const int redo = SCI(s, SC_REDO, env);
         const int buf = (SI(s, I_FLAGS, env) & kFlagBuf) ? 1 : 0;
-        if (lane < SI(s, I_NENT, env)) {  // <= kMaxEnt < 64
-            float hb[6];
-            entity_step(s, env, lane, 1 - buf, redo, hb);
-        }
+        if (lane < SI(s, I_NENT, env)) entity_redo(s, env, lane, 1 - buf, redo);  // <= kMaxEnt < 64
         if (lane == 0) SCI(s, SC_REDO, env) = 0;
     }
 }

@@ -383,6 +383,10 @@ PG_D void prep_meta_out(PrepLds<GRID, E, MAXSPAN>& P, const PrepOut& out, int en
             const int c = counts[e];
             const bool fat = P.fat[e] != 0 || c > kPrepDraws;
 #if defined(PG_FAT_WHY)  // (diagnostic build, tools/build_exp.py GAME fatwhy -DPG_FAT_WHY: why frames are handed back, counted per launch)
+            // NOT TO BE TRUSTED beyond a few hundred envs: the workgroup that prints zeroes the counters with plain stores,
+            // which are written back when the kernel ends — over what the other workgroups have added atomically in the
+            // meantime.  At 65 536 envs it shows 0–4 frames a launch where about 100 are handed back (docs/OPTLOG.md "The
+            // step's private memory": counted there by atomics that a LATER kernel reads and zeroes).
             if (fat) {
                 for (int b = 0; b < 4; b++)
                     if (P.fat[e] & (1u << b)) atomicAdd(&g_fat_why[b], 1u);
@@ -465,6 +469,13 @@ struct PrepDrawPass {
     int done[2];         // draws stored so far, per env of the wave
     int touch[2];        // `cover` only: some draw that was kept reaches into the covered part's bounding box (cover[kObsH])
 };
+// The camera of a lane's env, of the wave's two, BY VALUE: five selects.  (As `const Camera& cam = is_b ? cam_b : cam_a` the
+// per-lane choice between two structs was served through private memory — both stored, one loaded back through the chosen
+// address: 40 B of scratch, 4 stores and 13 loads a wavefront in a kernel whose whole vector-memory count is 18 loads.)
+PG_D Camera prep_camera(bool is_b, const Camera& cam_a, const Camera& cam_b) {
+    return Camera{is_b ? cam_b.px : cam_a.px, is_b ? cam_b.py : cam_a.py, is_b ? cam_b.sw : cam_a.sw, is_b ? cam_b.sh : cam_a.sh,
+                  is_b ? cam_b.scale : cam_a.scale};
+}
 // The tails of everything queued, ranks, stores.  desc: the atlas descriptor table (in LDS); cam: the two envs' cameras.
 // `cover` (optional): what a later, OPAQUE part of every frame hides — per pixel row y a word lo | hi << 8, the columns
 // [lo, hi] that part overwrites (lo > hi: none), valley- / hill-shaped over the rows, so that a rectangle whose first and
@@ -488,7 +499,7 @@ PG_D void prep_draws_flush(PrepDrawQueue& Q, PrepDrawPass& st, const int4* desc,
     const bool mine = j < st.queued;
     const PrepDrawEntry en = Q.e[mine ? j : 0];
     const bool is_b = (en.misc >> 31) != 0;
-    const Camera& cam = is_b ? cam_b : cam_a;
+    const Camera cam = prep_camera(is_b, cam_a, cam_b);
     const int4 d = desc[en.misc & 0xffu];
     Span x, y;
     x.d0 = x.dn = x.s0 = x.sn = 0;
@@ -554,7 +565,7 @@ PG_D void prep_draws_flush(PrepDrawQueue& Q, PrepDrawPass& st, const int4* desc,
 PG_D void prep_draws_pass(PrepDrawQueue& Q, PrepDrawPass& st, const int4* desc, const Camera& cam_a, const Camera& cam_b,
                           uint32_t* draws_a, uint32_t* draws_b, bool valid, bool is_b, const DrawCall& p, int lane,
                           const uint32_t* cover = nullptr, const uint4* stamps = nullptr) {
-    const Camera& cam = is_b ? cam_b : cam_a;
+    const Camera cam = prep_camera(is_b, cam_a, cam_b);
     AxisHead hx{0.0f, 0.0f}, hy{0.0f, 0.0f};
     bool alive = valid && p.go;
     if (alive) {

@@ -3,6 +3,11 @@
 (tools/build_exp.py GAME fw -DPG_FAT_WHY) counts them per launch by reason and prints the counts of the previous launch.
 
     python tools/probe/fat_why.py coinrun procgen2_amd/lib/libpg_exp_fw.so [steps]
+
+WARNING: at this script's 65 536 envs the counts are far too low (coinrun: 0-4 frames a launch shown, about 100 handed back).
+The workgroup that prints the counters zeroes them with plain stores, which are written back when the kernel ends, over what
+the other workgroups added atomically in the meantime (pg_prepass.h prep_meta_out; docs/OPTLOG.md "The step's private
+memory").  Trust it for a few hundred envs (one wave of workgroups) only, or count with atomics that a LATER kernel reads.
 """
 import os
 import sys
