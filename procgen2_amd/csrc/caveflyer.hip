@@ -954,170 +954,97 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The render pre-pass (pg_prepass.h; coinrun.hip's setup_kernel is the commented model): tile spans, per-pixel
+// The render pre-pass (pg_prepass.h prep_setup: the kernel; here what is caveflyer's own): tile spans, per-pixel
 // candidates, the cell table and the resolved, culled SPRITES of kPrepEnvs envs per workgroup.  The rotated draws —
 // particles, bullets, the ship — stay with the render wave: resolve_rotated_at has no division and no cull, and their
-// sines and cosines come from the logic kernel.  Reference arithmetic moved here unchanged: renderer.cpp:5-82,
-// tilemap.cpp:280-289 (the window), common_systems.cpp:26-48 (sprites).
+// sines and cosines come from the logic kernel.  Reference arithmetic moved here unchanged: tilemap.cpp:280-289 (the
+// window), common_systems.cpp:26-48 (sprites).
 // ------------------------------------------------------------------------------------------------
-constexpr int kPrepEnvs = 8, kPrepThreads = 256;
 enum { GW_SHOTS = 0, GW_SHIP_X, GW_SHIP_Y, GW_SHIP_SN, GW_SHIP_CS, GW_CAM_X, GW_CAM_Y };  // PM_GAME words: s_next | s_count << 16, the ship, the camera
 
 struct PrepEnv {
     int32_t n_draw, s_count;
 };
-struct SetupLds {
-    PrepLds<kGrid, kPrepEnvs, kSpan> P;
-    PrepEnv env[kPrepEnvs];
-    int4 desc[kTexCount];
-    uint32_t draw_order[kPrepEnvs][kEntStride / 4];  // EB_DRAW of every env: fetched before anything needs it
-    uint32_t row_valid[kPrepEnvs][kGrid / 4];
-    int32_t counts[kPrepEnvs];
-    PrepDrawQueue queue[kPrepThreads / 64];
+struct Setup : PrepPlain {
+    using State = caveflyer::State;
+    static constexpr int kGrid = caveflyer::kGrid, kSpan = caveflyer::kSpan, kW = W, kH = H, kTexCount = caveflyer::kTexCount, kOob = kWall;
+    static constexpr bool kTwo = false;
+    struct Lds {
+        PrepEnv env[kPrepEnvs];
+        uint32_t draw_order[kPrepEnvs][kEntStride / 4];  // EB_DRAW of every env
+    };
+    struct Regs {
+        Camera cam;
+        int backdrop;
+        float bgshift;
+        uint32_t game_words[7];
+    };
+    static PG_D void stage(Lds& L, const State& s, int env0, int tid) {
+        static_assert(kPrepEnvs * (kEntStride / 4) <= kPrepThreads, "one word per thread");
+        if (tid < kPrepEnvs * (kEntStride / 4)) {
+            const int e = tid / (kEntStride / 4), w = tid - e * (kEntStride / 4);
+            if (env0 + e < s.n) L.draw_order[e][w] = reinterpret_cast<const uint32_t*>(&EB(s, EB_DRAW, 0, env0 + e))[w];
+        }
+    }
+    static PG_D void load(const State& s, int env, Regs& r, PrepEnv& out) {
+        r.cam = Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), 64.0f, 64.0f, 0.5f * 64.0f / 64.0f};
+        r.game_words[GW_CAM_X] = __float_as_uint(r.cam.px);
+        r.game_words[GW_CAM_Y] = __float_as_uint(r.cam.py);
+        r.backdrop = SI(s, I_BACKDROP, env);
+        r.bgshift = SF(s, F_BGSHIFT, env);
+        const int sflags = SI(s, I_FLAGS, env);
+        PrepEnv pe{};
+        pe.n_draw = (sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;  // empty right after a reset
+        pe.s_count = SI(s, I_SCOUNT, env);
+        out = pe;
+        r.game_words[GW_SHOTS] = pack_halves(SI(s, I_SNEXT, env), pe.s_count);
+        r.game_words[GW_SHIP_X] = __float_as_uint(SF(s, F_AX, env));
+        r.game_words[GW_SHIP_Y] = __float_as_uint(SF(s, F_AY, env));
+        r.game_words[GW_SHIP_SN] = __float_as_uint(SF(s, F_SHIP_SN, env));
+        r.game_words[GW_SHIP_CS] = __float_as_uint(SF(s, F_SHIP_CS, env));
+    }
+    static PG_D bool view(const int4* desc, const Regs& r, int, PrepView& v, uint32_t& soft, uint32_t& hard, uint32_t* meta, Lds&, int) {
+        const int4 d = desc[kTexSpace + r.backdrop];
+        v.bg = backdrop_draw(d, r.bgshift);  // caveflyer.cpp:427-432
+        const int4 wall_d = desc[kTexWall];
+        v.tw = wall_d.y;
+        v.th = wall_d.z;
+        v.th2 = 0;
+        v.tile_scale = kUnitPx / wall_d.y;
+        soft = static_cast<uint32_t>(soft_rows_of(d.w, wall_d.w));
+        hard = static_cast<uint32_t>(hard_rows_of(d.w, wall_d.w));
+#pragma unroll
+        for (int k = 0; k < kPrepKinds; k++) meta[PM_KINDS + k] = kNoTexel;
+        meta[PM_KINDS + 0] = static_cast<uint32_t>(wall_d.x) * 4u;  // the one tile kind
+#pragma unroll
+        for (int k = 0; k < 7; k++) meta[PM_GAME + k] = r.game_words[k];
+        return false;
+    }
+    static PG_D const uint8_t* tiles(const State& s, int env) { return s.tiles + size_t(env) * kTileStride; }
+    static PG_D uint32_t kinds(uint32_t raw, const Lds&, int, uint32_t& kind_bytes) {  // wall → 0, empty → none
+        const uint32_t t = raw & 0x07070707u;
+        const uint32_t any = (t | (t >> 1) | (t >> 2)) & 0x01010101u;  // 1 where the cell is not empty
+        kind_bytes = ~(any * 0xffu);                                  // kind 0 for walls; 0xff: no tile
+        return 0u;
+    }
+    // The positive-z sprites (common_systems.cpp:26-48: goal, meteors, targets, enemies) in draw order.
+    static PG_D int count(const PrepEnv& pe) { return pe.n_draw; }
+    static PG_D DrawCall draw(const State& s, const Lds& L, const int4* desc, int e, int env, int slot) {
+        const int ent = (L.draw_order[e][slot >> 2] >> (8 * (slot & 3))) & 0xffu;
+        const int kind = EB(s, EB_INFO, ent, env) & kKindMask;
+        const float ex = EF(s, EF_X, ent, env), ey = EF(s, EF_Y, ent, env);
+        return sprite_draw(kind, ex, ey, desc[kTexKind + kind]);
+    }
+    // (the render wave's one pass: particles, these sprites, the bullets, the ship — 64 lanes)
+    static PG_D int close(int done, bool on, const PrepEnv& pe, bool, uint32_t*) {
+        const int room = 64 - kPuffs - 1 - (on ? pe.s_count : 0);
+        return done > room ? kPrepDraws + 1 : done;
+    }
 };
 
 __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView atlas, const uint8_t* mask, int flags) {
-    __shared__ SetupLds S;
-    PrepLds<kGrid, kPrepEnvs, kSpan>& P = S.P;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int env0 = prep_block(blockIdx.x, gridDim.x) * kPrepEnvs;  // (pg_prepass.h: the groups of one XCD are consecutive)
-    const PrepOut& out = s.prep;
-
-    // ---- one memory round trip: descriptor table, the envs' scalars (lane = env), their draw orders
-    for (int q = tid; q < kPrepEnvs * 2 * 64; q += kPrepThreads) (&P.cover[0][0][0])[q] = 0u;
-    if (tid < kTexCount) S.desc[tid] = atlas.desc[tid];
-    static_assert(kTexCount <= kPrepThreads && kPrepEnvs * (kEntStride / 4) <= kPrepThreads, "one word per thread");
-    if (tid < kPrepEnvs * (kEntStride / 4)) {
-        const int e = tid / (kEntStride / 4), w = tid - e * (kEntStride / 4);
-        if (env0 + e < s.n) S.draw_order[e][w] = reinterpret_cast<const uint32_t*>(&EB(s, EB_DRAW, 0, env0 + e))[w];
-    }
-    Camera cam{};
-    int backdrop = 0;
-    float bgshift = 0.0f;
-    bool active = false;
-    uint32_t game_words[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    if (tid < kPrepEnvs) {
-        const int e = tid, env = env0 + e;
-        active = env < s.n && (!mask || mask[env]);
-        if (active) {
-            cam = Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), 64.0f, 64.0f, 0.5f * 64.0f / 64.0f};
-            game_words[GW_CAM_X] = __float_as_uint(cam.px);
-            game_words[GW_CAM_Y] = __float_as_uint(cam.py);
-            backdrop = SI(s, I_BACKDROP, env);
-            bgshift = SF(s, F_BGSHIFT, env);
-            const int sflags = SI(s, I_FLAGS, env);
-            PrepEnv pe{};
-            pe.n_draw = (sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;  // empty right after a reset
-            pe.s_count = SI(s, I_SCOUNT, env);
-            S.env[e] = pe;
-            game_words[GW_SHOTS] = pack_halves(SI(s, I_SNEXT, env), pe.s_count);
-            game_words[GW_SHIP_X] = __float_as_uint(SF(s, F_AX, env));
-            game_words[GW_SHIP_Y] = __float_as_uint(SF(s, F_AY, env));
-            game_words[GW_SHIP_SN] = __float_as_uint(SF(s, F_SHIP_SN, env));
-            game_words[GW_SHIP_CS] = __float_as_uint(SF(s, F_SHIP_CS, env));
-        }
-    }
-    __syncthreads();
-    // ---- per env (lane = env): camera, tile window, background draw — render_full's preamble
-    if (tid < kPrepEnvs) {
-        const int e = tid;
-        PrepView v{};
-        P.fat[e] = 0;
-        P.soft_rows[e] = P.hard_rows[e] = 0;
-        S.counts[e] = 0;
-        if (active) {
-            v.cam = cam;
-            const int4 d = S.desc[kTexSpace + backdrop];
-            v.bg = backdrop_draw(d, bgshift);  // caveflyer.cpp:427-432
-            const TileWindow win = tile_window(cam);  // tilemap.cpp:280-289
-            v.x0 = win.x0;
-            v.y0 = win.y0;
-            v.cols = win.x1 - win.x0 + 1;
-            v.rows = win.y1 - win.y0 + 1;
-            const int4 wall_d = S.desc[kTexWall];
-            v.tw = wall_d.y;
-            v.th = wall_d.z;
-            v.th2 = 0;
-            v.tile_scale = kUnitPx / wall_d.y;
-            if (v.cols > kGrid || v.rows > kGrid || ((flags & kDebugFatThirds) && (env0 + e) % 3 == 0)) {
-                P.fat[e] = 1;
-                active = false;
-            }
-            P.soft_rows[e] = static_cast<uint32_t>(soft_rows_of(d.w, wall_d.w));
-            P.hard_rows[e] = static_cast<uint32_t>(hard_rows_of(d.w, wall_d.w));
-#pragma unroll
-            for (int k = 0; k < kPrepKinds; k++) P.meta[e][PM_KINDS + k] = kNoTexel;
-            P.meta[e][PM_KINDS + 0] = static_cast<uint32_t>(wall_d.x) * 4u;  // the one tile kind
-#pragma unroll
-            for (int k = 0; k < 7; k++) P.meta[e][PM_GAME + k] = game_words[k];
-            prep_row_valid<kGrid, H>(v.y0, S.row_valid[e]);
-        }
-        v.active = active ? 1 : 0;
-        P.view[e] = v;
-    }
-    __syncthreads();
-
-    // ---- the cell table: lane = (env, grid column), one 16-byte load of the column-major map (pg_prepass.h) …
-    const int cell_e = tid / kGrid, cell_c = tid - cell_e * kGrid;
-    bool cell_lane = false, cell_x_ok = false;
-    uint32_t column[kGrid / 4] = {};
-    if (tid < kPrepEnvs * kGrid && P.view[cell_e].active) {
-        cell_lane = true;
-        prep_column_fetch<kGrid, W, H>(s.tiles + size_t(env0 + cell_e) * kTileStride, P.view[cell_e].x0 + cell_c, P.view[cell_e].y0, cell_x_ok, column);
-    }
-    // … the spans are worked out while it travels …
-    prep_spans<kGrid, kSpan, kPrepEnvs>(P, tid, kPrepThreads);
-    // … then the kind bytes: wall → 0, empty → none
-    if (cell_lane) {
-        uint32_t in_rows[kGrid / 4], kinds[kGrid / 4];
-        prep_column_rows<kGrid>(column, S.row_valid[cell_e], cell_x_ok, kWall, in_rows);  // out of bounds is a wall (tilemap.h:78-83)
-#pragma unroll
-        for (int w = 0; w < kGrid / 4; w++) {
-            const uint32_t t = in_rows[w] & 0x07070707u;
-            const uint32_t any = (t | (t >> 1) | (t >> 2)) & 0x01010101u;  // 1 where the cell is not empty
-            kinds[w] = ~(any * 0xffu);                                    // kind 0 for walls; 0xff: no tile
-        }
-        prep_column_store<kGrid>(out.cells + size_t(env0 + cell_e) * (kGrid * kGrid), cell_c, kinds);
-    }
-    __syncthreads();
-    prep_axes<kGrid, kSpan, kPrepEnvs>(P, out, env0, wave, kPrepThreads / 64, lane);
-
-    // ---- the positive-z sprites (common_systems.cpp:26-48: goal, meteors, targets, enemies) in draw order.  Two envs per
-    // wavefront, cull first (pg_prepass.h prep_draws_pass).
-    static_assert(kPrepEnvs == 2 * (kPrepThreads / 64), "two envs per wavefront");
-    {
-        const int ea = 2 * wave, eb = 2 * wave + 1;
-        const bool on_a = P.view[ea].active != 0, on_b = P.view[eb].active != 0;
-        const Camera cam_a = P.view[ea].cam, cam_b = P.view[eb].cam;
-        const int cnt_a = on_a ? S.env[ea].n_draw : 0, cnt_b = on_b ? S.env[eb].n_draw : 0;
-        uint32_t* const draws_a = out.draws + size_t(env0 + ea) * kPrepDraws * kBlitWords;
-        uint32_t* const draws_b = out.draws + size_t(env0 + eb) * kPrepDraws * kBlitWords;
-        PrepDrawPass st{0, {0, 0}, {0, 0}};
-        PrepDrawQueue& Q = S.queue[wave];
-        for (int base = 0; base < cnt_a + cnt_b; base += 64) {  // wave-uniform
-            const int q = base + lane;
-            const bool is_b = q >= cnt_a;
-            const int e = is_b ? eb : ea, env = env0 + e;
-            const int slot = is_b ? q - cnt_a : q;
-            const bool valid = q < cnt_a + cnt_b;
-            DrawCall p = kNoDraw;
-            if (valid) {
-                const int ent = (S.draw_order[e][slot >> 2] >> (8 * (slot & 3))) & 0xffu;
-                const int kind = EB(s, EB_INFO, ent, env) & kKindMask;
-                const float ex = EF(s, EF_X, ent, env), ey = EF(s, EF_Y, ent, env);
-                p = sprite_draw(kind, ex, ey, S.desc[kTexKind + kind]);
-            }
-            prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane);
-        }
-        prep_draws_flush(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, lane);
-        if (lane == 0) {  // (the render wave's one pass: particles, these sprites, the bullets, the ship — 64 lanes)
-            const int room_a = 64 - kPuffs - 1 - (on_a ? S.env[ea].s_count : 0), room_b = 64 - kPuffs - 1 - (on_b ? S.env[eb].s_count : 0);
-            S.counts[ea] = st.done[0] > room_a ? kPrepDraws + 1 : st.done[0];
-            S.counts[eb] = st.done[1] > room_b ? kPrepDraws + 1 : st.done[1];
-        }
-    }
-    __syncthreads();
-    prep_meta_out<kGrid, kSpan, kPrepEnvs>(P, out, env0, S.counts, tid, kPrepThreads);
+    __shared__ SetupLds<Setup> S;
+    prep_setup<Setup>(S, s, atlas, mask, flags);
 }
 
 // render_game(true) (caveflyer.cpp:413-440): one workgroup of two wavefronts per env; a lean frame starts from what
@@ -1322,8 +1249,7 @@ class CaveflyerGame final : public PrefetchingGame<Gen> {
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
     void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_.prep, n); }
     void launch_prepass(hipStream_t st, const uint8_t* mask) override {
-        if (!(debug_flags & (1 | kDebugNoPrepass)))
-            hipLaunchKernelGGL(setup_kernel, dim3((s_.n + kPrepEnvs - 1) / kPrepEnvs), dim3(kPrepThreads), 0, st, s_, atlas_, mask, debug_flags);
+        prep_launch(setup_kernel, st, s_, atlas_, mask, debug_flags);
     }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);

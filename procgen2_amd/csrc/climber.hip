@@ -667,173 +667,79 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The render pre-pass (pg_prepass.h; coinrun.hip's setup_kernel is the commented model): tile spans, per-pixel
+// The render pre-pass (pg_prepass.h prep_setup: the kernel; here what is climber's own): tile spans, per-pixel
 // candidates, the cell table and the resolved, culled draws of kPrepEnvs envs per workgroup.
-// Reference arithmetic moved here unchanged: renderer.cpp:5-82, tilemap.cpp:172-198 (the window),
-// common_systems.cpp:41-63,272-298 (sprites, agent).
+// Reference arithmetic moved here unchanged: tilemap.cpp:172-198 (the window), common_systems.cpp:41-63,272-298
+// (sprites, agent).
 // ------------------------------------------------------------------------------------------------
-constexpr int kPrepEnvs = 8, kPrepThreads = 256;
-
 struct PrepEnv {
     int32_t sflags, n_draw, suit;
     float avx, aphase, ax, ay;
 };
-struct SetupLds {
-    PrepLds<kGrid, kPrepEnvs, kMaxSpan> P;
-    PrepEnv env[kPrepEnvs];
-    int4 desc[kTexCount];
-    uint32_t draw_order[kPrepEnvs][kEntStride / 4];  // EB_DRAW of every env: fetched before anything needs it
-    uint32_t row_valid[kPrepEnvs][kGrid / 4];
-    int32_t counts[kPrepEnvs];
-    PrepDrawQueue queue[kPrepThreads / 64];
+struct Setup : PrepPlain {
+    using State = climber::State;
+    static constexpr int kGrid = climber::kGrid, kSpan = kMaxSpan, kW = W, kH = H, kTexCount = climber::kTexCount, kOob = kWallMid;
+    static constexpr bool kTwo = true;
+    struct Lds {
+        PrepEnv env[kPrepEnvs];
+        uint32_t draw_order[kPrepEnvs][kEntStride / 4];  // EB_DRAW of every env
+    };
+    struct Regs {
+        Camera cam;
+        int themes;
+        float bgshift;
+    };
+    static PG_D void stage(Lds& L, const State& s, int env0, int tid) {
+        static_assert(kPrepEnvs * (kEntStride / 4) <= kPrepThreads, "one word per thread");
+        if (tid < kPrepEnvs * (kEntStride / 4)) {
+            const int e = tid / (kEntStride / 4), w = tid - e * (kEntStride / 4);
+            if (env0 + e < s.n) L.draw_order[e][w] = reinterpret_cast<const uint32_t*>(&EB(s, EB_DRAW, 0, env0 + e))[w];
+        }
+    }
+    static PG_D void load(const State& s, int env, Regs& r, PrepEnv& out) {
+        r.cam = Camera{W / 2.0f * kUnitPx, SF(s, F_CAMY, env), 64.0f, 64.0f, 0.2f * 64.0f / 64.0f};
+        r.themes = SI(s, I_THEMES, env);
+        r.bgshift = SF(s, F_BGSHIFT, env);
+        PrepEnv pe{};
+        pe.sflags = SI(s, I_FLAGS, env);
+        pe.n_draw = (pe.sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;  // empty right after a reset (D2)
+        pe.suit = (r.themes >> 8) & 0xff;
+        pe.avx = SF(s, F_AVX, env);
+        pe.aphase = SF(s, F_APHASE, env);
+        pe.ax = SF(s, F_AX, env);
+        pe.ay = SF(s, F_AY, env);
+        out = pe;
+    }
+    static PG_D bool view(const int4* desc, const Regs& r, int, PrepView& v, uint32_t& soft, uint32_t& hard, uint32_t* meta, Lds&, int) {
+        const int backdrop = r.themes & 0xff, theme = (r.themes >> 16) & 0xff;
+        const int4 d = desc[kTexBackdrop + backdrop];
+        v.bg = backdrop_draw(d, r.bgshift);  // climber.cpp:447-452
+        return prep_view_cap_body(d, desc[kTexTop + theme], desc[kTexMid + theme], v, soft, hard, meta);
+    }
+    static PG_D const uint8_t* tiles(const State& s, int env) { return s.tiles + size_t(env) * (W * H); }
+    static PG_D uint32_t kinds(uint32_t raw, const Lds&, int, uint32_t& kind_bytes) {  // kEmpty 0, kWallTop 1, kWallMid 2
+        kind_bytes = prep_kinds_cap_body(raw);
+        return 0u;
+    }
+    // The draws in the reference's order: the positive-z sprites (common_systems.cpp:41-63), then the agent (:272-298).
+    static PG_D int count(const PrepEnv& pe) { return pe.n_draw + 1; }
+    static PG_D DrawCall draw(const State& s, const Lds& L, const int4* desc, int e, int env, int slot) {
+        const PrepEnv& pe = L.env[e];
+        if (slot < pe.n_draw) {
+            const int ent = (L.draw_order[e][slot >> 2] >> (8 * (slot & 3))) & 0xffu;
+            const int info = EB(s, EB_INFO, ent, env);
+            const float ex = EF(s, EF_X, ent, env), ey = EF(s, EF_Y, ent, env);
+            const int tex = entity_tex(info);
+            return entity_draw(info, ex, ey, tex, desc[tex]);
+        }
+        const int tex = agent_tex(pe.sflags, pe.avx, pe.aphase, pe.suit);
+        return agent_draw(pe.sflags, pe.ax, pe.ay, tex, desc[tex]);
+    }
 };
 
 __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView atlas, const uint8_t* mask, int flags) {
-    __shared__ SetupLds S;
-    PrepLds<kGrid, kPrepEnvs, kMaxSpan>& P = S.P;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int env0 = prep_block(blockIdx.x, gridDim.x) * kPrepEnvs;  // (pg_prepass.h: the groups of one XCD are consecutive)
-    const PrepOut& out = s.prep;
-
-    // ---- one memory round trip: descriptor table, the envs' scalars (lane = env), their draw orders
-    for (int q = tid; q < kPrepEnvs * 2 * 64; q += kPrepThreads) (&P.cover[0][0][0])[q] = 0u;
-    if (tid < kTexCount) S.desc[tid] = atlas.desc[tid];
-    static_assert(kTexCount <= kPrepThreads, "one descriptor per thread");
-    if (tid < kPrepEnvs * (kEntStride / 4)) {
-        const int e = tid / (kEntStride / 4), w = tid - e * (kEntStride / 4);
-        if (env0 + e < s.n) S.draw_order[e][w] = reinterpret_cast<const uint32_t*>(&EB(s, EB_DRAW, 0, env0 + e))[w];
-    }
-    Camera cam{};
-    int themes = 0;
-    float bgshift = 0.0f;
-    bool active = false;
-    if (tid < kPrepEnvs) {
-        const int e = tid, env = env0 + e;
-        active = env < s.n && (!mask || mask[env]);
-        if (active) {
-            cam = Camera{W / 2.0f * kUnitPx, SF(s, F_CAMY, env), 64.0f, 64.0f, 0.2f * 64.0f / 64.0f};
-            themes = SI(s, I_THEMES, env);
-            bgshift = SF(s, F_BGSHIFT, env);
-            PrepEnv pe{};
-            pe.sflags = SI(s, I_FLAGS, env);
-            pe.n_draw = (pe.sflags & kFlagListed) ? SI(s, I_NDRAW, env) : 0;  // empty right after a reset (D2)
-            pe.suit = (themes >> 8) & 0xff;
-            pe.avx = SF(s, F_AVX, env);
-            pe.aphase = SF(s, F_APHASE, env);
-            pe.ax = SF(s, F_AX, env);
-            pe.ay = SF(s, F_AY, env);
-            S.env[e] = pe;
-        }
-    }
-    __syncthreads();
-    // ---- per env (lane = env): camera, tile window, background draw — render_full's preamble
-    if (tid < kPrepEnvs) {
-        const int e = tid;
-        PrepView v{};
-        P.fat[e] = 0;
-        P.soft_rows[e] = P.hard_rows[e] = 0;
-        S.counts[e] = 0;
-        if (active) {
-            v.cam = cam;
-            const int backdrop = themes & 0xff, theme = (themes >> 16) & 0xff;
-            const int4 d = S.desc[kTexBackdrop + backdrop];
-            v.bg = backdrop_draw(d, bgshift);  // climber.cpp:447-452
-            const TileWindow win = tile_window(cam);  // tilemap.cpp:172-181
-            v.x0 = win.x0;
-            v.y0 = win.y0;
-            v.cols = win.x1 - win.x0 + 1;
-            v.rows = win.y1 - win.y0 + 1;
-            const int4 top_d = S.desc[kTexTop + theme], mid_d = S.desc[kTexMid + theme];
-            const bool two = top_d.z != mid_d.z;  // the brown theme's cap tile is 64×53 next to 64×64 bodies
-            v.tw = mid_d.y;
-            v.th = mid_d.z;
-            v.th2 = two ? top_d.z : 0;
-            v.tile_scale = kUnitPx / mid_d.y;
-            if (v.cols > kGrid || v.rows > kGrid || top_d.y != mid_d.y || top_d.z > mid_d.z || ((flags & kDebugFatThirds) && (env0 + e) % 3 == 0)) {
-                P.fat[e] = 1;
-                active = false;
-            }
-            P.soft_rows[e] = static_cast<uint32_t>(soft_rows_of(d.w, top_d.w | mid_d.w));
-            P.hard_rows[e] = static_cast<uint32_t>(hard_rows_of(d.w, mid_d.w));  // (cap tiles are few: always worth the attempt)
-            // tile kinds: 0 = cap (bit 0 of its offset: the layer's second texture), 1 = body
-#pragma unroll
-            for (int k = 0; k < kPrepKinds; k++) P.meta[e][PM_KINDS + k] = kNoTexel;
-            P.meta[e][PM_KINDS + 0] = (static_cast<uint32_t>(top_d.x) * 4u) | (two ? 1u : 0u);
-            P.meta[e][PM_KINDS + 1] = static_cast<uint32_t>(mid_d.x) * 4u;
-            prep_row_valid<kGrid, H>(v.y0, S.row_valid[e]);
-        }
-        v.active = active ? 1 : 0;
-        P.view[e] = v;
-    }
-    __syncthreads();
-
-    // ---- the cell table: lane = (env, grid column), the column's 24 bytes of the column-major map (pg_prepass.h) …
-    static_assert(kPrepEnvs * kGrid <= kPrepThreads, "one window column per thread");
-    const int cell_e = tid / kGrid, cell_c = tid - cell_e * kGrid;
-    bool cell_lane = false, cell_x_ok = false;
-    uint32_t column[kGrid / 4] = {};
-    if (tid < kPrepEnvs * kGrid && P.view[cell_e].active) {
-        cell_lane = true;
-        prep_column_fetch<kGrid, W, H>(s.tiles + size_t(env0 + cell_e) * (W * H), P.view[cell_e].x0 + cell_c, P.view[cell_e].y0, cell_x_ok, column);
-    }
-    // … the spans are worked out while it travels …
-    prep_spans<kGrid, kMaxSpan, kPrepEnvs, true>(P, tid, kPrepThreads);
-    // … then the kind bytes: wall_top → 0, wall_mid → 1, empty → none
-    if (cell_lane) {
-        uint32_t in_rows[kGrid / 4], kinds[kGrid / 4];
-        prep_column_rows<kGrid>(column, S.row_valid[cell_e], cell_x_ok, kWallMid, in_rows);  // out of bounds is a wall (tilemap.h:66-68)
-#pragma unroll
-        for (int w = 0; w < kGrid / 4; w++) {
-            const uint32_t t = in_rows[w] & 0x07070707u;  // kEmpty 0, kWallTop 1, kWallMid 2
-            const uint32_t lo = t & 0x01010101u, hi = (t >> 1) & 0x01010101u;
-            const uint32_t wall = (lo ^ hi) * 0xffu;  // 0xff where t is 1 or 2
-            kinds[w] = (hi & wall) | ~wall;           // kind = t - 1 for walls; 0xff: no tile
-        }
-        prep_column_store<kGrid>(out.cells + size_t(env0 + cell_e) * (kGrid * kGrid), cell_c, kinds);
-    }
-    __syncthreads();
-    prep_axes<kGrid, kMaxSpan, kPrepEnvs>(P, out, env0, wave, kPrepThreads / 64, lane);
-
-    // ---- the draws in the reference's order: the positive-z sprites (common_systems.cpp:41-63), then the agent
-    // (:272-298).  Two envs per wavefront, cull first (pg_prepass.h prep_draws_pass).
-    static_assert(kPrepEnvs == 2 * (kPrepThreads / 64), "two envs per wavefront");
-    {
-        const int ea = 2 * wave, eb = 2 * wave + 1;
-        const bool on_a = P.view[ea].active != 0, on_b = P.view[eb].active != 0;
-        const Camera cam_a = P.view[ea].cam, cam_b = P.view[eb].cam;
-        const int cnt_a = on_a ? S.env[ea].n_draw + 1 : 0, cnt_b = on_b ? S.env[eb].n_draw + 1 : 0;
-        uint32_t* const draws_a = out.draws + size_t(env0 + ea) * kPrepDraws * kBlitWords;
-        uint32_t* const draws_b = out.draws + size_t(env0 + eb) * kPrepDraws * kBlitWords;
-        PrepDrawPass st{0, {0, 0}, {0, 0}};
-        PrepDrawQueue& Q = S.queue[wave];
-        for (int base = 0; base < cnt_a + cnt_b; base += 64) {  // wave-uniform
-            const int q = base + lane;
-            const bool is_b = q >= cnt_a;
-            const int e = is_b ? eb : ea, env = env0 + e;
-            const int slot = is_b ? q - cnt_a : q;
-            const bool valid = q < cnt_a + cnt_b;
-            const PrepEnv& pe = S.env[e];
-            DrawCall p = kNoDraw;
-            if (valid && slot < pe.n_draw) {
-                const int ent = (S.draw_order[e][slot >> 2] >> (8 * (slot & 3))) & 0xffu;
-                const int info = EB(s, EB_INFO, ent, env);
-                const float ex = EF(s, EF_X, ent, env), ey = EF(s, EF_Y, ent, env);
-                const int tex = entity_tex(info);
-                p = entity_draw(info, ex, ey, tex, S.desc[tex]);
-            } else if (valid) {
-                const int tex = agent_tex(pe.sflags, pe.avx, pe.aphase, pe.suit);
-                p = agent_draw(pe.sflags, pe.ax, pe.ay, tex, S.desc[tex]);
-            }
-            prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane);
-        }
-        prep_draws_flush(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, lane);
-        if (lane == 0) {
-            S.counts[ea] = st.done[0];
-            S.counts[eb] = st.done[1];
-        }
-    }
-    __syncthreads();
-    prep_meta_out<kGrid, kMaxSpan, kPrepEnvs>(P, out, env0, S.counts, tid, kPrepThreads);
+    __shared__ SetupLds<Setup> S;
+    prep_setup<Setup>(S, s, atlas, mask, flags);
 }
 
 // render_game(true) (climber.cpp:431-459): one workgroup of two wavefronts per env; a lean frame starts from what
@@ -983,8 +889,7 @@ class ClimberGame final : public PrefetchingGame<Gen> {
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
     void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_.prep, n); }
     void launch_prepass(hipStream_t st, const uint8_t* mask) override {
-        if (!(debug_flags & (1 | kDebugNoPrepass)))
-            hipLaunchKernelGGL(setup_kernel, dim3((s_.n + kPrepEnvs - 1) / kPrepEnvs), dim3(kPrepThreads), 0, st, s_, atlas_, mask, debug_flags);
+        prep_launch(setup_kernel, st, s_, atlas_, mask, debug_flags);
     }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);

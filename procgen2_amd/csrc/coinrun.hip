@@ -1449,27 +1449,126 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The render pre-pass (pg_prepass.h): tile spans, per-pixel candidates, the cell table and the resolved, culled draws
-// of kPrepEnvs envs per workgroup, every phase with its lanes dealt densely over (env, thing).
-// Reference arithmetic moved here unchanged: renderer.cpp:5-82 (render_texture), tilemap.cpp:294-321 (the tile window),
-// common_systems.cpp:41-63,254-278,315-337 (sprites, agent, particles).
+// The render pre-pass (pg_prepass.h prep_setup: the kernel; here what is coinrun's own): tile spans, per-pixel
+// candidates, the cell table and the resolved, culled draws of kPrepEnvs envs per workgroup.
+// Reference arithmetic moved here unchanged: tilemap.cpp:294-321 (the tile window), common_systems.cpp:41-63,254-278,315-337
+// (sprites, agent, particles).
 // ------------------------------------------------------------------------------------------------
-constexpr int kPrepEnvs = 8, kPrepThreads = 256;
 constexpr int kSlotTop = 0, kSlotMid = 1, kSlotLavaTop = 2, kSlotLava = 3, kSlotCrate = 4;  // cell bytes: tile kinds
 
 struct PrepEnv {  // per env of the workgroup: what the draws' lanes need, loaded once
     int32_t sflags, buf, n_ent, n_mob, n_sprites, alien;
     float avx, aphase, ax, ay;
 };
-struct SetupLds {
-    PrepLds<kGrid, kPrepEnvs, kMaxSpan> P;
-    PrepEnv env[kPrepEnvs];
-    int4 desc[kTexCount];                    // the atlas descriptor table: every later lookup is an LDS read
-    uint8_t order[kPrepEnvs][2][kMaxEnt + 4];  // EB_SPARK_ORDER, EB_DRAW_ORDER of every env (fetched before anything needs them)
-    int32_t kind_soft[kPrepEnvs];            // bit k: tile kind k's texture has texels that are not opaque
-    uint32_t row_valid[kPrepEnvs][kGrid / 4];              // byte i: 0xff if map row ty_lo + i of the env's window exists (cells below)
-    int32_t counts[kPrepEnvs];
-    PrepDrawQueue queue[kPrepThreads / 64];  // one worklist per wavefront
+struct Setup : PrepPlain {
+    using State = coinrun::State;
+    static constexpr int kGrid = coinrun::kGrid, kSpan = kMaxSpan, kW = W, kH = H, kTexCount = coinrun::kTexCount, kOob = kWallMid;
+    static constexpr bool kTwo = false;
+    static_assert(kGrid == 16 && H == 64, "a window column is one 16-byte load");
+    struct Lds {
+        PrepEnv env[kPrepEnvs];
+        uint8_t order[kPrepEnvs][2][kMaxEnt + 4];  // EB_SPARK_ORDER, EB_DRAW_ORDER of every env
+        int32_t kind_soft[kPrepEnvs];              // bit k: tile kind k's texture has texels that are not opaque
+    };
+    struct Regs {
+        Camera cam;
+        int themes, redo;
+        float bgshift;
+    };
+    static PG_D void stage(Lds& L, const State& s, int env0, int tid) {  // lane = (env, slot)
+        for (int q = tid; q < kPrepEnvs * 2 * kMaxEnt; q += kPrepThreads) {
+            const int e = q / (2 * kMaxEnt), r = q - e * (2 * kMaxEnt), which = r / kMaxEnt, j = r - which * kMaxEnt;
+            if (env0 + e < s.n) L.order[e][which][j] = EB(s, which ? EB_DRAW_ORDER : EB_SPARK_ORDER, j, env0 + e);
+        }
+    }
+    static PG_D void load(const State& s, int env, Regs& r, PrepEnv& out) {
+        r.redo = SCI(s, SC_REDO, env);
+        r.cam = Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), 64.0f, 64.0f, 0.3f * 64.0f / 64.0f};
+        r.themes = SI(s, I_THEMES, env);
+        r.bgshift = SF(s, F_BGSHIFT, env);
+        PrepEnv pe{};
+        pe.sflags = SI(s, I_FLAGS, env);
+        pe.buf = (pe.sflags & kFlagBuf) ? 1 : 0;
+        pe.n_ent = SI(s, I_NENT, env);
+        pe.n_mob = SI(s, I_NMOB, env);
+        pe.n_sprites = (pe.sflags & kFlagListed) ? pe.n_ent : 0;  // the draw list is empty until the first update (D2)
+        pe.alien = (r.themes >> 8) & 0xff;
+        pe.avx = SF(s, F_AVX, env);
+        pe.aphase = SF(s, F_APHASE, env);
+        pe.ax = SF(s, F_AX, env);
+        pe.ay = SF(s, F_AY, env);
+        out = pe;
+    }
+    static PG_D bool early_end(const Regs& r) { return r.redo != 0; }  // the step ended early: the entity table is not final (resolve_kernel)
+    static PG_D bool view(const int4* desc, const Regs& r, int flags, PrepView& v, uint32_t& soft, uint32_t& hard, uint32_t* meta, Lds& L, int e) {
+        // (bit 4: timing experiment of the -DPG_ABLATE build — every env shows backdrop 9, the bound on what keeping
+        // the backdrops' texels closer to the workgroups that sample them could buy: render FETCH_SIZE 309 -> 45 MB,
+        // render 0.350 -> 0.333 ms)
+        const int4 d = desc[kTexBackdrop + (PG_ABL(flags, 16) ? 9 : (r.themes & 0xff))];
+        v.bg = backdrop_draw(d, r.bgshift);  // coinrun.cpp:459-464
+        const int4 tile_desc = desc[kTexMid];  // every tile texture is 128×128 (checked at make time)
+        v.tw = tile_desc.y;
+        v.th = tile_desc.z;
+        v.th2 = 0;
+        v.tile_scale = kUnitPx / tile_desc.y;
+        soft = d.w != 0 ? 0x80000000u : 0u;   // 9 of the 49 backdrops have texels that are not opaque
+        hard = (d.w & 2) ? 0x80000000u : 0u;  // … mostly cut-out: no one-texel attempt
+        // the tile kinds' textures
+        const int ground_theme = (r.themes >> 16) & 0xff;
+        int kind_soft = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int4 kd = desc[kind_tex(k, ground_theme)];
+            meta[PM_KINDS + k] = static_cast<uint32_t>(kd.x) * 4u;
+            if (kd.w != 0) kind_soft |= 1 << k;
+        }
+        L.kind_soft[e] = kind_soft;
+        return false;
+    }
+    static PG_D const uint8_t* tiles(const State& s, int env) { return s.tiles + size_t(env) * (W * H); }
+    // window rows 4w .. 4w + 3: raw byte = tile id | crate kind << 4 (crates only)
+    static PG_D uint32_t kinds(uint32_t raw, const Lds& L, int e, uint32_t& kind_bytes) {
+        // soft kinds as a byte table for v_perm: byte k = 0xff if kind k's texture has texels that are not opaque
+        const uint32_t soft_kinds = static_cast<uint32_t>(L.kind_soft[e]);
+        uint32_t soft_lo = 0u, soft_hi = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            soft_lo |= ((soft_kinds >> k) & 1u) ? 0xffu << (8 * k) : 0u;
+            soft_hi |= ((soft_kinds >> (4 + k)) & 1u) ? 0xffu << (8 * k) : 0u;
+        }
+        const uint32_t t = raw & 0x07070707u, crate = (raw >> 4) & 0x03030303u;
+        const uint32_t y = (t | 0x80808080u) - 0x01010101u;          // per byte: 0x7f if empty, else 0x80 + t - 1
+        const uint32_t there = ((y & 0x80808080u) >> 7) * 0xffu;      // 0xff where there is a tile
+        const uint32_t slots = (y & 0x07070707u) + crate;            // kSlotTop .. kSlotLava = t - 1, crates 4 + kind
+        kind_bytes = (slots & there) | ~there;                       // 0xff: no tile
+        const uint32_t sel = (slots & there) | (0x0c0c0c0cu & ~there);  // v_perm selector 0x0c: the constant 0x00
+        const uint32_t soft = __builtin_amdgcn_perm(soft_hi, soft_lo, sel) & 0x01010101u;
+        return (soft * 0x00204081u >> 21) & 0xfu;
+    }
+    // The draws in the reference's order: particles (owners in the particle system's set order), the sprites of the draw
+    // list, the agent.
+    static PG_D int count(const PrepEnv& pe) { return pe.n_mob * kSparks + pe.n_sprites + 1; }
+    static PG_D DrawCall draw(const State& s, const Lds& L, const int4* desc, int e, int env, int slot) {
+        const PrepEnv& pe = L.env[e];
+        const int n_parts = pe.n_mob * kSparks;
+        if (slot < n_parts) {  // System_Particles::render (common_systems.cpp:315-337)
+            const int m = slot / kSparks, k = slot - m * kSparks;
+            const int ent = L.order[e][0][m];
+            const float life = SP(s, pe.buf, 2, ent, k, env);
+            const float px = SP(s, pe.buf, 0, ent, k, env), py = SP(s, pe.buf, 1, ent, k, env);
+            return spark_draw(life, px, py, desc[kTexSpark]);
+        }
+        if (slot < n_parts + pe.n_sprites) {  // System_Sprite_Render::render (:41-63)
+            const int ent = L.order[e][1][slot - n_parts];
+            const int dyn = DB(s, pe.buf, ent, env);
+            const int tex0 = EB(s, EB_TEX, ent, env);
+            const float ex = DF(s, pe.buf, DF_X, ent, env), ey = EY(s, ent, env);
+            const int tex = sprite_tex(tex0, dyn);
+            return sprite_draw(dyn, ex, ey, tex, desc[tex]);
+        }
+        const int tex = agent_tex(pe.sflags, pe.avx, pe.aphase, pe.alien);  // the agent (:254-278)
+        return agent_draw(pe.sflags, pe.ax, pe.ay, tex, desc[tex]);
+    }
 };
 
 // (Measured and rejected, round 5: the pre-pass in two halves — views / cells / spans / axes, which need the step only
@@ -1480,202 +1579,8 @@ struct SetupLds {
 // every one of those slots for their whole 40 µs, and the pre-pass workgroups, dealt behind them, start when they end; and
 // the draws alone are a chain of round trips that the other phases of the same kernel used to hide.)
 __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView atlas, const uint8_t* mask, int flags) {
-    __shared__ SetupLds S;
-    PrepLds<kGrid, kPrepEnvs, kMaxSpan>& P = S.P;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int env0 = prep_block(blockIdx.x, gridDim.x) * kPrepEnvs;
-    const PrepOut& out = s.prep;
-
-    // ---- everything whose address does not depend on another load is requested first: the descriptor table, the envs'
-    // scalars (lane = env), the two entity orders (lane = (env, slot)) — one memory round trip for all of it
-    for (int q = tid; q < kPrepEnvs * 2 * 64; q += kPrepThreads) (&P.cover[0][0][0])[q] = 0u;
-    if (tid < kTexCount) S.desc[tid] = atlas.desc[tid];
-    static_assert(kTexCount <= kPrepThreads, "one descriptor per thread");
-    for (int q = tid; q < kPrepEnvs * 2 * kMaxEnt; q += kPrepThreads) {
-        const int e = q / (2 * kMaxEnt), r = q - e * (2 * kMaxEnt), which = r / kMaxEnt, j = r - which * kMaxEnt;
-        if (env0 + e < s.n) S.order[e][which][j] = EB(s, which ? EB_DRAW_ORDER : EB_SPARK_ORDER, j, env0 + e);
-    }
-    Camera cam{};
-    int themes = 0, redo = 0;
-    float bgshift = 0.0f;
-    bool active = false;
-    if (tid < kPrepEnvs) {
-        const int e = tid, env = env0 + e;
-        active = env < s.n && (!mask || mask[env]);
-        if (active) {
-            redo = SCI(s, SC_REDO, env);
-            cam = Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), 64.0f, 64.0f, 0.3f * 64.0f / 64.0f};
-            themes = SI(s, I_THEMES, env);
-            bgshift = SF(s, F_BGSHIFT, env);
-            PrepEnv pe{};
-            pe.sflags = SI(s, I_FLAGS, env);
-            pe.buf = (pe.sflags & kFlagBuf) ? 1 : 0;
-            pe.n_ent = SI(s, I_NENT, env);
-            pe.n_mob = SI(s, I_NMOB, env);
-            pe.n_sprites = (pe.sflags & kFlagListed) ? pe.n_ent : 0;  // the draw list is empty until the first update (D2)
-            pe.alien = (themes >> 8) & 0xff;
-            pe.avx = SF(s, F_AVX, env);
-            pe.aphase = SF(s, F_APHASE, env);
-            pe.ax = SF(s, F_AX, env);
-            pe.ay = SF(s, F_AY, env);
-            S.env[e] = pe;
-        }
-    }
-    __syncthreads();
-    // ---- per env (lane = env): camera, tile window, background draw — render_full's preamble
-    if (tid < kPrepEnvs) {
-        const int e = tid;
-        PrepView v{};
-        P.fat[e] = 0;
-        P.soft_rows[e] = P.hard_rows[e] = 0;
-        S.counts[e] = 0;
-        S.kind_soft[e] = 0;
-        if (active && redo != 0) {  // the step ended early: the entity table is not final (resolve_kernel)
-            P.fat[e] = 1;
-            active = false;
-        }
-        if (active) {
-            v.cam = cam;
-            // (bit 4: timing experiment of the -DPG_ABLATE build — every env shows backdrop 9, the bound on what keeping
-            // the backdrops' texels closer to the workgroups that sample them could buy: render FETCH_SIZE 309 -> 45 MB,
-            // render 0.350 -> 0.333 ms)
-            const int4 d = S.desc[kTexBackdrop + (PG_ABL(flags, 16) ? 9 : (themes & 0xff))];
-            v.bg = backdrop_draw(d, bgshift);  // coinrun.cpp:459-464
-            const TileWindow win = tile_window(cam);  // tilemap.cpp:294-304
-            v.x0 = win.x0;
-            v.y0 = win.y0;
-            v.cols = win.x1 - win.x0 + 1;
-            v.rows = win.y1 - win.y0 + 1;
-            const int4 tile_desc = S.desc[kTexMid];  // every tile texture is 128×128 (checked at make time)
-            v.tw = tile_desc.y;
-            v.th = tile_desc.z;
-            v.th2 = 0;
-            v.tile_scale = kUnitPx / tile_desc.y;
-            if (v.cols > kGrid || v.rows > kGrid || ((flags & kDebugFatThirds) && (env0 + e) % 3 == 0)) {
-                P.fat[e] = 1;
-                active = false;
-            }
-            P.soft_rows[e] = d.w != 0 ? 0x80000000u : 0u;   // 9 of the 49 backdrops have texels that are not opaque
-            P.hard_rows[e] = (d.w & 2) ? 0x80000000u : 0u;  // … mostly cut-out: no one-texel attempt
-            // the tile kinds' textures
-            const int ground_theme = (themes >> 16) & 0xff;
-            int soft = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int4 kd = S.desc[kind_tex(k, ground_theme)];
-                P.meta[e][PM_KINDS + k] = static_cast<uint32_t>(kd.x) * 4u;
-                    if (kd.w != 0) soft |= 1 << k;
-            }
-            S.kind_soft[e] = soft;
-            prep_row_valid<kGrid, H>(v.y0, S.row_valid[e]);  // which of the 16 map rows under the window exist
-        }
-        v.active = active ? 1 : 0;
-        P.view[e] = v;
-    }
-    __syncthreads();
-    if (PG_ABL(flags, 0x1000000)) return;  // (instruction inventory, -DPG_ABLATE builds only: the views alone)
-
-    // ---- the cell table, first half: lane = (env, grid column).  The map is column-major (tilemap.h:62-85), so the sixteen
-    // cells of a window column are sixteen consecutive bytes — one 16-byte load (unaligned; rows beyond the map's edge
-    // read the neighbouring column or the neighbouring env's map and are replaced below) …
-    static_assert(kGrid == 16 && H == 64, "a window column is one 16-byte load");
-    const int cell_e = tid / kGrid, cell_c = tid - cell_e * kGrid;
-    bool cell_lane = false, cell_x_ok = false;
-    uint32_t column[kGrid / 4] = {};
-    if (tid < kPrepEnvs * kGrid && P.view[cell_e].active) {
-        cell_lane = true;
-        prep_column_fetch<kGrid, W, H>(s.tiles + size_t(env0 + cell_e) * (W * H), P.view[cell_e].x0 + cell_c, P.view[cell_e].y0, cell_x_ok, column);
-    }
-    // … the spans are worked out while it travels …
-    if (!PG_ABL(flags, 0x2000000)) prep_spans<kGrid, kMaxSpan, kPrepEnvs>(P, tid, kPrepThreads);
-    // … second half: sixteen kind bytes, four cells at a time
-    if (cell_lane) {
-        const PrepView& v = P.view[cell_e];
-        uint32_t in_rows[4];
-        prep_column_rows<kGrid>(column, S.row_valid[cell_e], cell_x_ok, kWallMid, in_rows);  // out of bounds is a wall (tilemap.h:80-81)
-        // soft kinds as a byte table for v_perm: byte k = 0xff if kind k's texture has texels that are not opaque
-        const uint32_t soft_kinds = static_cast<uint32_t>(S.kind_soft[cell_e]);
-        uint32_t soft_lo = 0u, soft_hi = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            soft_lo |= ((soft_kinds >> k) & 1u) ? 0xffu << (8 * k) : 0u;
-            soft_hi |= ((soft_kinds >> (4 + k)) & 1u) ? 0xffu << (8 * k) : 0u;
-        }
-        uint32_t kinds[4], soft_rows = 0u;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {  // window rows 4w .. 4w + 3: raw byte = tile id | crate kind << 4 (crates only)
-            const uint32_t raw = in_rows[w];
-            const uint32_t t = raw & 0x07070707u, crate = (raw >> 4) & 0x03030303u;
-            const uint32_t y = (t | 0x80808080u) - 0x01010101u;          // per byte: 0x7f if empty, else 0x80 + t - 1
-            const uint32_t there = ((y & 0x80808080u) >> 7) * 0xffu;      // 0xff where there is a tile
-            const uint32_t slots = (y & 0x07070707u) + crate;            // kSlotTop .. kSlotLava = t - 1, crates 4 + kind
-            kinds[w] = (slots & there) | ~there;                         // 0xff: no tile
-            // the rows that show a soft texture (only the window's own rows and columns count)
-            const uint32_t sel = (slots & there) | (0x0c0c0c0cu & ~there);  // v_perm selector 0x0c: the constant 0x00
-            const uint32_t soft = __builtin_amdgcn_perm(soft_hi, soft_lo, sel) & 0x01010101u;
-            soft_rows |= ((soft * 0x00204081u >> 21) & 0xfu) << (4 * w);
-        }
-        if (cell_c >= v.cols) soft_rows = 0u;
-        soft_rows &= (v.rows >= 32 ? ~0u : (1u << v.rows) - 1u);
-        prep_column_store<kGrid>(out.cells + size_t(env0 + cell_e) * (kGrid * kGrid), cell_c, kinds);
-        if (soft_rows) atomicOr(&P.soft_rows[cell_e], soft_rows);
-    }
-    __syncthreads();
-    if (PG_ABL(flags, 0x4000000)) return;
-    if (!PG_ABL(flags, 0x8000000)) prep_axes<kGrid, kMaxSpan, kPrepEnvs>(P, out, env0, wave, kPrepThreads / 64, lane);
-    if (PG_ABL(flags, 0x10000000)) return;
-
-    // ---- the draws, in the reference's order — particles (owners in the particle system's set order), the sprites of
-    // the draw list, the agent.  A wavefront takes two envs of the workgroup, their lists dealt densely over its passes;
-    // a draw that survives render_texture's cull waits in the wave's worklist for the rest of the arithmetic
-    // (pg_prepass.h prep_draws_pass).
-    static_assert(kPrepEnvs == 2 * (kPrepThreads / 64), "two envs per wavefront");
-    {
-        const int ea = 2 * wave, eb = 2 * wave + 1;
-        const bool on_a = P.view[ea].active != 0, on_b = P.view[eb].active != 0;
-        const Camera cam_a = P.view[ea].cam, cam_b = P.view[eb].cam;
-        const int cnt_a = on_a ? S.env[ea].n_mob * kSparks + S.env[ea].n_sprites + 1 : 0;
-        const int cnt_b = on_b ? S.env[eb].n_mob * kSparks + S.env[eb].n_sprites + 1 : 0;
-        uint32_t* const draws_a = out.draws + size_t(env0 + ea) * kPrepDraws * kBlitWords;
-        uint32_t* const draws_b = out.draws + size_t(env0 + eb) * kPrepDraws * kBlitWords;
-        PrepDrawPass st{0, {0, 0}, {0, 0}};
-        PrepDrawQueue& Q = S.queue[wave];
-        for (int base = 0; base < cnt_a + cnt_b; base += 64) {  // wave-uniform
-            const int q = base + lane;
-            const bool is_b = q >= cnt_a;
-            const int e = is_b ? eb : ea, env = env0 + e;
-            const int slot = is_b ? q - cnt_a : q;
-            const bool valid = q < cnt_a + cnt_b;
-            const PrepEnv& pe = S.env[e];
-            const int n_parts = pe.n_mob * kSparks;
-            DrawCall p = kNoDraw;
-            if (valid && slot < n_parts) {  // System_Particles::render (common_systems.cpp:315-337)
-                const int m = slot / kSparks, k = slot - m * kSparks;
-                const int ent = S.order[e][0][m];
-                const float life = SP(s, pe.buf, 2, ent, k, env);
-                const float px = SP(s, pe.buf, 0, ent, k, env), py = SP(s, pe.buf, 1, ent, k, env);
-                p = spark_draw(life, px, py, S.desc[kTexSpark]);
-            } else if (valid && slot < n_parts + pe.n_sprites) {  // System_Sprite_Render::render (:41-63)
-                const int ent = S.order[e][1][slot - n_parts];
-                const int dyn = DB(s, pe.buf, ent, env);
-                const int tex0 = EB(s, EB_TEX, ent, env);
-                const float ex = DF(s, pe.buf, DF_X, ent, env), ey = EY(s, ent, env);
-                const int tex = sprite_tex(tex0, dyn);
-                p = sprite_draw(dyn, ex, ey, tex, S.desc[tex]);
-            } else if (valid) {  // the agent (:254-278)
-                const int tex = agent_tex(pe.sflags, pe.avx, pe.aphase, pe.alien);
-                p = agent_draw(pe.sflags, pe.ax, pe.ay, tex, S.desc[tex]);
-            }
-            prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane);
-        }
-        prep_draws_flush(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, lane);
-        if (lane == 0) {
-            S.counts[ea] = st.done[0];
-            S.counts[eb] = st.done[1];
-        }
-    }
-    __syncthreads();
-    prep_meta_out<kGrid, kMaxSpan, kPrepEnvs>(P, out, env0, S.counts, tid, kPrepThreads);
+    __shared__ SetupLds<Setup> S;
+    prep_setup<Setup>(S, s, atlas, mask, flags);
 }
 
 // render_game(true) (coinrun.cpp:443-470): one workgroup of two wavefronts per env.  A lean frame starts from what
@@ -1920,8 +1825,7 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
         launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     void launch_prepass(hipStream_t st, const uint8_t* mask) override {
-        if (!(debug_flags & (1 | kDebugNoPrepass)) && !PG_ABL(debug_flags, 1 << 22))  // (experiment: the last frame's pre-pass again)
-            hipLaunchKernelGGL(setup_kernel, dim3((s_.n + kPrepEnvs - 1) / kPrepEnvs), dim3(kPrepThreads), 0, st, s_, atlas_, mask, debug_flags);
+        if (!PG_ABL(debug_flags, 1 << 22)) prep_launch(setup_kernel, st, s_, atlas_, mask, debug_flags);  // (experiment: the last frame's pre-pass again)
     }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(64 * kRenderWaves), 0, st, s_, atlas_, mask, io,

@@ -917,207 +917,121 @@ PG_D void render_full(const State& s, const AtlasView& atlas, const StepIO& io, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The render pre-pass (pg_prepass.h; coinrun.hip's setup_kernel is the commented model): tile spans, per-pixel
+// The render pre-pass (pg_prepass.h prep_setup: the kernel; here what is jumper's own): tile spans, per-pixel
 // candidates, the cell table and the resolved, culled draws of kPrepEnvs envs per workgroup.
-// Reference arithmetic moved here unchanged: renderer.cpp:5-82, tilemap.cpp:255-280 (the window),
-// common_systems.cpp:26-48,204-247,285-308 (sprites, bunny, particles).  The compass stays with the render wave: its
-// ring is a prepared overlay, needle and bar are raw screen-space draws without a division (jumper.cpp:473-509).
+// Reference arithmetic moved here unchanged: tilemap.cpp:255-280 (the window), common_systems.cpp:26-48,204-247,285-308
+// (sprites, bunny, particles).  The compass stays with the render wave: its ring is a prepared overlay, needle and bar
+// are raw screen-space draws without a division (jumper.cpp:473-509).
 // ------------------------------------------------------------------------------------------------
-constexpr int kPrepEnvs = 8, kPrepThreads = 256;
 enum { GW_NEEDLE_X = 0, GW_NEEDLE_Y, GW_BAR_W, GW_NEEDLE_SN, GW_NEEDLE_CS, GW_TOUCH };  // PM_GAME words (GW_TOUCH: a kept draw reaches into the compass disc's box, pg_prepass.h PrepDrawPass::touch)
 
 struct PrepEnv {
     int32_t sflags, n_draw;
     float avx, aphase, ax, ay, gx, gy;
 };
-struct SetupLds {
-    PrepLds<kGrid, kPrepEnvs, kMaxSpan> P;
-    PrepEnv env[kPrepEnvs];
-    int4 desc[kTexCount];
-    uint32_t draw_ids[kPrepEnvs][kSpikeSlots / 4];    // State::draw of every env …
-    uint32_t spike_cells[kPrepEnvs][kSpikeSlots / 2];  // … and State::spike_cell: fetched before anything needs them
-    uint32_t row_valid[kPrepEnvs][kGrid / 4];
-    int32_t counts[kPrepEnvs];
-    PrepDrawQueue queue[kPrepThreads / 64];
+struct Setup : PrepPlain {
+    using State = jumper::State;
+    static constexpr int kGrid = jumper::kGrid, kSpan = kMaxSpan, kW = W, kH = H, kTexCount = jumper::kTexCount, kOob = kWallMid;
+    static constexpr bool kTwo = true;
+    struct Lds {
+        PrepEnv env[kPrepEnvs];
+        uint32_t draw_ids[kPrepEnvs][kSpikeSlots / 4];     // State::draw of every env …
+        uint32_t spike_cells[kPrepEnvs][kSpikeSlots / 2];  // … and State::spike_cell
+    };
+    struct Regs {
+        Camera cam;
+        int themes;
+        float bgshift;
+        uint32_t game_words[5];
+    };
+    static PG_D void stage(Lds& L, const State& s, int env0, int tid) {
+        static_assert(kPrepEnvs * kSpikeSlots / 4 == kPrepThreads, "one word of the draw lists per thread");
+        const int e = tid / (kSpikeSlots / 4), w = tid - e * (kSpikeSlots / 4);
+        if (env0 + e < s.n) {
+            L.draw_ids[e][w] = reinterpret_cast<const uint32_t*>(s.draw + size_t(env0 + e) * kSpikeSlots)[w];
+            const uint32_t* cells = reinterpret_cast<const uint32_t*>(s.spike_cell + size_t(env0 + e) * kSpikeSlots);
+            L.spike_cells[e][2 * w] = cells[2 * w];
+            L.spike_cells[e][2 * w + 1] = cells[2 * w + 1];
+        }
+    }
+    static PG_D void load(const State& s, int env, Regs& r, PrepEnv& out) {
+        r.cam = Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), 64.0f, 64.0f, kObsZoom * 64.0f / 64.0f};
+        r.themes = SI(s, I_THEMES, env);
+        r.bgshift = SF(s, F_BGSHIFT, env);
+        PrepEnv pe{};
+        pe.sflags = SI(s, I_FLAGS, env);
+        pe.n_draw = (pe.sflags & kFlagListed) ? SI(s, I_NSPIKES, env) + 1 : 0;  // empty right after a reset
+        pe.avx = SF(s, F_AVX, env);
+        pe.aphase = SF(s, F_APHASE, env);
+        pe.ax = SF(s, F_AX, env);
+        pe.ay = SF(s, F_AY, env);
+        pe.gx = SF(s, F_GX, env);
+        pe.gy = SF(s, F_GY, env);
+        out = pe;
+        r.game_words[GW_NEEDLE_X] = __float_as_uint(SF(s, F_NEEDLE_X, env));
+        r.game_words[GW_NEEDLE_Y] = __float_as_uint(SF(s, F_NEEDLE_Y, env));
+        r.game_words[GW_BAR_W] = __float_as_uint(SF(s, F_BAR_W, env));
+        r.game_words[GW_NEEDLE_SN] = static_cast<uint32_t>(SI(s, I_NEEDLE_SN, env));
+        r.game_words[GW_NEEDLE_CS] = static_cast<uint32_t>(SI(s, I_NEEDLE_CS, env));
+    }
+    static PG_D bool view(const int4* desc, const Regs& r, int flags, PrepView& v, uint32_t& soft, uint32_t& hard, uint32_t* meta, Lds&, int) {
+        // (bit 4: traffic experiment of the -DPG_ABLATE build — every env shows backdrop 9: what the backdrops' share of
+        // the render kernel's FETCH_SIZE is, and what the kernel would gain if it were not there)
+        const int backdrop = PG_ABL(flags, 16) ? 9 : (r.themes & 0xff), theme = (r.themes >> 8) & 0xff;
+        const int4 d = desc[kTexBackdrop + backdrop];
+        v.bg = backdrop_draw(d, r.bgshift);  // jumper.cpp:459-464
+#pragma unroll
+        for (int k = 0; k < 5; k++) meta[PM_GAME + k] = r.game_words[k];
+        return prep_view_cap_body(d, desc[kTexTop + theme], desc[kTexMid + theme], v, soft, hard, meta);
+    }
+    static PG_D const uint8_t* tiles(const State& s, int env) { return s.tiles + size_t(env) * kTileStride; }
+    static PG_D uint32_t kinds(uint32_t raw, const Lds&, int, uint32_t& kind_bytes) {  // kEmpty 0, kWallTop 1, kWallMid 2, kSpike 3 (no tile)
+        kind_bytes = prep_kinds_cap_body(raw);
+        return 0u;
+    }
+    // The draws in the reference's order: particles (common_systems.cpp:285-308), the positive-z sprites (carrot and
+    // spikes, :26-48), the bunny (:204-247).
+    static PG_D int count(const PrepEnv& pe) { return kPuffs + pe.n_draw + 1; }
+    static PG_D DrawCall draw(const State& s, const Lds& L, const int4* desc, int e, int env, int slot) {
+        const PrepEnv& pe = L.env[e];
+        if (slot < kPuffs) {
+            const float life = PF(s, PF_LIFE, slot, env), px = PF(s, PF_X, slot, env), py = PF(s, PF_Y, slot, env);
+            return puff_draw(life, px, py, desc[kTexPuff]);
+        }
+        if (slot < kPuffs + pe.n_draw) {
+            const int k = slot - kPuffs;
+            const int id = (L.draw_ids[e][k >> 2] >> (8 * (k & 3))) & 0xffu;
+            const int j = id == 0 ? 0 : id - 2;
+            const int cell = (L.spike_cells[e][j >> 1] >> (16 * (j & 1))) & 0xffffu;
+            return sprite_draw(id, pe.gx, pe.gy, cell, desc[sprite_tex(id)]);
+        }
+        const int tex = bunny_tex(pe.sflags, pe.avx, pe.aphase);
+        return bunny_draw(pe.sflags, pe.ax, pe.ay, tex, desc[tex]);
+    }
+    // everything drawn here lies beneath the compass ring, which is opaque over two thirds of the frame: what lands
+    // wholly under it — the bunny, nearly always — is not handed to the render wave at all
+    static PG_D const uint32_t* cover(const State& s, const AtlasView& atlas, int flags) {
+        return (s.hud_cover != 0u && !PG_ABL(flags, 0x10000)) ? atlas.texels + s.hud_cover : nullptr;
+    }
+    // (the compass's needle and bar take two more lanes of the render wave)
+    static PG_D int close(int done, bool, const PrepEnv&, bool touched, uint32_t* meta) {
+        meta[PM_GAME + GW_TOUCH] = touched ? 1u : 0u;
+        return done > kPrepDraws - 3 ? kPrepDraws + 1 : done;
+    }
+    // the frames handed back, listed for render_full_kernel
+    static PG_D void finish(const State& s, const uint32_t* fat, const int32_t* counts, int env0, int tid) {
+        if (tid < kPrepEnvs && (fat[tid] != 0 || counts[tid] > kPrepDraws) && env0 + tid < s.n)  // (prep_meta_out's own test)
+#if defined(PG_FAT_WHY)
+            s.fat[1 + atomicAdd(s.fat, 1u)] = static_cast<uint32_t>(env0 + tid) | (fat[tid] << 24) | (counts[tid] > kPrepDraws ? 16u << 24 : 0u);
+#else
+            s.fat[1 + atomicAdd(s.fat, 1u)] = static_cast<uint32_t>(env0 + tid);
+#endif
+    }
 };
 
 __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView atlas, const uint8_t* mask, int flags) {
-    __shared__ SetupLds S;
-    PrepLds<kGrid, kPrepEnvs, kMaxSpan>& P = S.P;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int env0 = prep_block(blockIdx.x, gridDim.x) * kPrepEnvs;  // (pg_prepass.h: the groups of one XCD are consecutive)
-    const PrepOut& out = s.prep;
-
-    // ---- one memory round trip: descriptor table, the envs' scalars (lane = env), their draw lists and spike cells
-    for (int q = tid; q < kPrepEnvs * 2 * 64; q += kPrepThreads) (&P.cover[0][0][0])[q] = 0u;
-    if (tid < kTexCount) S.desc[tid] = atlas.desc[tid];
-    static_assert(kTexCount <= kPrepThreads, "one descriptor per thread");
-    static_assert(kPrepEnvs * kSpikeSlots / 4 == kPrepThreads, "one word of the draw lists per thread");
-    {
-        const int e = tid / (kSpikeSlots / 4), w = tid - e * (kSpikeSlots / 4);
-        if (env0 + e < s.n) {
-            S.draw_ids[e][w] = reinterpret_cast<const uint32_t*>(s.draw + size_t(env0 + e) * kSpikeSlots)[w];
-            const uint32_t* cells = reinterpret_cast<const uint32_t*>(s.spike_cell + size_t(env0 + e) * kSpikeSlots);
-            S.spike_cells[e][2 * w] = cells[2 * w];
-            S.spike_cells[e][2 * w + 1] = cells[2 * w + 1];
-        }
-    }
-    Camera cam{};
-    int themes = 0;
-    float bgshift = 0.0f;
-    bool active = false;
-    uint32_t game_words[5] = {0u, 0u, 0u, 0u, 0u};
-    if (tid < kPrepEnvs) {
-        const int e = tid, env = env0 + e;
-        active = env < s.n && (!mask || mask[env]);
-        if (active) {
-            cam = Camera{SF(s, F_CAMX, env), SF(s, F_CAMY, env), 64.0f, 64.0f, kObsZoom * 64.0f / 64.0f};
-            themes = SI(s, I_THEMES, env);
-            bgshift = SF(s, F_BGSHIFT, env);
-            PrepEnv pe{};
-            pe.sflags = SI(s, I_FLAGS, env);
-            pe.n_draw = (pe.sflags & kFlagListed) ? SI(s, I_NSPIKES, env) + 1 : 0;  // empty right after a reset
-            pe.avx = SF(s, F_AVX, env);
-            pe.aphase = SF(s, F_APHASE, env);
-            pe.ax = SF(s, F_AX, env);
-            pe.ay = SF(s, F_AY, env);
-            pe.gx = SF(s, F_GX, env);
-            pe.gy = SF(s, F_GY, env);
-            S.env[e] = pe;
-            game_words[GW_NEEDLE_X] = __float_as_uint(SF(s, F_NEEDLE_X, env));
-            game_words[GW_NEEDLE_Y] = __float_as_uint(SF(s, F_NEEDLE_Y, env));
-            game_words[GW_BAR_W] = __float_as_uint(SF(s, F_BAR_W, env));
-            game_words[GW_NEEDLE_SN] = static_cast<uint32_t>(SI(s, I_NEEDLE_SN, env));
-            game_words[GW_NEEDLE_CS] = static_cast<uint32_t>(SI(s, I_NEEDLE_CS, env));
-        }
-    }
-    __syncthreads();
-    // ---- per env (lane = env): camera, tile window, background draw — render_full's preamble
-    if (tid < kPrepEnvs) {
-        const int e = tid;
-        PrepView v{};
-        P.fat[e] = 0;
-        P.soft_rows[e] = P.hard_rows[e] = 0;
-        S.counts[e] = 0;
-        if (active) {
-            v.cam = cam;
-            // (bit 4: traffic experiment of the -DPG_ABLATE build — every env shows backdrop 9: what the backdrops' share of
-            // the render kernel's FETCH_SIZE is, and what the kernel would gain if it were not there)
-            const int backdrop = PG_ABL(flags, 16) ? 9 : (themes & 0xff), theme = (themes >> 8) & 0xff;
-            const int4 d = S.desc[kTexBackdrop + backdrop];
-            v.bg = backdrop_draw(d, bgshift);  // jumper.cpp:459-464
-            const TileWindow win = tile_window(cam);  // tilemap.cpp:255-264
-            v.x0 = win.x0;
-            v.y0 = win.y0;
-            v.cols = win.x1 - win.x0 + 1;
-            v.rows = win.y1 - win.y0 + 1;
-            const int4 top_d = S.desc[kTexTop + theme], mid_d = S.desc[kTexMid + theme];
-            const bool two = top_d.z != mid_d.z;  // the brown cap tile is 64×53 (see climber.hip)
-            v.tw = mid_d.y;
-            v.th = mid_d.z;
-            v.th2 = two ? top_d.z : 0;
-            v.tile_scale = kUnitPx / mid_d.y;
-            if (v.cols > kGrid || v.rows > kGrid || top_d.y != mid_d.y || top_d.z > mid_d.z || ((flags & kDebugFatThirds) && (env0 + e) % 3 == 0)) {
-                P.fat[e] = 1;
-                active = false;
-            }
-            P.soft_rows[e] = static_cast<uint32_t>(soft_rows_of(d.w, top_d.w | mid_d.w));
-            P.hard_rows[e] = static_cast<uint32_t>(hard_rows_of(d.w, mid_d.w));  // (cap tiles are few: always worth the attempt)
-            // tile kinds: 0 = cap (bit 0 of its offset: the layer's second texture), 1 = body
-#pragma unroll
-            for (int k = 0; k < kPrepKinds; k++) P.meta[e][PM_KINDS + k] = kNoTexel;
-            P.meta[e][PM_KINDS + 0] = (static_cast<uint32_t>(top_d.x) * 4u) | (two ? 1u : 0u);
-            P.meta[e][PM_KINDS + 1] = static_cast<uint32_t>(mid_d.x) * 4u;
-#pragma unroll
-            for (int k = 0; k < 5; k++) P.meta[e][PM_GAME + k] = game_words[k];
-            prep_row_valid<kGrid, H>(v.y0, S.row_valid[e]);
-        }
-        v.active = active ? 1 : 0;
-        P.view[e] = v;
-    }
-    __syncthreads();
-
-    // ---- the cell table: lane = (env, grid column), one 16-byte load of the column-major map (pg_prepass.h) …
-    const int cell_e = tid / kGrid, cell_c = tid - cell_e * kGrid;
-    bool cell_lane = false, cell_x_ok = false;
-    uint32_t column[kGrid / 4] = {};
-    if (tid < kPrepEnvs * kGrid && P.view[cell_e].active) {
-        cell_lane = true;
-        prep_column_fetch<kGrid, W, H>(s.tiles + size_t(env0 + cell_e) * kTileStride, P.view[cell_e].x0 + cell_c, P.view[cell_e].y0, cell_x_ok, column);
-    }
-    // … the spans are worked out while it travels …
-    prep_spans<kGrid, kMaxSpan, kPrepEnvs, true>(P, tid, kPrepThreads);
-    // … then sixteen kind bytes: wall_top → 0, wall_mid → 1, everything else (empty, spike) no tile
-    if (cell_lane) {
-        uint32_t in_rows[4];
-        prep_column_rows<kGrid>(column, S.row_valid[cell_e], cell_x_ok, kWallMid, in_rows);  // out of bounds is a wall (tilemap.h:84-89)
-        uint32_t kinds[4];
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const uint32_t t = in_rows[w] & 0x07070707u;                  // kEmpty 0, kWallTop 1, kWallMid 2, kSpike 3
-            const uint32_t lo = t & 0x01010101u, hi = (t >> 1) & 0x01010101u;
-            const uint32_t wall = (lo ^ hi) * 0xffu;                      // 0xff where t is 1 or 2
-            kinds[w] = (hi & wall) | ~wall;                               // kind = t - 1 for walls; 0xff: no tile
-        }
-        prep_column_store<kGrid>(out.cells + size_t(env0 + cell_e) * (kGrid * kGrid), cell_c, kinds);
-    }
-    __syncthreads();
-    prep_axes<kGrid, kMaxSpan, kPrepEnvs>(P, out, env0, wave, kPrepThreads / 64, lane);
-
-    // ---- the draws in the reference's order: particles (common_systems.cpp:285-308), the positive-z sprites (carrot and
-    // spikes, :26-48), the bunny (:204-247).  Two envs per wavefront, cull first (pg_prepass.h prep_draws_pass).
-    static_assert(kPrepEnvs == 2 * (kPrepThreads / 64), "two envs per wavefront");
-    {
-        const int ea = 2 * wave, eb = 2 * wave + 1;
-        const bool on_a = P.view[ea].active != 0, on_b = P.view[eb].active != 0;
-        const Camera cam_a = P.view[ea].cam, cam_b = P.view[eb].cam;
-        const int cnt_a = on_a ? kPuffs + S.env[ea].n_draw + 1 : 0, cnt_b = on_b ? kPuffs + S.env[eb].n_draw + 1 : 0;
-        uint32_t* const draws_a = out.draws + size_t(env0 + ea) * kPrepDraws * kBlitWords;
-        uint32_t* const draws_b = out.draws + size_t(env0 + eb) * kPrepDraws * kBlitWords;
-        PrepDrawPass st{0, {0, 0}, {0, 0}};
-        PrepDrawQueue& Q = S.queue[wave];
-        // everything drawn here lies beneath the compass ring, which is opaque over two thirds of the frame: what lands
-        // wholly under it — the bunny, nearly always — is not handed to the render wave at all
-        const uint32_t* const cover = (s.hud_cover != 0u && !PG_ABL(flags, 0x10000)) ? atlas.texels + s.hud_cover : nullptr;
-        for (int base = 0; base < cnt_a + cnt_b; base += 64) {  // wave-uniform
-            const int q = base + lane;
-            const bool is_b = q >= cnt_a;
-            const int e = is_b ? eb : ea, env = env0 + e;
-            const int slot = is_b ? q - cnt_a : q;
-            const bool valid = q < cnt_a + cnt_b;
-            const PrepEnv& pe = S.env[e];
-            DrawCall p = kNoDraw;
-            if (valid && slot < kPuffs) {
-                const float life = PF(s, PF_LIFE, slot, env), px = PF(s, PF_X, slot, env), py = PF(s, PF_Y, slot, env);
-                p = puff_draw(life, px, py, S.desc[kTexPuff]);
-            } else if (valid && slot < kPuffs + pe.n_draw) {
-                const int k = slot - kPuffs;
-                const int id = (S.draw_ids[e][k >> 2] >> (8 * (k & 3))) & 0xffu;
-                const int j = id == 0 ? 0 : id - 2;
-                const int cell = (S.spike_cells[e][j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                p = sprite_draw(id, pe.gx, pe.gy, cell, S.desc[sprite_tex(id)]);
-            } else if (valid) {
-                const int tex = bunny_tex(pe.sflags, pe.avx, pe.aphase);
-                p = bunny_draw(pe.sflags, pe.ax, pe.ay, tex, S.desc[tex]);
-            }
-            prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane, cover);
-        }
-        prep_draws_flush(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, lane, cover);
-        if (lane == 0) {  // (the compass's needle and bar take two more lanes of the render wave)
-            S.counts[ea] = st.done[0] > kPrepDraws - 3 ? kPrepDraws + 1 : st.done[0];
-            S.counts[eb] = st.done[1] > kPrepDraws - 3 ? kPrepDraws + 1 : st.done[1];
-            P.meta[ea][PM_GAME + GW_TOUCH] = (cover == nullptr || st.touch[0]) ? 1u : 0u;
-            P.meta[eb][PM_GAME + GW_TOUCH] = (cover == nullptr || st.touch[1]) ? 1u : 0u;
-        }
-    }
-    __syncthreads();
-    prep_meta_out<kGrid, kMaxSpan, kPrepEnvs>(P, out, env0, S.counts, tid, kPrepThreads);
-    if (tid < kPrepEnvs && (P.fat[tid] != 0 || S.counts[tid] > kPrepDraws) && env0 + tid < s.n)  // (prep_meta_out's own test)
-#if defined(PG_FAT_WHY)
-        s.fat[1 + atomicAdd(s.fat, 1u)] = static_cast<uint32_t>(env0 + tid) | (P.fat[tid] << 24) | (S.counts[tid] > kPrepDraws ? 16u << 24 : 0u);
-#else
-        s.fat[1 + atomicAdd(s.fat, 1u)] = static_cast<uint32_t>(env0 + tid);
-#endif
+    __shared__ SetupLds<Setup> S;
+    prep_setup<Setup>(S, s, atlas, mask, flags);
 }
 
 // The complete path as a kernel of its own: every env (`listed` = 0: the draw-list replay, kDebugNoPrepass), or the few
@@ -1497,12 +1411,9 @@ class JumperGame final : public PrefetchingGame<Gen> {
     }
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
     void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_, n); }
-    bool lean() const { return !(debug_flags & (1 | kDebugNoPrepass)); }
-    void launch_prepass(hipStream_t st, const uint8_t* mask) override {
-        if (lean()) hipLaunchKernelGGL(setup_kernel, dim3((s_.n + kPrepEnvs - 1) / kPrepEnvs), dim3(kPrepThreads), 0, st, s_, atlas_, mask, debug_flags);
-    }
+    void launch_prepass(hipStream_t st, const uint8_t* mask) override { prep_launch(setup_kernel, st, s_, atlas_, mask, debug_flags); }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
-        if (lean()) {
+        if (prep_lean(debug_flags)) {
             hipLaunchKernelGGL(render_full_kernel, dim3(kFatBlocks), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags, 1);
             hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);
         } else {

@@ -13,6 +13,28 @@
 //
 // A frame the scheme does not cover (a span wider than MAXSPAN, a third covering tile, more than 64 visible draws, a
 // game-specific rare case) is marked `fat`: its render workgroup then takes the game's complete path, as before.
+//
+// The kernel itself is stated ONCE, for the four games whose tile layer is a column-major byte map (coinrun, climber,
+// caveflyer, jumper): prep_setup<G> below — six phases of one workgroup, kPrepEnvs envs, their barriers and their
+// measurement exits.  A game's `__global__ setup_kernel` declares a SetupLds<G> and calls it; G is a struct of constants
+// and static PG_D functions in the game's source, which says only what the games do not share:
+//   kGrid, kSpan, kW, kH, kTexCount, kOob, kTwo   window and span tables, the map, the out-of-bounds cell, a second tile texture
+//   Lds        env[kPrepEnvs] (G's PrepEnv: what the draws' lanes need of an env) and the env's lists, staged
+//   Regs       lane = env: the camera and whatever else the view needs, in registers between load and view
+//   stage      the lists into Lds, one word or byte per thread                                  (phase 1)
+//   load       the env's scalars into Regs and its PrepEnv                                      (phase 2)
+//   early_end  a frame handed back before its view is built (coinrun's pending redo)            (phase 3)
+//   view       background, tile texture(s), row classes, kind and game words; returns `fat`     (phase 3)
+//   tiles      the env's map
+//   kinds      the byte-parallel kind decode of four cells; returns their soft bits             (phase 4)
+//   count, draw  the env's draw list: its length, and slot → DrawCall                           (phase 5)
+//   cover      what hides draws (jumper's compass), or nullptr                                  (phase 5)
+//   close      the draw count as the render wave may take it, and what else the pass found out  (phase 5)
+//   finish     after the meta lines (jumper's list of handed-back frames)                       (phase 6)
+// early_end, cover, close and finish have a plain answer (PrepPlain: no, none, the count as it is, nothing) that G inherits.
+// Everything is forced inline and nothing is chosen through a pointer, so a game's kernel holds no call and no trace of the
+// other games; a per-lane choice between two objects by pointer or reference goes through private memory (prep_camera).
+// What the compiler makes of the four kernels: tests/test_coinrun_resources.py, docs/OPTLOG.md "The pre-pass kernel, once".
 #pragma once
 
 #include "pg_render.h"
@@ -23,6 +45,7 @@ namespace pg {
 constexpr int kPrepMetaWords = 32;  // one 128-byte line per env
 constexpr int kPrepKinds = 8;       // tile kinds a game may have (cell byte → byte offset of the kind's texture)
 constexpr int kPrepDraws = 64;      // visible draws a lean frame may have (one per lane of the render wave)
+constexpr int kPrepEnvs = 8, kPrepThreads = 256;  // prep_setup's workgroup: envs, threads (two envs per wavefront in the draws)
 enum PrepMetaWord {
     PM_SECOND = 0,  // 64-bit row masks (lo, hi): two grid rows cover the pixel row
     PM_SOFT = 2,    //   … a covering grid row (or the background) shows texels that are not opaque
@@ -654,6 +677,192 @@ PG_D Blit prep_draw_load(const uint32_t* at, bool has) {
     d.rot_sn = 0;
     d.rot_cs = 65536;
     return d;
+}
+
+// ---- the kernel: prep_setup<G> (what G is: the head of this file) ----------------------------------------------------
+
+// The workgroup's LDS: the generic phases' tables, the game's part, what the phases hand each other.
+template <class G>
+struct SetupLds {
+    PrepLds<G::kGrid, kPrepEnvs, G::kSpan> P;
+    int4 desc[G::kTexCount];                      // the atlas descriptor table: every later lookup is an LDS read
+    typename G::Lds game;                         // per env what the draws' lanes need, loaded once, and its lists (fetched before anything needs them)
+    uint32_t row_valid[kPrepEnvs][G::kGrid / 4];  // byte i: 0xff if map row ty_lo + i of the env's window exists (cells below)
+    int32_t counts[kPrepEnvs];
+    PrepDrawQueue queue[kPrepThreads / 64];       // one worklist per wavefront
+};
+
+// What most games say for the hooks only one of them needs: G derives from this and states its own where it differs.
+struct PrepPlain {
+    template <class Regs>
+    static PG_D bool early_end(const Regs&) { return false; }
+    template <class State>
+    static PG_D const uint32_t* cover(const State&, const AtlasView&, int) { return nullptr; }
+    template <class Env>
+    static PG_D int close(int done, bool, const Env&, bool, uint32_t*) { return done; }
+    template <class State>
+    static PG_D void finish(const State&, const uint32_t*, const int32_t*, int, int) {}
+};
+
+// Tile layers of a cap texture over body textures (climber, jumper): the view's part of them, `fat` returned — the cap
+// must be as wide as the body and no taller.  Kind 0 = cap (bit 0 of its offset: the layer's second texture), 1 = body.
+// (The descriptors BY VALUE: as references into the LDS table they would be read again behind every store through `meta`.)
+PG_D bool prep_view_cap_body(int4 bg_d, int4 top_d, int4 mid_d, PrepView& v, uint32_t& soft, uint32_t& hard, uint32_t* meta) {
+    const bool two = top_d.z != mid_d.z;  // the brown theme's cap tile is 64×53 next to 64×64 bodies
+    v.tw = mid_d.y;
+    v.th = mid_d.z;
+    v.th2 = two ? top_d.z : 0;
+    v.tile_scale = kUnitPx / mid_d.y;
+    soft = static_cast<uint32_t>(soft_rows_of(bg_d.w, top_d.w | mid_d.w));
+    hard = static_cast<uint32_t>(hard_rows_of(bg_d.w, mid_d.w));  // (cap tiles are few: always worth the attempt)
+#pragma unroll
+    for (int k = 0; k < kPrepKinds; k++) meta[PM_KINDS + k] = kNoTexel;
+    meta[PM_KINDS + 0] = (static_cast<uint32_t>(top_d.x) * 4u) | (two ? 1u : 0u);
+    meta[PM_KINDS + 1] = static_cast<uint32_t>(mid_d.x) * 4u;
+    return top_d.y != mid_d.y || top_d.z > mid_d.z;
+}
+// … and their kind bytes, four cells at a time: cell 1 (cap) → 0, cell 2 (body) → 1, anything else no tile.
+PG_D uint32_t prep_kinds_cap_body(uint32_t raw) {
+    const uint32_t t = raw & 0x07070707u;
+    const uint32_t lo = t & 0x01010101u, hi = (t >> 1) & 0x01010101u;
+    const uint32_t wall = (lo ^ hi) * 0xffu;  // 0xff where t is 1 or 2
+    return (hi & wall) | ~wall;               // kind = t - 1 for walls; 0xff: no tile
+}
+
+// The pre-pass of kPrepEnvs envs: one workgroup of kPrepThreads, every phase with its lanes dealt densely over
+// (env, thing).  Reference arithmetic moved here unchanged: renderer.cpp:5-82 (render_texture), the games' tilemap.cpp (the
+// tile window), common_systems.cpp (the draws: G::draw).
+// Every global access sits behind `env0 + e < s.n` (the lists) or `active` (everything else): the last workgroup may be
+// partly filled, and a masked env is not touched.
+// (The PG_ABL exits are the instruction inventory's, -DPG_ABLATE builds only: tools/probe/setup_inventory.sh.)
+template <class G>
+PG_D void prep_setup(SetupLds<G>& S, const typename G::State& s, const AtlasView& atlas, const uint8_t* mask, int flags) {
+    constexpr int GRID = G::kGrid, SPAN = G::kSpan;
+    PrepLds<GRID, kPrepEnvs, SPAN>& P = S.P;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int env0 = prep_block(blockIdx.x, gridDim.x) * kPrepEnvs;  // (the groups of one XCD are consecutive)
+    const PrepOut& out = s.prep;
+
+    // ---- 1, 2: everything whose address does not depend on another load is requested first — the descriptor table, the
+    // envs' lists (G::stage), the envs' scalars (lane = env) — one memory round trip for all of it
+    for (int q = tid; q < kPrepEnvs * 2 * 64; q += kPrepThreads) (&P.cover[0][0][0])[q] = 0u;
+    static_assert(G::kTexCount <= kPrepThreads, "one descriptor per thread");
+    if (tid < G::kTexCount) S.desc[tid] = atlas.desc[tid];
+    G::stage(S.game, s, env0, tid);
+    typename G::Regs r{};
+    bool active = false;
+    if (tid < kPrepEnvs) {
+        const int e = tid, env = env0 + e;
+        active = env < s.n && (!mask || mask[env]);
+        if (active) G::load(s, env, r, S.game.env[e]);
+    }
+    __syncthreads();
+    // ---- 3: per env (lane = env): camera, tile window, background draw — the complete path's preamble
+    if (tid < kPrepEnvs) {
+        const int e = tid;
+        PrepView v{};
+        P.fat[e] = 0;
+        P.soft_rows[e] = P.hard_rows[e] = 0;
+        S.counts[e] = 0;
+        if (active && G::early_end(r)) {
+            P.fat[e] = 1;
+            active = false;
+        }
+        if (active) {
+            v.cam = r.cam;
+            const TileWindow win = tile_window(r.cam);
+            v.x0 = win.x0;
+            v.y0 = win.y0;
+            v.cols = win.x1 - win.x0 + 1;
+            v.rows = win.y1 - win.y0 + 1;
+            const bool fat = G::view(S.desc, r, flags, v, P.soft_rows[e], P.hard_rows[e], P.meta[e], S.game, e);
+            if (v.cols > GRID || v.rows > GRID || fat || ((flags & kDebugFatThirds) && (env0 + e) % 3 == 0)) {
+                P.fat[e] = 1;
+                active = false;
+            }
+            prep_row_valid<GRID, G::kH>(v.y0, S.row_valid[e]);  // which of the map rows under the window exist
+        }
+        v.active = active ? 1 : 0;
+        P.view[e] = v;
+    }
+    __syncthreads();
+    if (PG_ABL(flags, 0x1000000)) return;  // (the views alone)
+
+    // ---- 4: the cell table, first half: lane = (env, grid column).  The map is column-major, so the cells of a window
+    // column are consecutive bytes — one 16-byte load (GRID = 24: and one of 8; unaligned; rows beyond the map's edge read
+    // the neighbouring column or the neighbouring env's map and are replaced below) …
+    static_assert(kPrepEnvs * GRID <= kPrepThreads, "one window column per thread");
+    const int cell_e = tid / GRID, cell_c = tid - cell_e * GRID;
+    bool cell_lane = false, cell_x_ok = false;
+    uint32_t column[GRID / 4] = {};
+    if (tid < kPrepEnvs * GRID && P.view[cell_e].active) {
+        cell_lane = true;
+        prep_column_fetch<GRID, G::kW, G::kH>(G::tiles(s, env0 + cell_e), P.view[cell_e].x0 + cell_c, P.view[cell_e].y0, cell_x_ok, column);
+    }
+    // … the spans are worked out while it travels …
+    if (!PG_ABL(flags, 0x2000000)) prep_spans<GRID, SPAN, kPrepEnvs, G::kTwo>(P, tid, kPrepThreads);
+    // … second half: the kind bytes, four cells at a time, and the rows that show a soft texture (only the window's own
+    // rows and columns count)
+    if (cell_lane) {
+        const PrepView& v = P.view[cell_e];
+        uint32_t in_rows[GRID / 4], kinds[GRID / 4], soft_rows = 0u;
+        prep_column_rows<GRID>(column, S.row_valid[cell_e], cell_x_ok, G::kOob, in_rows);  // out of bounds is a wall (the games' tilemap.h)
+#pragma unroll
+        for (int w = 0; w < GRID / 4; w++) soft_rows |= G::kinds(in_rows[w], S.game, cell_e, kinds[w]) << (4 * w);
+        if (cell_c >= v.cols) soft_rows = 0u;
+        soft_rows &= (v.rows >= 32 ? ~0u : (1u << v.rows) - 1u);
+        prep_column_store<GRID>(out.cells + size_t(env0 + cell_e) * (GRID * GRID), cell_c, kinds);
+        if (soft_rows) atomicOr(&P.soft_rows[cell_e], soft_rows);
+    }
+    __syncthreads();
+    if (PG_ABL(flags, 0x4000000)) return;
+    if (!PG_ABL(flags, 0x8000000)) prep_axes<GRID, SPAN, kPrepEnvs>(P, out, env0, wave, kPrepThreads / 64, lane);
+    if (PG_ABL(flags, 0x10000000)) return;
+
+    // ---- 5: the draws, in the reference's order (G::draw).  A wavefront takes two envs of the workgroup, their lists
+    // dealt densely over its passes; a draw that survives render_texture's cull waits in the wave's worklist for the rest
+    // of the arithmetic (prep_draws_pass).
+    static_assert(kPrepEnvs == 2 * (kPrepThreads / 64), "two envs per wavefront");
+    {
+        const int ea = 2 * wave, eb = 2 * wave + 1;
+        const bool on_a = P.view[ea].active != 0, on_b = P.view[eb].active != 0;
+        const Camera cam_a = P.view[ea].cam, cam_b = P.view[eb].cam;
+        const int cnt_a = on_a ? G::count(S.game.env[ea]) : 0, cnt_b = on_b ? G::count(S.game.env[eb]) : 0;
+        uint32_t* const draws_a = out.draws + size_t(env0 + ea) * kPrepDraws * kBlitWords;
+        uint32_t* const draws_b = out.draws + size_t(env0 + eb) * kPrepDraws * kBlitWords;
+        PrepDrawPass st{0, {0, 0}, {0, 0}};
+        PrepDrawQueue& Q = S.queue[wave];
+        const uint32_t* const cover = G::cover(s, atlas, flags);
+        for (int base = 0; base < cnt_a + cnt_b; base += 64) {  // wave-uniform
+            const int q = base + lane;
+            const bool is_b = q >= cnt_a;
+            const int e = is_b ? eb : ea;
+            const int slot = is_b ? q - cnt_a : q;
+            const bool valid = q < cnt_a + cnt_b;
+            DrawCall p = kNoDraw;
+            if (valid) p = G::draw(s, S.game, S.desc, e, env0 + e, slot);
+            prep_draws_pass(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, valid, is_b, p, lane, cover);
+        }
+        prep_draws_flush(Q, st, S.desc, cam_a, cam_b, draws_a, draws_b, lane, cover);
+        if (lane == 0) {
+            S.counts[ea] = G::close(st.done[0], on_a, S.game.env[ea], cover == nullptr || st.touch[0], P.meta[ea]);
+            S.counts[eb] = G::close(st.done[1], on_b, S.game.env[eb], cover == nullptr || st.touch[1], P.meta[eb]);
+        }
+    }
+    __syncthreads();
+    // ---- 6
+    prep_meta_out<GRID, SPAN, kPrepEnvs>(P, out, env0, S.counts, tid, kPrepThreads);
+    G::finish(s, P.fat, S.counts, env0, tid);
+}
+
+// The host's side of it: a game's setup_kernel over all envs — unless the debug word asks for frames without a pre-pass
+// (bit 0: the draw-list replay; kDebugNoPrepass), which is also what the game's launch_render may need to know.
+inline bool prep_lean(int debug_flags) { return !(debug_flags & (1 | kDebugNoPrepass)); }
+template <class State>
+void prep_launch(void (*kernel)(State, AtlasView, const uint8_t*, int), hipStream_t st, const State& s, const AtlasView& atlas,
+                 const uint8_t* mask, int debug_flags) {
+    if (prep_lean(debug_flags))
+        hipLaunchKernelGGL(kernel, dim3((s.n + kPrepEnvs - 1) / kPrepEnvs), dim3(kPrepThreads), 0, st, s, atlas, mask, debug_flags);
 }
 
 #endif  // __HIPCC__

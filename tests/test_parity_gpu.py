@@ -178,6 +178,37 @@ def test_frames_the_pre_pass_hands_back_equal_the_prepared_ones(game):
     thirds.close()
 
 
+@pytest.mark.parametrize("game", ["coinrun", "climber", "caveflyer", "jumper"])
+def test_pre_pass_with_a_partly_filled_last_workgroup(game):
+    """The pre-pass takes eight envs per workgroup (pg_prepass.h prep_setup), and the two tests above run sizes that are
+    multiples of eight.  75 envs are ten groups — prep_block permutes the first eight and leaves two in place — the last
+    of them with three envs: what its five empty places must not read or write is guarded by `env0 + e < s.n` and `active`.
+    Three engines on the same seeds — plain, without the pre-pass (bit 21), with every third frame handed back (bit 23) —
+    take 60 steps with one masked reset in the middle: observations, reward bits and dones equal among all three at every
+    step.  (No claim about episode ends: at this size nothing guarantees any.)"""
+    n = 75
+    engines = [EngineVec(game, n, seed_base=311) for _ in range(3)]
+    engines[1].set_debug(1 << 21)
+    engines[2].set_debug(1 << 23)
+
+    def same(results, what):
+        for k in (1, 2):
+            for a, b in zip(results[0], results[k]):
+                a, b = np.asarray(a), np.asarray(b)
+                if a.dtype == np.float32:
+                    a, b = a.view(np.uint32), b.view(np.uint32)
+                assert np.array_equal(a, b), "%s: engine %d differs from the plain one" % (what, k)
+
+    same([(e.reset(),) for e in engines], "reset")
+    for s in range(60):
+        same([e.step(None, run_seed=12) for e in engines], "step %d" % s)
+        if s == 30:
+            mask = (np.arange(n) % 4 == 2).astype(np.uint8)  # (env 74, in the last group, among them)
+            same([(e.reset(mask=mask),) for e in engines], "masked reset")
+    for e in engines:
+        e.close()
+
+
 def test_coinrun_other_seeds_and_action_stream():
     _lockstep("coinrun", 64, 300, seed_base=4294967000, run_seed=9)  # seeds wrap through 2^32 like `unsigned long`→u32
 
