@@ -586,7 +586,9 @@ PGV_API int32_t pgv_step_phases_many(pgv_env* const* envs, int32_t count, int32_
  * enemies take their turns one after the other on the env's random stream itself instead of side by side on outputs
  * peeked from it (what the last few words of a 624-word block take in a normal run).  Bit 26: a push of the policy
  * observations stores each lane's own 16 values per plane as they lie (lanes 32 or 64 bytes apart for 2- and 4-byte elements)
- * instead of exchanging them inside the wave for dense stores.  Any other bit is refused. */
+ * instead of exchanging them inside the wave for dense stores.  Bit 27: coinrun draws a frame its pre-pass hands back in
+ * that env's own block of the render launch instead of in one of the early blocks in front of the grid (what a frame
+ * does anyway that finds the list of such frames full).  Any other bit is refused. */
 PGV_API int32_t pgv_set_debug(pgv_env* env, int32_t flags);
 
 /* Parity taps (host pointers): game-defined state vector / tile ids of one env; return the full

@@ -111,7 +111,14 @@ struct State {
                      //                                   agent (hazard_near) for resolve_kernel
     uint32_t no;     // generator switches turned off (PGV_COINRUN_NO_*: coinrun/tilemap.h:42-45 allow_* = false)
     PrepOut prep;    // what setup_kernel leaves for render_kernel (pg_prepass.h); not part of the state blob
+    uint32_t* early; // [kEarlyWords]  the frames the pre-pass hands back, for render_kernel's early blocks: two counters, which
+                     //                the pre-pass launches take in turn, and the list of envs (scratch, zeroed by the engine)
+    int32_t early_n;     // F: early blocks in front of render_kernel's grid = slots of the list this launch (0: no list)
+    int32_t early_turn;  // which counter this pre-pass / render pair takes (the host's: CoinrunGame::launch_prepass)
 };
+// `early`: a counter per 128-byte line, then the list.  The launch of turn t counts in counter t and zeroes the other one,
+// whose last reader — the render launch before — has ended by stream order: no launch, no memset and no race resets it.
+constexpr int kEarlyCounter = 32, kEarlyList = 2 * kEarlyCounter, kEarlyMax = 1024, kEarlyWords = kEarlyList + kEarlyMax;
 
 // scratch rows: the agent after each of the 4 sub-steps, then one word of flags
 enum {
@@ -1480,6 +1487,17 @@ struct Setup : PrepPlain {
             const int e = q / (2 * kMaxEnt), r = q - e * (2 * kMaxEnt), which = r / kMaxEnt, j = r - which * kMaxEnt;
             if (env0 + e < s.n) L.order[e][which][j] = EB(s, which ? EB_DRAW_ORDER : EB_SPARK_ORDER, j, env0 + e);
         }
+        if (env0 == 0 && tid == 0) s.early[(1 - s.early_turn) * kEarlyCounter] = 0u;  // the next launch's counter (State::early)
+    }
+    // A frame left to the complete path takes a slot of the list; one of the first early_n is drawn by the early block of
+    // that number (render_kernel) and says so in its meta line, any other — the list is full, or there is none: kDebugFatInPlace
+    // — by its own block, as before.
+    static PG_D uint32_t hand_back(const State& s, int env) {
+        if (s.early_n == 0) return 0u;
+        const uint32_t slot = atomicAdd(&s.early[s.early_turn * kEarlyCounter], 1u);
+        if (slot >= static_cast<uint32_t>(s.early_n)) return 0u;
+        s.early[kEarlyList + slot] = static_cast<uint32_t>(env);
+        return kPrepEarly;
     }
     static PG_D void load(const State& s, int env, Regs& r, PrepEnv& out) {
         r.redo = SCI(s, SC_REDO, env);
@@ -1596,7 +1614,17 @@ __global__ void __launch_bounds__(kPrepThreads) setup_kernel(State s, AtlasView 
 //    then make both trips.)
 __global__ void __launch_bounds__(64 * kRenderWaves, PG_COINRUN_RENDER_WAVES) render_kernel(State s, AtlasView atlas, const uint8_t* mask,
                                                                    StepIO io, int flags) {
-    const int env = blockIdx.x;
+    // The grid: s.early_n EARLY blocks, then a block per env.  Early block b draws frame b of the pre-pass's list of
+    // handed-back frames (Setup::hand_back) — the long blocks of the launch, 34 µs against a lean frame's 9: as the lowest
+    // block indices they start first and run beside the others, where in their envs' own places the last of them kept the
+    // launch open behind every lean block (docs/OPTLOG.md "Long frames first").  One block draws an env, whichever.
+    int env = static_cast<int>(blockIdx.x) - s.early_n;
+    const bool early = env < 0;
+    if (early) {  // (an empty early block: one scalar load)
+        const uint32_t listed = s.early[s.early_turn * kEarlyCounter];
+        if (blockIdx.x >= listed) return;  // (blockIdx.x < early_n here: at most min(listed, early_n) blocks go on)
+        env = static_cast<int>(s.early[kEarlyList + blockIdx.x]);
+    }
     if (mask && !mask[env]) return;
     const int lane = threadIdx.x & 63, half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int halves = kRenderWaves;
@@ -1620,7 +1648,10 @@ __global__ void __launch_bounds__(64 * kRenderWaves, PG_COINRUN_RENDER_WAVES) re
     __syncthreads();  // the cell table is complete
     PG_TL(1);
     if ((flags & (1 | kDebugNoPrepass)) || M.fat()) {  // (wave-uniform)
+        if (!early && s.early_n != 0 && M.early()) return;  // an early block draws it (early_n = 0: there is none, the line may be old)
+#if !defined(PG_EXP_LEAN_ONLY)  // (the bound of docs/OPTLOG.md "Long frames first": a handed-back frame simply returns)
         render_full(s, atlas, io, flags, env, fb, L);
+#endif
         return;
     }
     const int row_lo = half * (kObsH / halves), row_hi = (half + 1) * (kObsH / halves);
@@ -1824,11 +1855,23 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
     void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
         launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
+    // F, the early blocks of the render launch = the slots of the pre-pass's list of handed-back frames: n / 256 — at
+    // 65 536 envs 256, where about 100 frames a step are handed back — but 64 at least and 1 024 (kEarlyMax) at most.  None
+    // without a pre-pass, and none under kDebugFatInPlace: every such frame in its own block, the grid of before.
+    int early_blocks() const {
+        if (!prep_lean(debug_flags) || (debug_flags & kDebugFatInPlace)) return 0;
+        return std::min(std::max(s_.n / 256, 64), kEarlyMax);
+    }
     void launch_prepass(hipStream_t st, const uint8_t* mask) override {
-        if (!PG_ABL(debug_flags, 1 << 22)) prep_launch(setup_kernel, st, s_, atlas_, mask, debug_flags);  // (experiment: the last frame's pre-pass again)
+        if (PG_ABL(debug_flags, 1 << 22)) return;  // (experiment: the last frame's pre-pass again)
+        // every pre-pass launch takes the counter the one before did not (State::early): the step's, pgv_render_obs's, a reset's
+        if (prep_lean(debug_flags)) s_.early_turn ^= 1;
+        s_.early_n = early_blocks();
+        prep_launch(setup_kernel, st, s_, atlas_, mask, debug_flags);
     }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
-        hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(64 * kRenderWaves), 0, st, s_, atlas_, mask, io,
+        s_.early_n = early_blocks();
+        hipLaunchKernelGGL(render_kernel, dim3(s_.early_n + s_.n), dim3(64 * kRenderWaves), 0, st, s_, atlas_, mask, io,
                            debug_flags);
     }
     void launch_no_frame(hipStream_t st, StepIO io) override {
@@ -1839,6 +1882,7 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
     // entity lanes and read by resolve_kernel of the same step, only where a candidate bit of that step says so.
     static void carve_scratch(Carve& c, State& s, int n) {
         prep_carve(c, s.prep, n, kGrid, kBlitWords, false);
+        c.take(s.early, size_t(kEarlyWords) * 4);  // (zeroed by the engine when made: both counters start at 0)
         c.take(s.hazx, size_t(kMaxEnt) * n * sizeof(float4));
         c.take(s.hazy, size_t(kMaxEnt) * n * sizeof(float2));
     }

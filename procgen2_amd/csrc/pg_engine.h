@@ -185,6 +185,7 @@ class Game {
     //         its tables do not hold — which some games never have in a normal run: the tests' way to that path.
     // Bit 24: coinrun — the entity lanes' hazard pre-selection assumes an agent that does not move (coinrun.hip hazard_near):
     //         the agent's own check of that assumption fails and resolve_kernel works the hazards out the long way.
+    // Bit 27: coinrun — the render launch has no early blocks: a handed-back frame is drawn by its env's own block.
     int debug_flags = 0;
     LevelPlan plan{};  // set by the engine after bind()
 };
@@ -195,6 +196,7 @@ constexpr int kDebugFatThirds = 1 << 23;
 constexpr int kDebugCoinrunNoReach = 1 << 24;
 constexpr int kDebugChaserSerialMobs = 1 << 25;  // chaser: the enemies one after the other on the stream itself (chaser.hip advance)
 constexpr int kDebugPolicyStrided = 1 << 26;     // policy observations: each lane stores its own units (pg_policy_obs.h), no exchange
+constexpr int kDebugFatInPlace = 1 << 27;        // coinrun: no early blocks in the render launch — a handed-back frame is drawn by its env's own block (coinrun.hip render_kernel)
 
 // The debug dumps (Game::dump_state, dump_tiles): one element of device memory; a dump's values copied out as far as cap
 // allows, returning how many there are; one env's tile bytes (each masked with `mask`).

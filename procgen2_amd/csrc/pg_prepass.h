@@ -30,8 +30,11 @@
 //   count, draw  the env's draw list: its length, and slot → DrawCall                           (phase 5)
 //   cover      what hides draws (jumper's compass), or nullptr                                  (phase 5)
 //   close      the draw count as the render wave may take it, and what else the pass found out  (phase 5)
+//   hand_back  a frame left to the complete path: further bits of its PM_FLAGS word, asked by the (phase 6)
+//              thread that stores the word (coinrun's list of such frames: render_kernel's early blocks)
 //   finish     after the meta lines (jumper's list of handed-back frames)                       (phase 6)
-// early_end, cover, close and finish have a plain answer (PrepPlain: no, none, the count as it is, nothing) that G inherits.
+// early_end, cover, close, hand_back and finish have a plain answer (PrepPlain: no, none, the count as it is, no bits,
+// nothing) that G inherits.
 // Everything is forced inline and nothing is chosen through a pointer, so a game's kernel holds no call and no trace of the
 // other games; a per-lane choice between two objects by pointer or reference goes through private memory (prep_camera).
 // What the compiler makes of the four kernels: tests/test_coinrun_resources.py, docs/OPTLOG.md "The pre-pass kernel, once".
@@ -45,13 +48,14 @@ namespace pg {
 constexpr int kPrepMetaWords = 32;  // one 128-byte line per env
 constexpr int kPrepKinds = 8;       // tile kinds a game may have (cell byte → byte offset of the kind's texture)
 constexpr int kPrepDraws = 64;      // visible draws a lean frame may have (one per lane of the render wave)
+constexpr uint32_t kPrepEarly = 4u;  // PM_FLAGS: the frame is on the game's list of handed-back frames and is drawn from there
 constexpr int kPrepEnvs = 8, kPrepThreads = 256;  // prep_setup's workgroup: envs, threads (two envs per wavefront in the draws)
 enum PrepMetaWord {
     PM_SECOND = 0,  // 64-bit row masks (lo, hi): two grid rows cover the pixel row
     PM_SOFT = 2,    //   … a covering grid row (or the background) shows texels that are not opaque
     PM_HARD = 4,    //   … so many that the one-texel attempt is not made
     PM_FLAGS = 6,   // bit 0: fat (take the complete path); bit 1: the layer has a second, shorter texture (kind 0 shows it);
-                    // bits 8-15: number of draws
+                    // bit 2 (kPrepEarly): fat, and another block of the render launch draws it (G::hand_back); bits 8-15: number of draws
     PM_BGX = 7,     // background, x axis: d0 | dn << 16 (signed halves), then s0 | sn << 16
     PM_BGY = 9,     // background, y axis
     PM_BGTEX = 11,  // background: first texel in the atlas
@@ -394,8 +398,9 @@ __device__ unsigned g_fat_why[6];
 #endif
 // The last phase: the envs' meta lines, coalesced.  `counts[e]` = draws of env e (> kPrepDraws: fat).  Needs a barrier
 // in front (every phase has written its part of P.meta / P.fat).
-template <int GRID, int MAXSPAN, int E>
-PG_D void prep_meta_out(PrepLds<GRID, E, MAXSPAN>& P, const PrepOut& out, int env0, const int32_t* counts, int tid, int nthreads) {
+template <class G, int GRID, int MAXSPAN, int E>
+PG_D void prep_meta_out(PrepLds<GRID, E, MAXSPAN>& P, const typename G::State& s, const PrepOut& out, int env0, const int32_t* counts, int tid,
+                        int nthreads) {
     for (int q = tid; q < E * kPrepMetaWords; q += nthreads) {
         const int e = q / kPrepMetaWords, w = q - e * kPrepMetaWords;
         if (!P.view[e].active && !P.fat[e]) continue;  // (an env the kernel sits out writes nothing; a fat one its flag)
@@ -423,6 +428,7 @@ PG_D void prep_meta_out(PrepLds<GRID, E, MAXSPAN>& P, const PrepOut& out, int en
             }
 #endif
             word = (fat ? 1u : 0u) | (P.view[e].th2 > 0 ? 2u : 0u) | (static_cast<uint32_t>(fat ? 0 : c) << 8);
+            if (fat) word |= G::hand_back(s, env0 + e);  // (this thread alone stores the word: what the game adds is in that store)
         }
         if (w == PM_BGTEX) word = static_cast<uint32_t>(P.view[e].bg.desc.x);
         if (w == PM_WIDTHS) word = pack_halves(P.view[e].bg.desc.y, P.view[e].tw);
@@ -437,6 +443,7 @@ struct PrepMeta {
     const uint32_t* w;
     PG_D uint32_t flags() const { return w[PM_FLAGS]; }
     PG_D bool fat() const { return (w[PM_FLAGS] & 1u) != 0; }
+    PG_D bool early() const { return (w[PM_FLAGS] & kPrepEarly) != 0; }
     PG_D int draws() const { return static_cast<int>((w[PM_FLAGS] >> 8) & 0xffu); }
     PG_D unsigned long long mask(int at) const { return static_cast<unsigned long long>(w[at]) | (static_cast<unsigned long long>(w[at + 1]) << 32); }
     PG_D BgAxis bg(int axis) const {
@@ -701,6 +708,8 @@ struct PrepPlain {
     template <class Env>
     static PG_D int close(int done, bool, const Env&, bool, uint32_t*) { return done; }
     template <class State>
+    static PG_D uint32_t hand_back(const State&, int) { return 0u; }
+    template <class State>
     static PG_D void finish(const State&, const uint32_t*, const int32_t*, int, int) {}
 };
 
@@ -851,7 +860,7 @@ PG_D void prep_setup(SetupLds<G>& S, const typename G::State& s, const AtlasView
     }
     __syncthreads();
     // ---- 6
-    prep_meta_out<GRID, SPAN, kPrepEnvs>(P, out, env0, S.counts, tid, kPrepThreads);
+    prep_meta_out<G, GRID, SPAN, kPrepEnvs>(P, s, out, env0, S.counts, tid, kPrepThreads);
     G::finish(s, P.fat, S.counts, env0, tid);
 }
 
