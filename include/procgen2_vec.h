@@ -546,6 +546,53 @@ PGV_API int32_t pgv_render_frames(pgv_env* env, const int32_t* d_indices, int32_
 PGV_API int32_t pgv_render_frames_host(pgv_env* env, const int32_t* h_indices, int32_t count, int32_t width,
                                        int32_t height, uint8_t* h_rgb);
 
+/* Symbolic observations: what the games know, for every env at once, in device memory — the agent, every entity's kind,
+ * position and liveness, the goal, the tile map — as the rows of floats and bytes that the parity taps below give for one
+ * env at a time.  For privileged critics, probes and auxiliary losses, scripted and planning agents; with
+ * pgv_step_sequence's frameless steps such an agent runs without a frame being drawn.
+ *
+ *   1. Layout.  pgv_state_layout_of(game_id, mode) is host-only and pure: no GPU, no env.  PGV_MODE_DEFAULT stands for the
+ *      mode the game is compiled with; a mode pgv_game_modes does not offer is refused, as are an unknown game id, out NULL
+ *      and a struct_size that is too small.  A state row is `width` floats: `fixed` floats that every row has, then up to
+ *      max_records records of `record` floats (record = 0: every row is `fixed` long).  A tile row is `cells` = tile_w *
+ *      tile_h bytes, cell (x, y) at byte y + x * tile_h, y counted as the game's tile map counts it; all three are 0 for a
+ *      game without a tile map (bossfight).  The layout is a function of (game, mode) alone.
+ *   2. Names.  pgv_state_names writes the names of the `fixed` floats, then '|', then the names of one record's floats,
+ *      names separated by single spaces, NUL-terminated and cut to cap bytes where cap is short, and returns the length the
+ *      whole string needs without its NUL (-1 where pgv_state_layout_of would refuse; buf may be NULL).  The names are
+ *      unique within a game and the first two are agent_x agent_y in every game.  INTEGRATION.md lists the columns of every
+ *      game, the rule from a cell index to (x, y), and the tile ids.
+ *   3. Rows.  d_rows is device f32 [count][width], contiguous.  Row k holds the state dump of env indices[k] — bit for bit
+ *      what pgv_dump_state gives — followed by +0.0f up to width; d_lengths[k] (device int32 [count], or NULL) is the
+ *      dump's length.  d_tiles is device u8 [count][cells], contiguous: exactly the bytes pgv_dump_tiles gives.
+ *   4. Indices.  d_indices is device int32 [count], or NULL for envs 0 .. count-1.  The same env may be named more than once;
+ *      an index outside the batch gives a row of zero bytes and length 0; nothing faults for any index value.
+ *   5. Ordering and state.  The calls read the state as it stands at that point of the env's stream: behind a step, a reset,
+ *      a same-step auto-reset (the new episode, as the observation shows), a frameless pgv_step_sequence; between any two
+ *      calls.  They change nothing — an engine that called them goes on exactly as one that did not, and a second call
+ *      gives the same bytes.  They are enqueued on the env's stream, allocate nothing and do not synchronise the host.
+ *      Nothing is written per step: an engine that never calls them launches nothing for them.
+ *   6. Checked on the host before anything is enqueued, each refusal leaving a message and the engine as it was: env NULL;
+ *      count < 0; with count > 0 an output that is NULL or whose base is not 16-byte aligned (d_lengths: 4-byte).  count = 0
+ *      succeeds and writes nothing; pgv_tile_rows on a game without a tile map succeeds and writes nothing.
+ *   7. The _host forms take host pointers, allocate and free their device buffers and are synchronous, as
+ *      pgv_render_frames_host is; they ask no alignment. */
+typedef struct pgv_state_layout {
+    uint32_t struct_size;
+    int32_t width;          /* floats per row: the longest dump this configuration can produce */
+    int32_t fixed;          /* floats every row has */
+    int32_t record;         /* floats per variable record behind them; 0: every row is `fixed` long */
+    int32_t max_records;    /* width == fixed + record * max_records */
+    int32_t cells;          /* bytes per tile row; 0 for a game without a tile map (bossfight) */
+    int32_t tile_w, tile_h; /* cells == tile_w * tile_h */
+} pgv_state_layout;
+PGV_API int32_t pgv_state_layout_of(int32_t game_id, int32_t mode, pgv_state_layout* out); /* set struct_size first */
+PGV_API int64_t pgv_state_names(int32_t game_id, int32_t mode, char* buf, int64_t cap);
+PGV_API int32_t pgv_state_rows(pgv_env* env, const int32_t* d_indices, int32_t count, float* d_rows, int32_t* d_lengths);
+PGV_API int32_t pgv_tile_rows(pgv_env* env, const int32_t* d_indices, int32_t count, uint8_t* d_tiles);
+PGV_API int32_t pgv_state_rows_host(pgv_env* env, const int32_t* h_indices, int32_t count, float* h_rows, int32_t* h_lengths);
+PGV_API int32_t pgv_tile_rows_host(pgv_env* env, const int32_t* h_indices, int32_t count, uint8_t* h_tiles);
+
 /* Measurement helper for bench.py: runs `steps` synthetic steps and returns, from HIP events recorded
  * on the env's stream, the total time of the region and the summed time of the dominant (render)
  * kernel launches inside it. */

@@ -26,6 +26,7 @@
 #include "pg_prepass.h"
 #include "pg_stamps.h"
 #include "pg_rng.h"
+#include "pg_state_obs.h"
 #include "pg_sincos.h"
 
 namespace pg {
@@ -1398,6 +1399,50 @@ __global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasVie
     P.store(fb);
 }
 
+// The state row (pg_state_obs.h): oracle/pgo_bossfight.cpp Bossfight::dump_state, column by column.  The 25 scalars come
+// from the field arrays, the two rings of shots from each env's own block.
+struct StateRow {
+    using State = bossfight::State;
+    static constexpr int kScalars = 25, kFixed = kScalars + 3 * (kAgentShots + kBossShots), kRecord = 0, kMaxRecords = 0;
+    static constexpr int kWidth = kFixed, kEnvCols = kScalars;
+    static __device__ int length(const State&, int) { return kFixed; }
+    static __device__ float value(const State& s, int env, int col) {
+        if (col >= kScalars) {
+            const int r = col - kScalars, k = r / 3, j = r - k * 3, fld = j == 0 ? S_X : j == 1 ? S_Y : S_FRAME;
+            if (k < kAgentShots) return s.ashot[(size_t(env) * S_COUNT + fld) * kAgentShots + k];
+            return s.bshot[(size_t(env) * S_COUNT + fld) * kBossShots + (k - kAgentShots)];
+        }
+        auto iv = [&](int field) { return static_cast<float>(SI(s, field, env)); };
+        switch (col) {
+            case 0: return SF(s, F_AX, env);
+            case 1: return SF(s, F_AY, env);
+            case 2: return SF(s, F_AVX, env);
+            case 3: return SF(s, F_AVY, env);
+            case 4: return (SI(s, I_FLAGS, env) & kFlagAlive) ? 1.0f : 0.0f;
+            case 5: return SF(s, F_ATIMER, env);
+            case 6: return iv(I_A_NEXT);
+            case 7: return iv(I_A_COUNT);
+            case 8: return SF(s, F_BX, env);
+            case 9: return SF(s, F_BY, env);
+            case 10: return SF(s, F_BVX, env);
+            case 11: return SF(s, F_BVY, env);
+            case 12: return SF(s, F_PHASE_T, env);
+            case 13: return iv(I_PHASE);
+            case 14: return iv(I_WEAPON);
+            case 15: return SF(s, F_ATTACK_T, env);
+            case 16: return iv(I_HP);
+            case 17: return iv(I_B_NEXT);
+            case 18: return iv(I_B_COUNT);
+            case 19: return iv(I_X_NEXT);
+            case 20: return iv(I_X_COUNT);
+            case 21: return SF(s, F_EXPLO_T, env);
+            case 22: return SF(s, F_DAMAGE_T, env);
+            case 23: return SF(s, F_MOVE_T, env);
+            default: return iv(I_NROCKS);
+        }
+    }
+};
+
 class BossfightGame final : public Game {
    public:
     const char* name() const override { return "bossfight"; }
@@ -1541,6 +1586,17 @@ class BossfightGame final : public Game {
         return dump_out(v, out, cap);
     }
     int dump_tiles(hipStream_t, int, uint8_t*, int) override { return 0; }
+    StateLayout state_layout() const override { return state_layout_of<StateRow>(0, 0); }  // (no tile map in this game)
+    std::string state_names() const override {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_alive agent_timer a_next a_count boss_x boss_y boss_vel_x boss_vel_y "
+               "phase_timer phase_index weapon_index attack_timer hp b_next b_count x_next x_count explosion_timer damage_timer "
+               "move_timer n_rocks" +
+               slot_names("a_shot", kAgentShots, {"x", "y", "frame"}) + slot_names("b_shot", kBossShots, {"x", "y", "frame"}) + "|";
+    }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t, const int32_t*, int, uint8_t*) override {}
 
    private:
     State s_{};

@@ -28,6 +28,7 @@
 #include "pg_prefetch.h"
 #include "pg_render.h"
 #include "pg_rng.h"
+#include "pg_state_obs.h"
 #include "pg_defs.h"
 // caveflyer/tilemap.cpp: world_dim by Distribution_Mode — hard_mode 40 (the reference's compile-time default, tilemap.h),
 // easy_mode 20, memory_mode 45 (the whole cave stays, not just the widened goal path).
@@ -1183,6 +1184,55 @@ __global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasVie
     P.store(fb);
 }
 
+// The state row (pg_state_obs.h): oracle/pgo_caveflyer.cpp Caveflyer::dump_state, column by column.  The 15 scalars come
+// from the field arrays; the shots, the puffs and the entity records — every entity but number 1, the ship, which the
+// scalars already describe — from each env's own tables.
+struct StateRow {
+    using State = caveflyer::State;
+    static constexpr int kScalars = 15, kFixed = kScalars + 3 * (kShots + kPuffs), kRecord = 6, kMaxRecords = kMaxEnt - 1;
+    static constexpr int kWidth = kFixed + kRecord * kMaxRecords, kEnvCols = kScalars;
+    static __device__ int length(const State& s, int env) {
+        const int n_ent = SI(s, I_NENT, env);
+        return kFixed + kRecord * (n_ent > 1 ? n_ent - 1 : n_ent);
+    }
+    static __device__ float value(const State& s, int env, int col) {
+        if (col >= kFixed) {
+            const int r = (col - kFixed) / kRecord, k = (col - kFixed) - r * kRecord, e = r == 0 ? 0 : r + 1;
+            const uint8_t info = EB(s, EB_INFO, e, env);
+            switch (k) {
+                case 0: return (info & kAlive) ? 1.0f : 0.0f;
+                case 1: return static_cast<float>(info & kKindMask);
+                case 2: return EF(s, EF_X, e, env);
+                case 3: return EF(s, EF_Y, e, env);
+                case 4: return EF(s, EF_VX, e, env);
+                default: return EF(s, EF_VY, e, env);
+            }
+        }
+        if (col >= kScalars) {
+            const int r = col - kScalars, k = r / 3, j = r - k * 3;
+            if (k < kShots) return s.sh[(size_t(env) * SH_COUNT + (j == 0 ? SH_X : j == 1 ? SH_Y : SH_FRAME)) * kShots + k];
+            return s.pf[(size_t(env) * PF_COUNT + (j == 0 ? PF_X : j == 1 ? PF_Y : PF_LIFE)) * kPuffSlots + (k - kShots)];
+        }
+        switch (col) {
+            case 0: return SF(s, F_AX, env);
+            case 1: return SF(s, F_AY, env);
+            case 2: return SF(s, F_AVX, env);
+            case 3: return SF(s, F_AVY, env);
+            case 4: return SF(s, F_ROT, env);
+            case 5: return SF(s, F_CAMX, env);
+            case 6: return SF(s, F_CAMY, env);
+            case 7: return static_cast<float>(SI(s, I_BACKDROP, env));
+            case 8: return SF(s, F_BGSHIFT, env);
+            case 9: return static_cast<float>(SI(s, I_SNEXT, env));
+            case 10: return static_cast<float>(SI(s, I_SCOUNT, env));
+            case 11: return SF(s, F_STIMER, env);
+            case 12: return SF(s, F_PTIMER, env);
+            case 13: return (SI(s, I_FLAGS, env) & kFlagPuffOn) ? 1.0f : 0.0f;
+            default: return static_cast<float>(SI(s, I_NENT, env));
+        }
+    }
+};
+
 class CaveflyerGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "caveflyer"; }
@@ -1253,6 +1303,19 @@ class CaveflyerGame final : public PrefetchingGame<Gen> {
     }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);
+    }
+    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
+    std::string state_names() const override {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_rot cam_x cam_y backdrop backdrop_shift s_next s_count s_timer "
+               "puff_timer puff_on n_things" +
+               slot_names("shot", kShots, {"x", "y", "frame"}) + slot_names("puff", kPuffs, {"x", "y", "life"}) +
+               "|alive kind x y vel_x vel_y";
+    }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
+        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
     }
     // Same layout as oracle/pgo_caveflyer.cpp Caveflyer::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

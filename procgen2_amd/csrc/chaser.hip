@@ -29,6 +29,7 @@
 #include "pg_render.h"
 #include "pg_prepass.h"
 #include "pg_rng.h"
+#include "pg_state_obs.h"
 #include "pg_setorder.h"
 
 namespace pg {
@@ -1471,6 +1472,53 @@ __global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasVie
     P.store(fb);
 }
 
+// The state row (pg_state_obs.h): oracle/pgo_chaser.cpp Chaser::dump_state, column by column.  The 13 scalars come from
+// the field arrays, the entity records from each env's own table — an orb or a point stands in the middle of its cell, an
+// enemy (kind kEgg, entities kOrbs .. kOrbs + kMobs − 1) has its floats in the enemies' field arrays.
+struct StateRow {
+    using State = chaser::State;
+    static constexpr int kFixed = 13, kRecord = 8, kMaxRecords = kOpenCells - 1, kWidth = kFixed + kRecord * kMaxRecords, kEnvCols = kFixed;
+    static __device__ int length(const State& s, int env) { return kFixed + kRecord * SI(s, I_NENT, env); }
+    static __device__ float value(const State& s, int env, int col) {
+        if (col >= kFixed) {
+            const int e = (col - kFixed) / kRecord, k = (col - kFixed) - e * kRecord;
+            const int info = EB(s, EB_INFO, e, env), kind = info & kKindMask;
+            if (k == 0) return (info & kAlive) ? 1.0f : 0.0f;
+            if (k == 1) return static_cast<float>(kind);
+            if (kind == kEgg) {
+                const int m = e - kOrbs;
+                switch (k) {
+                    case 2: return MF(s, MF_X, m, env);
+                    case 3: return MF(s, MF_Y, m, env);
+                    case 4: return MF(s, MF_VX, m, env);
+                    case 5: return MF(s, MF_VY, m, env);
+                    case 6: return MF(s, MF_HATCH, m, env);
+                    default: return static_cast<float>(MB(s, 0, m, env));
+                }
+            }
+            const int cell = EB(s, EB_CELL, e, env) | (kWideCells ? EB(s, EB_CELL_HI, e, env) << 8 : 0);
+            if (k == 2) return static_cast<float>(cell / H) + 0.5f;
+            if (k == 3) return static_cast<float>(H - 1 - cell % H) + 0.5f;
+            return 0.0f;
+        }
+        switch (col) {
+            case 0: return SF(s, F_AX, env);
+            case 1: return SF(s, F_AY, env);
+            case 2: return SF(s, F_AVX, env);
+            case 3: return SF(s, F_AVY, env);
+            case 4: return SF(s, F_NVX, env);
+            case 5: return SF(s, F_NVY, env);
+            case 6: return SF(s, F_INPUT_T, env);
+            case 7: return SF(s, F_ANIM_T, env);
+            case 8: return static_cast<float>(SI(s, I_ANIM_I, env));
+            case 9: return SF(s, F_EAT_T, env);
+            case 10: return static_cast<float>(SI(s, I_BG, env));
+            case 11: return SF(s, F_BGSHIFT, env);
+            default: return static_cast<float>(SI(s, I_NENT, env));
+        }
+    }
+};
+
 class ChaserGame final : public Game {
    public:
     const char* name() const override { return "chaser"; }
@@ -1655,6 +1703,17 @@ class ChaserGame final : public Game {
         const int groups = s_.n < 1024 ? s_.n : 1024;
         hipLaunchKernelGGL(render_list_kernel, dim3(groups + (s_.n + 127) / 128), dim3(128), 0, st, s_, atlas_, io, debug_flags, groups);
         return true;
+    }
+    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
+    std::string state_names() const override {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_next_x agent_next_y input_timer anim_timer anim_index eat_timer "
+               "backdrop backdrop_shift n_things|alive kind x y vel_x vel_y hatch_timer tex";
+    }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
+        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
     }
     // Same layout as oracle/pgo_chaser.cpp Chaser::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

@@ -22,6 +22,7 @@
 #include "pg_prepass.h"
 #include "pg_render.h"
 #include "pg_rng.h"
+#include "pg_state_obs.h"
 #include "pg_tiles.h"
 
 namespace pg {
@@ -820,6 +821,45 @@ __global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasVie
     P.store(fb);
 }
 
+// The state row (pg_state_obs.h): oracle/pgo_climber.cpp Climber::dump_state, column by column.  The 14 scalars come from
+// the field arrays, the entity records from each env's own tables.
+struct StateRow {
+    using State = climber::State;
+    static constexpr int kFixed = 14, kRecord = 6, kMaxRecords = kMaxEnt, kWidth = kFixed + kRecord * kMaxRecords, kEnvCols = kFixed;
+    static __device__ int length(const State& s, int env) { return kFixed + kRecord * SI(s, I_NENT, env); }
+    static __device__ float value(const State& s, int env, int col) {
+        if (col >= kFixed) {
+            const int e = (col - kFixed) / kRecord, k = (col - kFixed) - e * kRecord;
+            const uint8_t info = EB(s, EB_INFO, e, env);
+            switch (k) {
+                case 0: return (info & kAlive) ? 1.0f : 0.0f;
+                case 1: return EF(s, EF_X, e, env);
+                case 2: return EF(s, EF_Y, e, env);
+                case 3: return (info & kMob) ? EF(s, EF_VX, e, env) : 0.0f;
+                case 4: return (info & kFrame) ? 1.0f : 0.0f;
+                default: return EF(s, EF_ANIM_T, e, env);
+            }
+        }
+        const int themes = SI(s, I_THEMES, env);
+        switch (col) {
+            case 0: return SF(s, F_AX, env);
+            case 1: return SF(s, F_AY, env);
+            case 2: return SF(s, F_AVX, env);
+            case 3: return SF(s, F_AVY, env);
+            case 4: return (SI(s, I_FLAGS, env) & kFlagGround) ? 1.0f : 0.0f;
+            case 5: return (SI(s, I_FLAGS, env) & kFlagForward) ? 1.0f : 0.0f;
+            case 6: return SF(s, F_APHASE, env);
+            case 7: return W / 2.0f * kUnitPx;  // (the camera never moves sideways)
+            case 8: return SF(s, F_CAMY, env);
+            case 9: return static_cast<float>(themes & 0xff);
+            case 10: return SF(s, F_BGSHIFT, env);
+            case 11: return static_cast<float>((themes >> 8) & 0xff);
+            case 12: return static_cast<float>((themes >> 16) & 0xff);
+            default: return static_cast<float>(SI(s, I_NENT, env));
+        }
+    }
+};
+
 class ClimberGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "climber"; }
@@ -893,6 +933,17 @@ class ClimberGame final : public PrefetchingGame<Gen> {
     }
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);
+    }
+    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
+    std::string state_names() const override {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase cam_x cam_y backdrop backdrop_shift "
+               "suit theme n_things|alive x y vel_x frame anim_t";
+    }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
+        launch_tile_rows_of(st, s_.tiles, W * H, W * H, 0xff, s_.n, d_indices, count, d_tiles);
     }
     // Same layout as oracle/pgo_climber.cpp Climber::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

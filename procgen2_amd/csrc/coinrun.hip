@@ -35,6 +35,7 @@
 #include "pg_prepass.h"
 #include "pg_render.h"
 #include "pg_rng.h"
+#include "pg_state_obs.h"
 #include "pg_tiles.h"  // collide_any
 
 namespace pg {
@@ -1746,6 +1747,47 @@ __global__ void __launch_bounds__(64) redo_kernel(State s) {
 }
 static_assert(kMaxEnt <= 64, "a lane per entity");
 
+// The state row (pg_state_obs.h): oracle/pgo_coinrun.cpp Coinrun::dump_state, column by column.  Every source is a
+// [..][n] array, the entity tables included: all columns have the lanes along the envs.
+struct StateRow {
+    using State = coinrun::State;
+    static constexpr int kFixed = 14, kRecord = 5, kMaxRecords = kMaxEnt, kWidth = kFixed + kRecord * kMaxRecords, kEnvCols = kWidth;
+    static __device__ int length(const State& s, int env) { return kFixed + kRecord * SI(s, I_NENT, env); }
+    static __device__ float value(const State& s, int env, int col) {
+        const size_t n = s.n;
+        if (col >= kFixed) {
+            const int e = (col - kFixed) / kRecord, k = (col - kFixed) - e * kRecord;
+            const int buf = (SI(s, I_FLAGS, env) & kFlagBuf) ? 1 : 0;  // the live half of the double-buffered table
+            const int kind = EB(s, EB_KIND, e, env);
+            auto df = [&](int field) { return s.df[((size_t(buf) * DF_COUNT + field) * kMaxEnt + e) * n + env]; };
+            switch (k) {
+                case 0: return df(DF_X);
+                case 1: return EY(s, e, env);
+                case 2: return kind == kMob ? df(DF_VX) : 0.0f;
+                case 3: return (s.db[(size_t(buf) * kMaxEnt + e) * n + env] & kDynFrame) ? 1.0f : 0.0f;
+                default: return kind == kCoin ? 0.0f : df(DF_ANIM_T);
+            }
+        }
+        const int themes = SI(s, I_THEMES, env);
+        switch (col) {
+            case 0: return SF(s, F_AX, env);
+            case 1: return SF(s, F_AY, env);
+            case 2: return SF(s, F_AVX, env);
+            case 3: return SF(s, F_AVY, env);
+            case 4: return (SI(s, I_FLAGS, env) & kFlagGround) ? 1.0f : 0.0f;
+            case 5: return (SI(s, I_FLAGS, env) & kFlagForward) ? 1.0f : 0.0f;
+            case 6: return SF(s, F_APHASE, env);
+            case 7: return SF(s, F_CAMX, env);
+            case 8: return SF(s, F_CAMY, env);
+            case 9: return static_cast<float>(themes & 0xff);
+            case 10: return SF(s, F_BGSHIFT, env);
+            case 11: return static_cast<float>((themes >> 8) & 0xff);
+            case 12: return static_cast<float>((themes >> 16) & 0xff);
+            default: return static_cast<float>(SI(s, I_NENT, env));
+        }
+    }
+};
+
 class CoinrunGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "coinrun"; }
@@ -1889,6 +1931,17 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
     void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_, n); }
 
+    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
+    std::string state_names() const override {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase cam_x cam_y backdrop backdrop_shift "
+               "alien ground n_things|x y vel_x frame anim_t";
+    }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
+        launch_tile_rows_of(st, s_.tiles, W * H, W * H, 7, s_.n, d_indices, count, d_tiles);
+    }
     // Same layout as oracle/pgo_coinrun.cpp Coinrun::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {
         hipStreamSynchronize(st);

@@ -1663,6 +1663,111 @@ int32_t pgv_dump_tiles(pgv_env* e, int32_t index, uint8_t* h_out, int32_t cap) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Symbolic observations (include/procgen2_vec.h; pg_state_obs.h and every game's StateRow).
+// ------------------------------------------------------------------------------------------------
+namespace pg {
+// A Game fresh from its factory answers for its layout: host only, nothing bound, no GPU.
+static std::unique_ptr<Game> layout_game(const char* who, int32_t game_id, int32_t mode) {
+    if (game_id < 0 || game_id >= kNumGames) {
+        fail(std::string(who) + ": unknown game id " + std::to_string(game_id));
+        return nullptr;
+    }
+    const Variant* variant = find_variant(game_id, mode);
+    if (!variant) {
+        fail(std::string(who) + ": game '" + kGameNames[game_id] + "' has no distribution mode " + std::to_string(mode) +
+             " (see pgv_game_modes)");
+        return nullptr;
+    }
+    return variant->make();
+}
+}  // namespace pg
+
+int32_t pgv_state_layout_of(int32_t game_id, int32_t mode, pgv_state_layout* out) {
+    if (!out || out->struct_size < sizeof(pgv_state_layout)) return fail("pgv_state_layout_of: out is NULL or struct_size too small");
+    const std::unique_ptr<pg::Game> game = pg::layout_game("pgv_state_layout_of", game_id, mode);
+    if (!game) return 1;
+    const pg::StateLayout l = game->state_layout();
+    out->width = l.width, out->fixed = l.fixed, out->record = l.record, out->max_records = l.max_records;
+    out->cells = l.cells, out->tile_w = l.tile_w, out->tile_h = l.tile_h;
+    return 0;
+}
+
+int64_t pgv_state_names(int32_t game_id, int32_t mode, char* buf, int64_t cap) {
+    const std::unique_ptr<pg::Game> game = pg::layout_game("pgv_state_names", game_id, mode);
+    if (!game) return -1;
+    const std::string names = game->state_names();
+    if (buf && cap > 0) {
+        const size_t m = std::min(names.size(), static_cast<size_t>(cap - 1));
+        std::memcpy(buf, names.data(), m);
+        buf[m] = 0;
+    }
+    return static_cast<int64_t>(names.size());
+}
+
+int32_t pgv_state_rows(pgv_env* e, const int32_t* d_indices, int32_t count, float* d_rows, int32_t* d_lengths) {
+    if (!e) return fail("pgv_state_rows: env is NULL");
+    if (count < 0) return fail("pgv_state_rows: count is negative");
+    if (count == 0) return 0;
+    if (!d_rows) return fail("pgv_state_rows: the output buffer is NULL");
+    if (reinterpret_cast<uintptr_t>(d_rows) % 16) return fail("pgv_state_rows: d_rows is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_lengths) % 4) return fail("pgv_state_rows: d_lengths is not 4-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    e->game->launch_state_rows(e->stream, d_indices, count, d_rows, d_lengths);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_tile_rows(pgv_env* e, const int32_t* d_indices, int32_t count, uint8_t* d_tiles) {
+    if (!e) return fail("pgv_tile_rows: env is NULL");
+    if (count < 0) return fail("pgv_tile_rows: count is negative");
+    if (e->game->state_layout().cells == 0 || count == 0) return 0;  // (a game without a tile map: nothing to write)
+    if (!d_tiles) return fail("pgv_tile_rows: the output buffer is NULL");
+    if (reinterpret_cast<uintptr_t>(d_tiles) % 16) return fail("pgv_tile_rows: d_tiles is not 16-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    e->game->launch_tile_rows(e->stream, d_indices, count, d_tiles);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_state_rows_host(pgv_env* e, const int32_t* h_indices, int32_t count, float* h_rows, int32_t* h_lengths) {
+    if (!e) return fail("pgv_state_rows_host: env is NULL");
+    if (count < 0) return fail("pgv_state_rows_host: count is negative");
+    if (count == 0) return 0;
+    if (!h_rows) return fail("pgv_state_rows_host: the output buffer is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    const size_t floats = size_t(count) * size_t(e->game->state_layout().width);
+    pg::Staged dev{e->stream};
+    float* d_rows = dev.alloc<float>(floats);
+    int32_t* d_lengths = h_lengths ? dev.alloc<int32_t>(size_t(count)) : nullptr;
+    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_state_rows(e, d_indices, count, d_rows, d_lengths)) return rc;
+        dev.fetch(h_rows, d_rows, floats * 4);
+        if (h_lengths) dev.fetch(h_lengths, d_lengths, size_t(count) * 4);
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_state_rows_host: ") + hipGetErrorString(dev.err));
+    return 0;
+}
+
+int32_t pgv_tile_rows_host(pgv_env* e, const int32_t* h_indices, int32_t count, uint8_t* h_tiles) {
+    if (!e) return fail("pgv_tile_rows_host: env is NULL");
+    if (count < 0) return fail("pgv_tile_rows_host: count is negative");
+    const size_t bytes = size_t(count > 0 ? count : 0) * size_t(e->game->state_layout().cells);
+    if (bytes == 0) return 0;
+    if (!h_tiles) return fail("pgv_tile_rows_host: the output buffer is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    pg::Staged dev{e->stream};
+    uint8_t* d_tiles = dev.alloc<uint8_t>(bytes);
+    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_tile_rows(e, d_indices, count, d_tiles)) return rc;
+        dev.fetch(h_tiles, d_tiles, bytes);
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_tile_rows_host: ") + hipGetErrorString(dev.err));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // cenv ABI (include/procgen2_cenv.h) on top of one process-global vector env.
 // ------------------------------------------------------------------------------------------------
 cenv_make_data make_data;

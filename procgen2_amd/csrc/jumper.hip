@@ -23,6 +23,7 @@
 #include "pg_prepass.h"
 #include "pg_render.h"
 #include "pg_rng.h"
+#include "pg_state_obs.h"
 #include "pg_defs.h"
 // jumper/tilemap.cpp: world_dim by Distribution_Mode — hard_mode 40 (the reference's compile-time default, tilemap.h),
 // easy_mode 20, memory_mode 45 (no pruning to the goal path, no spikes).
@@ -1243,6 +1244,50 @@ __global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasVie
     P.store(fb);
 }
 
+// The state row (pg_state_obs.h): oracle/pgo_jumper.cpp Jumper::dump_state, column by column.  The 21 scalars come from the
+// field arrays; the puffs and the spike records — a spike stands in the middle of its cell — from each env's own tables.
+struct StateRow {
+    using State = jumper::State;
+    static constexpr int kScalars = 21, kFixed = kScalars + 3 * kPuffs, kRecord = 2, kMaxRecords = kMaxSpikes;
+    static constexpr int kWidth = kFixed + kRecord * kMaxRecords, kEnvCols = kScalars;
+    static __device__ int length(const State& s, int env) { return kFixed + kRecord * SI(s, I_NSPIKES, env); }
+    static __device__ float value(const State& s, int env, int col) {
+        if (col >= kFixed) {
+            const int k = (col - kFixed) / kRecord;
+            const int cell = SPK(s, k, env);
+            return ((col - kFixed) & 1) ? static_cast<float>(H - 1 - cell % H) + 0.5f : static_cast<float>(cell / H) + 0.5f;
+        }
+        if (col >= kScalars) {
+            const int r = col - kScalars, k = r / 3, j = r - k * 3;
+            return PF(s, j == 0 ? PF_X : j == 1 ? PF_Y : PF_LIFE, k, env);
+        }
+        const int flags = SI(s, I_FLAGS, env), themes = SI(s, I_THEMES, env);
+        switch (col) {
+            case 0: return SF(s, F_AX, env);
+            case 1: return SF(s, F_AY, env);
+            case 2: return SF(s, F_AVX, env);
+            case 3: return SF(s, F_AVY, env);
+            case 4: return (flags & kFlagGround) ? 1.0f : 0.0f;
+            case 5: return (flags & kFlagForward) ? 1.0f : 0.0f;
+            case 6: return SF(s, F_APHASE, env);
+            case 7: return SF(s, F_JUMP_T, env);
+            case 8: return static_cast<float>(SI(s, I_JUMPS, env));
+            case 9: return SF(s, F_CAMX, env);
+            case 10: return SF(s, F_CAMY, env);
+            case 11: return SF(s, F_TOGX, env);
+            case 12: return SF(s, F_TOGY, env);
+            case 13: return static_cast<float>(themes & 0xff);
+            case 14: return SF(s, F_BGSHIFT, env);
+            case 15: return static_cast<float>((themes >> 8) & 0xff);
+            case 16: return SF(s, F_PTIMER, env);
+            case 17: return (flags & kFlagPuffOn) ? 1.0f : 0.0f;
+            case 18: return SF(s, F_GX, env);
+            case 19: return SF(s, F_GY, env);
+            default: return static_cast<float>(SI(s, I_NSPIKES, env));
+        }
+    }
+};
+
 class JumperGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "jumper"; }
@@ -1419,6 +1464,18 @@ class JumperGame final : public PrefetchingGame<Gen> {
         } else {
             hipLaunchKernelGGL(render_full_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags, 0);
         }
+    }
+    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
+    std::string state_names() const override {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase agent_jump_timer agent_jumps cam_x "
+               "cam_y to_goal_x to_goal_y backdrop backdrop_shift theme puff_timer puff_on goal_x goal_y n_spikes" +
+               slot_names("puff", kPuffs, {"x", "y", "life"}) + "|x y";
+    }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
+        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
     }
     // Same layout as oracle/pgo_jumper.cpp Jumper::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

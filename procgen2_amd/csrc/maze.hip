@@ -19,6 +19,7 @@
 #include "pg_render.h"
 #include "pg_prepass.h"
 #include "pg_rng.h"
+#include "pg_state_obs.h"
 
 namespace pg {
 namespace PG_VARIANT_NS {
@@ -420,6 +421,27 @@ __global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasVie
     P.store(fb);
 }
 
+// The state row (pg_state_obs.h): oracle/pgo_maze.cpp Maze::dump_state, column by column.  Every source is a field array.
+struct StateRow {
+    using State = maze::State;
+    static constexpr int kFixed = 10, kRecord = 0, kMaxRecords = 0, kWidth = kFixed, kEnvCols = kWidth;
+    static __device__ int length(const State&, int) { return kFixed; }
+    static __device__ float value(const State& s, int env, int col) {
+        switch (col) {
+            case 0: return SF(s, F_AX, env);
+            case 1: return SF(s, F_AY, env);
+            case 2: return (SI(s, I_FLAGS, env) & kFlagForward) ? 1.0f : 0.0f;
+            case 3: return SF(s, F_GX, env);
+            case 4: return SF(s, F_GY, env);
+            case 5: return static_cast<float>(SI(s, I_STEPS, env));
+            case 6: return static_cast<float>(SI(s, I_BG, env));
+            case 7: return SF(s, F_BGSHIFT, env);
+            case 8: return SF(s, F_CAMX, env);
+            default: return SF(s, F_CAMY, env);
+        }
+    }
+};
+
 class MazeGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "maze"; }
@@ -497,6 +519,16 @@ class MazeGame final : public PrefetchingGame<Gen> {
     }
     int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
         return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
+    }
+    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
+    std::string state_names() const override {
+        return "agent_x agent_y agent_forward goal_x goal_y steps floor floor_shift cam_x cam_y|";
+    }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
+        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
     }
 
    private:

@@ -73,6 +73,12 @@ struct StepIO {
     uint8_t* pending;
 };
 
+// pgv_state_layout (include/procgen2_vec.h) without its struct_size: width == fixed + record * max_records floats a state
+// row, cells == tile_w * tile_h bytes a tile row (all three 0 for a game without a tile map).
+struct StateLayout {
+    int width, fixed, record, max_records, cells, tile_w, tile_h;
+};
+
 // Word 0 of a record (pg_records.h: here because a game's records_loaded looks at it too).
 constexpr uint32_t kRecordFull = 0x31524750u;  // "PGR1"
 constexpr uint32_t kRecordEmpty = 0u;
@@ -118,6 +124,15 @@ class Game {
     // Debug tap used by the parity tests: game-defined float dump of one env (host pointer).
     virtual int dump_state(hipStream_t s, int env, float* out, int cap) = 0;
     virtual int dump_tiles(hipStream_t s, int env, uint8_t* out, int cap) = 0;
+    // Symbolic observations (include/procgen2_vec.h pgv_state_rows / pgv_tile_rows; pg_state_obs.h): the same dumps for
+    // `count` envs at once into device memory, d_rows = f32 [count][width] (+0.0f behind a dump's end), d_lengths =
+    // int32 [count] or nullptr, d_tiles = u8 [count][cells].  d_indices as launch_frames takes them; an index outside the
+    // batch gives a row of zero bytes and length 0.  Read-only, on the given stream.  state_layout / state_names are
+    // host-only and need neither a bound state nor a GPU (pgv_state_layout_of asks a Game fresh from its factory).
+    virtual StateLayout state_layout() const = 0;
+    virtual std::string state_names() const = 0;  // "<fixed names>|<record names>", space-separated
+    virtual void launch_state_rows(hipStream_t s, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) = 0;
+    virtual void launch_tile_rows(hipStream_t s, const int32_t* d_indices, int count, uint8_t* d_tiles) = 0;
     // pgv_config.game_flags (include/procgen2_vec.h); false = this game does not know these switches.
     virtual bool set_game_flags(uint32_t flags) { return flags == 0; }
     // Called once between loading and uploading the atlas: a game may append data derived from its textures (jumper:

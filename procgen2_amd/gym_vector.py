@@ -45,6 +45,13 @@ Boxes; what RL code imports is a vector env with real spaces.  This class gives 
   (include/procgen2_vec.h pgv_history_enable); `.history` is the engine's HistoryTensors and `engine.history_gather()`
   builds stacked rows for a minibatch.  Every return value stays as it is.
 
+* `state_info=True` (opt-in): `reset` and `step` add the engine's symbolic observations to `info`, in every autoreset mode
+  and either output kind — `info["state"]` float32 [N, width], `info["state_length"]` int32 [N] and `info["tiles"]` uint8
+  [N, cells] (no such key for a game without a tile map, cells == 0): `engine.state_obs()` / `engine.tile_obs()`, whose
+  columns `engine.state_layout` names.  They describe the state the returned observation shows — in same_step mode the
+  new episode's.  The tensors are the adapter's own and are REUSED: the next reset or step overwrites them (output="numpy"
+  hands out copies, as for everything else).  Without the option infos are what they were.
+
 The class only talks to an *engine* object with `reset(mask, seeds) -> obs`, `step(actions) -> (obs, reward, done)`,
 `close()`, `num_envs`; `ProcgenVecEnv` is the real one.  The CPU tests drive the same code with an oracle-backed
 stand-in, so the wrapper logic is covered without a GPU.
@@ -150,7 +157,8 @@ class GymVectorAdapter(_VectorBase):
 
     metadata = {"render_modes": ["rgb_array"], "autoreset_mode": "next_step"}
 
-    def __init__(self, engine, output="torch", render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None, policy_obs=None):
+    def __init__(self, engine, output="torch", render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None, policy_obs=None,
+                 state_info=False):
         if output not in ("torch", "numpy"):
             raise ValueError("output must be 'torch' or 'numpy'")
         if episodes not in (None, "device"):
@@ -162,6 +170,10 @@ class GymVectorAdapter(_VectorBase):
                 raise ValueError("episodes='device': the engine was made with autoreset_mode=%r, the adapter with %r"
                                  % (getattr(engine, "autoreset_mode", None), autoreset_mode))
         self.episodes = episodes
+        self.state_info = bool(state_info)
+        if self.state_info and not (hasattr(engine, "state_obs") and hasattr(engine, "tile_obs")):
+            raise ValueError("state_info=True needs an engine with state_obs and tile_obs (ProcgenVecEnv)")
+        self._state = self._state_length = self._tiles = None  # the adapter's own tensors, reused by every call
         if autoreset_mode not in ("next_step", "same_step"):
             raise ValueError("autoreset_mode must be 'next_step' or 'same_step'")
         self.autoreset_mode = autoreset_mode
@@ -209,6 +221,16 @@ class GymVectorAdapter(_VectorBase):
         engine call that drew `obs` has pushed into; `obs` itself otherwise."""
         return self.engine.policy_obs if self.policy else obs
 
+    def _with_state(self, info):
+        """state_info=True: the engine's symbolic observations as they stand now, into the adapter's own tensors."""
+        if self.state_info:
+            self._state, self._state_length = self.engine.state_obs(out=self._state, lengths_out=self._state_length)
+            self._tiles = self.engine.tile_obs(out=self._tiles)
+            info["state"], info["state_length"] = self._out(self._state), self._out(self._state_length)
+            if self._tiles.shape[1]:
+                info["tiles"] = self._out(self._tiles)
+        return info
+
     def _seeds(self, seed):
         if seed is None:
             return None
@@ -234,7 +256,7 @@ class GymVectorAdapter(_VectorBase):
                 if mask.shape != (self.num_envs,):
                     raise ValueError("reset_mask must have shape (%d,)" % self.num_envs)
         obs = self.engine.reset(mask=mask, seeds=self._seeds(seed))
-        return self._out(self._observation(obs)), {}
+        return self._out(self._observation(obs)), self._with_state({})
 
     def step(self, actions):
         n = actions.numel() if hasattr(actions, "numel") else np.asarray(actions).size
@@ -277,7 +299,7 @@ class GymVectorAdapter(_VectorBase):
             reward, terminated = rew, mask
             info = {"final_obs": by_env, "_final_obs": self._out(mask, bool), "final_obs_compact": self._out(final),
                     "final_obs_env": self._out(where)}
-        return self._out(self._observation(obs)), self._out(reward), self._out(terminated, bool), truncated, info
+        return self._out(self._observation(obs)), self._out(reward), self._out(terminated, bool), truncated, self._with_state(info)
 
     def _step_device(self, actions):
         """episodes="device": one engine call; everything returned is a view of the engine's buffers (torch) or cut to the
@@ -291,10 +313,11 @@ class GymVectorAdapter(_VectorBase):
                     "final_count": counts.copy(),
                     "episode": {"r": cut(ep.ended_return, c), "l": cut(ep.ended_length, c), "level": cut(ep.ended_level, c),
                                 "level_known": cut(ep.ended_level_known, c)}}
-            return (self._out(self._observation(obs)), self._out(ep.reward), self._out(ep.terminated, bool), self._out(ep.truncated, bool), info)
+            return (self._out(self._observation(obs)), self._out(ep.reward), self._out(ep.terminated, bool), self._out(ep.truncated, bool),
+                    self._with_state(info))
         info = {"_final_obs": ep.ended != 0, "final_obs_compact": ep.final_obs, "final_obs_env": ep.ended_env, "final_count": ep.counts,
                 "episode": {"r": ep.ended_return, "l": ep.ended_length, "level": ep.ended_level, "level_known": ep.ended_level_known}}
-        return self._observation(obs), ep.reward, ep.terminated != 0, ep.truncated != 0, info
+        return self._observation(obs), ep.reward, ep.terminated != 0, ep.truncated != 0, self._with_state(info)
 
     def render(self, index=0):
         """The human-size frame of one env (the reference's `cenv_render`, coinrun.cpp:393-411; default 512×512 as its
@@ -344,7 +367,7 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
 
     def __init__(self, game, num_envs, device=0, seed=1, env_offset=0, output="torch", num_levels=0, start_level=0,
                  distribution_mode=None, render_mode=None, render_size=(512, 512), autoreset_mode="next_step", episodes=None,
-                 max_episode_steps=0, final_obs_capacity=0, policy_obs=None, history=None):
+                 max_episode_steps=0, final_obs_capacity=0, policy_obs=None, history=None, state_info=False):
         from .vec_env import ProcgenVecEnv
         if episodes not in (None, "device"):
             raise ValueError("episodes must be None or 'device'")
@@ -359,6 +382,7 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
         super().__init__(ProcgenVecEnv(game, num_envs, device=device, seed_base=seed, env_offset=env_offset,
                                        num_levels=num_levels, start_level=start_level,
                                        distribution_mode=distribution_mode, **more), output=output, render_mode=render_mode,
-                         render_size=render_size, autoreset_mode=autoreset_mode, episodes=episodes, policy_obs=policy_obs)
+                         render_size=render_size, autoreset_mode=autoreset_mode, episodes=episodes, policy_obs=policy_obs,
+                         state_info=state_info)
         self.game = game
         self.history = self.engine.history

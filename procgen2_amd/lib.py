@@ -3,6 +3,7 @@
 The shared library is the product; this module only declares prototypes.  It fails loudly when the
 library has not been built — there is no Python or CPU fallback for the hot path.
 """
+import collections
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
@@ -71,6 +72,30 @@ def history_enable(lib, h, capacity, gray=False, frames=None):
     """pgv_history_enable.  frames: a device pointer (integer) or None for a ring of the engine's own (pgv_history_frames)."""
     cfg = HistoryConfig(ctypes.sizeof(HistoryConfig), int(capacity), int(gray), frames)
     check(lib, lib.pgv_history_enable(h, ctypes.byref(cfg)), "pgv_history_enable")
+
+
+class StateLayoutStruct(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_state_layout`."""
+    _fields_ = [("struct_size", c_uint32), ("width", c_int32), ("fixed", c_int32), ("record", c_int32), ("max_records", c_int32),
+                ("cells", c_int32), ("tile_w", c_int32), ("tile_h", c_int32)]
+
+
+StateLayout = collections.namedtuple("StateLayout", "width fixed record max_records cells tile_w tile_h fixed_names record_names")
+
+
+def state_layout(lib, game, mode=None):
+    """pgv_state_layout_of + pgv_state_names → StateLayout (host only: no GPU, no env).  game: a name or the id."""
+    game_id = lib.pgv_game_id(game.encode()) if isinstance(game, str) else int(game)
+    out = StateLayoutStruct(ctypes.sizeof(StateLayoutStruct))
+    check(lib, lib.pgv_state_layout_of(game_id, mode_id(mode), ctypes.byref(out)), "pgv_state_layout_of")
+    need = lib.pgv_state_names(game_id, mode_id(mode), None, 0)
+    if need < 0:
+        check(lib, 1, "pgv_state_names")
+    buf = ctypes.create_string_buffer(need + 1)
+    lib.pgv_state_names(game_id, mode_id(mode), buf, need + 1)
+    fixed_names, record_names = buf.value.decode().split("|")
+    return StateLayout(out.width, out.fixed, out.record, out.max_records, out.cells, out.tile_w, out.tile_h,
+                       tuple(fixed_names.split()), tuple(record_names.split()))
 
 
 class GatherAug(ctypes.Structure):
@@ -243,6 +268,12 @@ def load(path=None):
         "pgv_set_debug": (c_int32, [P, c_int32]),
         "pgv_dump_state": (c_int32, [P, c_int32, POINTER(c_float), c_int32]),
         "pgv_dump_tiles": (c_int32, [P, c_int32, POINTER(c_uint8), c_int32]),
+        "pgv_state_layout_of": (c_int32, [c_int32, c_int32, POINTER(StateLayoutStruct)]),
+        "pgv_state_names": (c_int64, [c_int32, c_int32, c_char_p, c_int64]),
+        "pgv_state_rows": (c_int32, [P, P, c_int32, P, P]),
+        "pgv_tile_rows": (c_int32, [P, P, c_int32, P]),
+        "pgv_state_rows_host": (c_int32, [P, P, c_int32, P, P]),
+        "pgv_tile_rows_host": (c_int32, [P, P, c_int32, P]),
         "pgv_last_error": (c_char_p, []),
     }
     for name, (res, args) in proto.items():
@@ -271,6 +302,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_history_enable", "pgv_history_frames", "pgv_history_began", "pgv_history_pending", "pgv_history_head", "pgv_history_capacity", "pgv_history_push",
     "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
+    "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",
     "pgv_last_error",
 ]
 EXPORTED_CENV_SYMBOLS = [

@@ -79,6 +79,9 @@ class ProcgenVecEnv:
         self.num_levels, self.start_level = int(num_levels), int(start_level)
         self.distribution_mode = {v: k for k, v in pglib.MODES.items()}[self.L.pgv_mode(h)]
         self._h = h
+        # The columns of state_obs() / tile_obs() (include/procgen2_vec.h pgv_state_layout_of, pgv_state_names): width, fixed,
+        # record, max_records, cells, tile_w, tile_h, fixed_names, record_names.
+        self.state_layout = pglib.state_layout(self.L, game, self.distribution_mode)
         self._sequences = {}  # step_sequence's result tensors, by T: the _SEQUENCES_KEPT most recently used
         # torch owns the result buffers; the engine writes straight into them.
         if out is not None:
@@ -439,6 +442,47 @@ class ProcgenVecEnv:
                                                          count, width, height, c_void_p(out.data_ptr())), "pgv_render_frames")
             self._after()
             self._keep_frames = (idx, out)
+        return out
+
+    # -- symbolic observations (include/procgen2_vec.h pgv_state_rows / pgv_tile_rows) ------------
+    def _obs_out(self, out, shape, dtype, name):
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if (tuple(out.shape) != shape or out.dtype != dtype or out.device != self.device or not out.is_contiguous()
+                or out.data_ptr() % 16):
+            raise ValueError("%s: expected a contiguous, 16-byte aligned %s tensor of shape %s on %s" % (name, dtype, shape, self.device))
+        return out
+
+    def state_obs(self, envs=None, out=None, lengths_out=None):
+        """What the game knows about the envs `envs` (None: all of them, in order; otherwise anything torch.as_tensor takes —
+        an env may appear more than once, an index outside the batch gives a row of zeros and length 0), as it stands now:
+        (rows float32 [B, state_layout.width], lengths int32 [B]) on this env's device.  Row k is the env's state dump —
+        state_layout.fixed_names, then lengths[k] - fixed floats of records of state_layout.record_names — and +0.0 behind
+        it.  Written on the device with the same stream hand-shake as step() and no host synchronisation; reads only.
+        out / lengths_out: caller-owned contiguous tensors of those shapes to write into (and return)."""
+        idx, count = self._indices(envs)
+        out = self._obs_out(out, (count, self.state_layout.width), torch.float32, "out")
+        lengths_out = self._obs_out(lengths_out, (count,), torch.int32, "lengths_out")
+        if count:
+            self._before()
+            pglib.check(self.L, self.L.pgv_state_rows(self._h, c_void_p(idx.data_ptr()) if idx is not None else None, count,
+                                                      c_void_p(out.data_ptr()), c_void_p(lengths_out.data_ptr())), "pgv_state_rows")
+            self._after()
+            self._keep_state_obs = (idx, out, lengths_out)
+        return out, lengths_out
+
+    def tile_obs(self, envs=None, out=None):
+        """The tile maps of the envs `envs` (as state_obs takes them): uint8 [B, state_layout.cells] on this env's device,
+        cell (x, y) at column y + x * state_layout.tile_h — [B, 0] for a game without a tile map (bossfight).  An index
+        outside the batch gives a row of zeros.  out: a caller-owned contiguous tensor of that shape to write into."""
+        idx, count = self._indices(envs)
+        out = self._obs_out(out, (count, self.state_layout.cells), torch.uint8, "out")
+        if count and self.state_layout.cells:
+            self._before()
+            pglib.check(self.L, self.L.pgv_tile_rows(self._h, c_void_p(idx.data_ptr()) if idx is not None else None, count,
+                                                     c_void_p(out.data_ptr())), "pgv_tile_rows")
+            self._after()
+            self._keep_tile_obs = (idx, out)
         return out
 
     def save_state(self):

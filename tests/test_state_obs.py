@@ -1,0 +1,139 @@
+"""Symbolic observations, the part that needs no GPU (include/procgen2_vec.h pgv_state_layout_of, pgv_state_names): the
+layouts against the oracle's dumps, the names, the refusals, the exported symbols, and the Gymnasium adapter's state_info
+over a fake engine."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from state_obs_util import FIXED_RECORD, GAMES, TABLE, FakeStateEngine, oracle_run
+
+from procgen2_amd import lib as pglib
+from procgen2_amd.gym_vector import GymVectorAdapter
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host",
+               "pgv_tile_rows_host")
+
+
+def _error(L):
+    return (L.pgv_last_error() or b"").decode()
+
+
+def _layout(L, gid, mode):
+    out = pglib.StateLayoutStruct(ctypes.sizeof(pglib.StateLayoutStruct))
+    assert L.pgv_state_layout_of(gid, mode, ctypes.byref(out)) == 0, _error(L)
+    return out
+
+
+@pytest.mark.parametrize("game", GAMES)
+def test_layouts_hold_every_oracle_dump(engine_lib, game):
+    L = engine_lib
+    gid = L.pgv_game_id(game.encode())
+    default, modes = TABLE[game]
+    assert L.pgv_game_modes(gid) == sum(1 << m for m in modes)
+    for mode in (0,) + tuple(modes):
+        lay = _layout(L, gid, mode)
+        assert (lay.fixed, lay.record) == FIXED_RECORD[game], (game, mode)
+        assert lay.width == lay.fixed + lay.record * lay.max_records, (game, mode)
+        assert lay.cells == lay.tile_w * lay.tile_h, (game, mode)
+        assert (lay.record == 0) == (lay.max_records == 0), (game, mode)
+        at, first_done = oracle_run(game, mode)
+        assert first_done is not None or mode != 0, game  # (the default run finishes episodes in every game)
+        for step, sample in at.items():
+            for st, tl in zip(sample.states, sample.tiles):
+                assert lay.fixed <= st.size <= lay.width, (game, mode, step, st.size)
+                if lay.record:
+                    assert (st.size - lay.fixed) % lay.record == 0, (game, mode, step, st.size)
+                else:
+                    assert st.size == lay.fixed, (game, mode, step, st.size)
+                assert tl.size == lay.cells, (game, mode, step, tl.size)
+        if mode == 0:  # PGV_MODE_DEFAULT is the mode the game is compiled with
+            named = _layout(L, gid, default)
+            assert all(getattr(lay, f) == getattr(named, f) for f, _ in pglib.StateLayoutStruct._fields_), game
+
+
+@pytest.mark.parametrize("game", GAMES)
+def test_names(engine_lib, game):
+    L = engine_lib
+    gid = L.pgv_game_id(game.encode())
+    for mode in (0,) + tuple(TABLE[game][1]):
+        need = L.pgv_state_names(gid, mode, None, 0)
+        assert need > 0
+        buf = ctypes.create_string_buffer(need + 1)
+        assert L.pgv_state_names(gid, mode, buf, need + 1) == need
+        text = buf.value.decode()
+        assert len(text) == need and text.count("|") == 1 and "  " not in text and text == text.strip()
+        fixed, record = (part.split(" ") if part else [] for part in text.split("|"))
+        assert (len(fixed), len(record)) == FIXED_RECORD[game], (game, mode)
+        assert fixed[:2] == ["agent_x", "agent_y"]
+        assert len(set(fixed + record)) == len(fixed) + len(record), "names are unique"
+        assert all(name and name.replace("_", "").isalnum() for name in fixed + record)
+        short = ctypes.create_string_buffer(b"#" * 16, 16)  # a short cap truncates, NUL-terminated, and still reports the whole length
+        assert L.pgv_state_names(gid, mode, short, 10) == need
+        assert short.raw[:10] == text[:9].encode() + b"\0" and short.raw[10:] == b"#" * 6
+        lay = pglib.state_layout(L, game, mode)
+        assert lay.fixed_names == tuple(fixed) and lay.record_names == tuple(record) and lay.width == _layout(L, gid, mode).width
+
+
+def test_refusals(engine_lib):
+    L = engine_lib
+    out = pglib.StateLayoutStruct(ctypes.sizeof(pglib.StateLayoutStruct))
+    maze, chaser = L.pgv_game_id(b"maze"), L.pgv_game_id(b"chaser")
+    for gid, mode, word in ((maze, 4, "mode"), (chaser, 3, "mode"), (maze, 9, "mode"), (maze, -1, "mode"), (7, 0, "game"), (-1, 0, "game")):
+        assert L.pgv_state_layout_of(gid, mode, ctypes.byref(out)) != 0, (gid, mode)
+        assert word in _error(L) and "pgv_state_layout_of" in _error(L), _error(L)
+        assert L.pgv_state_names(gid, mode, None, 0) == -1
+        assert word in _error(L) and "pgv_state_names" in _error(L), _error(L)
+    small = pglib.StateLayoutStruct(ctypes.sizeof(pglib.StateLayoutStruct) - 4)
+    assert L.pgv_state_layout_of(maze, 0, ctypes.byref(small)) != 0 and "struct_size" in _error(L)
+    assert small.width == 0
+    assert L.pgv_state_layout_of(maze, 0, None) != 0 and "NULL" in _error(L)
+    # a NULL env, for the four row calls (nothing is touched: the buffers need not exist)
+    rows = (ctypes.c_float * 64)()
+    for name, args in (("pgv_state_rows", (None, None, 1, rows, None)), ("pgv_tile_rows", (None, None, 1, rows)),
+                       ("pgv_state_rows_host", (None, None, 1, rows, None)), ("pgv_tile_rows_host", (None, None, 1, rows))):
+        assert getattr(L, name)(*args) != 0, name
+        assert name + ":" in _error(L) and "NULL" in _error(L), _error(L)
+
+
+def test_symbols_are_declared_and_listed(engine_lib):
+    header = open(os.path.join(ROOT, "include", "procgen2_vec.h")).read()
+    for name in NEW_SYMBOLS:
+        assert "PGV_API" in header and (" " + name + "(") in header, name
+        assert name in pglib.EXPORTED_VEC_SYMBOLS, name
+        assert getattr(engine_lib, name).argtypes is not None, name
+    assert "typedef struct pgv_state_layout {" in header
+
+
+@pytest.mark.parametrize("output", ["torch", "numpy"])
+@pytest.mark.parametrize("autoreset_mode", ["next_step", "same_step"])
+def test_adapter_state_info(output, autoreset_mode):
+    eng = FakeStateEngine(n=5, width=7, cells=6)
+    env = GymVectorAdapter(eng, output=output, autoreset_mode=autoreset_mode, state_info=True)
+    _, info = env.reset()
+    for _ in range(3):
+        assert set(info) >= {"state", "state_length", "tiles"}
+        state, length, tiles = (np.asarray(info[k]) for k in ("state", "state_length", "tiles"))
+        assert state.shape == (5, 7) and state.dtype == np.float32
+        assert length.shape == (5,) and length.dtype == np.int32 and (length == 6).all()
+        assert tiles.shape == (5, 6) and tiles.dtype == np.uint8
+        # the rows describe the state behind the call's LAST engine call (same_step: behind the reset of the ended envs)
+        assert (state == eng.calls).all() and (tiles == eng.calls).all()
+        _, _, _, _, info = env.step(np.zeros(5, np.int64))
+    assert env._state is not None and env._tiles is not None  # the adapter's own tensors, reused
+
+
+def test_adapter_without_tiles_and_without_the_option():
+    env = GymVectorAdapter(FakeStateEngine(cells=0), output="numpy", state_info=True)
+    _, info = env.reset()
+    assert "tiles" not in info and {"state", "state_length"} <= set(info)
+    assert "tiles" not in env.step(np.zeros(5, np.int64))[4]
+    plain = GymVectorAdapter(FakeStateEngine(), output="numpy")
+    assert plain.reset()[1] == {} and plain.step(np.zeros(5, np.int64))[4] == {}
+
+    class NoState:
+        num_envs = 3
+    with pytest.raises(ValueError):
+        GymVectorAdapter(NoState(), state_info=True)
