@@ -593,6 +593,66 @@ PGV_API int32_t pgv_tile_rows(pgv_env* env, const int32_t* d_indices, int32_t co
 PGV_API int32_t pgv_state_rows_host(pgv_env* env, const int32_t* h_indices, int32_t count, float* h_rows, int32_t* h_lengths);
 PGV_API int32_t pgv_tile_rows_host(pgv_env* env, const int32_t* h_indices, int32_t count, uint8_t* h_tiles);
 
+/* Path distances: the breadth-first distance field of every named env's tile map from one source cell, and what a second
+ * cell — the probe — sees of it.  The first thing a scripted or planning agent, a privileged critic or a level-scoring
+ * curriculum computes from a tile map: the distance from the mouse to the cheese and the move that shortens it, from a
+ * chaser enemy to the agent, the optimal episode length of a maze.  The field is a geometric distance over cells: in the
+ * platformers it knows nothing of jumps or gravity.
+ *
+ *   1. Cells.  Cell (x, y) is index y + x * tile_h, exactly as in pgv_tile_rows.  The cell of a world point (wx, wy) is
+ *      x = floor(wx), y = tile_h - 1 - floor(wy); a point whose cell is outside the map has no cell.
+ *   2. The agent's cell is the cell of the centre of the agent's body box, (agent_x, agent_y + agent_dy), the sum one
+ *      float32 addition: agent_dy is 0 in maze, chaser and caveflyer, -0.5f in coinrun and climber, -0.4f in jumper.
+ *      The goal's cell is the cell of (goal_x, goal_y) in maze and jumper and of record 0's (x, y) in caveflyer (entity 0
+ *      is the goal); the other games have no goal.  pgv_path_layout_of gives both facts, and the map's size, on the host:
+ *      no GPU, no env, refusals as pgv_state_layout_of.  cells is 0 for a game without a tile map (bossfight).
+ *   3. Passable.  Bit t of `passable` set: a cell whose tile id, as pgv_tile_rows gives it, is t may be entered.  Ids >= 32
+ *      are never passable; a mask of 0 is legal.  INTEGRATION.md lists the tile ids and a sensible set for every game.
+ *   4. Distance.  The source cell has distance 0 whatever its tile.  A cell has distance d + 1 when it is passable, is not
+ *      yet reached, and has a 4-neighbour at distance d.  There is no wrap at any edge.  Any other cell is -1.  dist is
+ *      device int16 [count][cells], laid out as the tile rows are (the longest path is below 4 096); a row with no source
+ *      is all -1.
+ *   5. Probe.  probe_dist[k] is the distance at the probe cell, -1 when it is not reached or the row has no probe cell.
+ *      probe_step[k] is 0 when that distance is <= 0, otherwise the first of x-1 (code 1), x+1 (2), y-1 (3), y+1 (4)
+ *      whose distance is one less.  cells_out[k] = {source cell, probe cell}, -1 for none.
+ *   6. Source and probe are each PGV_PATH_AGENT, PGV_PATH_GOAL or PGV_PATH_CELLS — caller-given cells, device int32 [count],
+ *      a value outside 0 .. cells-1 meaning no cell; the probe may also be PGV_PATH_NONE.
+ *   7. Indices, ordering and state are points 4 and 5 of the symbolic observations: d_indices may be NULL, may repeat and
+ *      may name an env outside the batch — such a row is -1 everywhere, with a -1 probe distance, step 0 and cells -1.
+ *      The call is enqueued on the env's stream, allocates nothing, does not synchronise and changes nothing; an engine
+ *      that never calls it launches nothing for it.  count = 0 succeeds and writes nothing.
+ *   8. Checked on the host before anything is enqueued, each refusal leaving a message and the engine as it was: env or
+ *      struct NULL; struct_size too small; count < 0; an unknown source or probe, or source = PGV_PATH_NONE;
+ *      PGV_PATH_GOAL on a game without a goal; PGV_PATH_CELLS with a NULL cell pointer and count > 0; dist not 16-byte
+ *      aligned, probe_dist or cells_out not 4-byte aligned; every output NULL with count > 0; a game without a tile map.
+ *   9. The _host form takes host pointers throughout (indices, cells, outputs), allocates and frees its device buffers and
+ *      is synchronous, as pgv_tile_rows_host is; it asks no alignment. */
+#define PGV_PATH_NONE 0 /* probe only */
+#define PGV_PATH_AGENT 1
+#define PGV_PATH_GOAL 2
+#define PGV_PATH_CELLS 3
+typedef struct pgv_tile_paths {
+    uint32_t struct_size;
+    uint32_t passable;           /* bit t: tile id t may be entered */
+    int32_t source;              /* PGV_PATH_AGENT, _GOAL or _CELLS */
+    const int32_t* source_cells; /* [count], for PGV_PATH_CELLS */
+    int32_t probe;               /* PGV_PATH_NONE, _AGENT, _GOAL or _CELLS */
+    const int32_t* probe_cells;  /* [count], for PGV_PATH_CELLS */
+    int16_t* dist;               /* [count][cells], base 16-byte aligned, or NULL */
+    int32_t* probe_dist;         /* [count] or NULL */
+    uint8_t* probe_step;         /* [count] or NULL */
+    int32_t* cells_out;          /* [count][2]: source cell, probe cell, -1 for none; or NULL */
+} pgv_tile_paths;
+PGV_API int32_t pgv_tile_paths_rows(pgv_env* env, const int32_t* d_indices, int32_t count, const pgv_tile_paths* paths);
+PGV_API int32_t pgv_tile_paths_rows_host(pgv_env* env, const int32_t* h_indices, int32_t count, const pgv_tile_paths* paths);
+typedef struct pgv_path_layout {
+    uint32_t struct_size;
+    int32_t cells, tile_w, tile_h; /* as pgv_state_layout has them */
+    int32_t has_goal;              /* 1: PGV_PATH_GOAL is served */
+    float agent_dx, agent_dy;      /* the agent's cell is the cell of (agent_x + agent_dx, agent_y + agent_dy); agent_dx is 0 */
+} pgv_path_layout;
+PGV_API int32_t pgv_path_layout_of(int32_t game_id, int32_t mode, pgv_path_layout* out); /* set struct_size first */
+
 /* Measurement helper for bench.py: runs `steps` synthetic steps and returns, from HIP events recorded
  * on the env's stream, the total time of the region and the summed time of the dominant (render)
  * kernel launches inside it. */

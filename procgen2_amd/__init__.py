@@ -17,4 +17,9 @@ import os as _os
 # (engine.hip), for callers that bind the C ABI directly.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-__all__ = ["lib", "cenv", "vec_env", "build"]
+# Step code of the path distances (include/procgen2_vec.h pgv_tile_paths.probe_step: 0 stay, 1 x-1, 2 x+1, 3 y-1 = world up,
+# 4 y+1 = world down) → maze action: table[paths.probe_step.long()] with source = goal and probe = agent is the optimal maze
+# policy, on the device.
+MAZE_STEP_ACTIONS = (4, 1, 7, 3, 5)
+
+__all__ = ["lib", "cenv", "vec_env", "build", "MAZE_STEP_ACTIONS"]

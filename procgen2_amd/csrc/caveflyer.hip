@@ -1233,6 +1233,13 @@ struct StateRow {
     }
 };
 
+// The points of the path distances (pg_paths.h): the ship's box is centred on its point; the goal is entity 0, record 0 of the row.
+struct PathRow {
+    using Row = StateRow;
+    static constexpr float kAgentDy = 0.0f;
+    static constexpr int kGoalX = StateRow::kFixed + 2, kGoalY = StateRow::kFixed + 3;
+};
+
 class CaveflyerGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "caveflyer"; }
@@ -1316,6 +1323,10 @@ class CaveflyerGame final : public PrefetchingGame<Gen> {
     }
     void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
         launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
+    }
+    PathPoints path_points() const override { return path_points_of<PathRow>(); }
+    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
+        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
     }
     // Same layout as oracle/pgo_caveflyer.cpp Caveflyer::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

@@ -1519,6 +1519,13 @@ struct StateRow {
     }
 };
 
+// The points of the path distances (pg_paths.h): the agent fills its cell; the game has no goal.
+struct PathRow {
+    using Row = StateRow;
+    static constexpr float kAgentDy = 0.0f;
+    static constexpr int kGoalX = -1, kGoalY = -1;
+};
+
 class ChaserGame final : public Game {
    public:
     const char* name() const override { return "chaser"; }
@@ -1714,6 +1721,10 @@ class ChaserGame final : public Game {
     }
     void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
         launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
+    }
+    PathPoints path_points() const override { return path_points_of<PathRow>(); }
+    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
+        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
     }
     // Same layout as oracle/pgo_chaser.cpp Chaser::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

@@ -860,6 +860,13 @@ struct StateRow {
     }
 };
 
+// The points of the path distances (pg_paths.h): the body box spans agent_y - 1 .. agent_y; the game has no goal point.
+struct PathRow {
+    using Row = StateRow;
+    static constexpr float kAgentDy = -0.5f;
+    static constexpr int kGoalX = -1, kGoalY = -1;
+};
+
 class ClimberGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "climber"; }
@@ -944,6 +951,10 @@ class ClimberGame final : public PrefetchingGame<Gen> {
     }
     void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
         launch_tile_rows_of(st, s_.tiles, W * H, W * H, 0xff, s_.n, d_indices, count, d_tiles);
+    }
+    PathPoints path_points() const override { return path_points_of<PathRow>(); }
+    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
+        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, W * H, W * H, 0xff, W, H, s_.n, q);
     }
     // Same layout as oracle/pgo_climber.cpp Climber::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

@@ -1788,6 +1788,13 @@ struct StateRow {
     }
 };
 
+// The points of the path distances (pg_paths.h): the body box spans agent_y - 1 .. agent_y (a_bounds); the coin is an entity, not a goal point.
+struct PathRow {
+    using Row = StateRow;
+    static constexpr float kAgentDy = -0.5f;
+    static constexpr int kGoalX = -1, kGoalY = -1;
+};
+
 class CoinrunGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "coinrun"; }
@@ -1941,6 +1948,10 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
     }
     void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
         launch_tile_rows_of(st, s_.tiles, W * H, W * H, 7, s_.n, d_indices, count, d_tiles);
+    }
+    PathPoints path_points() const override { return path_points_of<PathRow>(); }
+    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
+        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, W * H, W * H, 7, W, H, s_.n, q);
     }
     // Same layout as oracle/pgo_coinrun.cpp Coinrun::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

@@ -1768,6 +1768,83 @@ int32_t pgv_tile_rows_host(pgv_env* e, const int32_t* h_indices, int32_t count, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Path distances (include/procgen2_vec.h; pg_paths.h and every tile game's PathRow).
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_path_layout_of(int32_t game_id, int32_t mode, pgv_path_layout* out) {
+    if (!out || out->struct_size < sizeof(pgv_path_layout)) return fail("pgv_path_layout_of: out is NULL or struct_size too small");
+    const std::unique_ptr<pg::Game> game = pg::layout_game("pgv_path_layout_of", game_id, mode);
+    if (!game) return 1;
+    const pg::StateLayout l = game->state_layout();
+    const pg::PathPoints p = game->path_points();
+    out->cells = l.cells, out->tile_w = l.tile_w, out->tile_h = l.tile_h;
+    out->has_goal = p.has_goal ? 1 : 0, out->agent_dx = p.agent_dx, out->agent_dy = p.agent_dy;
+    return 0;
+}
+
+namespace pg {
+// Points 8 of the path distances that do not depend on where the pointers live: nullptr, or why the call is refused.
+static const char* tile_paths_error(const pgv_env* e, int32_t count, const pgv_tile_paths* p) {
+    if (!e) return "env is NULL";
+    if (!p) return "the pgv_tile_paths struct is NULL";
+    if (p->struct_size < sizeof(pgv_tile_paths)) return "struct_size is too small";
+    if (count < 0) return "count is negative";
+    if (e->game->state_layout().cells == 0) return "this game has no tile map";
+    if (p->source != PGV_PATH_AGENT && p->source != PGV_PATH_GOAL && p->source != PGV_PATH_CELLS)
+        return "source must be PGV_PATH_AGENT, PGV_PATH_GOAL or PGV_PATH_CELLS";
+    if (p->probe != PGV_PATH_NONE && p->probe != PGV_PATH_AGENT && p->probe != PGV_PATH_GOAL && p->probe != PGV_PATH_CELLS)
+        return "unknown probe";
+    if ((p->source == PGV_PATH_GOAL || p->probe == PGV_PATH_GOAL) && !e->game->path_points().has_goal)
+        return "PGV_PATH_GOAL: this game has no goal";
+    if (count > 0 && p->source == PGV_PATH_CELLS && !p->source_cells) return "source_cells is NULL";
+    if (count > 0 && p->probe == PGV_PATH_CELLS && !p->probe_cells) return "probe_cells is NULL";
+    if (count > 0 && !p->dist && !p->probe_dist && !p->probe_step && !p->cells_out) return "every output is NULL";
+    return nullptr;
+}
+}  // namespace pg
+
+int32_t pgv_tile_paths_rows(pgv_env* e, const int32_t* d_indices, int32_t count, const pgv_tile_paths* p) {
+    if (const char* why = pg::tile_paths_error(e, count, p)) return fail(std::string("pgv_tile_paths_rows: ") + why);
+    if (reinterpret_cast<uintptr_t>(p->dist) % 16) return fail("pgv_tile_paths_rows: dist is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(p->probe_dist) % 4) return fail("pgv_tile_paths_rows: probe_dist is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(p->cells_out) % 4) return fail("pgv_tile_paths_rows: cells_out is not 4-byte aligned");
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    pg::TilePaths q{};
+    q.passable = p->passable, q.source = p->source, q.probe = p->probe;
+    q.source_cells = p->source_cells, q.probe_cells = p->probe_cells;
+    q.dist = p->dist, q.probe_dist = p->probe_dist, q.probe_step = p->probe_step, q.cells_out = p->cells_out;
+    q.indices = d_indices, q.count = count;
+    e->game->launch_tile_paths(e->stream, q);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_tile_paths_rows_host(pgv_env* e, const int32_t* h_indices, int32_t count, const pgv_tile_paths* p) {
+    if (const char* why = pg::tile_paths_error(e, count, p)) return fail(std::string("pgv_tile_paths_rows_host: ") + why);
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    const size_t rows = size_t(count), dists = rows * size_t(e->game->state_layout().cells);
+    pg::Staged dev{e->stream};
+    pgv_tile_paths d = *p;
+    d.source_cells = p->source == PGV_PATH_CELLS ? dev.alloc(rows, p->source_cells) : nullptr;
+    d.probe_cells = p->probe == PGV_PATH_CELLS ? dev.alloc(rows, p->probe_cells) : nullptr;
+    d.dist = p->dist ? dev.alloc<int16_t>(dists) : nullptr;
+    d.probe_dist = p->probe_dist ? dev.alloc<int32_t>(rows) : nullptr;
+    d.probe_step = p->probe_step ? dev.alloc<uint8_t>(rows) : nullptr;
+    d.cells_out = p->cells_out ? dev.alloc<int32_t>(rows * 2) : nullptr;
+    const int32_t* d_indices = h_indices ? dev.alloc(rows, h_indices) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_tile_paths_rows(e, d_indices, count, &d)) return rc;
+        if (p->dist) dev.fetch(p->dist, d.dist, dists * 2);
+        if (p->probe_dist) dev.fetch(p->probe_dist, d.probe_dist, rows * 4);
+        if (p->probe_step) dev.fetch(p->probe_step, d.probe_step, rows);
+        if (p->cells_out) dev.fetch(p->cells_out, d.cells_out, rows * 8);
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_tile_paths_rows_host: ") + hipGetErrorString(dev.err));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // cenv ABI (include/procgen2_cenv.h) on top of one process-global vector env.
 // ------------------------------------------------------------------------------------------------
 cenv_make_data make_data;

@@ -1288,6 +1288,13 @@ struct StateRow {
     }
 };
 
+// The points of the path distances (pg_paths.h): the body box spans agent_y - 0.8 .. agent_y; the goal is goal_x, goal_y.
+struct PathRow {
+    using Row = StateRow;
+    static constexpr float kAgentDy = -0.4f;
+    static constexpr int kGoalX = 18, kGoalY = 19;
+};
+
 class JumperGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "jumper"; }
@@ -1476,6 +1483,10 @@ class JumperGame final : public PrefetchingGame<Gen> {
     }
     void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
         launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
+    }
+    PathPoints path_points() const override { return path_points_of<PathRow>(); }
+    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
+        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
     }
     // Same layout as oracle/pgo_jumper.cpp Jumper::dump_state.
     int dump_state(hipStream_t st, int env, float* out, int cap) override {

@@ -442,6 +442,13 @@ struct StateRow {
     }
 };
 
+// The points of the path distances (pg_paths.h): the mouse fills its cell; the goal is the cheese.
+struct PathRow {
+    using Row = StateRow;
+    static constexpr float kAgentDy = 0.0f;
+    static constexpr int kGoalX = 3, kGoalY = 4;
+};
+
 class MazeGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "maze"; }
@@ -529,6 +536,10 @@ class MazeGame final : public PrefetchingGame<Gen> {
     }
     void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
         launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
+    }
+    PathPoints path_points() const override { return path_points_of<PathRow>(); }
+    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
+        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
     }
 
    private:

@@ -10,6 +10,7 @@
 
 #include "pg_carve.h"
 #include "pg_defs.h"
+#include "pg_paths.h"
 
 namespace pg {
 
@@ -133,6 +134,11 @@ class Game {
     virtual std::string state_names() const = 0;  // "<fixed names>|<record names>", space-separated
     virtual void launch_state_rows(hipStream_t s, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) = 0;
     virtual void launch_tile_rows(hipStream_t s, const int32_t* d_indices, int count, uint8_t* d_tiles) = 0;
+    // Path distances (include/procgen2_vec.h pgv_tile_paths_rows; pg_paths.h): the breadth-first distance field of `q.count`
+    // envs' tile maps, with the map's own fields of q (tiles .. tile_h, n) filled in by the game.  Read-only, on the given
+    // stream.  path_points is host-only, as state_layout is.  A game without a tile map (bossfight) has neither.
+    virtual PathPoints path_points() const { return {false, 0.0f, 0.0f}; }
+    virtual void launch_tile_paths(hipStream_t s, const TilePaths& q) { (void)s; (void)q; }
     // pgv_config.game_flags (include/procgen2_vec.h); false = this game does not know these switches.
     virtual bool set_game_flags(uint32_t flags) { return flags == 0; }
     // Called once between loading and uploading the atlas: a game may append data derived from its textures (jumper:

@@ -98,6 +98,46 @@ def state_layout(lib, game, mode=None):
                        tuple(fixed_names.split()), tuple(record_names.split()))
 
 
+class TilePathsStruct(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_tile_paths`."""
+    _fields_ = [("struct_size", c_uint32), ("passable", c_uint32), ("source", c_int32), ("source_cells", c_void_p),
+                ("probe", c_int32), ("probe_cells", c_void_p), ("dist", c_void_p), ("probe_dist", c_void_p),
+                ("probe_step", c_void_p), ("cells_out", c_void_p)]
+
+
+class PathLayoutStruct(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_path_layout`."""
+    _fields_ = [("struct_size", c_uint32), ("cells", c_int32), ("tile_w", c_int32), ("tile_h", c_int32), ("has_goal", c_int32),
+                ("agent_dx", c_float), ("agent_dy", c_float)]
+
+
+PATH_POINTS = {"none": 0, "agent": 1, "goal": 2, "cells": 3}  # PGV_PATH_*
+PathLayout = collections.namedtuple("PathLayout", "cells tile_w tile_h has_goal agent_dx agent_dy")
+
+
+def path_layout(lib, game, mode=None):
+    """pgv_path_layout_of → PathLayout (host only: no GPU, no env).  game: a name or the id."""
+    game_id = lib.pgv_game_id(game.encode()) if isinstance(game, str) else int(game)
+    out = PathLayoutStruct(ctypes.sizeof(PathLayoutStruct))
+    check(lib, lib.pgv_path_layout_of(game_id, mode_id(mode), ctypes.byref(out)), "pgv_path_layout_of")
+    return PathLayout(out.cells, out.tile_w, out.tile_h, bool(out.has_goal), out.agent_dx, out.agent_dy)
+
+
+def passable_mask(passable):
+    """An int as it is, or the tile ids of an iterable as bits."""
+    if isinstance(passable, int):
+        mask = passable
+    else:
+        mask = 0
+        for t in passable:
+            if not 0 <= int(t) < 32:
+                raise ValueError("passable: tile id %r is not in 0 .. 31" % (t,))
+            mask |= 1 << int(t)
+    if not 0 <= mask < 2 ** 32:
+        raise ValueError("passable: %r is not a 32-bit mask" % (passable,))
+    return mask
+
+
 class GatherAug(ctypes.Structure):
     """include/procgen2_vec.h `pgv_gather_aug`."""
     _fields_ = [("struct_size", c_uint32), ("out_height", c_int32), ("out_width", c_int32), ("pad", c_int32), ("edge", c_int32),
@@ -274,6 +314,9 @@ def load(path=None):
         "pgv_tile_rows": (c_int32, [P, P, c_int32, P]),
         "pgv_state_rows_host": (c_int32, [P, P, c_int32, P, P]),
         "pgv_tile_rows_host": (c_int32, [P, P, c_int32, P]),
+        "pgv_tile_paths_rows": (c_int32, [P, P, c_int32, POINTER(TilePathsStruct)]),
+        "pgv_tile_paths_rows_host": (c_int32, [P, P, c_int32, POINTER(TilePathsStruct)]),
+        "pgv_path_layout_of": (c_int32, [c_int32, c_int32, POINTER(PathLayoutStruct)]),
         "pgv_last_error": (c_char_p, []),
     }
     for name, (res, args) in proto.items():
@@ -303,6 +346,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",
+    "pgv_tile_paths_rows", "pgv_tile_paths_rows_host", "pgv_path_layout_of",
     "pgv_last_error",
 ]
 EXPORTED_CENV_SYMBOLS = [

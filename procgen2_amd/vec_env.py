@@ -82,6 +82,8 @@ class ProcgenVecEnv:
         # The columns of state_obs() / tile_obs() (include/procgen2_vec.h pgv_state_layout_of, pgv_state_names): width, fixed,
         # record, max_records, cells, tile_w, tile_h, fixed_names, record_names.
         self.state_layout = pglib.state_layout(self.L, game, self.distribution_mode)
+        # What tile_paths() goes by (include/procgen2_vec.h pgv_path_layout_of): cells, tile_w, tile_h, has_goal, agent_dx, agent_dy.
+        self.path_layout = pglib.path_layout(self.L, game, self.distribution_mode)
         self._sequences = {}  # step_sequence's result tensors, by T: the _SEQUENCES_KEPT most recently used
         # torch owns the result buffers; the engine writes straight into them.
         if out is not None:
@@ -485,6 +487,60 @@ class ProcgenVecEnv:
             self._keep_tile_obs = (idx, out)
         return out
 
+    # -- path distances (include/procgen2_vec.h pgv_tile_paths_rows) -----------------------------
+    def tile_paths(self, source="goal", probe="agent", passable=(0,), envs=None, source_cells=None, probe_cells=None, dist=True,
+                   out=None):
+        """Breadth-first path distances over the tile maps of the envs `envs` (as state_obs takes them), as they stand now.
+        The field is a geometric distance over cells (the platformers' physics are not in it).
+
+        source: "agent", "goal" or "cells"; probe: "none", "agent", "goal" or "cells".  The agent's cell is the cell of the
+        centre of its body box, (agent_x, agent_y + path_layout.agent_dy); the goal's that of goal_x, goal_y (maze,
+        jumper) or of entity 0 (caveflyer) — "goal" is refused for the other games.  "cells" takes source_cells /
+        probe_cells: int32 [B], cell (x, y) = y + x * tile_h as in tile_obs, a value outside 0 .. cells-1 meaning no cell.
+        passable: the tile ids (as tile_obs gives them, below 32) that may be entered, as an iterable or a 32-bit mask.
+        The source cell has distance 0 whatever its tile; a cell has distance d + 1 when it is passable, not yet reached and
+        has a 4-neighbour at distance d; no wrap at any edge; every other cell is -1.
+
+        Returns a TilePaths on this env's device: dist int16 [B, cells] (None with dist=False), probe_dist int32 [B] (-1:
+        not reached, or no probe cell), probe_step uint8 [B] (0 where probe_dist <= 0, else the first of x-1 (1), x+1 (2),
+        y-1 (3), y+1 (4) whose distance is one less) and cells int32 [B, 2] (source cell, probe cell; -1 for none).  A row
+        without a source, or of an env outside the batch, is -1 everywhere with step 0.  out: a caller-owned contiguous,
+        16-byte aligned int16 [B, cells] tensor for dist.  Same stream hand-shake as tile_obs(), no host synchronisation;
+        reads only.  In maze, torch.tensor(procgen2_amd.MAZE_STEP_ACTIONS)[paths.probe_step.long()] with the defaults is
+        the optimal policy."""
+        for name, value, kinds in (("source", source, ("agent", "goal", "cells")), ("probe", probe, ("none", "agent", "goal", "cells"))):
+            if value not in kinds:
+                raise ValueError("%s must be one of %s, not %r" % (name, ", ".join(kinds), value))
+        idx, count = self._indices(envs)
+        cells = self.path_layout.cells
+        given = []
+        for name, kind, value in (("source_cells", source, source_cells), ("probe_cells", probe, probe_cells)):
+            if kind != "cells":
+                given.append(None)
+                continue
+            if value is None:
+                raise ValueError("%s is needed with %s='cells'" % (name, name[:-6]))
+            value = torch.as_tensor(value, device=self.device).to(torch.int32).reshape(-1).contiguous()
+            if value.numel() != count:
+                raise ValueError("%s: expected %d cells, got %d" % (name, count, value.numel()))
+            given.append(value)
+        if out is not None and not dist:
+            raise ValueError("out is given with dist=False")
+        res = TilePaths(dist=self._obs_out(out, (count, cells), torch.int16, "out") if dist else None,
+                        probe_dist=torch.empty((count,), dtype=torch.int32, device=self.device),
+                        probe_step=torch.empty((count,), dtype=torch.uint8, device=self.device),
+                        cells=torch.empty((count, 2), dtype=torch.int32, device=self.device))
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+        q = pglib.TilePathsStruct(ctypes.sizeof(pglib.TilePathsStruct), pglib.passable_mask(passable), pglib.PATH_POINTS[source],
+                                  ptr(given[0]), pglib.PATH_POINTS[probe], ptr(given[1]), ptr(res.dist), ptr(res.probe_dist),
+                                  ptr(res.probe_step), ptr(res.cells))
+        self._before()
+        pglib.check(self.L, self.L.pgv_tile_paths_rows(self._h, c_void_p(idx.data_ptr()) if idx is not None and count else None, count,
+                                                       ctypes.byref(q)), "pgv_tile_paths_rows")
+        self._after()
+        self._keep_tile_paths = (idx, given, res)
+        return res
+
     def save_state(self):
         """Snapshot of the whole batch (state, RNG streams, prefetched levels, outputs) as a numpy byte array."""
         import numpy as np
@@ -793,6 +849,14 @@ class SequenceResult:
     def layout(T, n):
         return {"rewards": ((T, n), torch.float32), "dones": ((T, n), torch.uint8), "seq_return": ((n,), torch.float32),
                 "seq_length": ((n,), torch.int32), "seq_done": ((n,), torch.uint8)}
+
+
+class TilePaths:
+    """What ProcgenVecEnv.tile_paths returns: dist int16 [B, cells] or None, probe_dist int32 [B], probe_step uint8 [B],
+    cells int32 [B, 2] (source cell, probe cell)."""
+
+    def __init__(self, dist, probe_dist, probe_step, cells):
+        self.dist, self.probe_dist, self.probe_step, self.cells = dist, probe_dist, probe_step, cells
 
 
 class EnvRecords:
