@@ -228,7 +228,8 @@ PGV_API int32_t pgv_load_envs_host(pgv_env* env, const int32_t* h_indices, int32
  *      queue, none included (pgv_generator_launches counts it; measurements: docs/OPTLOG.md).
  *   8. pgv_level_numbers()[i] / pgv_level_known()[i] (device u32[N] / u8[N], valid from pgv_make until pgv_close, written
  *      on the env's stream): the number of the level env i is IN, and whether it has one — 1 in level-seed mode and for an
- *      assigned level, 0 (with number 0) for a free-mode level.  Whatever installs a level writes them: at the step that
+ *      assigned level, 0 (with number 0) for a free-mode level, 2 for a caller-made level with the caller's label as its
+ *      number (pgv_set_levels).  Whatever installs a level writes them: at the step that
  *      reports `done` they still name the level that just ended — what a scorer needs — and they change in the step that
  *      shows the new level's first frame.
  *   9. The pending assignment, the current number and its flag, and what the shadow slot knows about the level it holds
@@ -652,6 +653,93 @@ typedef struct pgv_path_layout {
     float agent_dx, agent_dy;      /* the agent's cell is the cell of (agent_x + agent_dx, agent_y + agent_dy); agent_dx is 0 */
 } pgv_path_layout;
 PGV_API int32_t pgv_path_layout_of(int32_t game_id, int32_t mode, pgv_path_layout* out); /* set struct_size first */
+
+/* Caller-made levels: levels as values.  pgv_get_levels reads the level of any envs into device memory, the caller edits it
+ * there, pgv_set_levels installs rows into any envs as the start of a new episode.  (What unsupervised environment design —
+ * PAIRED, ACCEL, robust PLR — maze interpretability and hand-built evaluation sets need; pgv_assign_levels only names a
+ * generator seed.  The reference has no counterpart.)  For maze, in every mode it has; the other games' levels carry entity
+ * lists and are refused.
+ *
+ * A level is a row of pgv_level_rows: the tile row as pgv_tile_rows lays it out (cells bytes, 0 open, 1 wall), the agent's
+ * and the goal's cell by the rule of point 1 of the path distances (cell (x, y) = y + x * tile_h; a point stands on its
+ * cell's centre, agent_x = x + 0.5, agent_y = tile_h - 1 - y + 0.5), the floor picture (0 .. backgrounds - 1) and its shift.
+ * pgv_level_layout_of is host-only and pure — no GPU, no env, refusals as pgv_state_layout_of — and says supported = 1 with
+ * the map's size for maze in each of its modes, supported = 0 and zeros for the six other games.
+ *
+ * pgv_get_levels is the read-only form: the level of each named env as it stands, the agent's current cell included; it
+ * changes nothing and a second call gives the same bytes.  Every field equals what pgv_tile_rows and pgv_state_rows give
+ * (background, background_shift: columns floor, floor_shift).  d_indices as for pgv_tile_rows: NULL for envs 0 .. count-1,
+ * repeats allowed, an index outside the batch gives a zero tile row, cells of -1, background 0 and shift +0.0f.  Any output
+ * pointer may be NULL; ids and status are not written.
+ *
+ * pgv_set_levels:
+ *   1. Every row is judged on the device and its status written to status[k] (where status is not NULL); nothing is
+ *      reported through the host.  A row that is refused leaves its env untouched.  The first that applies:
+ *        PGV_LEVEL_INSTALLED  0  installed;
+ *        PGV_LEVEL_NO_ENV     1  the index is outside the batch (a caller's way to a fixed-size call, as for
+ *                                pgv_assign_levels);
+ *        PGV_LEVEL_BAD_TILE   2  a tile byte is neither 0 (open) nor 1 (wall);
+ *        PGV_LEVEL_BAD_AGENT  3  the agent's cell is outside the map, or is a wall;
+ *        PGV_LEVEL_BAD_GOAL   4  the goal's cell is outside the map, is a wall, or is the agent's cell;
+ *        PGV_LEVEL_BAD_FLOOR  5  background is outside 0 .. backgrounds - 1, or background_shift is not a finite value in
+ *                                [0, 1).
+ *      With background or background_shift NULL every env keeps the value it has: an edited level keeps its look.
+ *   2. An accepted row is a pgv_reset of its env with the caller's level in place of a generated one.  The live state is
+ *      what the generator's own install leaves: the tiles (and the block's padding bytes), the two points, the floor, steps
+ *      0, facing forward, the camera on the world centre.  The env's obs row is the level's first frame, its reward 0, its
+ *      done 0, and an auto-reset that was pending for it is cleared.  Everything pgv_reset does for the envs it names is
+ *      done for the installed envs and for no other: the policy observations restart and are pushed under the mask (point 4
+ *      there), the frame history's newest slot is rewritten (point 5 there), the episodes' running return and length are
+ *      zeroed.
+ *   3. What an install does NOT touch: the env's mt19937 stream, its generator chain, its shadow slot, a pending level
+ *      assignment, its place in its level sequence.  When the custom episode ends, the auto-reset builds the level the env
+ *      would have built anyway; a caller who wants another custom level installs one on the envs that ended — behind a
+ *      same-step pgv_step_episodes that is indices = where(ended, arange, -1), with no look from the host.
+ *   4. Labels.  pgv_level_numbers[i] = ids[k], or 0 with ids NULL, and pgv_level_known[i] = 2, "the caller's label": so
+ *      ended_level / ended_level_known say which custom level an episode's return belongs to.  Nothing else writes 2.
+ *   5. The indices of one call must be distinct; d_indices NULL stands for envs 0 .. count-1.  Of two rows that name one
+ *      env, one is installed whole and the other is dropped, both with status 0 (nothing faults).
+ *   6. count = 0 succeeds and writes nothing.  Checked on the host before anything is enqueued, each refusal leaving a
+ *      message and the engine as it was: env or struct NULL; struct_size too small; count < 0; a game without caller-made
+ *      levels ("no caller-made levels for this game", pgv_get_levels too); tiles, agent_cell or goal_cell NULL with
+ *      count > 0; a pointer to 4-byte elements that is not 4-byte aligned (tiles may lie anywhere); with the policy
+ *      observations or the frame history enabled, an obs slab that is not 16-byte aligned.
+ *   7. The call is enqueued on the env's stream, allocates nothing and does not synchronise the host.  It touches nothing
+ *      the level generator's side stream reads or writes, so it is not ordered against it and launches no generator.  Cost:
+ *      one clear of the call's scratch, one launch of a wavefront a row, and pgv_reset's render and bookkeeping launches
+ *      under the mask (measurements: docs/OPTLOG.md).
+ *   8. Records and snapshots: a custom level is live state and nothing else, so it travels in pgv_save_envs and
+ *      pgv_save_state as any level does; neither layout changed.
+ * The _host forms take host pointers throughout (indices and every pointer of the struct), allocate and free their device
+ * buffers and are synchronous, as pgv_tile_rows_host is; they ask no alignment. */
+#define PGV_LEVEL_INSTALLED 0
+#define PGV_LEVEL_NO_ENV 1
+#define PGV_LEVEL_BAD_TILE 2
+#define PGV_LEVEL_BAD_AGENT 3
+#define PGV_LEVEL_BAD_GOAL 4
+#define PGV_LEVEL_BAD_FLOOR 5
+typedef struct pgv_level_layout {
+    uint32_t struct_size;
+    int32_t supported;       /* 1: pgv_get_levels / pgv_set_levels serve this game in this mode */
+    int32_t cells;           /* bytes per tile row */
+    int32_t tile_w, tile_h;  /* cells == tile_w * tile_h */
+    int32_t backgrounds;     /* floor pictures: background is 0 .. backgrounds - 1 */
+} pgv_level_layout;
+PGV_API int32_t pgv_level_layout_of(int32_t game_id, int32_t mode, pgv_level_layout* out); /* set struct_size first */
+typedef struct pgv_level_rows { /* device pointers; [count] rows parallel to the indices */
+    uint32_t struct_size;
+    uint8_t* tiles;          /* [count][cells], laid out as pgv_tile_rows */
+    int32_t* agent_cell;     /* [count]  cell index y + x * tile_h */
+    int32_t* goal_cell;      /* [count] */
+    int32_t* background;     /* [count]  floor picture; may be NULL */
+    float* background_shift; /* [count]  may be NULL */
+    uint32_t* ids;           /* [count]  the caller's labels, install only; may be NULL */
+    int32_t* status;         /* [count]  install only: PGV_LEVEL_* per row; may be NULL */
+} pgv_level_rows;
+PGV_API int32_t pgv_get_levels(pgv_env* env, const int32_t* d_indices, int32_t count, const pgv_level_rows* out);
+PGV_API int32_t pgv_set_levels(pgv_env* env, const int32_t* d_indices, int32_t count, const pgv_level_rows* in);
+PGV_API int32_t pgv_get_levels_host(pgv_env* env, const int32_t* h_indices, int32_t count, const pgv_level_rows* out);
+PGV_API int32_t pgv_set_levels_host(pgv_env* env, const int32_t* h_indices, int32_t count, const pgv_level_rows* in);
 
 /* Measurement helper for bench.py: runs `steps` synthetic steps and returns, from HIP events recorded
  * on the env's stream, the total time of the region and the summed time of the dominant (render)

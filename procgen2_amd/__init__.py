@@ -22,4 +22,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 # policy, on the device.
 MAZE_STEP_ACTIONS = (4, 1, 7, 3, 5)
 
-__all__ = ["lib", "cenv", "vec_env", "build", "MAZE_STEP_ACTIONS"]
+# What a row's status of ProcgenVecEnv.set_levels says (include/procgen2_vec.h PGV_LEVEL_*): LEVEL_STATUS[status[k]].
+LEVEL_STATUS = ("installed", "no_env", "bad_tile", "bad_agent", "bad_goal", "bad_floor")
+
+__all__ = ["lib", "cenv", "vec_env", "build", "MAZE_STEP_ACTIONS", "LEVEL_STATUS"]

@@ -273,6 +273,9 @@ struct pgv_env {
     // steps without frames (pg_sequence.h; pgv_step_sequence): the running values of the summary, one block
     void* d_sequence = nullptr;
     pg::SequenceBuffers seq{};
+    // caller-made levels (pg_levels.h; pgv_set_levels): an install's claim words and mask, one block, for a game that has them
+    void* d_levels = nullptr;
+    pg::LevelBuffers lev{};
     // policy-ready observations (pg_policy_obs.h; pgv_policy_obs_enable): off unless asked for.  One device block holds the
     // restart flags and the value table; the tensor is the caller's, or the engine's own.
     bool policy = false, own_policy_out = false;
@@ -368,6 +371,7 @@ void pgv_close(pgv_env* e) {
     if (e->d_pending) hipFree(e->d_pending);
     if (e->d_episodes) hipFree(e->d_episodes);
     if (e->d_sequence) hipFree(e->d_sequence);
+    if (e->d_levels) hipFree(e->d_levels);
     if (e->d_policy) hipFree(e->d_policy);
     if (e->own_policy_out && e->d_policy_out) hipFree(e->d_policy_out);
     if (e->d_history) hipFree(e->d_history);
@@ -532,6 +536,10 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
 
     PG_HIP(hipMalloc(&e->d_sequence, pg::Carve::size(pg::list_sequence, num_envs)));  // (written before it is read: pg_sequence.h)
     pg::Carve::bind(pg::list_sequence, e->d_sequence, e->seq, num_envs);
+    if (e->game->level_layout().supported) {  // (zeroed in front of every install)
+        PG_HIP(hipMalloc(&e->d_levels, pg::Carve::size(pg::list_levels, num_envs)));
+        pg::Carve::bind(pg::list_levels, e->d_levels, e->lev, num_envs);
+    }
 
     e->game->bind(e->d_state, num_envs, e->atlas.view());
     if (const size_t scratch = e->game->scratch_bytes(num_envs)) {
@@ -612,22 +620,29 @@ static int32_t end_with_pushes(const char* who, pgv_env* e) {
     return e->history ? history_push(e, false, nullptr) : 0;
 }
 
+// What a reset does for the envs of `d_mask` once their new levels are the live state: the first frame, the episodes'
+// running values, the stacks and the frame history.  `generated`: the levels came from the generator (pgv_reset), whose next
+// launch is then due; a caller's levels (pgv_set_levels) took nothing from it.
+static int32_t reset_shows(const char* who, pgv_env* e, const uint8_t* d_mask, bool generated) {
+    e->game->launch_prepass(e->stream, d_mask);
+    e->game->launch_render(e->stream, d_mask, e->io());
+    if (e->episodes) pg::launch_episode_clear(e->stream, e->ep, d_mask);  // the named envs start their episodes afresh
+    if (generated) pregen(e, true, true);
+    PG_HIP(hipGetLastError());
+    if (e->policy) {  // the named envs' stacks restart with the frame just drawn
+        pg::launch_policy_flag_mask(e->stream, e->pol.restart, e->n, d_mask);
+        if (policy_push(who, e, d_mask)) return 1;
+    }
+    if (e->history) return history_push(e, true, d_mask);  // … and their rows of the newest slot are that frame, began = 1
+    return 0;
+}
+
 int32_t pgv_reset(pgv_env* e, const uint8_t* d_mask, const int32_t* d_seeds) {
     if (!e) return fail("pgv_reset: env is NULL");
     if (slab_ready("pgv_reset", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     e->game->launch_reset(e->stream, d_mask, d_seeds, e->io());
-    e->game->launch_prepass(e->stream, d_mask);
-    e->game->launch_render(e->stream, d_mask, e->io());
-    if (e->episodes) pg::launch_episode_clear(e->stream, e->ep, d_mask);  // the named envs start their episodes afresh
-    pregen(e, true, true);
-    PG_HIP(hipGetLastError());
-    if (e->policy) {  // the named envs' stacks restart with the frame just drawn
-        pg::launch_policy_flag_mask(e->stream, e->pol.restart, e->n, d_mask);
-        if (policy_push("pgv_reset", e, d_mask)) return 1;
-    }
-    if (e->history) return history_push(e, true, d_mask);  // … and their rows of the newest slot are that frame, began = 1
-    return 0;
+    return reset_shows("pgv_reset", e, d_mask, true);
 }
 
 // One step's launches.  The launch status is read after each group of launches: hipGetLastError reports (and clears)
@@ -1841,6 +1856,121 @@ int32_t pgv_tile_paths_rows_host(pgv_env* e, const int32_t* h_indices, int32_t c
         if (p->cells_out) dev.fetch(p->cells_out, d.cells_out, rows * 8);
     }
     if (dev.err != hipSuccess) return fail(std::string("pgv_tile_paths_rows_host: ") + hipGetErrorString(dev.err));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Caller-made levels (include/procgen2_vec.h; pg_levels.h and maze's Custom).
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_level_layout_of(int32_t game_id, int32_t mode, pgv_level_layout* out) {
+    if (!out || out->struct_size < sizeof(pgv_level_layout)) return fail("pgv_level_layout_of: out is NULL or struct_size too small");
+    const std::unique_ptr<pg::Game> game = pg::layout_game("pgv_level_layout_of", game_id, mode);
+    if (!game) return 1;
+    const pg::LevelLayout l = game->level_layout();
+    out->supported = l.supported, out->cells = l.cells, out->tile_w = l.tile_w, out->tile_h = l.tile_h, out->backgrounds = l.backgrounds;
+    return 0;
+}
+
+namespace pg {
+// The host's refusals that do not depend on where the pointers live: nullptr, or why the call is refused.
+static const char* level_rows_error(const pgv_env* e, int32_t count, const pgv_level_rows* rows, bool install) {
+    if (!e) return "env is NULL";
+    if (!rows) return "the pgv_level_rows struct is NULL";
+    if (rows->struct_size < sizeof(pgv_level_rows)) return "struct_size is too small";
+    if (count < 0) return "count is negative";
+    if (!e->game->level_layout().supported) return "no caller-made levels for this game";
+    if (install && count > 0 && !rows->tiles) return "tiles is NULL";
+    if (install && count > 0 && !rows->agent_cell) return "agent_cell is NULL";
+    if (install && count > 0 && !rows->goal_cell) return "goal_cell is NULL";
+    return nullptr;
+}
+static const char* level_rows_misaligned(const pgv_level_rows* rows) {
+    for (auto [p, name] : {std::pair<const void*, const char*>{rows->agent_cell, "agent_cell"}, {rows->goal_cell, "goal_cell"},
+                           {rows->background, "background"}, {rows->background_shift, "background_shift"}, {rows->ids, "ids"},
+                           {rows->status, "status"}})
+        if (reinterpret_cast<uintptr_t>(p) % 4) return name;
+    return nullptr;
+}
+static LevelRows level_rows(const int32_t* d_indices, int32_t count, const pgv_level_rows* r) {
+    return LevelRows{d_indices, count, r->tiles, r->agent_cell, r->goal_cell, r->background, r->background_shift, r->ids, r->status};
+}
+}  // namespace pg
+
+int32_t pgv_get_levels(pgv_env* e, const int32_t* d_indices, int32_t count, const pgv_level_rows* out) {
+    if (const char* why = pg::level_rows_error(e, count, out, false)) return fail(std::string("pgv_get_levels: ") + why);
+    if (const char* name = pg::level_rows_misaligned(out)) return fail(std::string("pgv_get_levels: ") + name + " is not 4-byte aligned");
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    e->game->launch_get_levels(e->stream, pg::level_rows(d_indices, count, out));
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_set_levels(pgv_env* e, const int32_t* d_indices, int32_t count, const pgv_level_rows* in) {
+    if (const char* why = pg::level_rows_error(e, count, in, true)) return fail(std::string("pgv_set_levels: ") + why);
+    if (const char* name = pg::level_rows_misaligned(in)) return fail(std::string("pgv_set_levels: ") + name + " is not 4-byte aligned");
+    if (count == 0) return 0;
+    if (slab_ready("pgv_set_levels", e)) return 1;
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    // The install writes the live state, the engine's rows and the level words of the envs it names, all of them the env's
+    // stream's: the generator's side stream reads and writes the shadow slots, the chains and the slot words alone, so there
+    // is nothing to order against it (a reset waits for it through the slot word it consumes; an install consumes none).
+    PG_HIP(hipMemsetAsync(e->d_levels, 0, pg::Carve::size(pg::list_levels, e->n), e->stream));
+    pg::LevelInstall to{e->n, e->d_reward, e->d_done, e->d_pending, e->game->plan.number, e->game->plan.known, e->lev.claim, e->lev.mask};
+    e->game->launch_set_levels(e->stream, pg::level_rows(d_indices, count, in), to);
+    PG_HIP(hipGetLastError());
+    return reset_shows("pgv_set_levels", e, e->lev.mask, false);
+}
+
+int32_t pgv_get_levels_host(pgv_env* e, const int32_t* h_indices, int32_t count, const pgv_level_rows* out) {
+    if (const char* why = pg::level_rows_error(e, count, out, false)) return fail(std::string("pgv_get_levels_host: ") + why);
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    const size_t rows = size_t(count), bytes = rows * size_t(e->game->level_layout().cells);
+    pg::Staged dev{e->stream};
+    pgv_level_rows d = *out;
+    d.tiles = out->tiles ? dev.alloc<uint8_t>(bytes) : nullptr;
+    d.agent_cell = out->agent_cell ? dev.alloc<int32_t>(rows) : nullptr;
+    d.goal_cell = out->goal_cell ? dev.alloc<int32_t>(rows) : nullptr;
+    d.background = out->background ? dev.alloc<int32_t>(rows) : nullptr;
+    d.background_shift = out->background_shift ? dev.alloc<float>(rows) : nullptr;
+    d.ids = nullptr, d.status = nullptr;
+    const int32_t* d_indices = h_indices ? dev.alloc(rows, h_indices) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_get_levels(e, d_indices, count, &d)) return rc;
+        if (out->tiles) dev.fetch(out->tiles, d.tiles, bytes);
+        if (out->agent_cell) dev.fetch(out->agent_cell, d.agent_cell, rows * 4);
+        if (out->goal_cell) dev.fetch(out->goal_cell, d.goal_cell, rows * 4);
+        if (out->background) dev.fetch(out->background, d.background, rows * 4);
+        if (out->background_shift) dev.fetch(out->background_shift, d.background_shift, rows * 4);
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_get_levels_host: ") + hipGetErrorString(dev.err));
+    return 0;
+}
+
+int32_t pgv_set_levels_host(pgv_env* e, const int32_t* h_indices, int32_t count, const pgv_level_rows* in) {
+    if (const char* why = pg::level_rows_error(e, count, in, true)) return fail(std::string("pgv_set_levels_host: ") + why);
+    if (count == 0) return 0;
+    if (slab_ready("pgv_set_levels_host", e)) return 1;
+    PG_HIP(hipSetDevice(e->device));
+    const size_t rows = size_t(count), bytes = rows * size_t(e->game->level_layout().cells);
+    pg::Staged dev{e->stream};
+    pgv_level_rows d = *in;
+    d.tiles = dev.alloc(bytes, in->tiles);
+    d.agent_cell = dev.alloc(rows, in->agent_cell);
+    d.goal_cell = dev.alloc(rows, in->goal_cell);
+    d.background = in->background ? dev.alloc(rows, in->background) : nullptr;
+    d.background_shift = in->background_shift ? dev.alloc(rows, in->background_shift) : nullptr;
+    d.ids = in->ids ? dev.alloc(rows, in->ids) : nullptr;
+    d.status = in->status ? dev.alloc<int32_t>(rows) : nullptr;
+    const int32_t* d_indices = h_indices ? dev.alloc(rows, h_indices) : nullptr;
+    if (dev.err == hipSuccess) {
+        if (const int32_t rc = pgv_set_levels(e, d_indices, count, &d)) return rc;
+        if (in->status) dev.fetch(in->status, d.status, rows * 4);
+        dev.finish();  // (the host buffers are the caller's)
+    }
+    if (dev.err != hipSuccess) return fail(std::string("pgv_set_levels_host: ") + hipGetErrorString(dev.err));
     return 0;
 }
 

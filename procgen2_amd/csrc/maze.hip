@@ -449,6 +449,30 @@ struct PathRow {
     static constexpr int kGoalX = 3, kGoalY = 4;
 };
 
+// A level as a value (pg_levels.h): `Level` is all of it.  The floor pictures are the nine generate() draws from.
+struct Custom {
+    using State = maze::State;
+    using Level = maze::Level;
+    static constexpr int kW = W, kH = H, kStride = kTileStride, kBackgrounds = 9;
+    static constexpr uint8_t kOpen = maze::kOpen, kPad = kWall;  // (generate() fills the whole block with walls first)
+    static __device__ const uint8_t* tiles(const State& s) { return s.tiles; }
+    static __device__ void read(const State& s, int env, int& agent, int& goal, int& bg, float& shift) {
+        agent = path_cell_of(SF(s, F_AX, env), SF(s, F_AY, env), W, H);
+        goal = path_cell_of(SF(s, F_GX, env), SF(s, F_GY, env), W, H);
+        bg = SI(s, I_BG, env);
+        shift = SF(s, F_BGSHIFT, env);
+    }
+    static __device__ void fill(Level& lv, int agent, int goal, int bg, float shift) {
+        lv.ax = level_point_x(agent, H);
+        lv.ay = level_point_y(agent, H);
+        lv.gx = level_point_x(goal, H);
+        lv.gy = level_point_y(goal, H);
+        lv.bg = bg;
+        lv.bgshift = shift;
+    }
+    static __device__ void install(const State& s, int env, const Level& lv, int lane) { maze::install(s, env, lv, lane); }
+};
+
 class MazeGame final : public PrefetchingGame<Gen> {
    public:
     const char* name() const override { return "maze"; }
@@ -536,6 +560,11 @@ class MazeGame final : public PrefetchingGame<Gen> {
     }
     void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
         launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
+    }
+    LevelLayout level_layout() const override { return level_layout_of<Custom>(); }
+    void launch_get_levels(hipStream_t st, const LevelRows& out) override { launch_get_levels_of<Custom>(st, s_, out, s_.n); }
+    void launch_set_levels(hipStream_t st, const LevelRows& in, const LevelInstall& to) override {
+        launch_set_levels_of<Custom>(st, s_, in, to);
     }
     PathPoints path_points() const override { return path_points_of<PathRow>(); }
     void launch_tile_paths(hipStream_t st, const TilePaths& q) override {

@@ -10,6 +10,7 @@
 
 #include "pg_carve.h"
 #include "pg_defs.h"
+#include "pg_levels.h"
 #include "pg_paths.h"
 
 namespace pg {
@@ -139,6 +140,13 @@ class Game {
     // stream.  path_points is host-only, as state_layout is.  A game without a tile map (bossfight) has neither.
     virtual PathPoints path_points() const { return {false, 0.0f, 0.0f}; }
     virtual void launch_tile_paths(hipStream_t s, const TilePaths& q) { (void)s; (void)q; }
+    // Caller-made levels (include/procgen2_vec.h pgv_get_levels / pgv_set_levels; pg_levels.h): the levels of `count` envs
+    // read into the caller's rows, and the caller's rows installed as the named envs' live state (`to`: the engine's rows,
+    // level words and scratch of the call).  level_layout is host-only, as state_layout is; supported = 0 (every other field 0)
+    // for a game whose levels are more than a tile map and two points, and the engine then never calls the launches.
+    virtual LevelLayout level_layout() const { return {0, 0, 0, 0, 0}; }
+    virtual void launch_get_levels(hipStream_t s, const LevelRows& out) { (void)s; (void)out; }
+    virtual void launch_set_levels(hipStream_t s, const LevelRows& in, const LevelInstall& to) { (void)s; (void)in; (void)to; }
     // pgv_config.game_flags (include/procgen2_vec.h); false = this game does not know these switches.
     virtual bool set_game_flags(uint32_t flags) { return flags == 0; }
     // Called once between loading and uploading the atlas: a game may append data derived from its textures (jumper:

@@ -386,3 +386,13 @@ class ProcgenGymVectorEnv(GymVectorAdapter):
                          state_info=state_info)
         self.game = game
         self.history = self.engine.history
+        self.level_layout = self.engine.level_layout
+
+    def get_levels(self, envs=None, host=False):
+        """ProcgenVecEnv.get_levels: the sub-envs' levels as values (maze)."""
+        return self.engine.get_levels(envs, host=host)
+
+    def set_levels(self, levels=None, **fields):
+        """ProcgenVecEnv.set_levels: install caller-made levels as the start of new episodes; returns the rows' status.  The
+        installed sub-envs' observations are in the engine's obs (and policy_obs) tensors, as after a masked reset()."""
+        return self.engine.set_levels(levels, **fields)

@@ -138,6 +138,37 @@ def passable_mask(passable):
     return mask
 
 
+class LevelLayoutStruct(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_level_layout`."""
+    _fields_ = [("struct_size", c_uint32), ("supported", c_int32), ("cells", c_int32), ("tile_w", c_int32), ("tile_h", c_int32),
+                ("backgrounds", c_int32)]
+
+
+class LevelRowsStruct(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_level_rows` (device pointers; host pointers for the _host forms)."""
+    _fields_ = [("struct_size", c_uint32), ("tiles", c_void_p), ("agent_cell", c_void_p), ("goal_cell", c_void_p),
+                ("background", c_void_p), ("background_shift", c_void_p), ("ids", c_void_p), ("status", c_void_p)]
+
+
+# include/procgen2_vec.h PGV_LEVEL_*: what a row's status says
+LEVEL_STATUS = {"installed": 0, "no_env": 1, "bad_tile": 2, "bad_agent": 3, "bad_goal": 4, "bad_floor": 5}
+LEVEL_KNOWN_CUSTOM = 2  # pgv_level_known: the caller's label
+LevelLayout = collections.namedtuple("LevelLayout", "supported cells tile_w tile_h backgrounds")
+
+
+def level_layout(lib, game, mode=None):
+    """pgv_level_layout_of → LevelLayout (host only: no GPU, no env).  game: a name or the id."""
+    game_id = lib.pgv_game_id(game.encode()) if isinstance(game, str) else int(game)
+    out = LevelLayoutStruct(ctypes.sizeof(LevelLayoutStruct))
+    check(lib, lib.pgv_level_layout_of(game_id, mode_id(mode), ctypes.byref(out)), "pgv_level_layout_of")
+    return LevelLayout(bool(out.supported), out.cells, out.tile_w, out.tile_h, out.backgrounds)
+
+
+def level_rows(tiles=None, agent_cell=None, goal_cell=None, background=None, background_shift=None, ids=None, status=None):
+    """A filled-in LevelRowsStruct; the pointers are integers (data_ptr(), ctypes.data) or None."""
+    return LevelRowsStruct(ctypes.sizeof(LevelRowsStruct), tiles, agent_cell, goal_cell, background, background_shift, ids, status)
+
+
 class GatherAug(ctypes.Structure):
     """include/procgen2_vec.h `pgv_gather_aug`."""
     _fields_ = [("struct_size", c_uint32), ("out_height", c_int32), ("out_width", c_int32), ("pad", c_int32), ("edge", c_int32),
@@ -317,6 +348,11 @@ def load(path=None):
         "pgv_tile_paths_rows": (c_int32, [P, P, c_int32, POINTER(TilePathsStruct)]),
         "pgv_tile_paths_rows_host": (c_int32, [P, P, c_int32, POINTER(TilePathsStruct)]),
         "pgv_path_layout_of": (c_int32, [c_int32, c_int32, POINTER(PathLayoutStruct)]),
+        "pgv_level_layout_of": (c_int32, [c_int32, c_int32, POINTER(LevelLayoutStruct)]),
+        "pgv_get_levels": (c_int32, [P, P, c_int32, POINTER(LevelRowsStruct)]),
+        "pgv_set_levels": (c_int32, [P, P, c_int32, POINTER(LevelRowsStruct)]),
+        "pgv_get_levels_host": (c_int32, [P, P, c_int32, POINTER(LevelRowsStruct)]),
+        "pgv_set_levels_host": (c_int32, [P, P, c_int32, POINTER(LevelRowsStruct)]),
         "pgv_last_error": (c_char_p, []),
     }
     for name, (res, args) in proto.items():
@@ -347,6 +383,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",
     "pgv_tile_paths_rows", "pgv_tile_paths_rows_host", "pgv_path_layout_of",
+    "pgv_level_layout_of", "pgv_get_levels", "pgv_set_levels", "pgv_get_levels_host", "pgv_set_levels_host",
     "pgv_last_error",
 ]
 EXPORTED_CENV_SYMBOLS = [

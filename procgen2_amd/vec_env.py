@@ -9,6 +9,7 @@ Multi-GPU: one process per GPU; rank r owns global envs [r*N, (r+1)*N) (seed = s
 index, so results do not depend on the GPU count).  There is no collective in reset/step/render;
 `gather()` is the optional rooted gather of obs/reward/done to rank 0 over RCCL.
 """
+import collections
 import ctypes
 import os
 from ctypes import c_void_p
@@ -84,6 +85,8 @@ class ProcgenVecEnv:
         self.state_layout = pglib.state_layout(self.L, game, self.distribution_mode)
         # What tile_paths() goes by (include/procgen2_vec.h pgv_path_layout_of): cells, tile_w, tile_h, has_goal, agent_dx, agent_dy.
         self.path_layout = pglib.path_layout(self.L, game, self.distribution_mode)
+        # What get_levels() / set_levels() go by (include/procgen2_vec.h pgv_level_layout_of): supported, cells, tile_w, tile_h, backgrounds.
+        self.level_layout = pglib.level_layout(self.L, game, self.distribution_mode)
         self._sequences = {}  # step_sequence's result tensors, by T: the _SEQUENCES_KEPT most recently used
         # torch owns the result buffers; the engine writes straight into them.
         if out is not None:
@@ -541,6 +544,108 @@ class ProcgenVecEnv:
         self._keep_tile_paths = (idx, given, res)
         return res
 
+    # -- caller-made levels (include/procgen2_vec.h pgv_get_levels / pgv_set_levels) -----------------
+    def _needs_levels(self, who):
+        if not self.level_layout.supported:
+            raise pglib.EngineError("%s: no caller-made levels for this game (%s)" % (who, self.game))
+
+    def get_levels(self, envs=None, host=False):
+        """The levels of the envs `envs` (as state_obs takes them) as they stand now, the agent's current cell included: a
+        Levels of tiles uint8 [B, level_layout.cells] (0 open, 1 wall; cell (x, y) at column y + x * tile_h, as tile_obs),
+        agent_cell and goal_cell int32 [B], background int32 [B] (the floor picture, 0 .. level_layout.backgrounds - 1) and
+        background_shift float32 [B].  An index outside the batch gives a zero tile row and cells of -1.  Device tensors,
+        written there with the same stream hand-shake as step() and no host synchronisation; reads only.  host=True: numpy
+        arrays through the synchronous host form (envs then anything numpy takes).  maze only (level_layout.supported)."""
+        self._needs_levels("get_levels")
+        cells = self.level_layout.cells
+        if host:
+            import numpy as np
+            idx = None if envs is None else np.ascontiguousarray(np.asarray(envs).reshape(-1), np.int32)
+            count = self.num_envs if idx is None else idx.size
+            res = Levels(np.zeros((count, cells), np.uint8), np.zeros(count, np.int32), np.zeros(count, np.int32),
+                         np.zeros(count, np.int32), np.zeros(count, np.float32))
+            rows = pglib.level_rows(*(x.ctypes.data if count else None for x in res))
+            pglib.check(self.L, self.L.pgv_get_levels_host(self._h, c_void_p(idx.ctypes.data) if idx is not None and count else None,
+                                                           count, ctypes.byref(rows)), "pgv_get_levels_host")
+            return res
+        idx, count = self._indices(envs)
+        res = Levels(torch.empty((count, cells), dtype=torch.uint8, device=self.device),
+                     torch.empty((count,), dtype=torch.int32, device=self.device), torch.empty((count,), dtype=torch.int32, device=self.device),
+                     torch.empty((count,), dtype=torch.int32, device=self.device), torch.empty((count,), dtype=torch.float32, device=self.device))
+        if count:
+            rows = pglib.level_rows(*(x.data_ptr() for x in res))
+            self._before()
+            pglib.check(self.L, self.L.pgv_get_levels(self._h, c_void_p(idx.data_ptr()) if idx is not None else None, count,
+                                                      ctypes.byref(rows)), "pgv_get_levels")
+            self._after()
+            self._keep_get_levels = (idx, res)
+        return res
+
+    def set_levels(self, levels=None, *, tiles=None, agent_cell=None, goal_cell=None, background=None, background_shift=None,
+                   ids=None, indices=None):
+        """Install caller-made levels as the start of a new episode of the envs `indices` (None: row k into env k; otherwise
+        distinct indices, one outside the batch gives status 1).  levels: a Levels (what get_levels returns, edited in torch),
+        or the fields by keyword — tiles uint8 [B, cells] of 0 (open) and 1 (wall), agent_cell and goal_cell int32 [B]; with
+        background / background_shift None every env keeps the floor it has; ids uint32 labels [B] that level_numbers shows
+        (level_known is 2 for a caller-made level), 0 without.  A keyword overrides the field of `levels`.
+
+        Returns status int32 [B]: 0 installed, 1 no such env, 2 a tile byte that is neither 0 nor 1, 3 / 4 the agent's / the
+        goal's cell outside the map, on a wall (or the goal on the agent), 5 a background outside 0 .. backgrounds - 1 or a
+        shift outside [0, 1).  A refused row leaves its env untouched.  An installed env is as after reset(): obs shows the
+        level's first frame, reward and done are 0, stacks, history and running episode values restart; its random stream,
+        its prefetched next level and a pending assignment stay, so the level after the custom one is the one it would have
+        built anyway.  Device tensors stay on the device: same stream hand-shake as step(), no host synchronisation.  When
+        `tiles` is a numpy array the synchronous host form is used and status is a numpy array.  maze only."""
+        self._needs_levels("set_levels")
+        if levels is not None:
+            tiles = levels.tiles if tiles is None else tiles
+            agent_cell = levels.agent_cell if agent_cell is None else agent_cell
+            goal_cell = levels.goal_cell if goal_cell is None else goal_cell
+            background = levels.background if background is None else background
+            background_shift = levels.background_shift if background_shift is None else background_shift
+        if tiles is None or agent_cell is None or goal_cell is None:
+            raise ValueError("set_levels: tiles, agent_cell and goal_cell are needed")
+        cells = self.level_layout.cells
+        host = not torch.is_tensor(tiles)
+        if host:
+            import numpy as np
+            as_rows = lambda x, dtype: None if x is None else np.ascontiguousarray(np.asarray(x).reshape(-1), dtype)
+            t = np.ascontiguousarray(tiles, np.uint8).reshape(-1, cells)
+        else:
+            as_rows = lambda x, dtype: None if x is None else torch.as_tensor(x, device=self.device).to(getattr(torch, dtype)).reshape(-1).contiguous()
+            t = tiles.to(device=self.device, dtype=torch.uint8).reshape(-1, cells).contiguous()
+        count = t.shape[0]
+        label = ids
+        if label is not None and not host:  # (the 32-bit pattern: torch lacks most uint32 ops)
+            label = torch.as_tensor(label, device=self.device)
+            if label.dtype == torch.uint32:
+                label = label.view(torch.int32)
+            elif label.dtype != torch.int32:
+                label = label.to(torch.int64) & 0xFFFFFFFF
+                label = torch.where(label >= 1 << 31, label - (1 << 32), label).to(torch.int32)
+        given = {"agent_cell": as_rows(agent_cell, "int32"), "goal_cell": as_rows(goal_cell, "int32"),
+                 "background": as_rows(background, "int32"), "background_shift": as_rows(background_shift, "float32"),
+                 "ids": as_rows(label, "uint32" if host else "int32"), "indices": as_rows(indices, "int32")}
+        for name, x in given.items():
+            if x is not None and (x.size if host else x.numel()) != count:
+                raise ValueError("set_levels: %s has %d entries for %d tile rows" % (name, x.size if host else x.numel(), count))
+        if indices is None and count != self.num_envs:
+            raise ValueError("set_levels: expected %d levels, got %d (or give indices)" % (self.num_envs, count))
+        if host:
+            status = np.zeros(count, np.int32)
+            ptr = lambda x: x.ctypes.data if x is not None and count else None
+        else:
+            status = torch.zeros((count,), dtype=torch.int32, device=self.device)
+            ptr = lambda x: x.data_ptr() if x is not None and count else None
+        rows = pglib.level_rows(ptr(t), ptr(given["agent_cell"]), ptr(given["goal_cell"]), ptr(given["background"]),
+                                ptr(given["background_shift"]), ptr(given["ids"]), ptr(status))
+        call, name = (self.L.pgv_set_levels_host, "pgv_set_levels_host") if host else (self.L.pgv_set_levels, "pgv_set_levels")
+        self._before()
+        pglib.check(self.L, call(self._h, c_void_p(ptr(given["indices"])), count, ctypes.byref(rows)), name)
+        self._after()
+        self._keep_set_levels = (t, given, status)
+        return status
+
     def save_state(self):
         """Snapshot of the whole batch (state, RNG streams, prefetched levels, outputs) as a numpy byte array."""
         import numpy as np
@@ -849,6 +954,11 @@ class SequenceResult:
     def layout(T, n):
         return {"rewards": ((T, n), torch.float32), "dones": ((T, n), torch.uint8), "seq_return": ((n,), torch.float32),
                 "seq_length": ((n,), torch.int32), "seq_done": ((n,), torch.uint8)}
+
+
+# What ProcgenVecEnv.get_levels returns and set_levels takes: tiles uint8 [B, cells], agent_cell / goal_cell int32 [B],
+# background int32 [B], background_shift float32 [B].  The tensors are edited in place; _replace(...) swaps one for another.
+Levels = collections.namedtuple("Levels", "tiles agent_cell goal_cell background background_shift")
 
 
 class TilePaths:
