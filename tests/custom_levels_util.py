@@ -147,3 +147,23 @@ def oracle_levels(mode, n, seed_base, render=False):
     o = OracleVec("maze", n, seed_base=seed_base, render=render, mode=mode)
     o.reset()
     return o, levels_of_dumps(*oracle_dumps(o), SIDE[mode])
+
+
+def status_of(levels, indices, n, side):
+    """The status pgv_set_levels gives every row (numpy fields; indices None: row k into env k), the first code that applies:
+    1 no such env, 2 a tile byte that is neither 0 nor 1, 3 / 4 the agent's / the goal's cell outside the map or on a wall (or
+    the goal on the agent), 5 a background outside 0 .. BACKGROUNDS - 1 or a shift outside [0, 1) — NaN included."""
+    tiles = np.asarray(levels.tiles)
+    rows, cells = np.arange(tiles.shape[0]), side * side
+    idx = rows if indices is None else np.asarray(indices, np.int64)
+    agent, goal = np.asarray(levels.agent_cell, np.int64), np.asarray(levels.goal_cell, np.int64)
+    agent_in, goal_in = (agent >= 0) & (agent < cells), (goal >= 0) & (goal < cells)
+    shift = np.asarray(levels.background_shift, f32)
+    background = np.asarray(levels.background, np.int64)
+    status = np.zeros(rows.size, np.int32)
+    status[(background < 0) | (background >= BACKGROUNDS) | ~((shift >= 0) & (shift < 1))] = STATUS["bad_floor"]
+    status[~goal_in | (tiles[rows, np.where(goal_in, goal, 0)] != 0) | (goal == agent)] = STATUS["bad_goal"]
+    status[~agent_in | (tiles[rows, np.where(agent_in, agent, 0)] != 0)] = STATUS["bad_agent"]
+    status[(tiles > 1).any(axis=1)] = STATUS["bad_tile"]
+    status[(idx < 0) | (idx >= n)] = STATUS["no_env"]
+    return status

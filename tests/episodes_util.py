@@ -22,11 +22,14 @@ def synthetic_actions(run_seed, step, n, env_offset=0):
 
 
 class EpisodeModel:
-    def __init__(self, game, n, mode, max_episode_steps=0, final_capacity=0, seed_base=1, distribution_mode=0, render=True):
+    def __init__(self, game, n, mode, max_episode_steps=0, final_capacity=0, seed_base=1, distribution_mode=0, render=True,
+                 env_offset=0, threads=1):
         """`mode` is the autoreset mode; `distribution_mode` (0: the game's default) is OracleVec's `mode`.  render=False: the
-        counters alone (the frames are then meaningless)."""
+        counters alone (the frames are then meaningless).  env_offset=a: the model of rows [a, a + n) of a larger engine
+        (`ended_env` and the ring stay the slice's own: rows 0 .. n-1); threads: OracleVec's."""
         assert mode in (NEXT_STEP, SAME_STEP)
-        self.o = OracleVec(game, n, seed_base=seed_base, mode=distribution_mode, render=render)
+        self.o = OracleVec(game, n, seed_base=seed_base, mode=distribution_mode, render=render, env_offset=env_offset, threads=threads)
+        self.env_offset = env_offset
         self.n, self.mode, self.T, self.capacity = n, mode, int(max_episode_steps), int(final_capacity)
         self.running_return = np.zeros(n, np.float32)
         self.running_length = np.zeros(n, np.int32)

@@ -64,10 +64,11 @@ def aug_params(cfg, e, gray=False):
     return aug_params_many(cfg, [e], gray)[0]
 
 
-def augment(ring, pushes, envs, K, dtype, cfg):
-    """(bit patterns [B, K*C, H', W'], params int32 [B, 8]) of the entries (pushes[b], envs[b]) of a HistoryRing."""
+def augment(ring, pushes, envs, K, dtype, cfg, entries=None):
+    """(bit patterns [B, K*C, H', W'], params int32 [B, 8]) of the entries (pushes[b], envs[b]) of a HistoryRing.  entries:
+    the rows' positions in the call they are part of (what the draws go by), default 0 .. B-1."""
     table, C, H, W = value_table(dtype), ring.C, cfg["H"], cfg["W"]
-    params = aug_params_many(cfg, np.arange(len(pushes)), gray=ring.C == 1)
+    params = aug_params_many(cfg, np.arange(len(pushes)) if entries is None else entries, gray=ring.C == 1)
     out = np.zeros((len(pushes), K * C, H, W), DTYPES[dtype])
     y, x = np.arange(H)[:, None], np.arange(W)[None, :]
     for b, (p, i) in enumerate(zip(pushes, envs)):

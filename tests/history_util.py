@@ -121,8 +121,9 @@ class Frames:
 class HistoryVec:
     """OracleVec + the ring: pgv_reset and pgv_step."""
 
-    def __init__(self, game, n, T, gray_rule, policy=None, ring=True, seed_base=1):
-        self.o = OracleVec(game, n, seed_base=seed_base)
+    def __init__(self, game, n, T, gray_rule, policy=None, ring=True, seed_base=1, env_offset=0):
+        self.o = OracleVec(game, n, seed_base=seed_base, env_offset=env_offset)  # (env_offset=a: rows [a, a + n) of a larger engine)
+        self.env_offset = env_offset
         self.n = n
         self.f = Frames(n, T, gray_rule, policy, ring)
 

@@ -156,6 +156,7 @@ class OracleVec:
         self.n = n
         self.env_offset = env_offset
         self.threads = threads
+        self.render = bool(render)
         if threads > 1:  # the envs made (and, in reset(), given their first level) by several threads: full-size tests
             self.h = self.L.pgo_vec_make_threads(game.encode(), n, seed_base, env_offset, 1 if render else 0, num_levels,
                                                  start_level, mode, game_flags, threads)
@@ -185,12 +186,15 @@ class OracleVec:
         self.L.pgo_vec_obs(self.h, self.obs.ctypes.data_as(c_void_p))
         return self.obs
 
-    def step(self, actions=None, run_seed=0, threads=1):
+    def step(self, actions=None, run_seed=0, threads=None):
+        """threads: None = the number the vec was made with.  A vec made with render=False has no frames to hand out: its
+        `obs` rows keep what they held (at full batch size the copy alone would cost more than the step)."""
+        threads = self.threads if threads is None else threads
         a = None
         if actions is not None:
             actions = np.ascontiguousarray(actions, dtype=np.int32)
             a = actions.ctypes.data_as(c_void_p)
-        self.L.pgo_vec_step(self.h, a, run_seed, self.env_offset, threads, self.obs.ctypes.data_as(c_void_p),
+        self.L.pgo_vec_step(self.h, a, run_seed, self.env_offset, threads, self.obs.ctypes.data_as(c_void_p) if self.render else None,
                             self.reward.ctypes.data_as(c_void_p), self.done.ctypes.data_as(c_void_p))
         return self.obs, self.reward, self.done
 

@@ -71,8 +71,9 @@ class PolicyStack:
 class PolicyVec:
     """OracleVec + the stack: pgv_reset and pgv_step on an engine with policy observations."""
 
-    def __init__(self, game, n, K, gray_rule, dtype, seed_base=1, enabled=True):
-        self.o = OracleVec(game, n, seed_base=seed_base)
+    def __init__(self, game, n, K, gray_rule, dtype, seed_base=1, enabled=True, env_offset=0):
+        self.o = OracleVec(game, n, seed_base=seed_base, env_offset=env_offset)  # (env_offset=a: rows [a, a + n) of a larger engine)
+        self.env_offset = env_offset
         self.n = n
         self.stack = PolicyStack(n, K, gray_rule, dtype) if enabled else None
         self.args = (n, K, gray_rule, dtype)

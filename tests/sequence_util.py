@@ -71,8 +71,10 @@ def chaser_late_rows(mode):
 
 
 class SequenceModel:
-    def __init__(self, game, n, seed_base=1, render=True, mode=0):
-        self.o = OracleVec(game, n, seed_base=seed_base, render=render, mode=mode)
+    def __init__(self, game, n, seed_base=1, render=True, mode=0, env_offset=0, threads=1):
+        """env_offset=a: the model of rows [a, a + n) of a larger engine; threads: OracleVec's."""
+        self.o = OracleVec(game, n, seed_base=seed_base, render=render, mode=mode, env_offset=env_offset, threads=threads)
+        self.env_offset = env_offset
         self.n, self.can_draw = n, render
 
     obs = property(lambda self: self.o.obs)
