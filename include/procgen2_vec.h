@@ -548,8 +548,8 @@ PGV_API int32_t pgv_render_frames_host(pgv_env* env, const int32_t* h_indices, i
                                        int32_t height, uint8_t* h_rgb);
 
 /* Symbolic observations: what the games know, for every env at once, in device memory — the agent, every entity's kind,
- * position and liveness, the goal, the tile map — as the rows of floats and bytes that the parity taps below give for one
- * env at a time.  For privileged critics, probes and auxiliary losses, scripted and planning agents; with
+ * position and liveness, the goal, the tile map — as rows of floats and bytes (the parity taps below read one env's rows
+ * through the same kernels).  For privileged critics, probes and auxiliary losses, scripted and planning agents; with
  * pgv_step_sequence's frameless steps such an agent runs without a frame being drawn.
  *
  *   1. Layout.  pgv_state_layout_of(game_id, mode) is host-only and pure: no GPU, no env.  PGV_MODE_DEFAULT stands for the
@@ -564,8 +564,9 @@ PGV_API int32_t pgv_render_frames_host(pgv_env* env, const int32_t* h_indices, i
  *      unique within a game and the first two are agent_x agent_y in every game.  INTEGRATION.md lists the columns of every
  *      game, the rule from a cell index to (x, y), and the tile ids.
  *   3. Rows.  d_rows is device f32 [count][width], contiguous.  Row k holds the state dump of env indices[k] — bit for bit
- *      what pgv_dump_state gives — followed by +0.0f up to width; d_lengths[k] (device int32 [count], or NULL) is the
- *      dump's length.  d_tiles is device u8 [count][cells], contiguous: exactly the bytes pgv_dump_tiles gives.
+ *      the oracle's, and what pgv_dump_state copies out of such a row — followed by +0.0f up to width; d_lengths[k] (device
+ *      int32 [count], or NULL) is the dump's length.  d_tiles is device u8 [count][cells], contiguous: the env's tile ids, as
+ *      pgv_dump_tiles copies them out.
  *   4. Indices.  d_indices is device int32 [count], or NULL for envs 0 .. count-1.  The same env may be named more than once;
  *      an index outside the batch gives a row of zero bytes and length 0; nothing faults for any index value.
  *   5. Ordering and state.  The calls read the state as it stands at that point of the env's stream: behind a step, a reset,
@@ -786,8 +787,12 @@ PGV_API int32_t pgv_step_phases_many(pgv_env* const* envs, int32_t count, int32_
  * does anyway that finds the list of such frames full).  Any other bit is refused. */
 PGV_API int32_t pgv_set_debug(pgv_env* env, int32_t flags);
 
-/* Parity taps (host pointers): game-defined state vector / tile ids of one env; return the full
- * length, copy at most `cap` items. */
+/* Parity taps (host pointers): the state row / tile row of one env, read through the launches behind pgv_state_rows /
+ * pgv_tile_rows: row k = 0 of a call with indices = {index}, without its padding.  Return the dump's full length, whatever
+ * cap is, and copy min(cap, length) items (cap <= 0: nothing is written, h_out may be NULL); pgv_dump_tiles of a game
+ * without a tile map returns 0.  -1 for a NULL env or an index outside 0 .. n-1 — and for a HIP error inside the call,
+ * which then leaves its text in pgv_last_error.  Synchronous; a tap waits for the env's stream alone and allocates
+ * nothing. */
 PGV_API int32_t pgv_dump_state(pgv_env* env, int32_t index, float* h_out, int32_t cap);
 PGV_API int32_t pgv_dump_tiles(pgv_env* env, int32_t index, uint8_t* h_out, int32_t cap);
 

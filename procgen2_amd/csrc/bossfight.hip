@@ -1441,9 +1441,16 @@ struct StateRow {
             default: return iv(I_NROCKS);
         }
     }
+    static std::string names() {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_alive agent_timer a_next a_count boss_x boss_y boss_vel_x boss_vel_y "
+               "phase_timer phase_index weapon_index attack_timer hp b_next b_count x_next x_count explosion_timer damage_timer "
+               "move_timer n_rocks" +
+               slot_names("a_shot", kAgentShots, {"x", "y", "frame"}) + slot_names("b_shot", kBossShots, {"x", "y", "frame"}) + "|";
+    }
 };
 
-class BossfightGame final : public Game {
+// (no tile map in this game, so no map() in its row and no PathRow)
+class BossfightGame final : public ViewedGame<BoundGame<State>, StateRow, void> {
    public:
     const char* name() const override { return "bossfight"; }
     std::vector<std::string> texture_names() const override {
@@ -1568,39 +1575,8 @@ class BossfightGame final : public Game {
     void prepare_save(hipStream_t st) override {
         hipLaunchKernelGGL(streams_home_kernel, dim3((s_.n + 63) / 64), dim3(64), 0, st, s_);
     }
-    // Same layout as oracle/pgo_bossfight.cpp Bossfight::dump_state.
-    int dump_state(hipStream_t st, int env, float* out, int cap) override {
-        hipStreamSynchronize(st);
-        const size_t n = s_.n;
-        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
-        auto iv = [&](int field) { return static_cast<float>(read_one(s_.i + size_t(field) * n + env)); };
-        const int32_t flags = read_one(s_.i + size_t(I_FLAGS) * n + env);
-        std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), (flags & kFlagAlive) ? 1.0f : 0.0f, f(F_ATIMER),
-                                iv(I_A_NEXT), iv(I_A_COUNT), f(F_BX), f(F_BY), f(F_BVX), f(F_BVY), f(F_PHASE_T),
-                                iv(I_PHASE), iv(I_WEAPON), f(F_ATTACK_T), iv(I_HP), iv(I_B_NEXT), iv(I_B_COUNT),
-                                iv(I_X_NEXT), iv(I_X_COUNT), f(F_EXPLO_T), f(F_DAMAGE_T), f(F_MOVE_T), iv(I_NROCKS)};
-        for (int k = 0; k < kAgentShots; k++)
-            for (int fld : {S_X, S_Y, S_FRAME}) v.push_back(read_one(s_.ashot + (size_t(env) * S_COUNT + fld) * kAgentShots + k));
-        for (int k = 0; k < kBossShots; k++)
-            for (int fld : {S_X, S_Y, S_FRAME}) v.push_back(read_one(s_.bshot + (size_t(env) * S_COUNT + fld) * kBossShots + k));
-        return dump_out(v, out, cap);
-    }
-    int dump_tiles(hipStream_t, int, uint8_t*, int) override { return 0; }
-    StateLayout state_layout() const override { return state_layout_of<StateRow>(0, 0); }  // (no tile map in this game)
-    std::string state_names() const override {
-        return "agent_x agent_y agent_vel_x agent_vel_y agent_alive agent_timer a_next a_count boss_x boss_y boss_vel_x boss_vel_y "
-               "phase_timer phase_index weapon_index attack_timer hp b_next b_count x_next x_count explosion_timer damage_timer "
-               "move_timer n_rocks" +
-               slot_names("a_shot", kAgentShots, {"x", "y", "frame"}) + slot_names("b_shot", kBossShots, {"x", "y", "frame"}) + "|";
-    }
-    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
-        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
-    }
-    void launch_tile_rows(hipStream_t, const int32_t*, int, uint8_t*) override {}
 
    private:
-    State s_{};
-    AtlasView atlas_{};
     uint32_t stamps_at_ = 0;  // extend_atlas → bind
 };
 

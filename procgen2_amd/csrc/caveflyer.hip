@@ -1231,6 +1231,13 @@ struct StateRow {
             default: return static_cast<float>(SI(s, I_NENT, env));
         }
     }
+    static std::string names() {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_rot cam_x cam_y backdrop backdrop_shift s_next s_count s_timer "
+               "puff_timer puff_on n_things" +
+               slot_names("shot", kShots, {"x", "y", "frame"}) + slot_names("puff", kPuffs, {"x", "y", "life"}) +
+               "|alive kind x y vel_x vel_y";
+    }
+    static TileMaps map(const State& s) { return {s.tiles, kTileStride, kCells, 0xff, W, H}; }
 };
 
 // The points of the path distances (pg_paths.h): the ship's box is centred on its point; the goal is entity 0, record 0 of the row.
@@ -1240,7 +1247,7 @@ struct PathRow {
     static constexpr int kGoalX = StateRow::kFixed + 2, kGoalY = StateRow::kFixed + 3;
 };
 
-class CaveflyerGame final : public PrefetchingGame<Gen> {
+class CaveflyerGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
    public:
     const char* name() const override { return "caveflyer"; }
     std::vector<std::string> texture_names() const override {
@@ -1311,57 +1318,6 @@ class CaveflyerGame final : public PrefetchingGame<Gen> {
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);
     }
-    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
-    std::string state_names() const override {
-        return "agent_x agent_y agent_vel_x agent_vel_y agent_rot cam_x cam_y backdrop backdrop_shift s_next s_count s_timer "
-               "puff_timer puff_on n_things" +
-               slot_names("shot", kShots, {"x", "y", "frame"}) + slot_names("puff", kPuffs, {"x", "y", "life"}) +
-               "|alive kind x y vel_x vel_y";
-    }
-    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
-        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
-    }
-    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
-        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
-    }
-    PathPoints path_points() const override { return path_points_of<PathRow>(); }
-    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
-        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
-    }
-    // Same layout as oracle/pgo_caveflyer.cpp Caveflyer::dump_state.
-    int dump_state(hipStream_t st, int env, float* out, int cap) override {
-        hipStreamSynchronize(st);
-        const size_t n = s_.n;
-        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
-        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
-        const int flags = ri(I_FLAGS), n_ent = ri(I_NENT);
-        std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), f(F_ROT), f(F_CAMX), f(F_CAMY),
-                                static_cast<float>(ri(I_BACKDROP)), f(F_BGSHIFT), static_cast<float>(ri(I_SNEXT)),
-                                static_cast<float>(ri(I_SCOUNT)), f(F_STIMER), f(F_PTIMER),
-                                (flags & kFlagPuffOn) ? 1.0f : 0.0f, static_cast<float>(n_ent)};
-        for (int k = 0; k < kShots; k++)
-            for (int fld : {SH_X, SH_Y, SH_FRAME}) v.push_back(read_one(s_.sh + (size_t(env) * SH_COUNT + fld) * kShots + k));
-        for (int k = 0; k < kPuffs; k++)
-            for (int fld : {PF_X, PF_Y, PF_LIFE}) v.push_back(read_one(s_.pf + (size_t(env) * PF_COUNT + fld) * kPuffSlots + k));
-        for (int e = 0; e < n_ent; e++) {
-            if (e == 1) continue;
-            const uint8_t info = read_one(s_.eb + (size_t(env) * EB_COUNT + EB_INFO) * kEntStride + e);
-            auto ef = [&](int field) { return read_one(s_.ef + (size_t(env) * EF_COUNT + field) * kEntStride + e); };
-            v.push_back((info & kAlive) ? 1.0f : 0.0f);
-            v.push_back(static_cast<float>(info & kKindMask));
-            v.push_back(ef(EF_X));
-            v.push_back(ef(EF_Y));
-            v.push_back(ef(EF_VX));
-            v.push_back(ef(EF_VY));
-        }
-        return dump_out(v, out, cap);
-    }
-    int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
-    }
-
-   private:
-    AtlasView atlas_{};
 };
 
 }  // namespace caveflyer

@@ -1517,6 +1517,11 @@ struct StateRow {
             default: return static_cast<float>(SI(s, I_NENT, env));
         }
     }
+    static std::string names() {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_next_x agent_next_y input_timer anim_timer anim_index eat_timer "
+               "backdrop backdrop_shift n_things|alive kind x y vel_x vel_y hatch_timer tex";
+    }
+    static TileMaps map(const State& s) { return {s.tiles, kTileStride, kCells, 0xff, W, H}; }
 };
 
 // The points of the path distances (pg_paths.h): the agent fills its cell; the game has no goal.
@@ -1526,7 +1531,7 @@ struct PathRow {
     static constexpr int kGoalX = -1, kGoalY = -1;
 };
 
-class ChaserGame final : public Game {
+class ChaserGame final : public ViewedGame<BoundGame<State>, StateRow, PathRow> {
    public:
     const char* name() const override { return "chaser"; }
     std::vector<std::string> texture_names() const override {
@@ -1711,65 +1716,8 @@ class ChaserGame final : public Game {
         hipLaunchKernelGGL(render_list_kernel, dim3(groups + (s_.n + 127) / 128), dim3(128), 0, st, s_, atlas_, io, debug_flags, groups);
         return true;
     }
-    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
-    std::string state_names() const override {
-        return "agent_x agent_y agent_vel_x agent_vel_y agent_next_x agent_next_y input_timer anim_timer anim_index eat_timer "
-               "backdrop backdrop_shift n_things|alive kind x y vel_x vel_y hatch_timer tex";
-    }
-    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
-        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
-    }
-    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
-        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
-    }
-    PathPoints path_points() const override { return path_points_of<PathRow>(); }
-    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
-        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
-    }
-    // Same layout as oracle/pgo_chaser.cpp Chaser::dump_state.
-    int dump_state(hipStream_t st, int env, float* out, int cap) override {
-        hipStreamSynchronize(st);
-        const size_t n = s_.n;
-        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
-        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
-        auto eb = [&](int field, int e) { return read_one(s_.eb + (size_t(env) * EB_COUNT + field) * kMaxEnt + e); };
-        const int n_ent = ri(I_NENT);
-        std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), f(F_NVX), f(F_NVY), f(F_INPUT_T), f(F_ANIM_T),
-                                static_cast<float>(ri(I_ANIM_I)), f(F_EAT_T), static_cast<float>(ri(I_BG)), f(F_BGSHIFT),
-                                static_cast<float>(n_ent)};
-        for (int e = 0; e < n_ent; e++) {
-            const int info = eb(EB_INFO, e);
-            const int cell = eb(EB_CELL, e) | (kWideCells ? eb(EB_CELL_HI, e) << 8 : 0);
-            const int kind = info & kKindMask;
-            v.push_back((info & kAlive) ? 1.0f : 0.0f);
-            v.push_back(static_cast<float>(kind));
-            if (kind == kEgg) {
-                const int m = e - kOrbs;
-                auto mf = [&](int field) { return read_one(s_.mf + (size_t(field) * kMobs + m) * n + env); };
-                v.push_back(mf(MF_X));
-                v.push_back(mf(MF_Y));
-                v.push_back(mf(MF_VX));
-                v.push_back(mf(MF_VY));
-                v.push_back(mf(MF_HATCH));
-                v.push_back(static_cast<float>(read_one(s_.mb + (size_t(0) * kMobs + m) * n + env)));
-            } else {
-                v.push_back(static_cast<float>(cell / H) + 0.5f);
-                v.push_back(static_cast<float>(H - 1 - cell % H) + 0.5f);
-                v.push_back(0.0f);
-                v.push_back(0.0f);
-                v.push_back(0.0f);
-                v.push_back(0.0f);
-            }
-        }
-        return dump_out(v, out, cap);
-    }
-    int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
-    }
 
    private:
-    State s_{};
-    AtlasView atlas_{};
     bool base_valid_ = false;  // every env's base layer (State::base) is its current level's
     bool stamp_ok_ = false;    // the point sprite is an opaque box in a clear rim (extend_atlas)
 };

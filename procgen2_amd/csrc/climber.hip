@@ -858,6 +858,11 @@ struct StateRow {
             default: return static_cast<float>(SI(s, I_NENT, env));
         }
     }
+    static std::string names() {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase cam_x cam_y backdrop backdrop_shift "
+               "suit theme n_things|alive x y vel_x frame anim_t";
+    }
+    static TileMaps map(const State& s) { return {s.tiles, W * H, W * H, 0xff, W, H}; }
 };
 
 // The points of the path distances (pg_paths.h): the body box spans agent_y - 1 .. agent_y; the game has no goal point.
@@ -867,7 +872,7 @@ struct PathRow {
     static constexpr int kGoalX = -1, kGoalY = -1;
 };
 
-class ClimberGame final : public PrefetchingGame<Gen> {
+class ClimberGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
    public:
     const char* name() const override { return "climber"; }
     std::vector<std::string> texture_names() const override {
@@ -941,51 +946,6 @@ class ClimberGame final : public PrefetchingGame<Gen> {
     void launch_render(hipStream_t st, const uint8_t* mask, StepIO io) override {
         hipLaunchKernelGGL(render_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags);
     }
-    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
-    std::string state_names() const override {
-        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase cam_x cam_y backdrop backdrop_shift "
-               "suit theme n_things|alive x y vel_x frame anim_t";
-    }
-    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
-        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
-    }
-    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
-        launch_tile_rows_of(st, s_.tiles, W * H, W * H, 0xff, s_.n, d_indices, count, d_tiles);
-    }
-    PathPoints path_points() const override { return path_points_of<PathRow>(); }
-    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
-        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, W * H, W * H, 0xff, W, H, s_.n, q);
-    }
-    // Same layout as oracle/pgo_climber.cpp Climber::dump_state.
-    int dump_state(hipStream_t st, int env, float* out, int cap) override {
-        hipStreamSynchronize(st);
-        const size_t n = s_.n;
-        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
-        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
-        const int flags = ri(I_FLAGS), themes = ri(I_THEMES), n_ent = ri(I_NENT);
-        std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), (flags & kFlagGround) ? 1.0f : 0.0f,
-                                (flags & kFlagForward) ? 1.0f : 0.0f, f(F_APHASE), W / 2.0f * kUnitPx, f(F_CAMY),
-                                static_cast<float>(themes & 0xff), f(F_BGSHIFT),
-                                static_cast<float>((themes >> 8) & 0xff), static_cast<float>((themes >> 16) & 0xff),
-                                static_cast<float>(n_ent)};
-        for (int e = 0; e < n_ent; e++) {
-            const uint8_t info = read_one(s_.eb + (size_t(env) * EB_COUNT + EB_INFO) * kEntStride + e);
-            auto ef = [&](int field) { return read_one(s_.ef + (size_t(env) * EF_COUNT + field) * kEntStride + e); };
-            v.push_back((info & kAlive) ? 1.0f : 0.0f);
-            v.push_back(ef(EF_X));
-            v.push_back(ef(EF_Y));
-            v.push_back((info & kMob) ? ef(EF_VX) : 0.0f);
-            v.push_back((info & kFrame) ? 1.0f : 0.0f);
-            v.push_back(ef(EF_ANIM_T));
-        }
-        return dump_out(v, out, cap);
-    }
-    int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        return dump_env_tiles(st, s_.tiles, W * H, W * H, env, out, cap);
-    }
-
-   private:
-    AtlasView atlas_{};
 };
 
 }  // namespace climber

@@ -1786,6 +1786,11 @@ struct StateRow {
             default: return static_cast<float>(SI(s, I_NENT, env));
         }
     }
+    static std::string names() {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase cam_x cam_y backdrop backdrop_shift "
+               "alien ground n_things|x y vel_x frame anim_t";
+    }
+    static TileMaps map(const State& s) { return {s.tiles, W * H, W * H, 7, W, H}; }
 };
 
 // The points of the path distances (pg_paths.h): the body box spans agent_y - 1 .. agent_y (a_bounds); the coin is an entity, not a goal point.
@@ -1795,7 +1800,7 @@ struct PathRow {
     static constexpr int kGoalX = -1, kGoalY = -1;
 };
 
-class CoinrunGame final : public PrefetchingGame<Gen> {
+class CoinrunGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
    public:
     const char* name() const override { return "coinrun"; }
     bool set_game_flags(uint32_t flags) override {
@@ -1937,52 +1942,6 @@ class CoinrunGame final : public PrefetchingGame<Gen> {
     }
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
     void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_, n); }
-
-    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
-    std::string state_names() const override {
-        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase cam_x cam_y backdrop backdrop_shift "
-               "alien ground n_things|x y vel_x frame anim_t";
-    }
-    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
-        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
-    }
-    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
-        launch_tile_rows_of(st, s_.tiles, W * H, W * H, 7, s_.n, d_indices, count, d_tiles);
-    }
-    PathPoints path_points() const override { return path_points_of<PathRow>(); }
-    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
-        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, W * H, W * H, 7, W, H, s_.n, q);
-    }
-    // Same layout as oracle/pgo_coinrun.cpp Coinrun::dump_state.
-    int dump_state(hipStream_t st, int env, float* out, int cap) override {
-        hipStreamSynchronize(st);
-        const size_t n = s_.n;
-        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
-        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
-        const int flags = ri(I_FLAGS), themes = ri(I_THEMES), n_ent = ri(I_NENT);
-        const int buf = (flags & kFlagBuf) ? 1 : 0;
-        std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), (flags & kFlagGround) ? 1.0f : 0.0f,
-                                (flags & kFlagForward) ? 1.0f : 0.0f, f(F_APHASE), f(F_CAMX), f(F_CAMY),
-                                static_cast<float>(themes & 0xff), f(F_BGSHIFT), static_cast<float>((themes >> 8) & 0xff),
-                                static_cast<float>((themes >> 16) & 0xff), static_cast<float>(n_ent)};
-        for (int e = 0; e < n_ent; e++) {
-            const int kind = read_one(s_.eb + (size_t(EB_KIND) * kMaxEnt + e) * n + env);
-            const int dyn = read_one(s_.db + (size_t(buf) * kMaxEnt + e) * n + env);
-            auto df = [&](int field) { return read_one(s_.df + ((size_t(buf) * DF_COUNT + field) * kMaxEnt + e) * n + env); };
-            v.push_back(df(DF_X));
-            v.push_back(read_one(s_.ey + size_t(e) * n + env));
-            v.push_back(kind == kMob ? df(DF_VX) : 0.0f);
-            v.push_back((dyn & kDynFrame) ? 1.0f : 0.0f);
-            v.push_back(kind == kCoin ? 0.0f : df(DF_ANIM_T));
-        }
-        return dump_out(v, out, cap);
-    }
-    int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        return dump_env_tiles(st, s_.tiles, W * H, W * H, env, out, cap, 7);
-    }
-
-   private:
-    AtlasView atlas_{};
 };
 
 }  // namespace coinrun

@@ -276,6 +276,9 @@ struct pgv_env {
     // caller-made levels (pg_levels.h; pgv_set_levels): an install's claim words and mask, one block, for a game that has them
     void* d_levels = nullptr;
     pg::LevelBuffers lev{};
+    // the debug taps (pgv_dump_state / pgv_dump_tiles): room for one env's state row and tile row, one block
+    void* d_tap = nullptr;
+    pg::TapBuffers tap{};
     // policy-ready observations (pg_policy_obs.h; pgv_policy_obs_enable): off unless asked for.  One device block holds the
     // restart flags and the value table; the tensor is the caller's, or the engine's own.
     bool policy = false, own_policy_out = false;
@@ -372,6 +375,7 @@ void pgv_close(pgv_env* e) {
     if (e->d_episodes) hipFree(e->d_episodes);
     if (e->d_sequence) hipFree(e->d_sequence);
     if (e->d_levels) hipFree(e->d_levels);
+    if (e->d_tap) hipFree(e->d_tap);
     if (e->d_policy) hipFree(e->d_policy);
     if (e->own_policy_out && e->d_policy_out) hipFree(e->d_policy_out);
     if (e->d_history) hipFree(e->d_history);
@@ -551,6 +555,10 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     e->game->plan = pg::LevelPlan{num_levels, start_level};
     pg::Carve::bind(pg::list_plan, static_cast<uint8_t*>(e->d_state) + game_state_bytes(e.get()), e->game->plan, num_envs, &planned);
     if (plan_records(e.get(), planned)) return 1;
+    // (the last allocation of the call: a debug buffer does not move the addresses of what the step works on)
+    e->tap.width = e->game->state_layout().width, e->tap.cells = e->game->state_layout().cells;
+    PG_HIP(hipMalloc(&e->d_tap, pg::Carve::size(pg::list_tap, 1, e->tap)));  // (written before it is read, by every tap)
+    pg::Carve::bind(pg::list_tap, e->d_tap, e->tap, 1);
     e->game->launch_make(e->stream, seed_base, env_offset);
     PG_HIP(hipGetLastError());
     PG_HIP(hipStreamSynchronize(e->stream));
@@ -1665,16 +1673,48 @@ int32_t pgv_set_debug(pgv_env* e, int32_t flags) {
     return 0;
 }
 
+// The debug taps: one env's row through the launches behind pgv_state_rows / pgv_tile_rows into the engine's tap buffer,
+// and as much of it out as `cap` allows.  On the env's stream and no other: nothing is allocated or freed here, so a tap
+// waits neither for the level generator's stream nor for the reset stream.
+namespace pg {
+static int32_t tap_failed(const char* who, hipError_t err) {
+    g_error = std::string(who) + ": " + hipGetErrorString(err);
+    return -1;
+}
+}  // namespace pg
+
 int32_t pgv_dump_state(pgv_env* e, int32_t index, float* h_out, int32_t cap) {
     if (!e || index < 0 || index >= e->n) return -1;
-    hipSetDevice(e->device);
-    return e->game->dump_state(e->stream, index, h_out, cap);
+    const pg::TapBuffers& t = e->tap;
+    int32_t length = 0;
+    hipError_t err = hipSetDevice(e->device);
+    if (err == hipSuccess) err = hipMemsetD32Async(t.index, index, 1, e->stream);
+    if (err == hipSuccess) {
+        e->game->launch_state_rows(e->stream, t.index, 1, t.row, t.length);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(&length, t.length, 4, hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    const int32_t m = std::min(cap, length);
+    if (err == hipSuccess && m > 0 && h_out) err = hipMemcpy(h_out, t.row, size_t(m) * 4, hipMemcpyDeviceToHost);
+    return err == hipSuccess ? length : pg::tap_failed("pgv_dump_state", err);
 }
 
 int32_t pgv_dump_tiles(pgv_env* e, int32_t index, uint8_t* h_out, int32_t cap) {
     if (!e || index < 0 || index >= e->n) return -1;
-    hipSetDevice(e->device);
-    return e->game->dump_tiles(e->stream, index, h_out, cap);
+    const pg::TapBuffers& t = e->tap;
+    const int32_t m = h_out ? std::min(cap, t.cells) : 0;
+    hipError_t err = hipSetDevice(e->device);
+    if (m > 0) {
+        if (err == hipSuccess) err = hipMemsetD32Async(t.index, index, 1, e->stream);
+        if (err == hipSuccess) {
+            e->game->launch_tile_rows(e->stream, t.index, 1, t.tiles);
+            err = hipGetLastError();
+        }
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess && m > 0) err = hipMemcpy(h_out, t.tiles, size_t(m), hipMemcpyDeviceToHost);
+    return err == hipSuccess ? t.cells : pg::tap_failed("pgv_dump_tiles", err);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1286,6 +1286,12 @@ struct StateRow {
             default: return static_cast<float>(SI(s, I_NSPIKES, env));
         }
     }
+    static std::string names() {
+        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase agent_jump_timer agent_jumps cam_x "
+               "cam_y to_goal_x to_goal_y backdrop backdrop_shift theme puff_timer puff_on goal_x goal_y n_spikes" +
+               slot_names("puff", kPuffs, {"x", "y", "life"}) + "|x y";
+    }
+    static TileMaps map(const State& s) { return {s.tiles, kTileStride, kCells, 0xff, W, H}; }
 };
 
 // The points of the path distances (pg_paths.h): the body box spans agent_y - 0.8 .. agent_y; the goal is goal_x, goal_y.
@@ -1295,7 +1301,7 @@ struct PathRow {
     static constexpr int kGoalX = 18, kGoalY = 19;
 };
 
-class JumperGame final : public PrefetchingGame<Gen> {
+class JumperGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
    public:
     const char* name() const override { return "jumper"; }
     std::vector<std::string> texture_names() const override {
@@ -1472,50 +1478,6 @@ class JumperGame final : public PrefetchingGame<Gen> {
             hipLaunchKernelGGL(render_full_kernel, dim3(s_.n), dim3(128), 0, st, s_, atlas_, mask, io, debug_flags, 0);
         }
     }
-    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
-    std::string state_names() const override {
-        return "agent_x agent_y agent_vel_x agent_vel_y agent_ground agent_forward agent_phase agent_jump_timer agent_jumps cam_x "
-               "cam_y to_goal_x to_goal_y backdrop backdrop_shift theme puff_timer puff_on goal_x goal_y n_spikes" +
-               slot_names("puff", kPuffs, {"x", "y", "life"}) + "|x y";
-    }
-    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
-        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
-    }
-    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
-        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
-    }
-    PathPoints path_points() const override { return path_points_of<PathRow>(); }
-    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
-        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
-    }
-    // Same layout as oracle/pgo_jumper.cpp Jumper::dump_state.
-    int dump_state(hipStream_t st, int env, float* out, int cap) override {
-        hipStreamSynchronize(st);
-        const size_t n = s_.n;
-        auto f = [&](int field) { return read_one(s_.f + size_t(field) * n + env); };
-        auto ri = [&](int field) { return read_one(s_.i + size_t(field) * n + env); };
-        const int flags = ri(I_FLAGS), themes = ri(I_THEMES), n_spikes = ri(I_NSPIKES);
-        std::vector<float> v = {f(F_AX), f(F_AY), f(F_AVX), f(F_AVY), (flags & kFlagGround) ? 1.0f : 0.0f,
-                                (flags & kFlagForward) ? 1.0f : 0.0f, f(F_APHASE), f(F_JUMP_T),
-                                static_cast<float>(ri(I_JUMPS)), f(F_CAMX), f(F_CAMY), f(F_TOGX), f(F_TOGY),
-                                static_cast<float>(themes & 0xff), f(F_BGSHIFT), static_cast<float>((themes >> 8) & 0xff),
-                                f(F_PTIMER), (flags & kFlagPuffOn) ? 1.0f : 0.0f, f(F_GX), f(F_GY),
-                                static_cast<float>(n_spikes)};
-        for (int k = 0; k < kPuffs; k++)
-            for (int fld : {PF_X, PF_Y, PF_LIFE}) v.push_back(read_one(s_.pf + (size_t(env) * PF_COUNT + fld) * kPuffSlots + k));
-        for (int k = 0; k < n_spikes; k++) {
-            const uint16_t cell = read_one(s_.spike_cell + size_t(env) * kSpikeSlots + k);
-            v.push_back(static_cast<float>(cell / H) + 0.5f);
-            v.push_back(static_cast<float>(H - 1 - cell % H) + 0.5f);
-        }
-        return dump_out(v, out, cap);
-    }
-    int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
-    }
-
-   private:
-    AtlasView atlas_{};
 };
 
 }  // namespace jumper

@@ -440,6 +440,8 @@ struct StateRow {
             default: return SF(s, F_CAMY, env);
         }
     }
+    static std::string names() { return "agent_x agent_y agent_forward goal_x goal_y steps floor floor_shift cam_x cam_y|"; }
+    static TileMaps map(const State& s) { return {s.tiles, kTileStride, kCells, 0xff, W, H}; }
 };
 
 // The points of the path distances (pg_paths.h): the mouse fills its cell; the goal is the cheese.
@@ -473,7 +475,7 @@ struct Custom {
     static __device__ void install(const State& s, int env, const Level& lv, int lane) { maze::install(s, env, lv, lane); }
 };
 
-class MazeGame final : public PrefetchingGame<Gen> {
+class MazeGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
    public:
     const char* name() const override { return "maze"; }
     std::vector<std::string> texture_names() const override {
@@ -539,40 +541,11 @@ class MazeGame final : public PrefetchingGame<Gen> {
     }
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }
     void bind_scratch(void* d_scratch, int n) override { Carve::bind(carve_scratch, d_scratch, s_.prep, n); }
-    // Same layout as oracle/pgo_maze.cpp Maze::dump_state.
-    int dump_state(hipStream_t st, int env, float* out, int cap) override {
-        hipStreamSynchronize(st);
-        auto f = [&](int field) { return read_one(s_.f + size_t(field) * s_.n + env); };
-        auto iv = [&](int field) { return read_one(s_.i + size_t(field) * s_.n + env); };
-        return dump_out({f(F_AX), f(F_AY), (iv(I_FLAGS) & kFlagForward) ? 1.0f : 0.0f, f(F_GX), f(F_GY),
-                         static_cast<float>(iv(I_STEPS)), static_cast<float>(iv(I_BG)), f(F_BGSHIFT), f(F_CAMX), f(F_CAMY)},
-                        out, cap);
-    }
-    int dump_tiles(hipStream_t st, int env, uint8_t* out, int cap) override {
-        return dump_env_tiles(st, s_.tiles, kTileStride, kCells, env, out, cap);
-    }
-    StateLayout state_layout() const override { return state_layout_of<StateRow>(W, H); }
-    std::string state_names() const override {
-        return "agent_x agent_y agent_forward goal_x goal_y steps floor floor_shift cam_x cam_y|";
-    }
-    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
-        launch_state_rows_of<StateRow>(st, s_, s_.n, d_indices, count, d_rows, d_lengths);
-    }
-    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
-        launch_tile_rows_of(st, s_.tiles, kTileStride, kCells, 0xff, s_.n, d_indices, count, d_tiles);
-    }
     LevelLayout level_layout() const override { return level_layout_of<Custom>(); }
     void launch_get_levels(hipStream_t st, const LevelRows& out) override { launch_get_levels_of<Custom>(st, s_, out, s_.n); }
     void launch_set_levels(hipStream_t st, const LevelRows& in, const LevelInstall& to) override {
         launch_set_levels_of<Custom>(st, s_, in, to);
     }
-    PathPoints path_points() const override { return path_points_of<PathRow>(); }
-    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
-        launch_tile_paths_of<PathRow>(st, s_, s_.tiles, kTileStride, kCells, 0xff, W, H, s_.n, q);
-    }
-
-   private:
-    AtlasView atlas_{};
 };
 
 }  // namespace maze

@@ -81,6 +81,22 @@ struct StateLayout {
     int width, fixed, record, max_records, cells, tile_w, tile_h;
 };
 
+// The debug taps' buffer (include/procgen2_vec.h pgv_dump_state / pgv_dump_tiles): room for ONE env's rows, the
+// engine's own, so a tap allocates nothing.  `width` and `cells`: the game's StateLayout, set before the listing runs.
+struct TapBuffers {
+    int32_t* index;   // the env asked for: the launches' d_indices
+    int32_t* length;  // its dump's length
+    float* row;       // [width], at a 16-byte boundary as the row kernels want their outputs
+    uint8_t* tiles;   // [cells], likewise
+    int width, cells;
+};
+inline void list_tap(Carve& c, TapBuffers& b, int) {
+    c.take(b.index, 4, 8);
+    c.take(b.length, 4, 8);
+    c.take(b.row, size_t(b.width) * 4, 16);
+    c.take(b.tiles, size_t(b.cells), 16);
+}
+
 // Word 0 of a record (pg_records.h: here because a game's records_loaded looks at it too).
 constexpr uint32_t kRecordFull = 0x31524750u;  // "PGR1"
 constexpr uint32_t kRecordEmpty = 0u;
@@ -123,14 +139,13 @@ class Game {
     // tile (pg_frame.h TilePainter).  d_indices: device int32[count] or nullptr for envs 0 .. count-1; an index outside
     // the batch gives a frame of zeros.  Every game has it; a batch too big for one grid goes out in several launches.
     virtual void launch_frames(hipStream_t s, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) = 0;
-    // Debug tap used by the parity tests: game-defined float dump of one env (host pointer).
-    virtual int dump_state(hipStream_t s, int env, float* out, int cap) = 0;
-    virtual int dump_tiles(hipStream_t s, int env, uint8_t* out, int cap) = 0;
-    // Symbolic observations (include/procgen2_vec.h pgv_state_rows / pgv_tile_rows; pg_state_obs.h): the same dumps for
-    // `count` envs at once into device memory, d_rows = f32 [count][width] (+0.0f behind a dump's end), d_lengths =
-    // int32 [count] or nullptr, d_tiles = u8 [count][cells].  d_indices as launch_frames takes them; an index outside the
-    // batch gives a row of zero bytes and length 0.  Read-only, on the given stream.  state_layout / state_names are
-    // host-only and need neither a bound state nor a GPU (pgv_state_layout_of asks a Game fresh from its factory).
+    // Symbolic observations (include/procgen2_vec.h pgv_state_rows / pgv_tile_rows; pg_state_obs.h): the oracle's state
+    // dump and tile map of `count` envs at once into device memory, d_rows = f32 [count][width] (+0.0f behind a dump's end),
+    // d_lengths = int32 [count] or nullptr, d_tiles = u8 [count][cells].  d_indices as launch_frames takes them; an index
+    // outside the batch gives a row of zero bytes and length 0.  Read-only, on the given stream.  state_layout / state_names
+    // are host-only and need neither a bound state nor a GPU (pgv_state_layout_of asks a Game fresh from its factory).
+    // The parity tests' debug taps (pgv_dump_state / pgv_dump_tiles) are the engine's: one row through these two launches.
+    // Every game has the six functions from here to launch_tile_paths from ViewedGame (pg_state_obs.h).
     virtual StateLayout state_layout() const = 0;
     virtual std::string state_names() const = 0;  // "<fixed names>|<record names>", space-separated
     virtual void launch_state_rows(hipStream_t s, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) = 0;
@@ -227,26 +242,13 @@ constexpr int kDebugChaserSerialMobs = 1 << 25;  // chaser: the enemies one afte
 constexpr int kDebugPolicyStrided = 1 << 26;     // policy observations: each lane stores its own units (pg_policy_obs.h), no exchange
 constexpr int kDebugFatInPlace = 1 << 27;        // coinrun: no early blocks in the render launch — a handed-back frame is drawn by its env's own block (coinrun.hip render_kernel)
 
-// The debug dumps (Game::dump_state, dump_tiles): one element of device memory; a dump's values copied out as far as cap
-// allows, returning how many there are; one env's tile bytes (each masked with `mask`).
-template <class T>
-T read_one(const T* p) {
-    T v;
-    (void)hipMemcpy(&v, p, sizeof(T), hipMemcpyDeviceToHost);
-    return v;
-}
-inline int dump_out(const std::vector<float>& v, float* out, int cap) {
-    for (int k = 0; k < cap && k < static_cast<int>(v.size()); k++) out[k] = v[k];
-    return static_cast<int>(v.size());
-}
-inline int dump_env_tiles(hipStream_t st, const uint8_t* tiles, size_t stride, int count, int env, uint8_t* out, int cap,
-                          uint8_t mask = 0xff) {
-    (void)hipStreamSynchronize(st);
-    const int m = cap < count ? cap : count;
-    (void)hipMemcpy(out, tiles + size_t(env) * stride, m, hipMemcpyDeviceToHost);
-    for (int k = 0; k < m; k++) out[k] &= mask;
-    return count;
-}
+// What every game's host class keeps: its device view and the atlas, left there by its bind().
+template <class S>
+class BoundGame : public Game {
+   protected:
+    S s_{};
+    AtlasView atlas_{};
+};
 
 // Factories, one per compiled variant of a game (pg_defs.h PG_VARIANT; v0 = the reference's compile-time default).
 std::unique_ptr<Game> make_coinrun_v0();

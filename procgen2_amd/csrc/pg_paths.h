@@ -169,6 +169,15 @@ PG_HD void path_probe(const int16_t* row, int tile_w, int tile_h, int probe, int
     else if (py < tile_h - 1 && row[probe + 1] == want) step = 4;
 }
 
+// A game's tile maps as its read-only views take them (the tile rows of pg_state_obs.h, the path distances here): stated
+// once per tile game, as the host function map(State) of its StateRow.  w and h need no bound state.
+struct TileMaps {
+    const uint8_t* tiles;  // [n][stride] bytes, a map in the first `cells` of each
+    int stride, cells;
+    int mask;              // what a tile byte is taken & with
+    int w, h;
+};
+
 // pgv_tile_paths (include/procgen2_vec.h) with what the game knows of its map, as the kernel takes it.
 struct TilePaths {
     const uint8_t* tiles;  // [n][stride] bytes, a map in the first `cells` of each
@@ -261,12 +270,11 @@ __global__ void __launch_bounds__(256) tile_paths_kernel(typename Points::Row::S
 
 // (65 536 rows are 16 384 groups: one grid)
 template <class Points>
-void launch_tile_paths_of(hipStream_t st, const typename Points::Row::State& s, const uint8_t* tiles, int stride, int cells, int mask,
-                          int tile_w, int tile_h, int n, const TilePaths& asked) {
+void launch_tile_paths_of(hipStream_t st, const typename Points::Row::State& s, const TileMaps& m, int n, const TilePaths& asked) {
     static_assert(Points::kGoalX < Points::Row::kWidth && Points::kGoalY < Points::Row::kWidth, "the goal's columns");
     TilePaths q = asked;
-    q.tiles = tiles, q.stride = static_cast<uint32_t>(stride), q.cells = static_cast<uint32_t>(cells);
-    q.tile_mask = static_cast<uint32_t>(mask), q.tile_w = tile_w, q.tile_h = tile_h, q.n = n;
+    q.tiles = m.tiles, q.stride = static_cast<uint32_t>(m.stride), q.cells = static_cast<uint32_t>(m.cells);
+    q.tile_mask = static_cast<uint32_t>(m.mask), q.tile_w = m.w, q.tile_h = m.h, q.n = n;
     const uint32_t groups = (static_cast<uint32_t>(q.count) + kPathGroupRows - 1u) / kPathGroupRows;  // (unsigned: any count up to INT_MAX)
     const size_t lds = ((size_t(kPathGroupRows) * q.cells + 8) * sizeof(int16_t) + 15) & ~size_t(15);
     hipLaunchKernelGGL(tile_paths_kernel<Points>, dim3(groups), dim3(256), lds, st, s, q);

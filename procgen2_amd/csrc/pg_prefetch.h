@@ -356,8 +356,12 @@ struct LevelLaunch {
 // own grid (install_prefetched) — without prefetch the level kernel serves every reset in front of the logic, with it only
 // the levels that were not ready, behind.  The game launches its own logic kernels.
 template <class G>
-class PrefetchingGame : public Game {
+class PrefetchingGame : public BoundGame<typename G::State> {
+    using Bound = BoundGame<typename G::State>;
+
    public:
+    using Bound::debug_flags;
+    using Bound::plan;
     void launch_reset(hipStream_t st, const uint8_t* mask, const int32_t* seeds, StepIO io) override {
         LevelLaunch<G>::reset(st, s_, prefetch(), mask, seeds, io, plan);
     }
@@ -380,7 +384,7 @@ class PrefetchingGame : public Game {
     void reset_after_logic(hipStream_t st, uint32_t step_index, StepIO io) {
         if (prefetch()) auto_reset(st, step_index, io);
     }
-    typename G::State s_{};
+    using Bound::s_;
 
    private:
     void auto_reset(hipStream_t st, uint32_t step_index, StepIO io) {

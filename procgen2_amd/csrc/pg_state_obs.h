@@ -7,7 +7,11 @@
 //     kEnvCols                           the leading columns whose sources are [field][n] arrays
 //     length(s, env)                     floats of this env's dump
 //     value(s, env, col)                 column col of it, col < length(s, env)
-// — the same statement as its host tap Game::dump_state, element by element — and state_rows_kernel<Row> lays the rows out.
+//     names()                            host only: the columns' names, "<fixed names>|<record names>", space-separated
+//     map(s)                             host only, tile games: the game's TileMaps (pg_paths.h)
+// and state_rows_kernel<Row> lays the rows out.  It is the engine's only statement of the layout — the oracle's dump_state is
+// the other one — and the debug taps read one row through it (engine.hip pgv_dump_state), so whatever test holds a tap to
+// the oracle holds this.  ViewedGame, below, derives a game's host functions for these views from the Row.
 //
 // One kernel for every game, the shape of pg_records.h: a workgroup of 256 lanes takes 64 consecutive rows.  The two kinds
 // of source get opposite lane mappings:
@@ -33,6 +37,7 @@
 
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "pg_engine.h"
 
@@ -131,18 +136,55 @@ void launch_state_rows_of(hipStream_t st, const typename Row::State& s, int n, c
     const uint32_t groups = (static_cast<uint32_t>(count) + kStateGroup - 1u) / kStateGroup;  // (unsigned: any count up to INT_MAX)
     hipLaunchKernelGGL(state_rows_kernel<Row>, dim3(groups), dim3(256), 0, st, s, n, d_indices, count, d_rows, d_lengths);
 }
-inline void launch_tile_rows_of(hipStream_t st, const uint8_t* tiles, int stride, int cells, int mask, int n,
-                                const int32_t* d_indices, int count, uint8_t* d_tiles) {
-    const size_t vecs = (size_t(count) * cells + 15) / 16;
-    hipLaunchKernelGGL(tile_rows_kernel, dim3(static_cast<uint32_t>((vecs + 255) / 256)), dim3(256), 0, st, tiles,
-                       static_cast<uint32_t>(stride), static_cast<uint32_t>(cells), static_cast<uint32_t>(mask), n, d_indices, count,
-                       d_tiles);
+inline void launch_tile_rows_of(hipStream_t st, const TileMaps& m, int n, const int32_t* d_indices, int count, uint8_t* d_tiles) {
+    const size_t vecs = (size_t(count) * m.cells + 15) / 16;
+    hipLaunchKernelGGL(tile_rows_kernel, dim3(static_cast<uint32_t>((vecs + 255) / 256)), dim3(256), 0, st, m.tiles,
+                       static_cast<uint32_t>(m.stride), static_cast<uint32_t>(m.cells), static_cast<uint32_t>(m.mask), n, d_indices,
+                       count, d_tiles);
 }
 
 template <class Row>
-constexpr StateLayout state_layout_of(int tile_w, int tile_h) {
-    return {Row::kWidth, Row::kFixed, Row::kRecord, Row::kMaxRecords, tile_w * tile_h, tile_w, tile_h};
+constexpr StateLayout state_layout_of(const TileMaps& m) {
+    return {Row::kWidth, Row::kFixed, Row::kRecord, Row::kMaxRecords, m.cells, m.w, m.h};
 }
+
+// Whether a Row states a tile map (bossfight's does not).
+template <class Row, class = void>
+struct HasTileMap {
+    static constexpr bool value = false;
+};
+template <class Row>
+struct HasTileMap<Row, decltype(static_cast<void>(&Row::map))> {
+    static constexpr bool value = true;
+};
+
+// The host side of the read-only views, written once: a game's class derives from ViewedGame<Base, its StateRow, its PathRow
+// or void> — Base: whatever it derived from otherwise, a BoundGame (pg_engine.h) — and has all six.
+template <class Base, class Row, class Points>
+class ViewedGame : public Base {
+   public:
+    StateLayout state_layout() const override { return state_layout_of<Row>(map()); }
+    std::string state_names() const override { return Row::names(); }
+    void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {
+        launch_state_rows_of<Row>(st, this->s_, this->s_.n, d_indices, count, d_rows, d_lengths);
+    }
+    void launch_tile_rows(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_tiles) override {
+        if constexpr (HasTileMap<Row>::value) launch_tile_rows_of(st, map(), this->s_.n, d_indices, count, d_tiles);
+    }
+    PathPoints path_points() const override {
+        if constexpr (std::is_void<Points>::value) return Game::path_points();
+        else return path_points_of<Points>();
+    }
+    void launch_tile_paths(hipStream_t st, const TilePaths& q) override {
+        if constexpr (!std::is_void<Points>::value) launch_tile_paths_of<Points>(st, this->s_, map(), this->s_.n, q);
+    }
+
+   private:
+    TileMaps map() const {
+        if constexpr (HasTileMap<Row>::value) return Row::map(this->s_);
+        else return TileMaps{nullptr, 0, 0, 0, 0, 0};
+    }
+};
 #endif
 
 // "p0_x p0_y p0_life p1_x …": the names of `count` slots of `fields` floats each, with a space in front of every one.

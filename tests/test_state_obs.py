@@ -58,7 +58,9 @@ def test_layouts_hold_every_oracle_dump(engine_lib, game):
 def test_names(engine_lib, game):
     L = engine_lib
     gid = L.pgv_game_id(game.encode())
-    for mode in (0,) + tuple(TABLE[game][1]):
+    offered = tuple(m for m in range(32) if L.pgv_game_modes(gid) >> m & 1)
+    assert offered == tuple(sorted(TABLE[game][1]))
+    for mode in (0,) + offered:  # every (game, mode) pair of pgv_game_modes, and PGV_MODE_DEFAULT
         need = L.pgv_state_names(gid, mode, None, 0)
         assert need > 0
         buf = ctypes.create_string_buffer(need + 1)
@@ -75,6 +77,7 @@ def test_names(engine_lib, game):
         assert short.raw[:10] == text[:9].encode() + b"\0" and short.raw[10:] == b"#" * 6
         lay = pglib.state_layout(L, game, mode)
         assert lay.fixed_names == tuple(fixed) and lay.record_names == tuple(record) and lay.width == _layout(L, gid, mode).width
+        assert len(lay.fixed_names) == lay.fixed and len(lay.record_names) == lay.record, (game, mode)
 
 
 def test_refusals(engine_lib):

@@ -127,21 +127,42 @@ def test_the_calls_change_nothing(game):
 
 
 @pytest.mark.parametrize("game", GAMES)
-def test_two_statements_of_one_layout(game):
+def test_taps_and_host_forms_against_the_device_rows(game):
+    """The parity taps pgv_dump_state / pgv_dump_tiles and the host-pointer forms give what the device rows hold, bit for
+    bit, on both sides of the row kernel's group boundaries and for the last env; and the taps keep their contract: the
+    full length whatever cap is, exactly min(cap, length) items written, -1 for an index outside the batch, 0 for
+    bossfight's tiles."""
     env = make(game)
     for _ in range(24):
         env.step_synthetic(RUN_SEED)
     rows, lengths, tiles = observe(env)
     env.sync()
-    sampled = np.array([0, 1, 17, 63, 64, 65, 100, 130], np.int32)
+    L, h = env.L, env._h
+    sampled = np.array([0, 1, 17, 63, 64, 65, 100, N - 1], np.int32)
     for e in (int(x) for x in sampled):
-        st = _dump(lambda buf, m: env.L.pgv_dump_state(env._h, e, buf, m), c_float, np.float32)
-        tl = _dump(lambda buf, m: env.L.pgv_dump_tiles(env._h, e, buf, m), c_uint8, np.uint8)
+        st = _dump(lambda buf, m: L.pgv_dump_state(h, e, buf, m), c_float, np.float32)
+        tl = _dump(lambda buf, m: L.pgv_dump_tiles(h, e, buf, m), c_uint8, np.uint8)
         assert lengths[e] == st.size and np.array_equal(rows[e, :st.size].view(np.uint32), st.view(np.uint32)), (game, e)
         assert tiles.shape[1] == tl.size and np.array_equal(tiles[e], tl), (game, e)
+        # a short cap: the full length comes back, cap items are written, the canary behind them stays; cap 0 writes nothing
+        for tap, ctype, whole, canary in ((L.pgv_dump_state, c_float, st, 7.5), (L.pgv_dump_tiles, c_uint8, tl, 0xAB)):
+            for cap in (0, 3, whole.size - 1):
+                if cap < 0 or cap >= whole.size:
+                    continue  # (bossfight has no tiles to cut short)
+                buf = (ctype * (whole.size + 1))(*([canary] * (whole.size + 1)))
+                assert tap(h, e, buf, cap) == whole.size, (game, e, cap)
+                got = np.array(buf[:], whole.dtype)
+                assert np.array_equal(got[:cap].view(np.uint8), whole[:cap].view(np.uint8)), (game, e, cap)
+                assert (got[cap:] == canary).all(), (game, e, cap)
+    one_f, one_b = (c_float * 1)(7.5), (c_uint8 * 1)(0xAB)
+    for outside in (-1, N):
+        assert L.pgv_dump_state(h, outside, one_f, 1) == -1 and L.pgv_dump_tiles(h, outside, one_b, 1) == -1, (game, outside)
+    assert one_f[0] == 7.5 and one_b[0] == 0xAB
+    if game == "bossfight":
+        assert L.pgv_dump_tiles(h, 0, one_b, 1) == 0 and one_b[0] == 0xAB
     # the host-pointer forms: the same rows for the sampled envs (uploaded indices), with and without the lengths, and for
     # the first envs under NULL indices; unaligned host buffers are fine
-    L, h, lay = env.L, env._h, env.state_layout
+    lay = env.state_layout
     k = sampled.size
     raw = np.full(k * lay.width + 1, np.nan, np.float32)
     h_rows, h_lengths = raw[1:].reshape(k, lay.width), np.full(k, -7, np.int32)
