@@ -1,0 +1,456 @@
+"""The protocol of tests/test_scripted_play_gpu.py, stated once: scripted agents that play bossfight, chaser and climber to
+win on the CPU oracle.  The GPU half feeds their actions to the HIP engine beside the oracle; tests/test_scripted_play.py runs
+the protocol on the oracle alone and asserts that it reaches the ground random play never does (the boss's six phases and its
+death, cleared boards, levels with every coin collected), so the GPU tests are known not to be vacuous before a GPU is touched.
+
+A policy is a pure function of (the oracle's state dump, the oracle's tile dump, step, env, a seeded numpy Generator) that
+returns an action.  It reads the ORACLE's dumps, never the engine's: the test stays valid if the engine's state rows are wrong,
+and a divergence shows as a byte mismatch at the step where it happens.  Columns are named through the layout the project
+states (pgv_state_layout_of / pgv_state_names: host-only), never by bare index.
+
+Lock-step protocol: N = 65 envs (one wavefront and one lane: the second wavefront is all but empty), seed_base 17, the
+engine's own auto-reset, no masked resets, STEPS[(game, mode)] steps.  Events are counted from the oracle's dumps and outputs
+(Counter), and assert_covers holds the floors.
+"""
+import ctypes
+import functools
+import math
+
+import numpy as np
+
+from test_modes import EASY, EXTREME, HARD, TABLE  # noqa: F401
+
+GAMES = ("bossfight", "chaser", "climber")
+PAIRS = [(g, m) for g in GAMES for m in TABLE[g][1]]  # 7
+N, SEED_BASE, POLICY_SEED = 65, 17, 9
+# The fewest steps (rounded up to the next 50) after which the oracle's run holds every floor of assert_covers; the step at
+# which the last floor is reached: bossfight 684 / 732, chaser 1023 / 954 / 1429, climber 140 / 152.
+STEPS = {("bossfight", EASY): 700, ("bossfight", HARD): 750, ("chaser", EASY): 1050, ("chaser", HARD): 1000,
+         ("chaser", EXTREME): 1450, ("climber", EASY): 200, ("climber", HARD): 200}
+# chaser's modes that fall back from a cleared board to an episode that ate at least 85 % of its points and orbs
+ATE_85_INSTEAD = {("chaser", EXTREME)}
+RARE_ENVS = 8  # state and tile rows are compared in at most this many envs a step
+
+LEFT, NOOP, RIGHT, UP, DOWN, JUMP_LEFT, JUMP_RIGHT, FIRE = 1, 4, 7, 3, 5, 2, 8, 9  # (up and down: chaser's; world y grows with 3)
+ORB, POINT, EGG = 0, 1, 2   # chaser's record kinds (oracle/pgo_chaser.cpp)
+HATCH_TIME = 50.0
+WALL = 1                    # chaser's wall tile; climber's walls are every non-zero tile
+
+
+class Columns:
+    """A game's state row by name: f[name] a fixed column, r[name] the offset inside a record."""
+
+    def __init__(self, lay):
+        self.f = {name: i for i, name in enumerate(lay.fixed_names)}
+        self.r = {name: i for i, name in enumerate(lay.record_names)}
+        self.fixed, self.record, self.width = lay.fixed, lay.record, lay.width
+        self.cells, self.tile_w, self.tile_h = lay.cells, lay.tile_w, lay.tile_h
+        assert len(self.f) == lay.fixed and len(self.r) == lay.record
+
+    def records(self, st):
+        k = int(st[self.f["n_things"]])
+        return st[self.fixed:self.fixed + k * self.record].reshape(k, self.record)
+
+
+@functools.lru_cache(maxsize=None)
+def columns(game, mode):
+    from engine_util import pglib
+    return Columns(pglib.state_layout(pglib.load(), game, mode))
+
+
+class Dumps:
+    """Every env's oracle dumps at one point: states float32 [n, width] (+0.0 behind a dump), tiles uint8 [n, cells]."""
+
+    def __init__(self, ora, c):
+        n = ora.n
+        self.states = np.zeros((n, c.width), np.float32)
+        self.lengths = np.zeros(n, np.int32)
+        self.tiles = np.zeros((n, max(1, c.cells)), np.uint8)
+        fp, bp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)
+        s0, t0, dump_state, dump_tiles, h = self.states.ctypes.data, self.tiles.ctypes.data, ora.L.pgo_vec_dump_state, ora.L.pgo_vec_dump_tiles, ora.h
+        for e in range(n):
+            self.lengths[e] = got = dump_state(h, e, ctypes.cast(s0 + e * c.width * 4, fp), c.width)
+            assert 0 < got <= c.width, (e, got)
+            if c.cells:
+                assert dump_tiles(h, e, ctypes.cast(t0 + e * c.cells, bp), c.cells) == c.cells
+
+    def state(self, e):
+        return self.states[e, :self.lengths[e]]
+
+
+# ---------------------------------------------------------------------------------------------------------- the policies
+
+def bossfight_policy(c, st, tiles, step, env, rng):
+    """Steps aside from live boss bullets close to the ship, follows the boss's x and fires while the shield is down,
+    otherwise fires 30 % of the time.  Every fourth env does not dodge: the run keeps its deaths."""
+    f = c.f
+    u = rng.random()
+    ax, ay, bx = float(st[f["agent_x"]]), float(st[f["agent_y"]]), float(st[f["boss_x"]])
+    first = f["b_shot0_x"]
+    shots = st[first:first + 64 * 3].reshape(64, 3)
+    dx, dy = shots[:, 0] - ax, ay - shots[:, 1]
+    near = (shots[:, 2] == 0) & (np.abs(dx) < 0.45) & (dy > -0.2) & (dy < 0.6)
+    if env % 4 != 3 and near.any():
+        k = int(np.argmin(np.where(near, np.abs(dx) + np.abs(dy), np.inf)))
+        go = LEFT if dx[k] >= 0 else RIGHT
+        if ax < -1.6:
+            go = RIGHT
+        elif ax > 1.6:
+            go = LEFT
+        return go
+    if int(st[f["phase_index"]]) % 2 == 1:
+        if abs(bx - ax) < 0.35:
+            return FIRE
+        return RIGHT if bx > ax else LEFT
+    return FIRE if u < 0.3 else NOOP
+
+
+@functools.lru_cache(maxsize=None)
+def _neighbours(W, H):
+    """cell → ((cell beside it, its action), …), a cell being y + x * H.  Tile row y - 1 is world y + 1: action 3."""
+    out = []
+    for x in range(W):
+        for y in range(H):
+            out.append(tuple((c, a) for ok, c, a in ((x > 0, y + (x - 1) * H, LEFT), (x < W - 1, y + (x + 1) * H, RIGHT),
+                                                     (y > 0, y - 1 + x * H, UP), (y < H - 1, y + 1 + x * H, DOWN)) if ok))
+    return tuple(out)
+
+
+FAR = 10 ** 6
+ORB_WHEN = 3
+BOLD_EVERY, BOLD_FOR = 50, 12
+HORIZON = 5  # chaser looks out for enemies this many steps ahead; they turn at random half the time
+
+
+def _field(nb, wall, sources):
+    """Steps from the nearest of `sources` to every cell, through cells that are no wall; FAR where there is no way."""
+    dist = [FAR] * len(nb)
+    frontier = list(sources)
+    for c in frontier:
+        dist[c] = 0
+    d = 0
+    while frontier:
+        d += 1
+        nxt = []
+        for c in frontier:
+            for p, _ in nb[c]:
+                if dist[p] == FAR and not wall[p]:
+                    dist[p] = d
+                    nxt.append(p)
+        frontier = nxt
+    return dist
+
+
+def _walk(nb, wall, start, targets, enemy, limit=FAR, horizon=HORIZON):
+    """Breadth-first from `start` through cells the agent reaches well before an enemy can (an enemy is a quarter faster):
+    (the action of the first step towards the nearest cell of `targets`, or None; the action towards the reached cell that
+    is safest when it is reached, or None)."""
+    seen = {start}
+    frontier = [(start, None)]
+    d, best, flee = 0, enemy[start] if enemy[start] < FAR else FAR, None
+    while frontier and d < limit:
+        d += 1
+        nxt = []
+        for c, first in frontier:
+            for p, a in nb[c]:
+                if p in seen or wall[p] or (d <= horizon and enemy[p] <= 1.25 * d + 1.5):
+                    continue
+                seen.add(p)
+                if p in targets:
+                    return first or a, flee
+                slack = enemy[p] - 1.25 * d
+                if slack > best:
+                    best, flee = slack, first or a
+                nxt.append((p, first or a))
+        frontier = nxt
+    return None, flee
+
+
+def _cell(x, y, H):
+    return (H - 1 - int(math.floor(y))) + int(math.floor(x)) * H
+
+
+def chaser_policy(c, st, tiles, step, env, rng):
+    """Between two cells, with no enemy within 4, it keeps going.  Otherwise it walks to the nearest point by breadth-first
+    search through the cells it reaches well before a hatched (or nearly hatched) enemy can; an orb counts as a point when an
+    enemy is within 3 steps or no point is left; with an orb's timer running it hunts the hatched enemies within 10 steps
+    first; with nowhere safe to go it makes for the cell it reaches with the most to spare, then away from the enemies, then
+    on regardless."""
+    f, r = c.f, c.r
+    W, H = c.tile_w, c.tile_h
+    rng.random()
+    ax, ay = float(st[f["agent_x"]]), float(st[f["agent_y"]])
+    vx, vy = float(st[f["agent_vel_x"]]), float(st[f["agent_vel_y"]])
+    rec = c.records(st)
+    powered = float(st[f["eat_timer"]]) > 10.0
+    kind = rec[:, r["kind"]]
+    eggs = rec[(kind == EGG) & (rec[:, r["alive"]] != 0)]
+    threat = eggs[eggs[:, r["hatch_timer"]] >= HATCH_TIME - 12]
+    if (vx != 0 or vy != 0) and max(abs(ax - math.floor(ax) - 0.5), abs(ay - math.floor(ay) - 0.5)) > 0.11:
+        if powered or not len(threat) or (np.abs(threat[:, r["x"]] - ax) + np.abs(threat[:, r["y"]] - ay)).min() > 4.5:
+            return RIGHT if vx > 0 else LEFT if vx < 0 else UP if vy > 0 else DOWN
+    nb = _neighbours(W, H)
+    wall = (tiles == WALL).tolist()
+    start = _cell(ax, ay, H)
+
+    def cells_of(rows):
+        at = (H - 1 - np.floor(rows[:, r["y"]]).astype(int)) + np.floor(rows[:, r["x"]]).astype(int) * H
+        return set(at[(at >= 0) & (at < W * H)].tolist())
+    food = rec[(kind != EGG) & (rec[:, r["alive"]] != 0)]
+    points, orbs = cells_of(food[food[:, r["kind"]] == POINT]), cells_of(food[food[:, r["kind"]] == ORB])
+    if powered:
+        enemy = [FAR] * (W * H)
+        hatched = cells_of(eggs[eggs[:, r["hatch_timer"]] >= HATCH_TIME])
+        if hatched:
+            go, _ = _walk(nb, wall, start, hatched, enemy, limit=min(10, int(float(st[f["eat_timer"]]) * 0.08)))
+            if go is not None:
+                return go
+    else:
+        enemy = _field(nb, wall, cells_of(threat))
+    targets = points | orbs if not points or enemy[start] <= ORB_WHEN else points
+    bold = (step + 7 * env) % BOLD_EVERY < BOLD_FOR  # (a stand-off with enemies that hover at the mouth of a dead end is broken in time)
+    go, flee = _walk(nb, wall, start, targets, enemy, horizon=1 if bold else HORIZON)
+    if go is None and orbs and not powered:
+        go, flee = _walk(nb, wall, start, orbs, enemy)
+    if go is None:
+        go = flee
+    if go is None:  # nothing is safe: the neighbour farther from the enemies, or on regardless
+        best = enemy[start]
+        for p, a in nb[start]:
+            if not wall[p] and enemy[p] > best:
+                best, go = enemy[p], a
+    if go is None:
+        go, _ = _walk(nb, wall, start, points | orbs, [FAR] * (W * H))
+    return NOOP if go is None else go
+
+
+def climber_policy(c, st, tiles, step, env, rng):
+    """Goes for the lowest coin.  On its level it walks to it; below a coin it walks to the column beside the end of the next
+    platform up (the lowest row of wall above the one it stands on), waits while a mob is near the way up, and jumps towards
+    the platform; in the air it steers onto the platform."""
+    f, r = c.f, c.r
+    W, H = c.tile_w, c.tile_h
+    rng.random()
+    ax, ay, vx = float(st[f["agent_x"]]), float(st[f["agent_y"]]), float(st[f["agent_vel_x"]])
+    ground = st[f["agent_ground"]] != 0
+    rec = c.records(st)
+    alive = rec[:, r["alive"]] != 0
+    is_mob = alive & (rec[:, r["vel_x"]] != 0)
+    is_coin = alive & (rec[:, r["vel_x"]] == 0)
+    if not is_coin.any():
+        return NOOP
+    grid = tiles.reshape(W, H) != 0  # grid[x, row], row 0 the floor; world y = H - 1 - row at a tile's top
+    feet = min(H - 1, max(0, H - 1 - int(math.floor(ay))))
+    stand = 0
+    for col in {int(math.floor(ax - 0.49)), int(math.floor(ax + 0.49))}:
+        col = min(W - 1, max(0, col))
+        below = np.nonzero(grid[col, :feet + 1])[0]
+        stand = max(stand, int(below[-1]) if below.size else 0)
+    body = stand + 1
+    coins = rec[is_coin]
+    coin_rows = H - 1 - np.floor(coins[:, r["y"]]).astype(int)
+    lowest = coin_rows.min()
+    pick = coins[coin_rows == lowest]
+    coin_x = float(pick[np.argmin(np.abs(pick[:, r["x"]] - ax)), r["x"]])
+    above = np.nonzero(grid[1:W - 1, stand + 1:].any(axis=0))[0]
+    if lowest <= body or above.size == 0 or stand + 1 + int(above[0]) >= H - 1:
+        return RIGHT if coin_x > ax else LEFT
+    row = stand + 1 + int(above[0])
+    span = np.nonzero(grid[1:W - 1, row])[0] + 1
+    lo, hi = int(span[0]), int(span[-1])
+    best = None
+    for col, way in ((lo - 1, 1), (hi + 1, -1)):
+        if not 1 <= col <= W - 2:
+            continue
+        ok = bool(grid[col, stand]) and not grid[col, stand + 1:row + 2].any()
+        cost = abs(col + 0.5 - ax) + (0 if ok else 100)
+        if best is None or cost < best[0]:
+            best = (cost, col, way)
+    _, col, way = best
+    tx = col + 0.5
+    if not ground:
+        if ay < H - 1 - stand - 0.05:  # off the ground: onto the platform
+            return RIGHT if way > 0 else LEFT
+        return RIGHT if tx > ax else LEFT
+    if abs(ax - tx) <= 0.3:
+        mobs = rec[is_mob]
+        mob_rows = H - 1 - np.floor(mobs[:, r["y"]]).astype(int)
+        if ((mob_rows >= body) & (mob_rows <= row + 2) & (np.abs(mobs[:, r["x"]] - (tx + 0.6 * way)) < 2.2)).any():
+            return NOOP
+        if vx * way >= -0.01:
+            return JUMP_RIGHT if way > 0 else JUMP_LEFT
+        return RIGHT if way > 0 else LEFT
+    return RIGHT if tx > ax else LEFT
+
+
+POLICIES = {"bossfight": bossfight_policy, "chaser": chaser_policy, "climber": climber_policy}
+
+
+def choose_actions(game, mode, dumps, step, rng):
+    """The scripted action of every env, in env order, from the oracle's dumps before the step."""
+    c, policy = columns(game, mode), POLICIES[game]
+    return np.array([policy(c, dumps.states[e], dumps.tiles[e], step, e, rng) for e in range(dumps.states.shape[0])], np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------- events and floors
+
+class Counter:
+    """Events of a run, counted from the oracle's dumps before and after every step and from its reward and done rows.  The
+    engine's own auto-reset is the next step's: an env that ended keeps its terminal state in the dump after that step, and
+    its next step (whatever the action) installs the next level and counts for nothing here."""
+
+    def __init__(self, game, mode, n):
+        self.game, self.mode, self.c = game, mode, columns(game, mode)
+        self.counts = dict(wins=0, deaths=0, ends=0)
+        self.rare, self.after = [], None  # the envs in a rare state after the last step counted, and that step's dumps
+        self.first = True
+        self.resetting = np.zeros(n, bool)  # the envs whose next step is their reset step
+        if game == "bossfight":
+            self.counts.update(phases=set(), damaged=0, win_and_death_steps=0)
+        if game == "climber":
+            self.counts.update(coins=0, wins_with_3_coins=0, rewards_11=0, most_coins_in_a_win=0)
+            self.level_coins = np.zeros(n, int)
+            self.lost_coin = np.zeros(n, bool)
+        if game == "chaser":
+            self.counts.update(eaten_enemies=0, wins_or_85=0, best_share=0.0)
+            self.board = np.zeros(n, int)
+            self.ate_85 = np.zeros(n, bool)
+
+    def _records(self, dumps):
+        c = self.c
+        return dumps.states[:, c.fixed:].reshape(dumps.states.shape[0], -1, c.record)  # (zeros behind an env's last record)
+
+    def climber_coins(self, dumps):
+        rec = self._records(dumps)
+        return ((rec[:, :, self.c.r["alive"]] != 0) & (rec[:, :, self.c.r["vel_x"]] == 0)).sum(axis=1)
+
+    def chaser_food(self, dumps):
+        rec = self._records(dumps)
+        return ((rec[:, :, self.c.r["alive"]] != 0) & (rec[:, :, self.c.r["kind"]] != EGG)).sum(axis=1)
+
+    def step(self, before, after, reward, done):
+        c, k, f, r = self.c, self.counts, self.c.f, self.c.r
+        n = done.size
+        starts = np.ones(n, bool) if self.first else self.resetting  # the envs whose level begins: in `before` at first, then in `after`
+        level = before if self.first else after
+        self.first = False
+        playing = ~self.resetting
+        ended = (done != 0) & playing
+        win = ended & ((reward > 0) if self.game == "bossfight" else (reward >= 10))
+        death = ended & ~win
+        k["wins"] += int(win.sum())
+        k["deaths"] += int(death.sum())
+        k["ends"] += int(ended.sum())
+        rare = np.zeros(n, bool)
+        if self.game == "bossfight":
+            k["win_and_death_steps"] += int(win.any() and (ended & (reward < 0)).any())
+            phase, hp, booms = (after.states[:, f[name]].astype(int) for name in ("phase_index", "hp", "x_count"))
+            k["phases"] |= set(phase[playing].tolist())
+            k["damaged"] += int((playing & (hp == 0) & (booms > 0)).sum())
+            rare = playing & ((phase % 2 == 1) | (hp == 0) | (booms > 0) | (phase >= 4))
+        elif self.game == "climber":
+            k["rewards_11"] += int((ended & (reward >= 11)).sum())
+            had, has = self.climber_coins(before), self.climber_coins(after)
+            self.level_coins[starts] = self.climber_coins(level)[starts]
+            lost = playing & (has < had)
+            k["coins"] += int((had - has)[playing].sum())
+            assert not has[win].any()
+            k["wins_with_3_coins"] += int((self.level_coins[win] >= 3).sum())
+            k["most_coins_in_a_win"] = max([k["most_coins_in_a_win"]] + self.level_coins[win].tolist())
+            rare = lost | (self.lost_coin & playing)  # a coin just destroyed, and the step after
+            self.lost_coin = lost
+        elif self.game == "chaser":
+            self.board[starts] = self.chaser_food(level)[starts]
+            self.ate_85[starts] = False
+            share = 1.0 - self.chaser_food(after) / self.board.astype(float)
+            k["best_share"] = max(k["best_share"], float(share[playing].max()) if playing.any() else 0.0)
+            crossed = playing & (share >= 0.85) & ~self.ate_85  # (once an episode)
+            self.ate_85 |= crossed
+            k["wins_or_85"] += int(crossed.sum())
+            b, a = self._records(before), self._records(after)
+            back = ((b[:, :, r["kind"]] == EGG) & (b[:, :, r["alive"]] != 0) & (b[:, :, r["hatch_timer"]] >= HATCH_TIME)
+                    & (a[:, :, r["hatch_timer"]] < 1.0)).sum(axis=1)
+            back[~playing | (before.states[:, f["eat_timer"]] <= 0)] = 0
+            k["eaten_enemies"] += int(back.sum())
+            rare = (back > 0) & (after.states[:, f["eat_timer"]] > 0)
+        self.rare = [int(e) for e in np.nonzero(rare)[0][:RARE_ENVS]]
+        self.after = after
+        self.resetting = done != 0
+
+
+def run_on_oracle(game, mode, each_step=None, at_start=None, render=False, threads=1, n=N, steps=None, ora=None, actions_of=None):
+    """The lock-step protocol on an OracleVec.  at_start(ora) before the first step; each_step(s, ora, actions, obs, reward,
+    done, counter) after every step, counter.rare naming the envs in a rare state.  Returns the counts.  `ora`: an oracle
+    the caller made (and closes); actions_of(step, n): other actions than the agents' (the census of random play)."""
+    from oracle_util import OracleVec
+    own = ora is None
+    if own:
+        ora = OracleVec(game, n, seed_base=SEED_BASE, render=render, mode=mode, threads=threads)
+    c, counter, rng = columns(game, mode), Counter(game, mode, n), np.random.default_rng(POLICY_SEED)
+    try:
+        if at_start:
+            at_start(ora)
+        before = Dumps(ora, c)
+        for s in range(STEPS[(game, mode)] if steps is None else steps):
+            a = choose_actions(game, mode, before, s, rng) if actions_of is None else actions_of(s, n)
+            obs, reward, done = ora.step(a, threads=threads)
+            after = Dumps(ora, c)
+            counter.step(before, after, reward, done)
+            if each_step:
+                each_step(s, ora, a, obs, reward, done, counter)
+            before = after
+    finally:
+        if own:
+            ora.close()
+    return counter.counts
+
+
+def floors(game, mode):
+    """count name → the least a run must reach."""
+    if game == "bossfight":
+        return dict(wins=5, deaths=5, damaged=50, win_and_death_steps=1)
+    if game == "climber":
+        return dict(wins=5, wins_with_3_coins=1, rewards_11=1, coins=40, deaths=3)
+    out = dict(eaten_enemies=20, deaths=3)
+    out["wins_or_85" if (game, mode) in ATE_85_INSTEAD else "wins"] = 2 if mode == EASY else 1
+    return out
+
+
+def assert_covers(game, mode, counts):
+    for name, least in floors(game, mode).items():
+        assert counts[name] >= least, "%s mode %d: %s is %d, the floor is %d (%r)" % (game, mode, name, counts[name], least, counts)
+    if game == "bossfight":
+        assert counts["phases"] >= set(range(6)), "%s mode %d: phases seen %r" % (game, mode, sorted(counts["phases"]))
+
+
+# test_same_step_episodes_of_scripted_play (tests/test_scripted_play_gpu.py): the agents on the model of tests/episodes_util.py,
+# same-step auto-reset, no limit, a ring of 4 terminal frames, each game in its default mode, seed_base 1 as the model's
+SAME_STEP_RING, SAME_STEP_WINS = 4, 1
+DEFAULT_MODE = {g: TABLE[g][0] for g in GAMES}
+
+
+def run_same_step(game, model, eng=None, check_step=None, steps=None):
+    """The agents play on `model` (an EpisodeModel in same-step mode, after its first reset), reading the model's own oracle
+    (model.o: after a step it already shows the next level of an env that ended); an engine beside it gets the same actions
+    and check_step(eng, model, got, t) holds it to the model.  Returns the counts."""
+    mode = DEFAULT_MODE[game]
+    c, rng = columns(game, mode), np.random.default_rng(POLICY_SEED)
+    k = dict(ends=0, wins=0, wins_with_frame=0, longest_win=0, best_return=0.0)
+    for t in range(STEPS[(game, mode)] if steps is None else steps):
+        a = choose_actions(game, mode, Dumps(model.o, c), t, rng)
+        got = eng.step(a) if eng is not None else None
+        model.step(a)
+        if eng is not None:
+            check_step(eng, model, got, t)
+        won = model.reward[model.ended_env] > 0 if game == "bossfight" else model.reward[model.ended_env] >= 10
+        k["ends"] += int(model.counts[0])
+        k["wins"] += int(won.sum())
+        k["wins_with_frame"] += int(won[:model.counts[1]].sum())
+        if won.any():
+            k["longest_win"] = max(k["longest_win"], int(model.ended_length[won].max()))
+            k["best_return"] = max(k["best_return"], float(model.ended_return[won].max()))
+    return k
+
+
+def assert_same_step_covers(game, counts):
+    assert counts["wins_with_frame"] >= SAME_STEP_WINS, "%s: %r" % (game, counts)

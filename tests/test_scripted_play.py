@@ -1,0 +1,79 @@
+"""The CPU half of tests/test_scripted_play_gpu.py: the scripted agents of tests/scripted_play_util.py play bossfight, chaser
+and climber on the oracle alone, frames off, and every floor the GPU half leans on is asserted here — wins, the boss's
+phases 0 to 5 and its damaged state, a win and a death in one step, cleared boards and eaten enemies, levels won with three
+coins and more — so the GPU tests are known not to be vacuous before a GPU is touched.  The counts are printed (pytest -s).
+
+chaser in extreme mode falls back: no agent here clears a 19 x 19 board with five enemies in a run of a length the suite
+can afford (the agent eats at most one cell in five steps, so its 190 or so points and orbs take 950 steps at the least; the
+best of 65 envs stands at 79 % after 1 250 steps, at 89 % after 1 500 and dies at 95 %; none clears a board in 2 500).  Its
+cleared-board floor is therefore an episode that ate at least 85 % of its board's points and orbs, reached at step 1 429.  Every
+other floor, and every floor of chaser's easy and hard modes (2 and 1 cleared boards), stands as it is.
+"""
+import numpy as np
+import pytest
+
+import scripted_play_util as sp
+import variant_paths_util as vp
+from episodes_util import SAME_STEP, EpisodeModel
+from oracle_util import OracleVec
+from test_modes import EXTREME
+
+
+def test_the_protocol_is_what_the_file_says():
+    assert sp.N >= 65 and sp.N % 64 != 0
+    assert len(sp.PAIRS) == 7 and set(sp.PAIRS) == set(sp.STEPS) and {g for g, _ in sp.PAIRS} == set(sp.POLICIES)
+    assert sp.ATE_85_INSTEAD == {("chaser", EXTREME)}
+    for game, mode in sp.PAIRS:
+        c = sp.columns(game, mode)
+        assert (c.width - c.fixed) % max(1, c.record) == 0 and "agent_x" in c.f
+        assert all(least > 0 for least in sp.floors(game, mode).values())
+
+
+@pytest.mark.parametrize("game,mode", sp.PAIRS)
+def test_scripted_play_covers(game, mode):
+    counts = sp.run_on_oracle(game, mode)
+    print("scripted play: %s mode %d, %d envs, %d steps: %r" % (game, mode, sp.N, sp.STEPS[(game, mode)], counts))
+    sp.assert_covers(game, mode, counts)
+
+
+@pytest.mark.parametrize("game,mode", sp.PAIRS)
+def test_random_play_does_not_cover(game, mode):
+    """The floors ask for something: the variant-path protocol's actions, over its 200 steps at this batch size, miss them."""
+    counts = sp.run_on_oracle(game, mode, steps=vp.steps_of(game, mode), actions_of=vp.actions)
+    print("random play: %s mode %d, %d envs, %d steps: %r" % (game, mode, sp.N, vp.steps_of(game, mode), counts))
+    with pytest.raises(AssertionError):
+        sp.assert_covers(game, mode, counts)
+    assert counts["wins"] == 0
+
+
+@pytest.mark.parametrize("game", sp.GAMES)
+def test_same_step_protocol_ends_in_wins(game):
+    """The same-step case of the GPU half on the model alone: at least one winning episode whose terminal frame is kept."""
+    model = EpisodeModel(game, sp.N, SAME_STEP, 0, sp.SAME_STEP_RING, render=False)
+    model.first_reset()
+    counts = sp.run_same_step(game, model)
+    model.close()
+    print("scripted play, same-step: %s, %d envs, %d steps: %r" % (game, sp.N, sp.STEPS[(game, sp.DEFAULT_MODE[game])], counts))
+    sp.assert_same_step_covers(game, counts)
+
+
+@pytest.mark.parametrize("game", sp.GAMES)
+def test_policies_are_functions_of_what_they_are_given(game):
+    """The same dumps, step and generator state give the same actions, the dumps are left as they were, and every action is
+    one the games know."""
+    mode = 1
+    ora = OracleVec(game, 9, seed_base=sp.SEED_BASE, render=False, mode=mode)
+    c = sp.columns(game, mode)
+    for s in range(40):
+        d = sp.Dumps(ora, c)
+        kept = d.states.copy(), d.tiles.copy()
+        a = sp.choose_actions(game, mode, d, s, np.random.default_rng(s))
+        b = sp.choose_actions(game, mode, d, s, np.random.default_rng(s))
+        assert np.array_equal(a, b) and a.dtype == np.int32 and ((a >= 0) & (a < 15)).all()
+        assert np.array_equal(d.states.view(np.uint32), kept[0].view(np.uint32)) and np.array_equal(d.tiles, kept[1])
+        for e in (0, 8):  # the dumps the policies read are the oracle's own
+            st = ora.state(e)
+            assert np.array_equal(d.states[e, :st.size].view(np.uint32), st.view(np.uint32)) and not d.states[e, st.size:].any()
+            assert np.array_equal(d.tiles[e, :c.cells], ora.tiles(e))
+        ora.step(a)
+    ora.close()

@@ -1,0 +1,135 @@
+"""Play to win: the HIP engine against the oracle on the games' winning and late-game paths (need an MI355X).
+
+Every other lock-step test is driven by random or one-key action streams, and those lose: bossfight never leaves its second
+phase, no chaser board is cleared, climber picks up two or three coins in a run.  Here the scripted agents of
+tests/scripted_play_util.py play bossfight, chaser and climber on the oracle — reading the oracle's dumps, never the
+engine's — and their actions go to the engine under its default path AND every alternate path behind pgv_set_debug, side by
+side: dones, reward bit patterns and every observation byte after every step, and state_obs / tile_obs rows against the
+oracle's dumps wherever an env is in a state random play does not visit (bossfight: the shield down, hp 0, explosions, phase
+4 and later; chaser: an enemy just eaten under an orb's timer; climber: a coin just destroyed, and the step after).  One
+case a game runs the agents through step_episodes in same-step mode against the model of tests/episodes_util.py: the
+returns, lengths and terminal frames of winning episodes.  The floors of tests/test_scripted_play.py are asserted again on
+the runs made here.
+
+chaser in extreme mode falls back, as tests/test_scripted_play.py explains: no board is cleared in its 1 450 steps (nor in
+2 500), so its cleared-board floor is one episode that ate at least 85 % of its board's points and orbs (the best reaches
+87.6 % inside the run).  Every other floor stands as the other modes have it.
+"""
+import numpy as np
+import pytest
+
+import scripted_play_util as sp
+import variant_paths_util as vp
+from episodes_util import SAME_STEP, EpisodeModel
+from oracle_util import OBS_BYTES, assert_same_dump
+from procgen2_amd import lib as pglib
+from test_episodes_gpu import Engine as EpisodeEngine
+from test_episodes_gpu import check_step
+from test_parity_gpu import _host_threads
+
+pytestmark = pytest.mark.gpu
+
+
+class PathEngine:
+    """ProcgenVecEnv under one pgv_set_debug word, driven with host arrays and read back as numpy."""
+
+    def __init__(self, game, mode, debug):
+        import torch
+        from procgen2_amd.vec_env import ProcgenVecEnv
+        self.torch, self.name = torch, vp.PATH_NAMES[debug]
+        self.v = ProcgenVecEnv(game, sp.N, seed_base=sp.SEED_BASE, distribution_mode=mode)
+        assert self.v.L.pgv_mode(self.v._h) == mode
+        if debug:
+            pglib.check(self.v.L, self.v.L.pgv_set_debug(self.v._h, debug), "pgv_set_debug")
+
+    def rows(self):
+        v = self.v
+        return v.obs.reshape(sp.N, OBS_BYTES).cpu().numpy(), v.reward.cpu().numpy(), v.done.cpu().numpy()
+
+    def reset(self):
+        self.v.reset()
+        return self.rows()[0]
+
+    def step(self, actions):
+        self.v.step(self.torch.as_tensor(actions))
+        return self.rows()
+
+    def symbolic(self, envs):
+        idx = np.asarray(envs, np.int32)
+        rows, lengths = self.v.state_obs(idx)
+        return rows.cpu().numpy(), lengths.cpu().numpy(), self.v.tile_obs(idx).cpu().numpy()
+
+    def close(self):
+        self.v.close()
+
+
+def _same_frames(got, want, what):
+    if not np.array_equal(got, want):
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        first = np.nonzero(got[bad[0]] != want[bad[0]])[0]
+        raise AssertionError("%s: obs differ in %d envs (first env %d, %d bytes, the first at %d: %d, the oracle's %d)" %
+                             (what, bad.size, bad[0], first.size, first[0], got[bad[0], first[0]], want[bad[0], first[0]]))
+
+
+def _same_rows(eng, a, s, obs, reward, done):
+    oe, re_, de = eng.step(a)
+    what = "%s, step %d" % (eng.name, s)
+    if not np.array_equal(de, done):
+        raise AssertionError("%s: done differs, first env %d" % (what, np.nonzero(de != done)[0][0]))
+    if not np.array_equal(re_.view(np.uint32), reward.view(np.uint32)):
+        e = np.nonzero(re_.view(np.uint32) != reward.view(np.uint32))[0][0]
+        raise AssertionError("%s: reward bits differ, first env %d: %r, the oracle's %r" % (what, e, re_[e], reward[e]))
+    _same_frames(oe, obs, what)
+
+
+def _same_symbolic(eng, dumps, envs, s):
+    """state_obs / tile_obs rows of `envs` against the oracle's dumps after the step (the ones the event counter read)."""
+    rows, lengths, tiles = eng.symbolic(envs)
+    cells = eng.v.state_layout.cells
+    for k, e in enumerate(envs):
+        what = "%s, step %d: %%s of env %d" % (eng.name, s, e)
+        assert_same_dump(rows[k, :lengths[k]], dumps.state(e), what % "state row")
+        assert not rows[k, lengths[k]:].view(np.uint32).any(), what % "the row behind the state"
+        assert_same_dump(tiles[k], dumps.tiles[e, :cells], what % "tile row")
+
+
+@pytest.mark.parametrize("game,mode", sp.PAIRS)
+def test_every_path_matches_the_oracle_under_scripted_play(game, mode):
+    engines = [PathEngine(game, mode, debug) for debug in vp.paths(game)]
+    compared = [0]
+
+    def at_start(ora):
+        for eng in engines:
+            _same_frames(eng.reset(), ora.reset_obs(), "%s, first reset" % eng.name)
+
+    def each_step(s, ora, a, obs, reward, done, counter):
+        for eng in engines:
+            _same_rows(eng, a, s, obs, reward, done)
+            if counter.rare:
+                _same_symbolic(eng, counter.after, counter.rare, s)
+        compared[0] += len(counter.rare)
+
+    try:
+        counts = sp.run_on_oracle(game, mode, each_step, at_start, render=True, threads=_host_threads())
+        print("scripted play: %s mode %d, %d envs, %d steps, %d paths: %r; state and tile rows of %d envs in rare states" %
+              (game, mode, sp.N, sp.STEPS[(game, mode)], len(engines), counts, compared[0]))
+        sp.assert_covers(game, mode, counts)
+        assert compared[0] >= 20, compared[0]
+    finally:
+        for eng in engines:
+            eng.close()
+
+
+@pytest.mark.parametrize("game", sp.GAMES)
+def test_same_step_episodes_of_scripted_play(game):
+    """step_episodes in same-step mode under the agents, against the model: every step's rows, and with them the float32
+    returns (chaser's: a long sum of 0.04s and one 10.04), the lengths and the terminal frames of the episodes that were won."""
+    eng = EpisodeEngine(game, sp.N, SAME_STEP, 0, sp.SAME_STEP_RING)
+    model = EpisodeModel(game, sp.N, SAME_STEP, 0, sp.SAME_STEP_RING, threads=_host_threads())
+    try:
+        assert np.array_equal(eng.reset(), model.first_reset())
+        counts = sp.run_same_step(game, model, eng, check_step)
+        print("scripted play, same-step: %s, %d envs: %r" % (game, sp.N, counts))
+        sp.assert_same_step_covers(game, counts)
+    finally:
+        eng.close(), model.close()
