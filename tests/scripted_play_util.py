@@ -1,7 +1,8 @@
-"""The protocol of tests/test_scripted_play_gpu.py, stated once: scripted agents that play bossfight, chaser and climber to
-win on the CPU oracle.  The GPU half feeds their actions to the HIP engine beside the oracle; tests/test_scripted_play.py runs
-the protocol on the oracle alone and asserts that it reaches the ground random play never does (the boss's six phases and its
-death, cleared boards, levels with every coin collected), so the GPU tests are known not to be vacuous before a GPU is touched.
+"""The protocol of tests/test_scripted_play_gpu.py, stated once: scripted agents that play bossfight, chaser, climber and
+caveflyer to win on the CPU oracle.  The GPU half feeds their actions to the HIP engine beside the oracle;
+tests/test_scripted_play.py runs the protocol on the oracle alone and asserts that it reaches the ground random play never does
+(the boss's six phases and its death, cleared boards, levels with every coin collected, caveflyer's destroyed targets, its full
+bullet ring and more sprites than a wavefront has lanes), so the GPU tests are known not to be vacuous before a GPU is touched.
 
 A policy is a pure function of (the oracle's state dump, the oracle's tile dump, step, env, a seeded numpy Generator) that
 returns an action.  It reads the ORACLE's dumps, never the engine's: the test stays valid if the engine's state rows are wrong,
@@ -18,15 +19,17 @@ import math
 
 import numpy as np
 
-from test_modes import EASY, EXTREME, HARD, TABLE  # noqa: F401
+from test_modes import EASY, EXTREME, HARD, MEMORY, TABLE  # noqa: F401
 
-GAMES = ("bossfight", "chaser", "climber")
-PAIRS = [(g, m) for g in GAMES for m in TABLE[g][1]]  # 7
+GAMES = ("bossfight", "chaser", "climber", "caveflyer")
+PAIRS = [(g, m) for g in GAMES for m in TABLE[g][1]]  # 10
 N, SEED_BASE, POLICY_SEED = 65, 17, 9
 # The fewest steps (rounded up to the next 50) after which the oracle's run holds every floor of assert_covers; the step at
-# which the last floor is reached: bossfight 684 / 732, chaser 1023 / 954 / 1429, climber 140 / 152.
+# which the last floor is reached: bossfight 684 / 732, chaser 1023 / 954 / 1429, climber 140 / 152, caveflyer 251 (the
+# turning turret's full turn) / 284 (the fifth step with a target's 3.0) / 212 (a full turn), steps counted from 0.
 STEPS = {("bossfight", EASY): 700, ("bossfight", HARD): 750, ("chaser", EASY): 1050, ("chaser", HARD): 1000,
-         ("chaser", EXTREME): 1450, ("climber", EASY): 200, ("climber", HARD): 200}
+         ("chaser", EXTREME): 1450, ("climber", EASY): 200, ("climber", HARD): 200,
+         ("caveflyer", EASY): 300, ("caveflyer", HARD): 300, ("caveflyer", MEMORY): 250}
 # chaser's modes that fall back from a cleared board to an episode that ate at least 85 % of its points and orbs
 ATE_85_INSTEAD = {("chaser", EXTREME)}
 RARE_ENVS = 8  # state and tile rows are compared in at most this many envs a step
@@ -40,22 +43,38 @@ WALL = 1                    # chaser's wall tile; climber's walls are every non-
 class Columns:
     """A game's state row by name: f[name] a fixed column, r[name] the offset inside a record."""
 
-    def __init__(self, lay):
+    def __init__(self, lay, unlisted=()):
         self.f = {name: i for i, name in enumerate(lay.fixed_names)}
         self.r = {name: i for i, name in enumerate(lay.record_names)}
         self.fixed, self.record, self.width = lay.fixed, lay.record, lay.width
         self.cells, self.tile_w, self.tile_h = lay.cells, lay.tile_w, lay.tile_h
+        self.unlisted = tuple(unlisted)  # the things the row has no record of: their scalars describe them
         assert len(self.f) == lay.fixed and len(self.r) == lay.record
 
+    def count(self, st):
+        """The records of a row: one a thing, but for the unlisted ones among the row's n_things."""
+        n = int(st[self.f["n_things"]])
+        return n - sum(1 for thing in self.unlisted if thing < n)
+
     def records(self, st):
-        k = int(st[self.f["n_things"]])
+        k = self.count(st)
         return st[self.fixed:self.fixed + k * self.record].reshape(k, self.record)
+
+    def slots(self, prefix, field):
+        """The fixed columns prefix0_field, prefix1_field, … of a row's slot table, in slot order."""
+        out = []
+        while "%s%d_%s" % (prefix, len(out), field) in self.f:
+            out.append(self.f["%s%d_%s" % (prefix, len(out), field)])
+        return out
+
+
+UNLISTED = {"caveflyer": (1,)}  # the ship is entity 1 and has no record (oracle/pgo_caveflyer.cpp dump_state)
 
 
 @functools.lru_cache(maxsize=None)
 def columns(game, mode):
     from engine_util import pglib
-    return Columns(pglib.state_layout(pglib.load(), game, mode))
+    return Columns(pglib.state_layout(pglib.load(), game, mode), UNLISTED.get(game, ()))
 
 
 class Dumps:
@@ -71,6 +90,7 @@ class Dumps:
         for e in range(n):
             self.lengths[e] = got = dump_state(h, e, ctypes.cast(s0 + e * c.width * 4, fp), c.width)
             assert 0 < got <= c.width, (e, got)
+            assert "n_things" not in c.f or got == c.fixed + c.record * c.count(self.states[e]), (e, got)
             if c.cells:
                 assert dump_tiles(h, e, ctypes.cast(t0 + e * c.cells, bp), c.cells) == c.cells
 
@@ -283,7 +303,159 @@ def climber_policy(c, st, tiles, step, env, rng):
     return RIGHT if tx > ax else LEFT
 
 
-POLICIES = {"bossfight": bossfight_policy, "chaser": chaser_policy, "climber": climber_policy}
+# caveflyer (oracle/pgo_caveflyer.cpp agent_update): actions 0-2 turn the ship clockwise and 6-8 counter-clockwise by 0.05 a
+# step, 2 / 5 / 8 thrust along the nose, 0 / 3 / 6 thrust backwards at half strength, 9 fires (and does nothing else)
+SPIN_CW, SPIN_CCW, SPIN_CW_THRUST, THRUST, SPIN_CCW_THRUST, SPIN_CW_BACK, BACK, SPIN_CCW_BACK = 1, 7, 2, 5, 8, 0, 3, 6
+METEOR, TARGET, ENEMY, GOAL = 0, 1, 2, 3  # caveflyer's record kinds
+CRUISE = 0.3          # the speed the navigator asks for: the ship's own limit under thrust is 0.5 cells a step
+SIGHT = 12.0          # a target this far along the nose, in cells, is shot at
+HUNT_WITHIN = 6.0     # the hunter turns onto targets this near, in cells
+HUNT_EVERY, HUNT_FOR = 120, 80  # … for this many steps of every so many: a target behind a meteor is given up in time
+NAVIGATOR, HUNTER, GUNNER, TURRET = 0, 1, 2, 3  # caveflyer's roles, by env % 4
+
+
+@functools.lru_cache(maxsize=256)
+def _cave_fields(tiles, W, H, goal, hazards):
+    """Steps to `goal` from every cell of a caveflyer level (`tiles`: the tile dump's bytes), three times: through cells
+    that are neither a hazard's nor beside one, through cells that are no hazard's, through every cell that is no wall.  A
+    level's fields change only when a target is destroyed, so they are kept by what they were made from."""
+    nb = _neighbours(W, H)
+    wall = [t == WALL for t in tiles]
+    wide = list(wall)
+    narrow = list(wall)
+    for cell in hazards:
+        narrow[cell] = wide[cell] = True
+        for p, _ in nb[cell]:
+            wide[p] = True
+    narrow[goal] = wide[goal] = False
+    return _field(nb, wide, (goal,)), _field(nb, narrow, (goal,)), _field(nb, wall, (goal,))
+
+
+def _turn(angle):
+    """`angle` brought into [-pi, pi)."""
+    return (angle + math.pi) % (2.0 * math.pi) - math.pi
+
+
+def _clear_line(tiles, H, W, ax, ay, bx, by):
+    """No wall on the straight line between two points, looked at every quarter of a cell."""
+    n = max(1, int(4.0 * math.hypot(bx - ax, by - ay)))
+    for k in range(1, n + 1):
+        x, y = ax + (bx - ax) * k / n, ay + (by - ay) * k / n
+        if not (0 <= x < W and 0 <= y < H) or tiles[_cell(x, y, H)] == WALL:
+            return False
+    return True
+
+
+@functools.lru_cache(maxsize=256)
+def _longest_line(tiles, W, H, ax, ay):
+    """The heading, of 64, along which a bullet from (ax, ay) flies farthest before it meets a wall (`tiles`: the dump's bytes)."""
+    best = (-1, 0.0)
+    for k in range(64):
+        heading = k * math.pi / 32.0
+        ux, uy = 0.25 * math.cos(heading), 0.25 * math.sin(heading)
+        n, x, y = 0, ax, ay
+        while 0 <= x < W and 0 <= y < H and tiles[_cell(x, y, H)] != WALL:
+            n, x, y = n + 1, x + ux, y + uy
+        best = max(best, (n, heading))
+    return best[1]
+
+
+def caveflyer_policy(c, st, tiles, step, env, rng):
+    """Four roles by env % 4.  The navigator flies down a breadth-first field from the goal's cell — through cells that are
+    not beside a meteor or a target while such a way exists — at CRUISE cells a step, pushed aside by whatever hazard comes
+    near: it turns the nose (or the tail) onto the change of velocity it wants and thrusts when that is within reach, and
+    fires when a target lies on the line of fire.  The hunter is the navigator, but turns onto a target in sight within
+    HUNT_WITHIN cells first, braking as it turns.  The gunner is the navigator firing every other step.  The turret never
+    thrusts, and comes in three kinds by (env // 4) % 3: one fires and turns one way, step about (the ring fills while
+    agent_rot passes a full turn); one only fires; one turns onto the nearest target in sight, then onto the longest free
+    line there is from where it stands, and fires along it (what fills the ring of 32)."""
+    f, r = c.f, c.r
+    W, H = c.tile_w, c.tile_h
+    rng.random()
+    role, turret = env % 4, (env // 4) % 3
+    if role == TURRET and turret == 0:
+        return SPIN_CCW if step % 2 == 1 else FIRE
+    if role == TURRET and turret == 1:
+        return FIRE
+    ax, ay, rot = float(st[f["agent_x"]]), float(st[f["agent_y"]]), float(st[f["agent_rot"]])
+    vx, vy = float(st[f["agent_vel_x"]]), float(st[f["agent_vel_y"]])
+    nose_x, nose_y = math.cos(rot), math.sin(rot)
+    rec = c.records(st)
+    live = rec[rec[:, r["alive"]] != 0]
+    kind = live[:, r["kind"]]
+    goal, hazards = live[kind == GOAL], live[kind != GOAL]
+    fixed = hazards[hazards[:, r["kind"]] != ENEMY]
+    if not len(goal):
+        return NOOP
+
+    # a target on the line of fire: shoot it
+    targets = hazards[hazards[:, r["kind"]] == TARGET]
+    dx, dy = targets[:, r["x"]] - ax, targets[:, r["y"]] - ay
+    along, off = dx * nose_x + dy * nose_y, dx * nose_y - dy * nose_x
+    for k in np.nonzero((along > 0.5) & (along < SIGHT) & (np.abs(off) < 0.2))[0]:
+        if _clear_line(tiles, H, W, ax, ay, ax + float(dx[k]), ay + float(dy[k])):
+            return FIRE
+    if role == GUNNER and step % 2 == 1:
+        return FIRE
+    if role == TURRET or (role == HUNTER and (step + 13 * env) % HUNT_EVERY < HUNT_FOR):
+        near = np.hypot(dx, dy)
+        for k in np.argsort(near):
+            if near[k] > (SIGHT if role == TURRET else HUNT_WITHIN):
+                break
+            if _clear_line(tiles, H, W, ax, ay, ax + float(dx[k]), ay + float(dy[k])):
+                to = _turn(math.atan2(float(dy[k]), float(dx[k])) - rot)
+                slide = vx * nose_x + vy * nose_y  # the hunter brakes what it can while it turns
+                if role == HUNTER and abs(slide) > 0.02:
+                    return (SPIN_CCW_BACK if to > 0 else SPIN_CW_BACK) if slide > 0 else (SPIN_CCW_THRUST if to > 0 else SPIN_CW_THRUST)
+                return SPIN_CCW if to > 0 else SPIN_CW
+    if role == TURRET:
+        to = _turn(_longest_line(tiles.tobytes(), W, H, ax, ay) - rot)
+        return FIRE if abs(to) < 0.03 else SPIN_CCW if to > 0 else SPIN_CW
+
+    # the velocity it wants: down the field, and away from what is near
+    def cells_of(rows):
+        return (H - 1 - np.floor(rows[:, r["y"]]).astype(int)) + np.floor(rows[:, r["x"]]).astype(int) * H
+    start = _cell(ax, ay, H)
+    fields = _cave_fields(tiles.tobytes(), W, H, int(cells_of(goal)[0]), tuple(sorted(set(cells_of(fixed).tolist()))))
+    field = next((d for d in fields if d[start] < FAR), None)
+    want_x = want_y = 0.0
+    if field is not None and field[start] > 0:
+        nb = _neighbours(W, H)
+        at = start
+        for _ in range(2):
+            at = min((p for p, _ in nb[at]), key=lambda p: field[p]) if field[at] > 0 else at
+        to_x, to_y = at // H + 0.5 - ax, H - 1 - at % H + 0.5 - ay
+        far = math.hypot(to_x, to_y)
+        want_x, want_y = CRUISE * to_x / max(far, 1e-6), CRUISE * to_y / max(far, 1e-6)
+    elif field is not None:
+        want_x, want_y = float(goal[0, r["x"]]) - ax, float(goal[0, r["y"]]) - ay
+    hx, hy = ax - hazards[:, r["x"]], ay - hazards[:, r["y"]]
+    reach = np.where(hazards[:, r["kind"]] == ENEMY, 2.5, 1.4)
+    dist = np.hypot(hx, hy)
+    push = np.where(dist < reach, (reach - dist) / reach, 0.0) / np.maximum(dist, 1e-6)
+    want_x += 0.6 * float((push * hx).sum())
+    want_y += 0.6 * float((push * hy).sum())
+
+    # the change of velocity, and the nose or the tail onto it
+    need_x, need_y = want_x - vx, want_y - vy
+    if math.hypot(need_x, need_y) < 0.03:
+        return NOOP
+    to = _turn(math.atan2(need_y, need_x) - rot)
+    if abs(to) <= 0.5 * math.pi:
+        if abs(to) < 0.03:
+            return THRUST
+        if abs(to) < 0.9:
+            return SPIN_CCW_THRUST if to > 0 else SPIN_CW_THRUST
+        return SPIN_CCW if to > 0 else SPIN_CW
+    to = _turn(to - math.pi)
+    if abs(to) < 0.03:
+        return BACK
+    if abs(to) < 0.9:
+        return SPIN_CCW_BACK if to > 0 else SPIN_CW_BACK
+    return SPIN_CCW if to > 0 else SPIN_CW
+
+
+POLICIES = {"bossfight": bossfight_policy, "chaser": chaser_policy, "climber": climber_policy, "caveflyer": caveflyer_policy}
 
 
 def choose_actions(game, mode, dumps, step, rng):
@@ -293,6 +465,16 @@ def choose_actions(game, mode, dumps, step, rng):
 
 
 # ---------------------------------------------------------------------------------------------------- events and floors
+
+LANES = 64                 # of a wavefront: caveflyer's render wave draws one thing a lane while everything fits
+FULL_TURN = 2.0 * math.pi  # caveflyer: the ship's rotation is never wrapped
+
+
+def cave_draws(c, sprites, shots):
+    """What a caveflyer frame draws behind its tiles, from the row's own numbers: every puff slot, the live sprites, the
+    bullets of the ring that count, the ship."""
+    return len(c.slots("puff", "life")) + sprites + shots + 1
+
 
 class Counter:
     """Events of a run, counted from the oracle's dumps before and after every step and from its reward and done rows.  The
@@ -315,6 +497,21 @@ class Counter:
             self.counts.update(eaten_enemies=0, wins_or_85=0, best_share=0.0)
             self.board = np.zeros(n, int)
             self.ate_85 = np.zeros(n, bool)
+        if game == "caveflyer":
+            self.counts.update(target_steps=0, targets_destroyed=0, double_target_steps=0, goal_with_target_steps=0, most_shots=0, steps_over_8=0,
+                               steps_over_16=0, steps_over_24=0, ring_full_steps=0, overflow_steps=0, most_turn=0.0)
+            self.hit_target = np.zeros(n, bool)
+            self.turns = 0
+
+    def caveflyer_targets(self, dumps):
+        rec = self._records(dumps)
+        return ((rec[:, :, self.c.r["alive"]] != 0) & (rec[:, :, self.c.r["kind"]] == TARGET)).sum(axis=1)
+
+    def caveflyer_overflow(self, dumps):
+        """The envs whose puffs, live sprites, bullets and ship are more than a wavefront has lanes."""
+        c = self.c
+        sprites = (self._records(dumps)[:, :, c.r["alive"]] != 0).sum(axis=1)
+        return cave_draws(c, sprites, dumps.states[:, c.f["s_count"]].astype(int)) > LANES
 
     def _records(self, dumps):
         c = self.c
@@ -328,7 +525,8 @@ class Counter:
         rec = self._records(dumps)
         return ((rec[:, :, self.c.r["alive"]] != 0) & (rec[:, :, self.c.r["kind"]] != EGG)).sum(axis=1)
 
-    def step(self, before, after, reward, done):
+    def step(self, before, after, reward, done, actions=None):
+        """actions: the step's (caveflyer's full ring is counted after a step that fired)."""
         c, k, f, r = self.c, self.counts, self.c.f, self.c.r
         n = done.size
         starts = np.ones(n, bool) if self.first else self.resetting  # the envs whose level begins: in `before` at first, then in `after`
@@ -373,6 +571,31 @@ class Counter:
             back[~playing | (before.states[:, f["eat_timer"]] <= 0)] = 0
             k["eaten_enemies"] += int(back.sum())
             rare = (back > 0) & (after.states[:, f["eat_timer"]] > 0)
+        elif self.game == "caveflyer":
+            shots = after.states[:, f["s_count"]].astype(int)
+            targets = reward - np.where(reward >= 10, 10, 0)  # 3.0 a target, beside the goal's 10.0
+            hit = playing & (targets >= 3)
+            full = playing & (shots == len(c.slots("shot", "frame")))
+            over = playing & self.caveflyer_overflow(after)
+            k["target_steps"] += int(hit.sum())
+            k["double_target_steps"] += int((hit & (reward >= 6) & (reward < 10)).sum())
+            k["goal_with_target_steps"] += int((hit & (reward >= 13)).sum())
+            k["most_shots"] = max(k["most_shots"], int(shots[playing].max()) if playing.any() else 0)
+            for least in (8, 16, 24):
+                k["steps_over_%d" % least] += int((playing & (shots > least)).sum())
+            k["ring_full_steps"] += int((full & (np.asarray(actions) == FIRE)).sum())
+            k["overflow_steps"] += int(over.sum())
+            k["most_turn"] = max(k["most_turn"], float(np.abs(after.states[playing, f["agent_rot"]]).max()) if playing.any() else 0.0)
+            # (a step's reward is its last sub-step's: a target destroyed in one of the first three pays nothing)
+            lost = playing & (self.caveflyer_targets(after) < self.caveflyer_targets(before))
+            k["targets_destroyed"] += int((self.caveflyer_targets(before) - self.caveflyer_targets(after))[lost].sum())
+            # the rarest first: a target destroyed in this step and the step after, a full ring, more draws than lanes, then
+            # the envs with more than two gangs of bullets, another of them first in every step
+            order = [np.nonzero(x)[0] for x in (hit | lost | (self.hit_target & playing), full, over, playing & (shots > 16))]
+            order = np.concatenate(order[:3] + [np.roll(order[3], -self.turns)])
+            rare[order[np.sort(np.unique(order, return_index=True)[1])][:RARE_ENVS]] = True
+            self.hit_target = hit | lost
+            self.turns += 1
         self.rare = [int(e) for e in np.nonzero(rare)[0][:RARE_ENVS]]
         self.after = after
         self.resetting = done != 0
@@ -395,7 +618,7 @@ def run_on_oracle(game, mode, each_step=None, at_start=None, render=False, threa
             a = choose_actions(game, mode, before, s, rng) if actions_of is None else actions_of(s, n)
             obs, reward, done = ora.step(a, threads=threads)
             after = Dumps(ora, c)
-            counter.step(before, after, reward, done)
+            counter.step(before, after, reward, done, a)
             if each_step:
                 each_step(s, ora, a, obs, reward, done, counter)
             before = after
@@ -411,6 +634,10 @@ def floors(game, mode):
         return dict(wins=5, deaths=5, damaged=50, win_and_death_steps=1)
     if game == "climber":
         return dict(wins=5, wins_with_3_coins=1, rewards_11=1, coins=40, deaths=3)
+    if game == "caveflyer":
+        out = dict(wins=5, deaths=3, target_steps=5, steps_over_8=100, steps_over_16=20)
+        out.update(dict(ring_full_steps=1, overflow_steps=20) if mode == MEMORY else dict(most_shots=20))
+        return out
     out = dict(eaten_enemies=20, deaths=3)
     out["wins_or_85" if (game, mode) in ATE_85_INSTEAD else "wins"] = 2 if mode == EASY else 1
     return out
@@ -421,6 +648,8 @@ def assert_covers(game, mode, counts):
         assert counts[name] >= least, "%s mode %d: %s is %d, the floor is %d (%r)" % (game, mode, name, counts[name], least, counts)
     if game == "bossfight":
         assert counts["phases"] >= set(range(6)), "%s mode %d: phases seen %r" % (game, mode, sorted(counts["phases"]))
+    if game == "caveflyer":
+        assert counts["most_turn"] > FULL_TURN, "%s mode %d: the ship turned %.3f at the most" % (game, mode, counts["most_turn"])
 
 
 # test_same_step_episodes_of_scripted_play (tests/test_scripted_play_gpu.py): the agents on the model of tests/episodes_util.py,

@@ -1,7 +1,9 @@
-"""The CPU half of tests/test_scripted_play_gpu.py: the scripted agents of tests/scripted_play_util.py play bossfight, chaser
-and climber on the oracle alone, frames off, and every floor the GPU half leans on is asserted here — wins, the boss's
-phases 0 to 5 and its damaged state, a win and a death in one step, cleared boards and eaten enemies, levels won with three
-coins and more — so the GPU tests are known not to be vacuous before a GPU is touched.  The counts are printed (pytest -s).
+"""The CPU half of tests/test_scripted_play_gpu.py: the scripted agents of tests/scripted_play_util.py play bossfight, chaser,
+climber and caveflyer on the oracle alone, frames off, and every floor the GPU half leans on is asserted here — wins, the
+boss's phases 0 to 5 and its damaged state, a win and a death in one step, cleared boards and eaten enemies, levels won with
+three coins and more, caveflyer's destroyed targets, more than one and two gangs of 8 live bullets, the full ring of 32, more
+draws than the render wave has lanes and a ship turned past a full turn — so the GPU tests are known not to be vacuous before
+a GPU is touched.  The counts are printed (pytest -s).
 
 chaser in extreme mode falls back: no agent here clears a 19 x 19 board with five enemies in a run of a length the suite
 can afford (the agent eats at most one cell in five steps, so its 190 or so points and orbs take 950 steps at the least; the
@@ -16,17 +18,35 @@ import scripted_play_util as sp
 import variant_paths_util as vp
 from episodes_util import SAME_STEP, EpisodeModel
 from oracle_util import OracleVec
-from test_modes import EXTREME
+from test_modes import EASY, EXTREME, HARD, MEMORY
 
 
 def test_the_protocol_is_what_the_file_says():
     assert sp.N >= 65 and sp.N % 64 != 0
-    assert len(sp.PAIRS) == 7 and set(sp.PAIRS) == set(sp.STEPS) and {g for g, _ in sp.PAIRS} == set(sp.POLICIES)
+    assert len(sp.PAIRS) == 10 and set(sp.PAIRS) == set(sp.STEPS) and {g for g, _ in sp.PAIRS} == set(sp.POLICIES)
     assert sp.ATE_85_INSTEAD == {("chaser", EXTREME)}
     for game, mode in sp.PAIRS:
         c = sp.columns(game, mode)
         assert (c.width - c.fixed) % max(1, c.record) == 0 and "agent_x" in c.f
         assert all(least > 0 for least in sp.floors(game, mode).values())
+    for mode in (EASY, HARD, MEMORY):
+        # caveflyer's overflow predicate is spelled from the row's own numbers: 10 puff slots, a ring of 32 bullets, one
+        # record a thing but for the ship, and the 64 lanes the render wave has for them and the ship
+        c = sp.columns("caveflyer", mode)
+        assert len(c.slots("puff", "life")) == 10 and len(c.slots("shot", "frame")) == 32 and sp.LANES == 64
+        assert sp.cave_draws(c, 0, 0) == 11 and sp.cave_draws(c, 37, 17) == 65
+        assert c.unlisted == (1,) and c.fixed == c.f["n_things"] + 1 + 3 * (32 + 10)
+        counter = sp.Counter("caveflyer", mode, 3)
+
+        class Rows:  # three made-up envs: 37 live sprites of 40 things, and 16, 17 and 32 bullets
+            states = np.zeros((3, c.width), np.float32)
+        Rows.states[:, c.f["n_things"]] = 40
+        Rows.states[:, c.f["s_count"]] = (16, 17, 32)
+        Rows.states[:, c.fixed + c.r["alive"]:c.fixed + 37 * c.record:c.record] = 1
+        assert [c.count(row) for row in Rows.states] == [39] * 3 and c.records(Rows.states[0])[:, c.r["alive"]].sum() == 37
+        assert counter.caveflyer_overflow(Rows).tolist() == [False, True, True]
+        Rows.states[0, c.f["n_things"]] = 1  # (the goal alone: the ship is not among the things yet)
+        assert c.count(Rows.states[0]) == 1
 
 
 @pytest.mark.parametrize("game,mode", sp.PAIRS)
@@ -43,7 +63,15 @@ def test_random_play_does_not_cover(game, mode):
     print("random play: %s mode %d, %d envs, %d steps: %r" % (game, mode, sp.N, vp.steps_of(game, mode), counts))
     with pytest.raises(AssertionError):
         sp.assert_covers(game, mode, counts)
-    assert counts["wins"] == 0
+    if game != "caveflyer":
+        assert counts["wins"] == 0
+        return
+    # caveflyer: random play does reach the goal.  What it misses is a second gang of bullets (at most 8 are live), with it
+    # every floor that counts them, a full turn, and in memory mode a frame with more draws than the render wave has lanes
+    floors = sp.floors(game, mode)
+    assert counts["wins"] > 0 and counts["most_shots"] <= 8 and counts["steps_over_8"] == 0 and counts["steps_over_16"] == 0
+    assert counts["most_turn"] < sp.FULL_TURN and counts["ring_full_steps"] == 0
+    assert counts["overflow_steps"] == 0 and (mode == MEMORY) == ("overflow_steps" in floors)
 
 
 @pytest.mark.parametrize("game", sp.GAMES)

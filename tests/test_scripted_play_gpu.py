@@ -2,11 +2,15 @@
 
 Every other lock-step test is driven by random or one-key action streams, and those lose: bossfight never leaves its second
 phase, no chaser board is cleared, climber picks up two or three coins in a run.  Here the scripted agents of
-tests/scripted_play_util.py play bossfight, chaser and climber on the oracle — reading the oracle's dumps, never the
+tests/scripted_play_util.py play bossfight, chaser, climber and caveflyer on the oracle — reading the oracle's dumps, never the
 engine's — and their actions go to the engine under its default path AND every alternate path behind pgv_set_debug, side by
 side: dones, reward bit patterns and every observation byte after every step, and state_obs / tile_obs rows against the
 oracle's dumps wherever an env is in a state random play does not visit (bossfight: the shield down, hp 0, explosions, phase
-4 and later; chaser: an enemy just eaten under an orb's timer; climber: a coin just destroyed, and the step after).  One
+4 and later; chaser: an enemy just eaten under an orb's timer; climber: a coin just destroyed, and the step after;
+caveflyer: a target just destroyed, and the step after, more than 16 live bullets — three and four trips of the bullet loop's
+gangs of 8 — the full ring of 32, and more draws than the render wave has lanes, which is where the complete render path and
+the frames the pre-pass hands back part from the default).  One case holds the batched human-size frames of caveflyer's
+memory mode to the oracle in those last two states.  One
 case a game runs the agents through step_episodes in same-step mode against the model of tests/episodes_util.py: the
 returns, lengths and terminal frames of winning episodes.  The floors of tests/test_scripted_play.py are asserted again on
 the runs made here.
@@ -20,11 +24,14 @@ import pytest
 
 import scripted_play_util as sp
 import variant_paths_util as vp
+from engine_util import EngineVec
 from episodes_util import SAME_STEP, EpisodeModel
-from oracle_util import OBS_BYTES, assert_same_dump
+from oracle_util import OBS_BYTES, assert_same_dump, oracle, oracle_state
 from procgen2_amd import lib as pglib
 from test_episodes_gpu import Engine as EpisodeEngine
 from test_episodes_gpu import check_step
+from test_frames_batch_gpu import _oracle_step, assert_frame, frames_host, oracle_frame
+from test_modes import MEMORY
 from test_parity_gpu import _host_threads
 
 pytestmark = pytest.mark.gpu
@@ -120,10 +127,75 @@ def test_every_path_matches_the_oracle_under_scripted_play(game, mode):
             eng.close()
 
 
+class _Played(Exception):
+    """Ends a run of the protocol before its last step."""
+
+
+def test_human_size_frames_with_a_full_ring():
+    """caveflyer's three renderers share one draw list, and under the cast it is longer than a wavefront with bullets behind
+    the sprites.  Memory mode, one default-path engine beside the oracle: at the first step after which at least four envs
+    draw more than 64 things, and at the first after which one holds all 32 bullets, the batched human-size frames of up to
+    four such envs — 128 x 128, and one 192 x 96 — against pgo_render_frame, byte for byte.  The oracle's frame comes from a
+    single env brought to the same state by the same actions (its state dump is held to the protocol's own first)."""
+    game, mode = "caveflyer", MEMORY
+    L = oracle()
+    c = sp.columns(game, mode)
+    eng = EngineVec(game, sp.N, seed_base=sp.SEED_BASE, mode=mode)
+    history, seen = [], {}
+
+    def single(env):
+        h = L.pgo_make_mode(game.encode(), sp.SEED_BASE + env, 1, mode)
+        L.pgo_reset(h, 0, 0)
+        pending = [False]
+        for a in history:
+            _oracle_step(L, [h], pending, a[env:env + 1])
+        return h
+
+    def frames_of(envs, dumps, what):
+        for k, (w, h) in enumerate(((128, 128), (192, 96))):
+            chosen = envs[:4] if k == 0 else envs[:1]
+            got = frames_host(eng, chosen, w, h)
+            for j, env in enumerate(chosen):
+                handle = single(env)
+                try:
+                    assert_same_dump(oracle_state(handle), dumps.state(env), "%s: the single env %d" % (what, env))
+                    assert_frame(got[j], oracle_frame(L, handle, w, h), "%s: env %d, %dx%d" % (what, env, w, h))
+                finally:
+                    L.pgo_close(handle)
+
+    def at_start(ora):
+        _same_frames(eng.reset(), ora.reset_obs(), "first reset")
+
+    def each_step(s, ora, a, obs, reward, done, counter):
+        history.append(a.copy())
+        oe, re_, de = eng.step(a)
+        assert np.array_equal(de, done) and np.array_equal(re_.view(np.uint32), reward.view(np.uint32)), s
+        _same_frames(oe, obs, "step %d" % s)
+        after = counter.after
+        shots = after.states[:, c.f["s_count"]].astype(int)
+        over, full = np.nonzero(counter.caveflyer_overflow(after))[0], np.nonzero(shots == len(c.slots("shot", "frame")))[0]
+        if "overflow" not in seen and over.size >= 4:
+            seen["overflow"] = (s, over.size, int(shots[over].max()))
+            frames_of(over.tolist(), after, "step %d, more than %d draws" % (s, sp.LANES))
+        if "full ring" not in seen and full.size >= 1:
+            seen["full ring"] = (s, full.size, int(shots[full].max()))
+            frames_of(full.tolist(), after, "step %d, a full ring" % s)
+        if len(seen) == 2:
+            raise _Played
+
+    try:
+        with pytest.raises(_Played):  # both states are met inside the protocol's run: tests/test_scripted_play.py's floors
+            sp.run_on_oracle(game, mode, each_step, at_start, render=True, threads=_host_threads())
+        print("human-size frames: caveflyer mode %d, (step, envs in the state, most bullets): %r" % (mode, seen))
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("game", sp.GAMES)
 def test_same_step_episodes_of_scripted_play(game):
     """step_episodes in same-step mode under the agents, against the model: every step's rows, and with them the float32
-    returns (chaser's: a long sum of 0.04s and one 10.04), the lengths and the terminal frames of the episodes that were won."""
+    returns (chaser's: a long sum of 0.04s and one 10.04; caveflyer's: 3.0s and a 10.0), the lengths and the terminal frames
+    of the episodes that were won."""
     eng = EpisodeEngine(game, sp.N, SAME_STEP, 0, sp.SAME_STEP_RING)
     model = EpisodeModel(game, sp.N, SAME_STEP, 0, sp.SAME_STEP_RING, threads=_host_threads())
     try:
