@@ -532,6 +532,97 @@ PGV_API int32_t pgv_history_gather_aug(pgv_env* env, const int64_t* d_pushes, co
 /* The draws of entry `entry` under `aug` (host, pure, no GPU, env not needed): h_params8[0..7] as `params` rows are. */
 PGV_API int32_t pgv_gather_aug_params(const pgv_gather_aug* aug, int32_t entry, int32_t* h_params8);
 
+/* Transitions on the device: the other half of a rollout beside the frame history — a ring of what every call did (the
+ * action, the reward, how it ended), the n-step transition gather of replay learners and the GAE recurrence of on-policy
+ * ones, each one launch.  The engine is the only party that knows, without a look from the host, the action of a synthetic
+ * step, the terminal reward a same-step reset wipes from the reward row, terminated against truncated, and the step that
+ * only served an auto-reset.  Opt-in per engine, on top of the frame history: an engine that never enables it launches
+ * nothing new and gives the same bytes as before at every entry point.
+ *
+ *   1. Rows.  `action` int32 [T][N], `reward` float32 [T][N], `flags` u8 [T][N], T the history's capacity.  Row q lives in
+ *      slot q % T and describes the call that made push q + 1: the action taken on frame q, what it earned, how it ended —
+ *      obs[t], action[t], reward[t], done[t].  Flag bits: PGV_TR_RECORDED, PGV_TR_TERMINATED, PGV_TR_TRUNCATED, PGV_TR_VOID.
+ *      VOID: the step found the env's `done` row set and only served its auto-reset; its action was ignored and it is no
+ *      step of an episode.  It is the event that sets the history's pending flag "from the `done` row as the step finds it",
+ *      filed by the same flag kernel into a pending byte of the feature's own, which the row's write reads and clears.
+ *   2. Who writes row head - 1, in front of the history push of the same call (head as the call finds it; at head = 0
+ *      there is no row and only the pending bytes are cleared): the single steps, with the caller's action as given — for a
+ *      synthetic step the value pgv_synthetic_action gives for (run_seed, the step's index, env_offset + i), evaluated on the
+ *      device —, the engine's reward row, TERMINATED from the `done` row, VOID from the pending byte, never TRUNCATED; the
+ *      three episode steps, with reward, TERMINATED and TRUNCATED from the episode outputs (the terminal step's values, which a
+ *      same-step reset has wiped from the engine's own rows) and VOID as above (it occurs in next-step mode, and after a load
+ *      of an env whose reset was due).  Every other call that opens a slot — the push by hand, and the drawn sequences —
+ *      writes action 0, reward 0, flags 0 for all envs: not recorded, so a stale row of push q - T is never taken for
+ *      row q.  pgv_reset writes no row: it rewrites the newest frame with began = 1, and that byte is how an interruption
+ *      from outside shows (a reset, a load of envs or of a snapshot, new levels).  A sequence without frames writes no row and
+ *      clears the pending bytes behind its last sub-step.  The measurement calls that step without pushing (pgv_timed_steps,
+ *      pgv_step_times, pgv_step_phases, pgv_step_synthetic_many, pgv_step_episodes_times) write no row and leave the pending
+ *      bytes they set: they are not for the middle of a recorded rollout.
+ *   3. Row q is COMPLETE when pushes q and q + 1 are both held, judged by head as the call is made, and RECORDED is set.  It
+ *      is CUT when it is complete, none of TERMINATED, TRUNCATED, VOID is set and began[q + 1][i] is.  The ring travels neither
+ *      in records nor in snapshots: pgv_snapshot_bytes and pgv_env_record_bytes are what they were.
+ *   4. pgv_transitions_gather, entry (p, i), n = `n` in 1 .. 64.  The entry is VALID when 0 <= i < N and row p is complete
+ *      and not VOID; an invalid entry gives rows of zero bytes and zero scalars, nothing faults for any index values, and an
+ *      entry may appear more than once.  The walk: m = 0, ret = 0, disc = 1; for k = 0 .. n-1: stop in front of row p + k if
+ *      it is not complete or is VOID; else t = disc * r; ret = ret + t; disc = disc * gamma; m = m + 1 — three float32
+ *      roundings, no fused multiply-add, the rule of `ended_return` —; then stop behind the row if it is TERMINATED,
+ *      TRUNCATED or CUT.  Outputs, each device pointer optional (NULL: not written): `action` row p's; `nstep_return` ret;
+ *      `steps` m; `discount` 0 if the last row walked was TERMINATED, else disc; `status` bit 0 = valid, and
+ *      PGV_TR_TERMINATED, PGV_TR_TRUNCATED, PGV_TR_CUT of the last row walked; `obs` exactly the row of
+ *      pgv_history_gather for (p, i, stack, dtype) and `next_obs` the row for (p + m, i, stack, dtype): the same walk over
+ *      `began`, the same value rule, the same zero row.  Under TRUNCATED or CUT the status says that next_obs is not the
+ *      successor state; under a same-step TERMINATED it is the new episode's first frame, and discount = 0 masks it.
+ *      Checked on the host before anything is enqueued: the query and its struct_size, n, stack, dtype, count < 0, obs and
+ *      next_obs 16-byte aligned, the int32 and float outputs 4-byte aligned, NULL index lists with count > 0.  count = 0
+ *      succeeds and does nothing.  One launch; the call changes nothing of the engine.
+ *   5. pgv_transitions_gae over rows first .. first + L - 1, L >= 1, all of which must have head - T <= q and q + 1 < head
+ *      (else refused): values f32 [L+1][N], optional trunc_values f32 [L][N], advantages f32 [L][N], optional returns f32
+ *      [L][N].  Per env, t = L-1 .. 0, carry = 0: a row that is not RECORDED or is VOID gives adv = 0, carry = 0, ret =
+ *      V[t]; else nv = V[t+1] if the row ends nothing, 0 if TERMINATED or CUT, trunc_values[t] (0 without the array) if
+ *      TRUNCATED; a = gamma * nv; b = r + a; delta = b - V[t]; adv = delta + c * carry with c = gamma * lambda computed
+ *      once if the row ends nothing, else delta — the product and the sum separate roundings —; carry = adv; ret = adv +
+ *      V[t].  One launch, nothing allocated, no atomics, no host synchronisation.
+ *   6. pgv_transitions_enable needs pgv_history_enable first and a capacity T >= 2, and may be called once, at any time; the
+ *      rows start as zeros (not recorded).  Each refusal leaves a message and the engine as it was. */
+#define PGV_TR_RECORDED 1
+#define PGV_TR_TERMINATED 2
+#define PGV_TR_TRUNCATED 4
+#define PGV_TR_VOID 8
+#define PGV_TR_CUT 16 /* in a gathered status only */
+typedef struct pgv_transitions_config {
+    uint32_t struct_size;
+    uint32_t reserved; /* 0 */
+} pgv_transitions_config;
+typedef struct pgv_transition_query {
+    uint32_t struct_size;
+    int32_t n;     /* 1 .. 64 */
+    float gamma;
+    int32_t stack; /* K, 1 .. 8 */
+    int32_t dtype; /* PGV_POLICY_* */
+    void* obs;           /* device [count][K*C][64][64] elements, 16-byte aligned, or NULL */
+    void* next_obs;      /* the same */
+    int32_t* action;     /* device [count] or NULL, and so on */
+    float* nstep_return;
+    float* discount;
+    int32_t* steps;
+    uint8_t* status;
+} pgv_transition_query;
+typedef struct pgv_gae {
+    uint32_t struct_size;
+    float gamma, lambda;
+    const float* values;       /* device f32 [L+1][N] */
+    const float* trunc_values; /* device f32 [L][N] or NULL */
+    float* advantages;         /* device f32 [L][N] */
+    float* returns;            /* device f32 [L][N] or NULL */
+} pgv_gae;
+PGV_API int32_t pgv_transitions_enable(pgv_env* env, const pgv_transitions_config* config);
+PGV_API const int32_t* pgv_transitions_action(pgv_env* env); /* device int32 [T][N]; NULL before enable */
+PGV_API const float* pgv_transitions_reward(pgv_env* env);   /* device f32 [T][N]; NULL before enable */
+PGV_API const uint8_t* pgv_transitions_flags(pgv_env* env);  /* device u8 [T][N]; NULL before enable */
+PGV_API int32_t pgv_transitions_gather(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count,
+                                       const pgv_transition_query* query);
+PGV_API int32_t pgv_transitions_gae(pgv_env* env, int64_t first, int32_t length, const pgv_gae* gae);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

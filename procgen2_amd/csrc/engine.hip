@@ -17,6 +17,7 @@
 #include "pg_order.h"
 #include "pg_history.h"
 #include "pg_history_aug.h"
+#include "pg_transitions.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
 #include "pg_sequence.h"
@@ -292,6 +293,11 @@ struct pgv_env {
     int64_t history_head = 0;
     void* d_history = nullptr;
     pg::HistoryBuffers hist{};
+    // transitions (pg_transitions.h; pgv_transitions_enable): off unless asked for, on top of the frame history.  One device
+    // block holds the pending bytes and the three [T][N] arrays; a row's slot follows `history_head`.
+    bool transitions = false;
+    void* d_transitions = nullptr;
+    pg::TransitionBuffers tr{};
     // both features' value tables, dtype by dtype (pg_planes.h): the uploads' source, so they live as long as the env
     uint32_t value_tables[pg::kPolicyTables][256];  // (filled where the env is made)
 
@@ -379,6 +385,7 @@ void pgv_close(pgv_env* e) {
     if (e->d_policy) hipFree(e->d_policy);
     if (e->own_policy_out && e->d_policy_out) hipFree(e->d_policy_out);
     if (e->d_history) hipFree(e->d_history);
+    if (e->d_transitions) hipFree(e->d_transitions);
     if (e->d_host_i32) hipFree(e->d_host_i32);
     if (e->d_host_u8) hipFree(e->d_host_u8);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -582,8 +589,11 @@ static int32_t slab_ready(const char* who, const pgv_env* e) {
 
 // The flag array of every enabled feature — the policy observations' restart flags, then the frame history's pending flags;
 // nullptr for one that is off: the stacks and the ring begin afresh at the same events, told by the same flag kernels.
-static std::array<uint8_t*, 2> flag_arrays(const pgv_env* e) {
-    return {{e->policy ? e->pol.restart : nullptr, e->history ? e->hist.pending : nullptr}};
+// `found_done`: the event is a step that finds the `done` row set — the one event the transitions' pending bytes (VOID) are
+// filed at, by the same kernel; at every other event their place is nullptr.
+static std::array<uint8_t*, 3> flag_arrays(const pgv_env* e, bool found_done = false) {
+    return {{e->policy ? e->pol.restart : nullptr, e->history ? e->hist.pending : nullptr,
+             found_done && e->transitions ? e->tr.pending : nullptr}};
 }
 
 // A push of the policy observations (pg_policy_obs.h) on the env's stream, for the calls that end with one: the obs slab as
@@ -622,9 +632,37 @@ static int32_t history_push(pgv_env* e, bool reset, const uint8_t* d_mask) {
     return 0;
 }
 
-// The pushes that end a call of point 4: the policy observations, then the frame history, whichever is enabled.
-static int32_t end_with_pushes(const char* who, pgv_env* e) {
+// What a call that opens a slot of the frame history says of itself for the transitions' row (pg_transitions.h): nothing
+// (`recorded` 0: the push by hand, a drawn sequence), or the single step it took — its actions (nullptr: synthetic, by
+// run_seed) and, for an episode step, that the episode outputs hold its reward and how it ended.
+struct RowOf {
+    int recorded = 0, episodes = 0;
+    const int32_t* actions = nullptr;
+    uint32_t run_seed = 0;
+};
+// The row head - 1, in front of the history push that makes push `head` (at head = 0 there is none: the pending bytes are
+// cleared all the same).  A step's index is the one step_impl just used.
+static int32_t transition_record(pgv_env* e, const RowOf& row) {
+    pg::TransitionRecord q{};
+    q.n = e->n;
+    q.slot = e->history_head > 0 ? pg::history_slot(e->history_head - 1, e->hist.capacity) : -1;
+    q.recorded = row.recorded;
+    q.run_seed = row.run_seed, q.step_index = e->step_index - 1u, q.env_offset = static_cast<uint32_t>(e->env_offset);
+    q.actions = row.actions;
+    q.reward = row.episodes ? e->ep.reward : e->d_reward;
+    q.terminated = row.episodes ? e->ep.terminated : e->d_done;
+    q.truncated = row.episodes ? e->ep.truncated : nullptr;
+    q.b = e->tr;
+    pg::launch_transition_record(e->stream, q);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// The pushes that end a call of point 4: the policy observations, then — behind the transitions' row of the call — the
+// frame history, whichever is enabled.
+static int32_t end_with_pushes(const char* who, pgv_env* e, const RowOf& row = RowOf{}) {
     if (e->policy && policy_push(who, e, nullptr)) return 1;
+    if (e->transitions && transition_record(e, row)) return 1;
     return e->history ? history_push(e, false, nullptr) : 0;
 }
 
@@ -668,7 +706,7 @@ static int32_t step_impl(pgv_env* e, const int32_t* d_actions, uint32_t run_seed
     // NotReady, say) is not this step's; start clean.
     (void)hipGetLastError();
     // (policy observations, frame history: the done row as this step finds it — in front of the fork, so no reset kernel is at the row yet)
-    for (uint8_t* flags : flag_arrays(e))
+    for (uint8_t* flags : flag_arrays(e, /*found_done=*/true))
         if (flags) pg::launch_policy_flag_done(e->stream, flags, e->n, e->d_done);
     const bool forked = e->reset_stream != nullptr;
     if (forked) {  // fork: the auto-resets of this step go beside its logic and render kernels
@@ -726,7 +764,7 @@ int32_t pgv_step(pgv_env* e, const int32_t* d_actions) {
     if (slab_ready("pgv_step", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (step_impl(e, d_actions, 0)) return 1;
-    return end_with_pushes("pgv_step", e);
+    return end_with_pushes("pgv_step", e, RowOf{1, 0, d_actions, 0});
 }
 
 int32_t pgv_step_synthetic(pgv_env* e, uint32_t run_seed) {
@@ -734,7 +772,7 @@ int32_t pgv_step_synthetic(pgv_env* e, uint32_t run_seed) {
     if (slab_ready("pgv_step_synthetic", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     if (step_impl(e, nullptr, run_seed)) return 1;
-    return end_with_pushes("pgv_step_synthetic", e);
+    return end_with_pushes("pgv_step_synthetic", e, RowOf{1, 0, nullptr, run_seed});
 }
 
 int32_t pgv_step_synthetic_many(pgv_env* const* envs, int32_t count, int32_t steps, uint32_t run_seed) {
@@ -875,7 +913,7 @@ static int32_t step_episodes_impl(const char* who, pgv_env* e, const int32_t* d_
 static int32_t step_episodes_push(const char* who, pgv_env* e, const int32_t* d_actions, uint32_t run_seed) {
     if (slab_ready(who, e)) return 1;
     if (step_episodes_impl(who, e, d_actions, run_seed)) return 1;
-    return end_with_pushes(who, e);
+    return end_with_pushes(who, e, RowOf{1, 1, d_actions, run_seed});
 }
 
 int32_t pgv_step_episodes(pgv_env* e, const int32_t* d_actions) {
@@ -945,7 +983,9 @@ int32_t pgv_step_sequence(pgv_env* e, const pgv_sequence* q) {
         pg::launch_sequence_row(e->stream, row);
         PG_HIP(hipGetLastError());
     }
-    return q->frames == PGV_FRAMES_LAST ? end_with_pushes("pgv_step_sequence", e) : 0;  // once, behind the drawn sub-step
+    if (q->frames == PGV_FRAMES_LAST) return end_with_pushes("pgv_step_sequence", e);  // once, behind the drawn sub-step (its row: not recorded)
+    if (e->transitions) PG_HIP(hipMemsetAsync(e->tr.pending, 0, size_t(e->n), e->stream));  // no slot, no row: what the sub-steps found is nobody's
+    return 0;
 }
 
 int32_t pgv_step_sequence_host(pgv_env* e, const pgv_sequence* q) {
@@ -1126,6 +1166,7 @@ int32_t pgv_history_push(pgv_env* e) {
     if (slab_ready("pgv_history_push", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
     (void)hipGetLastError();
+    if (e->transitions && transition_record(e, RowOf{})) return 1;  // the slot's row: not recorded
     return history_push(e, false, nullptr);
 }
 
@@ -1140,8 +1181,10 @@ static int32_t gather_aug_config(const char* who, const pgv_gather_aug* aug, pg:
 
 // What both gathers check of their arguments, in the order they check it, and the entry list they hand their kernel.  `cfg`
 // (the augmented gather): its config is checked between the count and the tensor.  Leaves q.count = 0 where nothing is asked for.
+// `out_optional` (the transition gather, whose rows are): a NULL tensor passes.
 static int32_t gather_arguments(const char* who, pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack,
-                                int32_t dtype, void* d_out, pg::HistoryGather& q, const pgv_gather_aug* aug = nullptr, pg::AugConfig* cfg = nullptr) {
+                                int32_t dtype, void* d_out, pg::HistoryGather& q, const pgv_gather_aug* aug = nullptr, pg::AugConfig* cfg = nullptr,
+                                bool out_optional = false) {
     if (!e) return fail(std::string(who) + ": env is NULL");
     if (!e->history) return fail(std::string(who) + ": call pgv_history_enable first");
     if (stack < 1 || stack > pg::kPolicyMaxStack) return fail(std::string(who) + ": stack must be in 1 .. 8");
@@ -1150,7 +1193,7 @@ static int32_t gather_arguments(const char* who, pgv_env* e, const int64_t* d_pu
     if (cfg && gather_aug_config(who, aug, *cfg)) return 1;
     if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail(std::string(who) + ": out must be 16-byte aligned");
     if (count == 0) return 0;
-    if (!d_pushes || !d_envs || !d_out) return fail(std::string(who) + ": pushes, envs or out is NULL");
+    if (!d_pushes || !d_envs || (!d_out && !out_optional)) return fail(std::string(who) + ": pushes, envs or out is NULL");
     PG_HIP(hipSetDevice(e->device));
     (void)hipGetLastError();
     q.n = e->n, q.stack = stack, q.count = count, q.head = e->history_head;
@@ -1184,6 +1227,93 @@ int32_t pgv_history_gather_aug(pgv_env* e, const int64_t* d_pushes, const int32_
     if (q.g.count == 0) return 0;
     q.params = aug->params;
     pg::launch_history_gather_aug(e->stream, q, pg::policy_element_bytes(dtype));
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Transitions (pg_transitions.h)
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_transitions_enable(pgv_env* e, const pgv_transitions_config* cfg) {
+    if (!e) return fail("pgv_transitions_enable: env is NULL");
+    if (!cfg || cfg->struct_size < sizeof(pgv_transitions_config)) return fail("pgv_transitions_enable: config is NULL or struct_size too small");
+    if (cfg->reserved != 0) return fail("pgv_transitions_enable: reserved must be 0");
+    if (e->transitions) return fail("pgv_transitions_enable: transitions are enabled already (once per env)");
+    if (!e->history) return fail("pgv_transitions_enable: call pgv_history_enable first");
+    if (e->hist.capacity < 2) return fail("pgv_transitions_enable: the frame history's capacity must be >= 2 (a row needs two held pushes)");
+    PG_HIP(hipSetDevice(e->device));
+    pg::TransitionBuffers b{};
+    b.capacity = e->hist.capacity;
+    const size_t bytes = pg::Carve::size(pg::list_transitions, e->n, b);
+    void* mem = nullptr;
+    hipError_t err = hipMalloc(&mem, bytes);
+    if (err == hipSuccess) err = hipMemsetAsync(mem, 0, bytes, e->stream);  // no row recorded, no reset found
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        if (mem) (void)hipFree(mem);
+        return fail(std::string("pgv_transitions_enable: ") + hipGetErrorString(err));
+    }
+    pg::Carve::bind(pg::list_transitions, mem, b, e->n);
+    e->d_transitions = mem;
+    e->tr = b;
+    e->transitions = true;
+    return 0;
+}
+
+const int32_t* pgv_transitions_action(pgv_env* e) { return e && e->transitions ? e->tr.action : nullptr; }
+const float* pgv_transitions_reward(pgv_env* e) { return e && e->transitions ? e->tr.reward : nullptr; }
+const uint8_t* pgv_transitions_flags(pgv_env* e) { return e && e->transitions ? e->tr.flags : nullptr; }
+
+static pg::TransitionRing transition_ring(const pgv_env* e) { return {e->n, e->hist.capacity, e->history_head, e->hist.began, e->tr}; }
+
+int32_t pgv_transitions_gather(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, const pgv_transition_query* query) {
+    const char* who = "pgv_transitions_gather";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!e->transitions) return fail(std::string(who) + ": call pgv_transitions_enable first");
+    if (!query || query->struct_size < sizeof(pgv_transition_query)) return fail(std::string(who) + ": query is NULL or struct_size too small");
+    if (query->n < 1 || query->n > pg::kTrMaxSteps) return fail(std::string(who) + ": n must be in 1 .. 64");
+    if (reinterpret_cast<uintptr_t>(query->next_obs) & 15u) return fail(std::string(who) + ": next_obs must be 16-byte aligned");
+    for (const void* p : {static_cast<const void*>(query->action), static_cast<const void*>(query->nstep_return),
+                          static_cast<const void*>(query->discount), static_cast<const void*>(query->steps)})
+        if (reinterpret_cast<uintptr_t>(p) & 3u) return fail(std::string(who) + ": action, nstep_return, discount and steps must be 4-byte aligned");
+    pg::TransitionGather q{};
+    // (what pgv_history_gather checks, the way it checks it)
+    if (gather_arguments(who, e, d_pushes, d_envs, count, query->stack, query->dtype, query->obs, q.g, nullptr, nullptr, /*out_optional=*/true)) return 1;
+    if (q.g.count == 0) return 0;
+    q.g.out = nullptr;  // (the two rows below)
+    q.steps = query->n;
+    q.gamma = query->gamma;
+    q.ring = transition_ring(e);
+    q.obs = static_cast<uint8_t*>(query->obs), q.next_obs = static_cast<uint8_t*>(query->next_obs);
+    q.action = query->action, q.nstep_return = query->nstep_return, q.discount = query->discount, q.step_count = query->steps, q.status = query->status;
+    pg::launch_transition_gather(e->stream, q, pg::policy_element_bytes(query->dtype));
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_transitions_gae(pgv_env* e, int64_t first, int32_t length, const pgv_gae* gae) {
+    const char* who = "pgv_transitions_gae";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!e->transitions) return fail(std::string(who) + ": call pgv_transitions_enable first");
+    if (!gae || gae->struct_size < sizeof(pgv_gae)) return fail(std::string(who) + ": gae is NULL or struct_size too small");
+    if (length < 1) return fail(std::string(who) + ": length must be >= 1");
+    const int64_t head = e->history_head;
+    // rows first .. first + length - 1, each with head - T <= q and q + 1 < head (length < T then, and nothing overflows)
+    if (first < 0 || first < head - e->hist.capacity || first >= head || int64_t(length) > head - 1 - first)
+        return fail(std::string(who) + ": rows " + std::to_string(first) + " .. + " + std::to_string(length) + " are not all held with their successors (head " +
+                    std::to_string(head) + ", capacity " + std::to_string(e->hist.capacity) + ")");
+    if (!gae->values || !gae->advantages) return fail(std::string(who) + ": values or advantages is NULL");
+    for (const void* p : {static_cast<const void*>(gae->values), static_cast<const void*>(gae->trunc_values),
+                          static_cast<const void*>(gae->advantages), static_cast<const void*>(gae->returns)})
+        if (reinterpret_cast<uintptr_t>(p) & 3u) return fail(std::string(who) + ": values, trunc_values, advantages and returns must be 4-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::TransitionGae q{};
+    q.n = e->n, q.length = length, q.first = first;
+    q.gamma = gae->gamma, q.lambda = gae->lambda;
+    q.values = gae->values, q.trunc_values = gae->trunc_values, q.advantages = gae->advantages, q.returns = gae->returns;
+    q.ring = transition_ring(e);
+    pg::launch_transition_gae(e->stream, q);
     PG_HIP(hipGetLastError());
     return 0;
 }

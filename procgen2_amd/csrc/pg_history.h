@@ -14,7 +14,7 @@
 // before anything is read or written.  The form pgv_reset uses (`reset` set) writes into the newest slot and files began = 1.
 //
 // The gather kernel: one workgroup of 256 lanes per entry, begun by gather_entry and fed by history_fetch (both shared with
-// pg_history_aug.h).  Per frame and plane a lane looks its 16 stored bytes up: 16·ES bytes, which at ES = 2 and 4 the wave
+// pg_history_aug.h); its body behind the head is gather_row, which pg_transitions.h calls for its two rows as well.  Per frame and plane a lane looks its 16 stored bytes up: 16·ES bytes, which at ES = 2 and 4 the wave
 // exchanges (measured against each lane storing its own units as they lie: -7 % at 2 bytes, -36 % at 4, docs/OPTLOG.md).
 // Where the walk repeats a frame the values already in registers are stored again.  An entry that is not held, or whose env
 // is outside the batch, gets a row of zero bytes.
@@ -114,19 +114,21 @@ __global__ void __launch_bounds__(kHistoryBlock) history_push_kernel(HistoryPush
 
 // The head of a gather kernel: all lanes copy the dtype's 256 table words into `table` while lane 0 validates the entry and,
 // where it is valid, walks back from its push (history_walk: at most K-1 dependent byte loads of began) into `frame`; one
-// barrier shares both (all three in LDS).  Returns the verdict (workgroup-uniform) and the entry's `env`.
-PG_D bool gather_entry(const HistoryGather& q, size_t entry, int tid, uint32_t* table, int64_t* frame, int* valid, int& env) {
+// barrier shares both (all three in LDS).  Returns the verdict (workgroup-uniform).  gather_entry_at: the entry's push and env
+// are the caller's (pg_transitions.h: the push behind an n-step walk); gather_entry reads them from the lists, and hands back `env`.
+PG_D bool gather_entry_at(const HistoryGather& q, int64_t push, int env, int tid, uint32_t* table, int64_t* frame, int* valid) {
     table[tid] = q.table[tid];
     if (tid == 0) {
-        const int64_t push = q.pushes[entry];
-        env = q.envs[entry];
         const int ok = env >= 0 && env < q.n && history_held(push, q.head, q.b.capacity);
         *valid = ok;
         if (ok) history_walk(q.b.began, q.n, q.b.capacity, q.head, push, env, q.stack, frame);
     }
     __syncthreads();  // the table is whole; the walk is shared
-    env = q.envs[entry];
     return *valid != 0;
+}
+PG_D bool gather_entry(const HistoryGather& q, size_t entry, int tid, uint32_t* table, int64_t* frame, int* valid, int& env) {
+    env = q.envs[entry];
+    return gather_entry_at(q, q.pushes[entry], env, tid, table, frame, valid);
 }
 // Lane tid's 16 stored bytes of each of the C planes of env's frame f (a held push).
 template <int C>
@@ -136,18 +138,13 @@ PG_D void history_fetch(const HistoryGather& q, int64_t f, int env, int tid, Pol
     for (int p = 0; p < C; p++) in[p] = *reinterpret_cast<const PolicyVec16*>(from + size_t(p) * kPolicyPlane);
 }
 
+// The body of a gather kernel behind its head: the row of an entry whose verdict is `ok` (workgroup-uniform) and whose walk
+// lies in `frame`, at `out` — the K frames through the value table, or the row of zero bytes.
 template <int ES, int C>  // element bytes; planes
-__global__ void __launch_bounds__(kHistoryBlock) history_gather_kernel(HistoryGather q) {
-    __shared__ uint32_t table[256];
-    __shared__ int64_t frame[kPolicyMaxStack];
-    __shared__ int valid;
-    __shared__ PolicyVec16 exchange[ES > 1 ? kHistoryBlock * ES : 1];  // a wave's units of one plane, in the wave's own quarter
-    const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
-    const size_t entry = blockIdx.x;
+PG_D void gather_row(const HistoryGather& q, bool ok, int env, int tid, const uint32_t* table, const int64_t* frame, PolicyVec16* exchange,
+                     uint8_t* out) {
+    const int lane = tid & 63, wave = tid >> 6;
     const int K = q.stack;
-    int env = 0;
-    const bool ok = gather_entry(q, entry, tid, table, frame, &valid, env);
-    uint8_t* const out = q.out + entry * policy_bytes_per_env(K, C, ES);
     const size_t channel = size_t(kPolicyPlane) * ES;
     if (!ok) {  // (workgroup-uniform)
         zero_row<PolicyVec16>(out, K * C, channel, kHistoryBlock * ES, tid);
@@ -179,6 +176,19 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_kernel(HistoryGa
 #pragma unroll
             for (int k = 0; k < ES; k++) *reinterpret_cast<PolicyVec16*>(to + p * channel + unit[k]) = held[p * ES + k];
     }
+}
+
+template <int ES, int C>
+__global__ void __launch_bounds__(kHistoryBlock) history_gather_kernel(HistoryGather q) {
+    __shared__ uint32_t table[256];
+    __shared__ int64_t frame[kPolicyMaxStack];
+    __shared__ int valid;
+    __shared__ PolicyVec16 exchange[ES > 1 ? kHistoryBlock * ES : 1];  // a wave's units of one plane, in the wave's own quarter
+    const int tid = static_cast<int>(threadIdx.x);
+    const size_t entry = blockIdx.x;
+    int env = 0;
+    const bool ok = gather_entry(q, entry, tid, table, frame, &valid, env);
+    gather_row<ES, C>(q, ok, env, tid, table, frame, exchange, q.out + entry * policy_bytes_per_env(q.stack, C, ES));
 }
 
 inline void launch_history_push(hipStream_t st, const HistoryPush& q) {

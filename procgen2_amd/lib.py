@@ -74,6 +74,46 @@ def history_enable(lib, h, capacity, gray=False, frames=None):
     check(lib, lib.pgv_history_enable(h, ctypes.byref(cfg)), "pgv_history_enable")
 
 
+class TransitionsConfig(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_transitions_config`."""
+    _fields_ = [("struct_size", c_uint32), ("reserved", c_uint32)]
+
+
+class TransitionQuery(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_transition_query` (device pointers, each optional)."""
+    _fields_ = [("struct_size", c_uint32), ("n", c_int32), ("gamma", c_float), ("stack", c_int32), ("dtype", c_int32),
+                ("obs", c_void_p), ("next_obs", c_void_p), ("action", c_void_p), ("nstep_return", c_void_p), ("discount", c_void_p),
+                ("steps", c_void_p), ("status", c_void_p)]
+
+
+class Gae(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_gae` (`lam`: the header's `lambda`)."""
+    _fields_ = [("struct_size", c_uint32), ("gamma", c_float), ("lam", c_float), ("values", c_void_p), ("trunc_values", c_void_p),
+                ("advantages", c_void_p), ("returns", c_void_p)]
+
+
+# include/procgen2_vec.h PGV_TR_*
+TR_RECORDED, TR_TERMINATED, TR_TRUNCATED, TR_VOID, TR_CUT = 1, 2, 4, 8, 16
+
+
+def transitions_enable(lib, h):
+    """pgv_transitions_enable (after history_enable)."""
+    cfg = TransitionsConfig(ctypes.sizeof(TransitionsConfig), 0)
+    check(lib, lib.pgv_transitions_enable(h, ctypes.byref(cfg)), "pgv_transitions_enable")
+
+
+def transition_query(n, gamma, stack, dtype, obs=None, next_obs=None, action=None, nstep_return=None, discount=None, steps=None, status=None):
+    """A filled-in TransitionQuery.  dtype: a name of POLICY_DTYPES or the number; the outputs: device pointers (integers) or None."""
+    number = POLICY_DTYPES[dtype][0] if dtype in POLICY_DTYPES else int(dtype)
+    return TransitionQuery(ctypes.sizeof(TransitionQuery), int(n), float(gamma), int(stack), number, obs, next_obs, action, nstep_return,
+                           discount, steps, status)
+
+
+def gae(gamma, lam, values, advantages, trunc_values=None, returns=None):
+    """A filled-in Gae of device pointers (integers)."""
+    return Gae(ctypes.sizeof(Gae), float(gamma), float(lam), values, trunc_values, advantages, returns)
+
+
 class StateLayoutStruct(ctypes.Structure):
     """include/procgen2_vec.h `pgv_state_layout`."""
     _fields_ = [("struct_size", c_uint32), ("width", c_int32), ("fixed", c_int32), ("record", c_int32), ("max_records", c_int32),
@@ -331,6 +371,12 @@ def load(path=None):
         "pgv_history_gather": (c_int32, [P, P, P, c_int32, c_int32, c_int32, P]),
         "pgv_history_gather_aug": (c_int32, [P, P, P, c_int32, c_int32, c_int32, POINTER(GatherAug), P]),
         "pgv_gather_aug_params": (c_int32, [POINTER(GatherAug), c_int32, POINTER(c_int32)]),
+        "pgv_transitions_enable": (c_int32, [P, POINTER(TransitionsConfig)]),
+        "pgv_transitions_action": (P, [P]),
+        "pgv_transitions_reward": (P, [P]),
+        "pgv_transitions_flags": (P, [P]),
+        "pgv_transitions_gather": (c_int32, [P, P, P, c_int32, POINTER(TransitionQuery)]),
+        "pgv_transitions_gae": (c_int32, [P, c_int64, c_int32, POINTER(Gae)]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -380,6 +426,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_policy_obs_enable", "pgv_policy_obs", "pgv_policy_obs_bytes_per_env", "pgv_policy_obs_restart", "pgv_policy_obs_push", "pgv_policy_obs_push_host",
     "pgv_history_enable", "pgv_history_frames", "pgv_history_began", "pgv_history_pending", "pgv_history_head", "pgv_history_capacity", "pgv_history_push",
     "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params",
+    "pgv_transitions_enable", "pgv_transitions_action", "pgv_transitions_reward", "pgv_transitions_flags", "pgv_transitions_gather", "pgv_transitions_gae",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",
     "pgv_tile_paths_rows", "pgv_tile_paths_rows_host", "pgv_path_layout_of",

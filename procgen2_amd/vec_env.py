@@ -32,8 +32,14 @@ def shard_range(total_envs, world_size, rank):
 class ProcgenVecEnv:
     def __init__(self, game, num_envs, device=0, seed_base=1, env_offset=0, lib_path=None, num_levels=0,
                  start_level=0, distribution_mode=None, game_flags=0, out=None, autoreset_mode=None, max_episode_steps=0,
-                 final_obs_capacity=0, policy_obs=None, history=None):
-        """history = None | dict(capacity=T, gray=False): frame history on the device (include/procgen2_vec.h
+                 final_obs_capacity=0, policy_obs=None, history=None, transitions=False):
+        """transitions = False | True (needs history=): the record ring beside the frame history (include/procgen2_vec.h
+        pgv_transitions_enable) — `transitions`, a TransitionTensors: zero-copy [T, N] views `action` int32, `reward` float32,
+        `flags` u8 (pglib.TR_* bits); row q describes the call that made push q + 1.  transition_gather() for n-step
+        transitions of any (push, env) pairs, transition_gae() for advantages over a stretch of the ring.  False changes nothing
+        at all.
+
+        history = None | dict(capacity=T, gray=False): frame history on the device (include/procgen2_vec.h
         pgv_history_enable) — `history`, a HistoryTensors: `frames` u8 [T, N, C, 64, 64] (C = 1 gray, 3 RGB), one frame per env
         and push in slot push % T, `began` u8 [T, N], `pending` u8 [N], `head` (the pushes so far) and `capacity`; every step,
         step_episodes and drawn sequence pushes a slot, reset() rewrites the newest; history_push() by hand and
@@ -62,6 +68,12 @@ class ProcgenVecEnv:
         self.env_offset = int(env_offset)
         policy = _policy_obs_config(policy_obs)  # (ValueError before anything is made)
         ring = _history_config(history)
+        if transitions not in (False, True):
+            raise ValueError("transitions must be True or False")
+        if transitions and ring is None:
+            raise ValueError("transitions=True needs history=dict(capacity=T, ...) with T >= 2")
+        if transitions and ring[0] < 2:
+            raise ValueError("transitions=True needs a history capacity >= 2")
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         # The engine gets a stream of its own (a torch stream, so torch can order against it): torch's default stream
@@ -149,6 +161,16 @@ class ProcgenVecEnv:
                 pglib.history_enable(self.L, h, capacity, gray, c_void_p(frames.data_ptr()))
                 self._after()
                 self.history = HistoryTensors(self, frames)
+            except Exception:
+                self.close()
+                raise
+        self.transitions = None
+        if transitions:
+            try:
+                self._before()
+                pglib.transitions_enable(self.L, h)
+                self._after()
+                self.transitions = TransitionTensors(self)
             except Exception:
                 self.close()
                 raise
@@ -379,6 +401,76 @@ class ProcgenVecEnv:
             self._after()
             self._keep_gather = (p, i, out, params)
         return (out, params) if return_params else out
+
+    def _needs_transitions(self, who):
+        if self.transitions is None:
+            raise pglib.EngineError(who + " needs an env made with history=dict(capacity=T, ...), transitions=True")
+
+    def transition_gather(self, pushes, envs, n=3, gamma=0.99, stack=4, dtype="float16", frames=True):
+        """The n-step transitions of the B pairs (pushes[b], envs[b]) in one launch (pgv_transitions_gather): a Transition of
+        obs and next_obs [B, K*C, 64, 64] of `dtype` — history_gather's rows for push p and for push p + steps —, action int32
+        [B], nstep_return and discount float32 [B] (discount 0 behind a terminal step, else gamma ** steps, rounded per step),
+        steps int32 [B] (the rows actually folded: fewer than n at an episode's end or the ring's), status u8 [B] (bit 0 valid,
+        pglib.TR_TERMINATED / TR_TRUNCATED / TR_CUT of the last row folded).  A pair whose row is not held with its
+        successor, not recorded or a reset's own step, or whose env is outside the batch, gives zeros.  frames=False: the
+        scalars alone (obs and next_obs None).  Same stream hand-shake as step(), no host synchronisation."""
+        self._needs_transitions("transition_gather")
+        if dtype not in pglib.POLICY_DTYPES:
+            raise ValueError("transition_gather: dtype must be one of %s" % ", ".join(pglib.POLICY_DTYPES))
+        if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= 8:
+            raise ValueError("transition_gather: stack must be an integer in 1 .. 8")
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 64:
+            raise ValueError("transition_gather: n must be an integer in 1 .. 64")
+        p = torch.as_tensor(pushes, device=self.device).to(torch.int64).reshape(-1).contiguous()
+        i = torch.as_tensor(envs, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        if p.numel() != i.numel():
+            raise ValueError("transition_gather: %d pushes but %d envs" % (p.numel(), i.numel()))
+        B = p.numel()
+        shape = (B, stack * self.history.frames.shape[2], 64, 64)
+        obs = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device) if frames else None
+        next_obs = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device) if frames else None
+        action = torch.empty(B, dtype=torch.int32, device=self.device)
+        ret = torch.empty(B, dtype=torch.float32, device=self.device)
+        discount = torch.empty(B, dtype=torch.float32, device=self.device)
+        steps = torch.empty(B, dtype=torch.int32, device=self.device)
+        status = torch.empty(B, dtype=torch.uint8, device=self.device)
+        if B:
+            q = pglib.transition_query(n, gamma, stack, dtype, obs.data_ptr() if frames else None, next_obs.data_ptr() if frames else None,
+                                       action.data_ptr(), ret.data_ptr(), discount.data_ptr(), steps.data_ptr(), status.data_ptr())
+            self._before()
+            pglib.check(self.L, self.L.pgv_transitions_gather(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), B, ctypes.byref(q)),
+                        "pgv_transitions_gather")
+            self._after()
+            self._keep_transitions = (p, i, obs, next_obs, action, ret, discount, steps, status)
+        return Transition(obs, next_obs, action, ret, discount, steps, status)
+
+    def transition_gae(self, first, steps, values, gamma=0.999, lam=0.95, trunc_values=None):
+        """(advantages, returns), float32 [steps, N], of the GAE recurrence over rows first .. first + steps - 1 of the record
+        ring in one launch (pgv_transitions_gae): values float32 [steps + 1, N] (the last row bootstraps), trunc_values
+        float32 [steps, N] or None: the value of the state a truncated step ended in (None: 0).  Every row must be held with
+        its successor: head - T <= q and q + 1 < head.  Terminal, truncated and cut rows end the recurrence; rows that are
+        not recorded, and a reset's own step, give advantage 0 and return V."""
+        self._needs_transitions("transition_gae")
+        steps = int(steps)
+        n = self.num_envs
+
+        def rows(x, count, name):
+            x = torch.as_tensor(x, device=self.device).to(torch.float32).contiguous()
+            if tuple(x.shape) != (count, n):
+                raise ValueError("transition_gae: %s must have shape (%d, %d)" % (name, count, n))
+            return x
+        if steps < 1:
+            raise ValueError("transition_gae: steps must be >= 1")
+        v = rows(values, steps + 1, "values")
+        tv = None if trunc_values is None else rows(trunc_values, steps, "trunc_values")
+        adv = torch.empty((steps, n), dtype=torch.float32, device=self.device)
+        ret = torch.empty((steps, n), dtype=torch.float32, device=self.device)
+        g = pglib.gae(gamma, lam, v.data_ptr(), adv.data_ptr(), None if tv is None else tv.data_ptr(), ret.data_ptr())
+        self._before()
+        pglib.check(self.L, self.L.pgv_transitions_gae(self._h, int(first), steps, ctypes.byref(g)), "pgv_transitions_gae")
+        self._after()
+        self._keep_gae = (v, tv, adv, ret)
+        return adv, ret
 
     def _before(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -820,6 +912,21 @@ class HistoryTensors:
     def head(self):
         """The pushes so far: push p is held while head - capacity <= p < head."""
         return int(self._env.L.pgv_history_head(self._env._h))
+
+
+class TransitionTensors:
+    """The record ring of a ProcgenVecEnv made with transitions=True: zero-copy [T, N] views; row q lives in slot q % T."""
+
+    def __init__(self, env):
+        L, h, n = env.L, env._h, env.num_envs
+        T = int(L.pgv_history_capacity(h))
+        self.capacity = T
+        self.action = _device_view(L.pgv_transitions_action(h), T * n, "<i4", env.device).view(T, n)
+        self.reward = _device_view(L.pgv_transitions_reward(h), T * n, "<f4", env.device).view(T, n)
+        self.flags = _device_view(L.pgv_transitions_flags(h), T * n, "|u1", env.device).view(T, n)
+
+
+Transition = collections.namedtuple("Transition", "obs next_obs action nstep_return discount steps status")
 
 
 def _augment_config(augment):
