@@ -1,8 +1,10 @@
-"""The protocol of tests/test_scripted_play_gpu.py, stated once: scripted agents that play bossfight, chaser, climber and
-caveflyer to win on the CPU oracle.  The GPU half feeds their actions to the HIP engine beside the oracle;
-tests/test_scripted_play.py runs the protocol on the oracle alone and asserts that it reaches the ground random play never does
-(the boss's six phases and its death, cleared boards, levels with every coin collected, caveflyer's destroyed targets, its full
-bullet ring and more sprites than a wavefront has lanes), so the GPU tests are known not to be vacuous before a GPU is touched.
+"""The protocol of tests/test_scripted_play_gpu.py, stated once: scripted agents that play all seven games — bossfight, chaser,
+climber, caveflyer, coinrun, jumper and maze — to win on the CPU oracle.  The GPU half feeds their actions to the HIP engine
+beside the oracle; tests/test_scripted_play.py runs the protocol on the oracle alone and asserts that it reaches the ground
+random play never does (the boss's six phases and its death, cleared boards, levels with every coin collected, caveflyer's
+destroyed targets, its full bullet ring and more sprites than a wavefront has lanes, the second half of coinrun's levels with
+its lava, crates dropped through and levels deep in an env's chain, jumper's memory world far from the start), so the GPU
+tests are known not to be vacuous before a GPU is touched.
 
 A policy is a pure function of (the oracle's state dump, the oracle's tile dump, step, env, a seeded numpy Generator) that
 returns an action.  It reads the ORACLE's dumps, never the engine's: the test stays valid if the engine's state rows are wrong,
@@ -21,15 +23,19 @@ import numpy as np
 
 from test_modes import EASY, EXTREME, HARD, MEMORY, TABLE  # noqa: F401
 
-GAMES = ("bossfight", "chaser", "climber", "caveflyer")
-PAIRS = [(g, m) for g in GAMES for m in TABLE[g][1]]  # 10
+GAMES = ("bossfight", "chaser", "climber", "caveflyer", "coinrun", "jumper", "maze")
+PAIRS = [(g, m) for g in GAMES for m in sorted(TABLE[g][1])]  # 18
 N, SEED_BASE, POLICY_SEED = 65, 17, 9
 # The fewest steps (rounded up to the next 50) after which the oracle's run holds every floor of assert_covers; the step at
 # which the last floor is reached: bossfight 684 / 732, chaser 1023 / 954 / 1429, climber 140 / 152, caveflyer 251 (the
-# turning turret's full turn) / 284 (the fifth step with a target's 3.0) / 212 (a full turn), steps counted from 0.
+# turning turret's full turn) / 284 (the fifth step with a target's 3.0) / 212 (a full turn), coinrun 250 / 250 (an env's
+# eighth ended episode), jumper 227 / 214 / 203 (5 000 env-steps with no jump left), maze 53 / 77 / 105 (the twentieth first
+# step of a sixth or later level), steps counted from 0.
 STEPS = {("bossfight", EASY): 700, ("bossfight", HARD): 750, ("chaser", EASY): 1050, ("chaser", HARD): 1000,
          ("chaser", EXTREME): 1450, ("climber", EASY): 200, ("climber", HARD): 200,
-         ("caveflyer", EASY): 300, ("caveflyer", HARD): 300, ("caveflyer", MEMORY): 250}
+         ("caveflyer", EASY): 300, ("caveflyer", HARD): 300, ("caveflyer", MEMORY): 250,
+         ("coinrun", EASY): 300, ("coinrun", HARD): 300, ("jumper", EASY): 250, ("jumper", HARD): 250, ("jumper", MEMORY): 250,
+         ("maze", EASY): 100, ("maze", HARD): 100, ("maze", MEMORY): 150}
 # chaser's modes that fall back from a cleared board to an episode that ate at least 85 % of its points and orbs
 ATE_85_INSTEAD = {("chaser", EXTREME)}
 RARE_ENVS = 8  # state and tile rows are compared in at most this many envs a step
@@ -53,7 +59,7 @@ class Columns:
 
     def count(self, st):
         """The records of a row: one a thing, but for the unlisted ones among the row's n_things."""
-        n = int(st[self.f["n_things"]])
+        n = int(st[self.f["n_things" if "n_things" in self.f else "n_spikes"]])  # (jumper's records are its spikes)
         return n - sum(1 for thing in self.unlisted if thing < n)
 
     def records(self, st):
@@ -455,7 +461,189 @@ def caveflyer_policy(c, st, tiles, step, env, rng):
     return SPIN_CCW if to > 0 else SPIN_CW
 
 
-POLICIES = {"bossfight": bossfight_policy, "chaser": chaser_policy, "climber": climber_policy, "caveflyer": caveflyer_policy}
+# coinrun (oracle/pgo_coinrun.cpp tick_agent): 6-8 move right and 0-2 left, 2 / 5 / 8 jump when grounded, 0 / 3 / 6 ("down") let
+# the agent through the crate it stands on.  World y grows downward; agent_y is the feet, the body the cell above them.
+CR_WALLS, CR_LAVA, CR_CRATE, CR_STANDS = (1, 2), (3, 4), 5, (1, 2, 5)
+CR_DOWN, CR_JUMP = 3, 5
+RUNNER, RUNNER_TOO, CRATE_WALKER, HOPPER = 0, 1, 2, 3  # coinrun's roles, by env % 4
+CR_JUMP_SPEED, CR_GRAVITY, CR_SPEED, CR_AIR_MIX = 1.55, 0.2, 0.5, 0.2 * 0.15
+CRATE_REACH = 8       # the crate walker looks this many columns ahead for a pile to land on
+CRATE_RISE = 5.0      # … whose top is at most this far above its feet (a jump rises 6 cells)
+LAND_WITHIN = 0.3     # … and jumps when it can come down this near the pile's middle
+
+
+def _cr_tile(tiles, W, H, x, row):
+    """Tile (x, row), row counted downward as the world's y is; a wall outside the map."""
+    if x < 0 or row < 0 or x >= W or row >= H:
+        return 2
+    return int(tiles[(H - 1 - row) + x * H])
+
+
+def _cr_lands(vx, vy, move, rise):
+    """How far along x a coinrun agent in the air comes down onto a surface `rise` cells above its feet (below them when
+    negative) while it holds `move` (-1, 0, 1); None when it never gets that high.  The tick's own arithmetic, in doubles,
+    nothing in the way."""
+    x = y = 0.0
+    above = rise < 0
+    for _ in range(4 * 48):
+        vx += CR_AIR_MIX * (CR_SPEED * move - vx) * 0.25
+        vy = min(vy + CR_GRAVITY * 0.25, CR_JUMP_SPEED)
+        x += vx * 0.25
+        y += vy * 0.25
+        if y < -rise:
+            above = True
+        elif vy > 0:
+            return x if above else None
+    return None
+
+
+def _cr_runner_jumps(c, st, tiles, ax, ay):
+    """The runner's rule: a wall in the body's row within two columns, no floor under the next column, lava in the feet's row
+    or the one below within two columns, or a hazard (every record but the last, the coin) 0 to 3 cells ahead and within 2
+    cells of the body's height."""
+    W, H, r = c.tile_w, c.tile_h, c.r
+    x, feet = int(math.floor(ax)), int(round(ay))
+    body = feet - 1
+    if any(_cr_tile(tiles, W, H, x + k, body) in CR_WALLS for k in (1, 2)):
+        return True
+    if _cr_tile(tiles, W, H, x + 1, feet) not in CR_STANDS:
+        return True
+    if any(_cr_tile(tiles, W, H, x + k, row) in CR_LAVA for k in (1, 2) for row in (feet, feet + 1)):
+        return True
+    rec = c.records(st)[:-1]
+    dx, dy = rec[:, r["x"]] - ax, rec[:, r["y"]] - (ay - 0.5)
+    return bool(((dx >= 0) & (dx <= 3) & (np.abs(dy) <= 2)).any())
+
+
+def on_crate(c, st, tiles):
+    """A coinrun row whose agent is grounded with a crate under its feet."""
+    f = c.f
+    if st[f["agent_ground"]] == 0:
+        return False
+    ax, feet = float(st[f["agent_x"]]), int(round(float(st[f["agent_y"]])))
+    return any(_cr_tile(tiles, c.tile_w, c.tile_h, col, feet) == CR_CRATE for col in {int(math.floor(ax - 0.49)), int(math.floor(ax + 0.49))})
+
+
+def coinrun_policy(c, st, tiles, step, env, rng):
+    """Four roles by env % 4.  Two runners hold RIGHT and jump, when grounded, by the rule of _cr_runner_jumps.  The crate
+    walker is a runner that presses down for the step when it stands on a crate (the one-way fall-through), and seeks the
+    crates: with a pile within CRATE_REACH columns ahead whose top it can reach, it speeds up or brakes until a jump from
+    where it stands comes down on the pile, jumps, and steers onto it in the air (the flight is worked out from the tick's
+    own numbers); the runner's rule comes first.  The hopper plays JUMP_RIGHT and nothing else: it is the one that dies."""
+    f = c.f
+    W, H = c.tile_w, c.tile_h
+    rng.random()
+    role = env % 4
+    if role == HOPPER:
+        return JUMP_RIGHT
+    ax, ay = float(st[f["agent_x"]]), float(st[f["agent_y"]])
+    ground = st[f["agent_ground"]] != 0
+    if role != CRATE_WALKER:
+        return JUMP_RIGHT if ground and _cr_runner_jumps(c, st, tiles, ax, ay) else RIGHT
+    if on_crate(c, st, tiles):
+        return CR_DOWN
+    vx, vy = float(st[f["agent_vel_x"]]), float(st[f["agent_vel_y"]])
+    if ground and _cr_runner_jumps(c, st, tiles, ax, ay):
+        return JUMP_RIGHT
+    # the nearest pile ahead: its column's topmost crate with nothing on it, its top within reach above the feet
+    x0 = int(math.floor(ax))
+    for col in range(x0 + 1, min(W - 1, x0 + CRATE_REACH) + 1):
+        rows = np.nonzero(tiles[col * H:(col + 1) * H] == CR_CRATE)[0]
+        if not rows.size:
+            continue
+        top = H - 1 - int(rows[-1])  # the row of the topmost crate: its upper edge is world y = top
+        rise, to = ay - top, col + 0.5 - ax
+        if rise > CRATE_RISE or to < 0.3 or (ground and rise < 0.5):
+            continue
+        if ground:
+            near, far = (_cr_lands(vx, -CR_JUMP_SPEED, move, rise) for move in (-1, 1))
+            if to > far + LAND_WITHIN:
+                return RIGHT
+            if to < near - LAND_WITHIN:
+                return LEFT if vx > 0.02 else NOOP
+            return JUMP_RIGHT if to > 0.5 * (near + far) else CR_JUMP
+        lands = [(abs(x - to), a) for x, a in ((_cr_lands(vx, vy, move, rise), a) for move, a in ((1, RIGHT), (0, NOOP), (-1, LEFT))) if x is not None]
+        if lands:
+            return min(lands)[1]
+        break
+    return RIGHT
+
+
+@functools.lru_cache(maxsize=512)
+def _goal_field(tiles, W, H, goal, walls):
+    """Steps to the cell `goal` from every cell of a level (`tiles`: the tile dump's bytes) through cells whose tile is not
+    among `walls`; kept by what it was made from, so once a level."""
+    return _field(_neighbours(W, H), [t in walls for t in tiles], (goal,))
+
+
+# jumper (oracle/pgo_jumper.cpp agent_update): 6-8 right, 0-2 left, 2 / 5 / 8 jump — twice off the ground, the second when
+# agent_jump_timer (3 steps) has run out.  agent_y is the feet; the body is 0.5 wide and 0.8 high.
+JP_WALLS = (1, 2)
+JP_CENTRED = 0.15      # a vertical move is made from this near the column's middle
+JP_SPIKE_AHEAD = 1.6   # a spike this near ahead at body height is jumped over
+JP_WANDER_EVERY, JP_WANDER_FOR = 48, 10  # an env that has to go up walks sideways, jumping, for so many steps of every so many
+
+
+def jumper_policy(c, st, tiles, step, env, rng):
+    """Down a breadth-first field from the goal's cell over the cells that are no wall (kept per level), gravity left out:
+    to the neighbour that is nearer, sideways before down before up.  For a vertical move it centres on the column to within
+    JP_CENTRED, and for one upward it jumps whenever a jump is to be had.  Every env but the fourth of four jumps over a
+    spike within JP_SPIKE_AHEAD cells ahead at body height; the fourth keeps the spike deaths.  The way out for an env that
+    stands under a ledge it cannot jump onto: while the move is upward, JP_WANDER_FOR steps of every JP_WANDER_EVERY (shifted
+    by env) go sideways, jumping, one way or the other by turns."""
+    f = c.f
+    W, H = c.tile_w, c.tile_h
+    rng.random()
+    ax, ay = float(st[f["agent_x"]]), float(st[f["agent_y"]])
+    can_jump = st[f["agent_jumps"]] > 0 and st[f["agent_jump_timer"]] == 0
+    field = _goal_field(tiles.tobytes(), W, H, _cell(float(st[f["goal_x"]]), float(st[f["goal_y"]]), H), JP_WALLS)
+    x, y = min(W - 1, max(0, int(math.floor(ax)))), min(H - 1, max(0, H - 1 - int(math.floor(ay - 0.4))))
+    here = field[y + x * H]
+    # (tile row y + 1 is the cell above: the world's y grows downward, the tile rows count upward)
+    ways = [(field[y + (x + dx) * H], 0, dx, 0) for dx in (1, -1) if 0 <= x + dx < W]
+    ways += [(field[y + dy + x * H], 1 if dy < 0 else 2, 0, dy) for dy in (-1, 1) if 0 <= y + dy < H]
+    best = min(ways)
+    if best[0] >= here:  # nowhere nearer (a cell the field does not reach): towards the goal as the crow flies
+        best = (0, 0, 1 if st[f["goal_x"]] > ax else -1, 0)
+    _, _, dx, dy = best
+    off = x + 0.5 - ax
+    if dy:
+        if dy > 0 and (step + 11 * env) % JP_WANDER_EVERY < JP_WANDER_FOR:
+            return (JUMP_RIGHT if can_jump else RIGHT) if ((step + 11 * env) // JP_WANDER_EVERY + env) % 2 else (JUMP_LEFT if can_jump else LEFT)
+        if abs(off) > JP_CENTRED:
+            return RIGHT if off > 0 else LEFT
+        return CR_JUMP if dy > 0 and can_jump else NOOP
+    if env % 4 != 3 and can_jump:
+        spikes = c.records(st)
+        ahead, high = (spikes[:, 0] - ax) * dx, spikes[:, 1] - (ay - 0.4)
+        if ((ahead > 0) & (ahead <= JP_SPIKE_AHEAD) & (np.abs(high) < 0.8)).any():
+            return JUMP_RIGHT if dx > 0 else JUMP_LEFT
+    return RIGHT if dx > 0 else LEFT
+
+
+MZ_WALLS = (1,)
+
+
+def maze_policy(c, st, tiles, step, env, rng):
+    """Down the breadth-first field from the goal's cell (kept per level).  Every fourth env plays the field's move two steps
+    in three and a move into a wall otherwise (the refused move); where no wall is beside it, the field's move."""
+    f = c.f
+    W, H = c.tile_w, c.tile_h
+    rng.random()
+    field = _goal_field(tiles.tobytes(), W, H, _cell(float(st[f["goal_x"]]), float(st[f["goal_y"]]), H), MZ_WALLS)
+    here = _cell(float(st[f["agent_x"]]), float(st[f["agent_y"]]), H)
+    nb = _neighbours(W, H)[here]
+    if env % 4 == 3 and step % 3 == 2:
+        taken = {a for p, a in nb if tiles[p] not in MZ_WALLS}
+        for a in (LEFT, UP, RIGHT, DOWN):
+            if a not in taken:
+                return a
+    near, go = min((field[p], a) for p, a in nb)
+    return go if near < field[here] else NOOP
+
+
+POLICIES = {"bossfight": bossfight_policy, "chaser": chaser_policy, "climber": climber_policy, "caveflyer": caveflyer_policy,
+            "coinrun": coinrun_policy, "jumper": jumper_policy, "maze": maze_policy}
 
 
 def choose_actions(game, mode, dumps, step, rng):
@@ -501,7 +689,79 @@ class Counter:
             self.counts.update(target_steps=0, targets_destroyed=0, double_target_steps=0, goal_with_target_steps=0, most_shots=0, steps_over_8=0,
                                steps_over_16=0, steps_over_24=0, ring_full_steps=0, overflow_steps=0, most_turn=0.0)
             self.hit_target = np.zeros(n, bool)
-            self.turns = 0
+        self.turns = 0
+        if game in ("coinrun", "jumper", "maze"):
+            self.counts.update(most_ends=0, deep_starts=0)
+            self.env_ends = np.zeros(n, int)  # the episodes every env has ended: its level is number env_ends + 1
+        if game == "coinrun":
+            self.counts.update(lava_deaths=0, saw_deaths=0, mob_deaths=0, other_deaths=0, env_steps=0, past_half=0, past_09=0, crate_steps=0, drop_steps=0,
+                               envs_with_3_ends=0)
+            self.dropped = np.zeros(n, bool)
+        if game == "jumper":
+            self.counts.update(no_jump_steps=0, no_jump_timer_steps=0, envs_with_no_end=n)
+            if mode == MEMORY:
+                self.counts.update(farthest=0.0, octants=set(), most_octants_in_an_env=0)
+                self.env_octants = np.zeros((n, 8), bool)
+            self.began_at = np.zeros((n, 2))
+        if game == "maze":
+            self.counts.update(median_ends=0, longest_episode=0)
+            self.length = np.zeros(n, int)
+
+    def coinrun_on_crate(self, dumps):
+        return np.array([on_crate(self.c, dumps.states[e], dumps.tiles[e]) for e in range(dumps.states.shape[0])])
+
+    def coinrun_progress(self, dumps):
+        """agent_x / coin_x, the coin being the row's last record."""
+        c, st = self.c, dumps.states
+        last = c.fixed + (st[:, c.f["n_things"]].astype(int) - 1) * c.record + c.r["x"]
+        return st[:, c.f["agent_x"]] / st[np.arange(st.shape[0]), last]
+
+    def coinrun_lava_near(self, dumps, within=8):
+        """The envs with a lava tile within `within` columns of the agent's."""
+        c = self.c
+        lava = np.isin(dumps.tiles.reshape(-1, c.tile_w, c.tile_h), CR_LAVA).any(axis=2)  # [env, x]
+        x = np.floor(dumps.states[:, c.f["agent_x"]]).astype(int)
+        return np.array([lava[e, max(0, x[e] - within):x[e] + within + 1].any() for e in range(x.size)])
+
+    def coinrun_hazard_in_view(self, dumps, within=6):
+        """The envs with a lava tile or a saw (a hazard record that does not walk) within `within` cells of the agent both
+        ways: a frame shows 13.3 cells across, the agent in the middle."""
+        c, st = self.c, dumps.states
+        out = np.zeros(st.shape[0], bool)
+        for e in range(st.shape[0]):
+            ax, ay = float(st[e, c.f["agent_x"]]), float(st[e, c.f["agent_y"]]) - 0.5
+            x, row = int(math.floor(ax)), int(math.floor(ay))
+            grid = dumps.tiles[e].reshape(c.tile_w, c.tile_h)[max(0, x - within):x + within + 1, max(0, c.tile_h - 1 - row - within):c.tile_h - row + within]
+            rec = c.records(st[e])[:-1]
+            saws = rec[rec[:, c.r["vel_x"]] == 0]
+            out[e] = np.isin(grid, CR_LAVA).any() or ((np.abs(saws[:, c.r["x"]] - ax) <= within) & (np.abs(saws[:, c.r["y"]] - ay) <= within)).any()
+        return out
+
+    def coinrun_death(self, st, tiles):
+        """What a terminal coinrun row died of: 'lava' with a lava tile under the body, else 'mob' or 'saw' by the first
+        hazard record (every record but the coin's; a mob's walks) whose box the body touches, else 'other'."""
+        c = self.c
+        ax, ay = float(st[c.f["agent_x"]]), float(st[c.f["agent_y"]])
+        x0, x1, y0, y1 = ax - 0.5, ax + 0.5, ay - 1.0, ay
+        for x in range(int(math.floor(x0)), int(math.ceil(x1))):
+            for row in range(int(math.floor(y0)), int(math.ceil(y1))):
+                if _cr_tile(tiles, c.tile_w, c.tile_h, x, row) in CR_LAVA:
+                    return "lava"
+        for rec in c.records(st)[:-1]:
+            mob = rec[c.r["vel_x"]] != 0
+            hx, hy, hw, hh = (rec[c.r["x"]] - 0.5, rec[c.r["y"]] - 0.48, 1.0, 0.98) if mob else (rec[c.r["x"]] - 0.5, rec[c.r["y"]] - 0.5, 1.0, 1.0)
+            if x0 < hx + hw and x1 > hx and y0 < hy + hh and y1 > hy:
+                return "mob" if mob else "saw"
+        return "other"
+
+    def _rare_in_order(self, groups, turning):
+        """At most RARE_ENVS envs: the groups' in the order given, then `turning`'s, another of them first in every step."""
+        order = [np.nonzero(x)[0] for x in groups] + [np.roll(np.nonzero(turning)[0], -self.turns)]
+        order = np.concatenate(order)
+        rare = np.zeros(turning.size, bool)
+        rare[order[np.sort(np.unique(order, return_index=True)[1])][:RARE_ENVS]] = True
+        self.turns += 1
+        return rare
 
     def caveflyer_targets(self, dumps):
         rec = self._records(dumps)
@@ -596,6 +856,51 @@ class Counter:
             rare[order[np.sort(np.unique(order, return_index=True)[1])][:RARE_ENVS]] = True
             self.hit_target = hit | lost
             self.turns += 1
+        if self.game in ("coinrun", "jumper", "maze"):
+            self.env_ends[ended] += 1
+            k["most_ends"] = int(self.env_ends.max())
+            least = 5 if self.game == "maze" else 3
+            deep = starts & (self.env_ends >= least) & (level is after)  # the first step of a level this deep in the env's chain
+            k["deep_starts"] += int(deep.sum())
+        if self.game == "coinrun":
+            k["envs_with_3_ends"] = int((self.env_ends >= 3).sum())
+            for e in np.nonzero(death)[0]:
+                k[self.coinrun_death(after.states[e], after.tiles[e]) + "_deaths"] += 1
+            share = self.coinrun_progress(after)
+            stood, stands = self.coinrun_on_crate(before) & playing, self.coinrun_on_crate(after) & playing
+            drop = stood & np.isin(np.asarray(actions), (0, 3, 6)) & (after.states[:, f["agent_y"]] > before.states[:, f["agent_y"]]) & ~ended
+            k["env_steps"] += int(playing.sum())
+            k["past_half"] += int((playing & (share > 0.5)).sum())
+            k["past_09"] += int((playing & (share > 0.9)).sum())
+            k["crate_steps"] += int(stands.sum())
+            k["drop_steps"] += int(drop.sum())
+            rare = self._rare_in_order((deep, drop | (self.dropped & playing), stands, playing & (share > 0.9)), playing & self.coinrun_lava_near(after))
+            self.dropped = drop
+        elif self.game == "jumper":
+            none_left = playing & (after.states[:, f["agent_jumps"]] == 0)
+            timed = none_left & (after.states[:, f["agent_jump_timer"]] > 0)
+            k["no_jump_steps"] += int(none_left.sum())
+            k["no_jump_timer_steps"] += int(timed.sum())
+            at = after.states[:, [f["agent_x"], f["agent_y"]]].astype(float)
+            self.began_at[starts] = level.states[:, [f["agent_x"], f["agent_y"]]][starts]
+            self.far_from_start = far = np.where(playing, np.hypot(*(at - self.began_at).T), 0.0)
+            groups = [deep]
+            if self.mode == MEMORY:
+                k["farthest"] = max(k["farthest"], float(far[playing].max()) if playing.any() else 0.0)
+                angle = np.arctan2(after.states[playing, f["to_goal_y"]].astype(float), after.states[playing, f["to_goal_x"]].astype(float))
+                octant = np.minimum(7, np.floor((angle + math.pi) / (0.25 * math.pi)).astype(int))
+                k["octants"] |= set(octant.tolist())
+                self.env_octants[np.nonzero(playing)[0], octant] = True
+                k["most_octants_in_an_env"] = int(self.env_octants.sum(axis=1).max())
+                groups.append(playing & (far > 15))
+            k["envs_with_no_end"] = int((self.env_ends == 0).sum())
+            rare = self._rare_in_order(groups, timed)
+        elif self.game == "maze":
+            self.length[playing] += 1
+            k["longest_episode"] = max([k["longest_episode"]] + self.length[ended].tolist())
+            self.length[ended] = 0
+            k["median_ends"] = float(np.median(self.env_ends))
+            rare = deep
         self.rare = [int(e) for e in np.nonzero(rare)[0][:RARE_ENVS]]
         self.after = after
         self.resetting = done != 0
@@ -628,6 +933,17 @@ def run_on_oracle(game, mode, each_step=None, at_start=None, render=False, threa
     return counter.counts
 
 
+RARE_FLOOR = 20  # the GPU half compares state and tile rows in at least this many envs a case
+COMPASS = set(range(8))  # jumper's memory mode: the octants of atan2(to_goal_y, to_goal_x)
+# maze: the episodes the median env of this protocol ends under random play (tests/variant_paths_util.py's actions), by mode:
+# (in STEPS steps, in that protocol's own 520); tests/test_scripted_play.py holds the figures to a run.  Twice the first asks
+# for nothing, so the floor is twice the larger of the two: what random play needs the 500-step cap and more for
+RANDOM_MAZE_MEDIAN = {EASY: (0, 1), HARD: (0, 1), MEMORY: (0, 1)}
+# jumper's memory mode: the compass's octants met inside ONE env — more than half the compass, so an agent that went round its
+# goal.  (All eight are met at step 0 already when 65 envs are counted together, under any play.)
+OCTANTS_IN_AN_ENV = 5
+
+
 def floors(game, mode):
     """count name → the least a run must reach."""
     if game == "bossfight":
@@ -638,6 +954,16 @@ def floors(game, mode):
         out = dict(wins=5, deaths=3, target_steps=5, steps_over_8=100, steps_over_16=20)
         out.update(dict(ring_full_steps=1, overflow_steps=20) if mode == MEMORY else dict(most_shots=20))
         return out
+    if game == "coinrun":
+        return dict(wins=100, deaths=30, lava_deaths=5, saw_deaths=5, mob_deaths=5, envs_with_3_ends=60, most_ends=8, crate_steps=20, drop_steps=5,
+                    deep_starts=RARE_FLOOR)
+    if game == "jumper":
+        out = dict(wins={EASY: 100, HARD: 40, MEMORY: 40}[mode], most_ends={EASY: 8, HARD: 6, MEMORY: 3}[mode], no_jump_steps=5000,
+                   no_jump_timer_steps=RARE_FLOOR)
+        out.update(dict(farthest=20, most_octants_in_an_env=OCTANTS_IN_AN_ENV) if mode == MEMORY else dict(deaths=20))
+        return out
+    if game == "maze":
+        return dict(wins=100, median_ends=2 * max(RANDOM_MAZE_MEDIAN[mode]), deep_starts=RARE_FLOOR)
     out = dict(eaten_enemies=20, deaths=3)
     out["wins_or_85" if (game, mode) in ATE_85_INSTEAD else "wins"] = 2 if mode == EASY else 1
     return out
@@ -648,6 +974,12 @@ def assert_covers(game, mode, counts):
         assert counts[name] >= least, "%s mode %d: %s is %d, the floor is %d (%r)" % (game, mode, name, counts[name], least, counts)
     if game == "bossfight":
         assert counts["phases"] >= set(range(6)), "%s mode %d: phases seen %r" % (game, mode, sorted(counts["phases"]))
+    if game == "coinrun":
+        for name, share in (("past_half", 0.25), ("past_09", 0.05)):
+            assert counts[name] >= share * counts["env_steps"], "%s mode %d: %s is %d of %d env-steps" % (game, mode, name, counts[name], counts["env_steps"])
+    if (game, mode) == ("jumper", MEMORY):
+        assert counts["deaths"] == 0, "jumper's memory mode has no spikes: %r" % counts
+        assert counts["octants"] == COMPASS, "jumper mode %d: the compass pointed into octants %r" % (mode, sorted(counts["octants"]))
     if game == "caveflyer":
         assert counts["most_turn"] > FULL_TURN, "%s mode %d: the ship turned %.3f at the most" % (game, mode, counts["most_turn"])
 

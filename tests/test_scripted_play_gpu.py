@@ -1,16 +1,22 @@
 """Play to win: the HIP engine against the oracle on the games' winning and late-game paths (need an MI355X).
 
 Every other lock-step test is driven by random or one-key action streams, and those lose: bossfight never leaves its second
-phase, no chaser board is cleared, climber picks up two or three coins in a run.  Here the scripted agents of
-tests/scripted_play_util.py play bossfight, chaser, climber and caveflyer on the oracle — reading the oracle's dumps, never the
+phase, no chaser board is cleared, climber picks up two or three coins in a run, coinrun stays in the first half of its
+levels and no env of it goes past its first auto-reset.  Here the scripted agents of tests/scripted_play_util.py play all seven
+games (bossfight, chaser, climber, caveflyer, coinrun, jumper, maze) on the oracle — reading the oracle's dumps, never the
 engine's — and their actions go to the engine under its default path AND every alternate path behind pgv_set_debug, side by
 side: dones, reward bit patterns and every observation byte after every step, and state_obs / tile_obs rows against the
 oracle's dumps wherever an env is in a state random play does not visit (bossfight: the shield down, hp 0, explosions, phase
 4 and later; chaser: an enemy just eaten under an orb's timer; climber: a coin just destroyed, and the step after;
 caveflyer: a target just destroyed, and the step after, more than 16 live bullets — three and four trips of the bullet loop's
 gangs of 8 — the full ring of 32, and more draws than the render wave has lanes, which is where the complete render path and
-the frames the pre-pass hands back part from the default).  One case holds the batched human-size frames of caveflyer's
-memory mode to the oracle in those last two states.  One
+the frames the pre-pass hands back part from the default; coinrun: the first step of an env's fourth and later level — a
+level deep in the generator's chain installed under prefetch, under generation inside the step and under every renderer at
+once — a crate dropped through, and the step after, an env grounded on a crate, past 0.9 of the way to the coin, with lava
+within 8 columns; jumper: the first step of a fourth and later level, in memory mode an agent more than 15 cells from where
+its episode began, no jump left with the timer running; maze: the first step of a sixth and later level).  One case holds
+the batched human-size frames of caveflyer's memory mode to the oracle in those last two states of its, one more those of
+coinrun late in its levels and of jumper's memory mode far from the start.  One
 case a game runs the agents through step_episodes in same-step mode against the model of tests/episodes_util.py: the
 returns, lengths and terminal frames of winning episodes.  The floors of tests/test_scripted_play.py are asserted again on
 the runs made here.
@@ -31,7 +37,7 @@ from procgen2_amd import lib as pglib
 from test_episodes_gpu import Engine as EpisodeEngine
 from test_episodes_gpu import check_step
 from test_frames_batch_gpu import _oracle_step, assert_frame, frames_host, oracle_frame
-from test_modes import MEMORY
+from test_modes import HARD, MEMORY
 from test_parity_gpu import _host_threads
 
 pytestmark = pytest.mark.gpu
@@ -189,6 +195,72 @@ def test_human_size_frames_with_a_full_ring():
         print("human-size frames: caveflyer mode %d, (step, envs in the state, most bullets): %r" % (mode, seen))
     finally:
         eng.close()
+
+
+def _frames_late_in_a_run(game, mode, state_of, what):
+    """One default-path engine beside the oracle under the agents of (game, mode), up to the first step after which
+    state_of(counter, done) names envs: the batched human-size frames of up to four of them, 128 x 128, and of the first at
+    192 x 96, against pgo_render_frame of a single oracle env brought to the same state by the same actions (its state dump
+    is held to the protocol's own first).  Returns (step, the envs)."""
+    L = oracle()
+    eng = EngineVec(game, sp.N, seed_base=sp.SEED_BASE, mode=mode)
+    history, seen = [], []
+
+    def single(env):
+        h = L.pgo_make_mode(game.encode(), sp.SEED_BASE + env, 1, mode)
+        L.pgo_reset(h, 0, 0)
+        pending = [False]
+        for a in history:
+            _oracle_step(L, [h], pending, a[env:env + 1])
+        return h
+
+    def at_start(ora):
+        _same_frames(eng.reset(), ora.reset_obs(), "first reset")
+
+    def each_step(s, ora, a, obs, reward, done, counter):
+        history.append(a.copy())
+        oe, re_, de = eng.step(a)
+        assert np.array_equal(de, done) and np.array_equal(re_.view(np.uint32), reward.view(np.uint32)), s
+        _same_frames(oe, obs, "step %d" % s)
+        envs = state_of(counter, done)
+        if not envs:
+            return
+        seen.append((s, envs[:4]))
+        for k, (w, h) in enumerate(((128, 128), (192, 96))):
+            chosen = envs[:4] if k == 0 else envs[:1]
+            got = frames_host(eng, chosen, w, h)
+            for j, env in enumerate(chosen):
+                handle = single(env)
+                try:
+                    assert_same_dump(oracle_state(handle), counter.after.state(env), "%s, step %d: the single env %d" % (what, s, env))
+                    assert_frame(got[j], oracle_frame(L, handle, w, h), "%s, step %d: env %d, %dx%d" % (what, s, env, w, h))
+                finally:
+                    L.pgo_close(handle)
+        raise _Played
+
+    try:
+        with pytest.raises(_Played):  # the state is met inside the protocol's run: tests/test_scripted_play.py's floors
+            sp.run_on_oracle(game, mode, each_step, at_start, render=True, threads=_host_threads())
+    finally:
+        eng.close()
+    return seen[0]
+
+
+def test_human_size_frames_late_in_the_level():
+    """The three renderers share one draw list, and its late-level inputs come only with the agents.  coinrun: the first
+    step after which four envs that play on are past 0.9 of the way to the coin with a lava tile or a saw in view — the
+    pits, the coin and the solid fill to the right of its column.  jumper's memory mode: the first step after which an agent
+    is 20 cells from where its episode began, in the 45 x 45 world.  Their batched human-size frames against the oracle's."""
+    def late(counter, done):
+        at = (counter.coinrun_progress(counter.after) > 0.9) & counter.coinrun_hazard_in_view(counter.after) & (done == 0)
+        return np.nonzero(at)[0].tolist() if at.sum() >= 4 else []
+
+    def far(counter, done):
+        return np.nonzero((counter.far_from_start >= 20) & (done == 0))[0].tolist()
+
+    seen = [_frames_late_in_a_run("coinrun", HARD, late, "coinrun past 0.9 of the way"),
+            _frames_late_in_a_run("jumper", MEMORY, far, "jumper 20 cells from its start")]
+    print("human-size frames late in the level: coinrun mode %d and jumper mode %d, (step, envs): %r" % (HARD, MEMORY, seen))
 
 
 @pytest.mark.parametrize("game", sp.GAMES)
