@@ -837,18 +837,13 @@ __global__ void __launch_bounds__(64, PG_BOSSFIGHT_WAVES) logic_kernel(State s, 
         }
         return;
     }
-    const int action =
-        actions ? actions[env] : synthetic_action(run_seed, step_index, static_cast<uint32_t>(env_offset + env));
+    const int action = step_action(actions, run_seed, step_index, env_offset, env);
     __shared__ RingsLds rings[64 / kGang];
     Rings R{&rings[(threadIdx.x & 63) / kGang], 0u, 0u, 0u};
     float reward;
     bool terminated;
     advance(s, R, q, env, action, reward, terminated);
-    if (q.g == 0) {
-        io.reward[env] = reward;
-        io.done[env] = terminated ? 1 : 0;
-        io.pending[env] = terminated ? 1 : 0;
-    }
+    if (q.g == 0) step_results(io, env, reward, terminated, 1);
 }
 
 // The draw list of bossfight.cpp:401-424, each kind of draw stated once, for render_full_kernel, setup_kernel and
@@ -1384,20 +1379,11 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     P.draw(centred_draw(kTexPlayer + a_ship, ax, ay, kAgentSize, 1.0f, 0.0f, P.desc(kTexPlayer + a_ship)));
 }
 
-// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    FramePainter P(t);
-    frame_draws(s, atlas, env, P);
-}
-
-// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
-__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
-    __shared__ uint32_t tile[kTilePx];
-    TilePainter P(tile, fb);
-    const int env = P.env(fb);
-    if (env >= 0) frame_draws(s, atlas, env, P);
-    P.store(fb);
-}
+struct Frames {  // pg_frame.h frame_kernel<Frames> / frames_kernel<Frames>
+    using State = bossfight::State;
+    template <class Painter>
+    static __device__ void draws(const State& s, const AtlasView& atlas, int env, Painter& P) { frame_draws(s, atlas, env, P); }
+};
 
 // The state row (pg_state_obs.h): oracle/pgo_bossfight.cpp Bossfight::dump_state, column by column.  The 25 scalars come
 // from the field arrays, the two rings of shots from each env's own block.
@@ -1450,7 +1436,7 @@ struct StateRow {
 };
 
 // (no tile map in this game, so no map() in its row and no PathRow)
-class BossfightGame final : public ViewedGame<BoundGame<State>, StateRow, void> {
+class BossfightGame final : public ViewedGame<BoundGame<State>, StateRow, void, Frames> {
    public:
     const char* name() const override { return "bossfight"; }
     std::vector<std::string> texture_names() const override {
@@ -1525,13 +1511,6 @@ class BossfightGame final : public ViewedGame<BoundGame<State>, StateRow, void> 
                       StepIO io) override {
         hipLaunchKernelGGL(logic_kernel, dim3((s_.n * kGang + 63) / 64), dim3(64), 0, st, s_, actions, run_seed, step_index,
                            env_offset, io, plan);
-    }
-    bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
-        hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
-        return true;
-    }
-    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
-        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     // (every flag that changes the frame's path — the draw-list replay, kDebugNoPrepass, the timing experiments — takes the complete kernel)
     bool lean() const { return (debug_flags & ~kDebugNoPrefetch) == 0; }

@@ -875,13 +875,6 @@ PG_D void advance(const State& s, StepLds& L, Q q, int env, int action, bool ser
     terminated_out = terminated;
 }
 
-__global__ void __launch_bounds__(64) make_kernel(State s) {
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= s.n) return;
-    fresh_chain(s, env);
-    fresh_live(s, env);
-}
-
 __global__ void __launch_bounds__(64, PG_CHASER_WAVES) logic_kernel(State s, const int32_t* actions, uint32_t run_seed,
                                                                     uint32_t step_index, int env_offset, StepIO io, int serial_mobs) {
     __shared__ StepLds lds[64 / kGang];
@@ -889,16 +882,11 @@ __global__ void __launch_bounds__(64, PG_CHASER_WAVES) logic_kernel(State s, con
     if (env >= s.n) return;
     if (io.pending[env] != 0) return;  // reset by the level kernel in this step, maybe right now (pg_engine.h StepIO)
     const Q q = Q::at(threadIdx.x);
-    const int action =
-        actions ? actions[env] : synthetic_action(run_seed, step_index, static_cast<uint32_t>(env_offset + env));
+    const int action = step_action(actions, run_seed, step_index, env_offset, env);
     float reward = 0.0f;
     bool terminated = false;
     advance(s, lds[(threadIdx.x & 63) / kGang], q, env, action, serial_mobs != 0, reward, terminated);
-    if (q.g == 0) {
-        io.reward[env] = reward;
-        io.done[env] = terminated ? 1 : 0;
-        io.pending[env] = terminated ? 3 : 0;  // (3, not 1: the level kernel may be running beside this one — pg_engine.h StepIO)
-    }
+    if (q.g == 0) step_results(io, env, reward, terminated, 3);  // (3, not 1: the level kernel may be running beside this one — pg_engine.h StepIO)
 }
 
 // render_game(true) (chaser.cpp:390-416): one workgroup of two wavefronts per env (pg_render.h).
@@ -1457,20 +1445,11 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     P.draw(agent_draw(SF(s, F_AX, env), SF(s, F_AY, env), P.desc(kTexAgent)));
 }
 
-// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    FramePainter P(t);
-    frame_draws(s, atlas, env, P);
-}
-
-// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
-__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
-    __shared__ uint32_t tile[kTilePx];
-    TilePainter P(tile, fb);
-    const int env = P.env(fb);
-    if (env >= 0) frame_draws(s, atlas, env, P);
-    P.store(fb);
-}
+struct Frames {  // pg_frame.h frame_kernel<Frames> / frames_kernel<Frames>
+    using State = chaser::State;
+    template <class Painter>
+    static __device__ void draws(const State& s, const AtlasView& atlas, int env, Painter& P) { frame_draws(s, atlas, env, P); }
+};
 
 // The state row (pg_state_obs.h): oracle/pgo_chaser.cpp Chaser::dump_state, column by column.  The 13 scalars come from
 // the field arrays, the entity records from each env's own table — an orb or a point stands in the middle of its cell, an
@@ -1531,7 +1510,7 @@ struct PathRow {
     static constexpr int kGoalX = -1, kGoalY = -1;
 };
 
-class ChaserGame final : public ViewedGame<BoundGame<State>, StateRow, PathRow> {
+class ChaserGame final : public ViewedGame<BoundGame<State>, StateRow, PathRow, Frames> {
    public:
     const char* name() const override { return "chaser"; }
     std::vector<std::string> texture_names() const override {
@@ -1626,9 +1605,8 @@ class ChaserGame final : public ViewedGame<BoundGame<State>, StateRow, PathRow> 
         s_.ranks = atlas.sort_ranks;
         atlas_ = atlas;
     }
-    int blocks() const { return (s_.n + 63) / 64; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
-        hipLaunchKernelGGL(make_kernel, dim3(blocks()), dim3(64), 0, st, s_);
+        LevelLaunch<Gen>::fresh(st, s_);
         hipLaunchKernelGGL(prepare_kernel, dim3(1), dim3(128), 0, st, s_, atlas_);
         LevelLaunch<Gen>::make(st, s_, 0, seed_base, env_offset, plan);
     }
@@ -1644,13 +1622,6 @@ class ChaserGame final : public ViewedGame<BoundGame<State>, StateRow, PathRow> 
         hipLaunchKernelGGL(due_level_kernel, dim3(s_.n < kDueBlocks ? s_.n : kDueBlocks), dim3(64), 0, reset_stream, s_, io, plan);
         hipLaunchKernelGGL(logic_kernel, dim3((s_.n * kGang + 63) / 64), dim3(64), 0, st, s_, actions, run_seed, step_index,
                            env_offset, io, (debug_flags & kDebugChaserSerialMobs) ? 1 : 0);
-    }
-    bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
-        hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
-        return true;
-    }
-    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
-        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     // (the draw-list replay and kDebugNoPrepass take the kernel that resolves its own draws)
     bool lean() const { return !(debug_flags & (1 | kDebugNoPrepass)); }

@@ -508,39 +508,17 @@ PG_D void advance(const State& s, StepLds& L, Q q, int env, int action, float& r
     terminated_out = terminated;
 }
 
-__global__ void __launch_bounds__(64) make_kernel(State s, uint32_t seed_base, int env_offset) {
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= s.n) return;
-    fresh_chain(s, env);
-    fresh_live(s, env);
-}
+struct Step {  // pg_prefetch.h logic_step<Gen, Step>: a gang per env
+    static constexpr int kGang = climber::kGang;
+    using Lds = StepLds;
+    PG_D static void advance(const State& s, Lds& L, int tid, int env, int action, float& reward, bool& terminated) {
+        climber::advance(s, L, Q::at(tid), env, action, reward, terminated);
+    }
+};
 
 __global__ void __launch_bounds__(64, PG_CLIMBER_WAVES) logic_kernel(State s, const int32_t* actions, uint32_t run_seed,
                                                                      uint32_t step_index, int env_offset, StepIO io, int prefetch, LevelPlan plan) {
-    // One block is EITHER a row of gangs stepping their envs (StepLds each) OR the install row (a Level staged on its way from
-    // the shadow slot to the live state): the same LDS serves both — as two arrays the logic blocks carried the Level's
-    // 2–3 KB for nothing and fewer of them fitted a CU (caveflyer: 11.8 KB a block, 13 blocks instead of 16).
-    constexpr size_t kLdsBytes = sizeof(StepLds) * (64 / kGang) > sizeof(Level) ? sizeof(StepLds) * (64 / kGang) : sizeof(Level);
-    __shared__ alignas(16) unsigned char lds_bytes[kLdsBytes];
-    StepLds* const lds = reinterpret_cast<StepLds*>(lds_bytes);
-    if (blockIdx.y == 1) {  // (block-uniform) the auto-resets whose level lies ready: a copy, beside the envs that step (pg_prefetch.h)
-        install_prefetched<Gen>(s, blockIdx.x * (64 / kGang), 64 / kGang, prefetch, io, plan, *reinterpret_cast<Level*>(lds_bytes), threadIdx.x, reset_served_mark(step_index), reset_due_mark(step_index));
-        return;
-    }
-    const int env = (blockIdx.x * 64 + threadIdx.x) / kGang;
-    if (env >= s.n) return;
-    const Q q = Q::at(threadIdx.x);
-    if (resets_in_step(io.pending[env], step_index)) return;  // this step is the env's reset (pg_prefetch.h: who serves it, and the byte)
-    const int action =
-        actions ? actions[env] : synthetic_action(run_seed, step_index, static_cast<uint32_t>(env_offset + env));
-    float reward = 0.0f;
-    bool terminated = false;
-    advance(s, lds[(threadIdx.x & 63) / kGang], q, env, action, reward, terminated);
-    if (q.g == 0) {
-        io.reward[env] = reward;
-        io.done[env] = terminated ? 1 : 0;
-        io.pending[env] = terminated ? static_cast<uint8_t>(reset_due_mark(step_index + 1u)) : 0;  // (pg_prefetch.h: the byte)
-    }
+    logic_step<Gen, Step>(s, actions, run_seed, step_index, env_offset, io, prefetch, plan);
 }
 
 // render_game(true) (climber.cpp:431-459): one workgroup of two wavefronts per env (pg_render.h).
@@ -806,20 +784,11 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     P.draw(agent_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), tex, P.desc(tex)));
 }
 
-// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    FramePainter P(t);
-    frame_draws(s, atlas, env, P);
-}
-
-// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
-__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
-    __shared__ uint32_t tile[kTilePx];
-    TilePainter P(tile, fb);
-    const int env = P.env(fb);
-    if (env >= 0) frame_draws(s, atlas, env, P);
-    P.store(fb);
-}
+struct Frames {  // pg_frame.h frame_kernel<Frames> / frames_kernel<Frames>
+    using State = climber::State;
+    template <class Painter>
+    static __device__ void draws(const State& s, const AtlasView& atlas, int env, Painter& P) { frame_draws(s, atlas, env, P); }
+};
 
 // The state row (pg_state_obs.h): oracle/pgo_climber.cpp Climber::dump_state, column by column.  The 14 scalars come from
 // the field arrays, the entity records from each env's own tables.
@@ -872,7 +841,7 @@ struct PathRow {
     static constexpr int kGoalX = -1, kGoalY = -1;
 };
 
-class ClimberGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
+class ClimberGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow, Frames> {
    public:
     const char* name() const override { return "climber"; }
     std::vector<std::string> texture_names() const override {
@@ -915,27 +884,12 @@ class ClimberGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, Path
         s_.ranks = atlas.sort_ranks;
         atlas_ = atlas;
     }
-    int blocks() const { return (s_.n + 63) / 64; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
-        hipLaunchKernelGGL(make_kernel, dim3(blocks()), dim3(64), 0, st, s_, seed_base, env_offset);
         make_levels(st, seed_base, env_offset);
     }
     void launch_logic(hipStream_t st, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
                       StepIO io) override {
-        // prefetched levels are installed beside the logic (its second row of blocks); the level kernel behind it
-        // generates, synchronously, the levels that were not ready — none in steady state (pg_prefetch.h install_prefetched)
-        const bool fused = prefetch() != 0;
-        reset_before_logic(st, step_index, io);
-        hipLaunchKernelGGL(logic_kernel, dim3((s_.n * kGang + 63) / 64, fused ? 2 : 1), dim3(64), 0, st, s_, actions, run_seed, step_index,
-                           env_offset, io, prefetch(), plan);
-        reset_after_logic(st, step_index, io);
-    }
-    bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
-        hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
-        return true;
-    }
-    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
-        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
+        launch_fused_logic(logic_kernel, Step::kGang, st, actions, run_seed, step_index, env_offset, io);
     }
     static void carve_scratch(Carve& c, PrepOut& p, int n) { prep_carve(c, p, n, kGrid, kBlitWords, true); }
     size_t scratch_bytes(int n) const override { return Carve::size(carve_scratch, n); }

@@ -965,13 +965,6 @@ PG_D void agent_substeps(const State& s, int env, int action, float reach_x, flo
 // ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) make_kernel(State s, uint32_t seed_base, int env_offset) {
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= s.n) return;
-    fresh_chain(s, env);
-    fresh_live(s, env);
-}
-
 // A + B — the agent's sub-steps and the entities' in ONE launch (round 5): neither needs the other.  The agent depends on
 // tiles, the entities on tiles and their own state; what joins them — does a hazard's box overlap the agent's after
 // sub-step ss — is held by resolve_kernel, behind both.  As two launches they were two latency chains end to end (34 and
@@ -1024,8 +1017,7 @@ __global__ void __launch_bounds__(64, PG_COINRUN_LOGIC_WAVES) logic_kernel(State
             SCI(s, SC_BITS, env) = 0;  // did not step: resolve_kernel leaves this env alone
             return;
         }
-        const int action =
-            actions ? actions[env] : synthetic_action(run_seed, step_index, static_cast<uint32_t>(env_offset + env));
+        const int action = step_action(actions, run_seed, step_index, env_offset, env);
         // (Measured, round 5: s_setprio(3) for this row — one long chain beside the entities' many shorter ones — changes
         // nothing: 59.5 against 59.4 µs.)
         agent_substeps(s, env, action, reach_x, reach_y);
@@ -1710,20 +1702,11 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     P.draw(agent_draw(sflags, SF(s, F_AX, env), SF(s, F_AY, env), tex, P.desc(tex)));
 }
 
-// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    FramePainter P(t);
-    frame_draws(s, atlas, env, P);
-}
-
-// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
-__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
-    __shared__ uint32_t tile[kTilePx];
-    TilePainter P(tile, fb);
-    const int env = P.env(fb);
-    if (env >= 0) frame_draws(s, atlas, env, P);
-    P.store(fb);
-}
+struct Frames {  // pg_frame.h frame_kernel<Frames> / frames_kernel<Frames>
+    using State = coinrun::State;
+    template <class Painter>
+    static __device__ void draws(const State& s, const AtlasView& atlas, int env, Painter& P) { frame_draws(s, atlas, env, P); }
+};
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1800,7 +1783,7 @@ struct PathRow {
     static constexpr int kGoalX = -1, kGoalY = -1;
 };
 
-class CoinrunGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
+class CoinrunGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow, Frames> {
    public:
     const char* name() const override { return "coinrun"; }
     bool set_game_flags(uint32_t flags) override {
@@ -1879,7 +1862,6 @@ class CoinrunGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, Path
     }
     int blocks() const { return (s_.n + 63) / 64; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
-        hipLaunchKernelGGL(make_kernel, dim3(blocks()), dim3(64), 0, st, s_, seed_base, env_offset);
         make_levels(st, seed_base, env_offset);
     }
     void launch_logic(hipStream_t st, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
@@ -1901,13 +1883,6 @@ class CoinrunGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, Path
         // The resets no prefetched level lay ready for ride in resolve_kernel's second row (see there: +0.6 to 1 %).
         hipLaunchKernelGGL(resolve_kernel, dim3((s_.n + 63) / 64, fused ? 2 : 1), dim3(64), 0, st, s_, io, step_index, prefetch(),
                            plan);
-    }
-    bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
-        hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
-        return true;
-    }
-    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
-        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
     }
     // F, the early blocks of the render launch = the slots of the pre-pass's list of handed-back frames: n / 256 — at
     // 65 536 envs 256, where about 100 frames a step are handed back — but 64 at least and 1 024 (kEarlyMax) at most.  None

@@ -628,31 +628,17 @@ PG_D void advance(const State& s, int env, int action, float& reward_out, bool& 
     terminated_out = !alive || achieved_goal;
 }
 
-__global__ void __launch_bounds__(64) make_kernel(State s) {
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= s.n) return;
-    fresh_chain(s, env);
-    fresh_live(s, env);
-}
+struct Step {  // pg_prefetch.h logic_step<Gen, Step>: a lane per env, nothing in LDS
+    static constexpr int kGang = 1;
+    struct Lds {};
+    PG_D static void advance(const State& s, Lds&, int, int env, int action, float& reward, bool& terminated) {
+        jumper::advance(s, env, action, reward, terminated);
+    }
+};
 
 __global__ void __launch_bounds__(64) logic_kernel(State s, const int32_t* actions, uint32_t run_seed,
                                                    uint32_t step_index, int env_offset, StepIO io, int prefetch, LevelPlan plan) {
-    if (blockIdx.y == 1) {  // (block-uniform) the auto-resets whose level lies ready: a copy, beside the envs that step (pg_prefetch.h)
-        __shared__ Level lv;
-        install_prefetched<Gen>(s, blockIdx.x * blockDim.x, blockDim.x, prefetch, io, plan, lv, threadIdx.x, reset_served_mark(step_index), reset_due_mark(step_index));
-        return;
-    }
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= s.n) return;
-    if (resets_in_step(io.pending[env], step_index)) return;  // this step is the env's reset (pg_prefetch.h: who serves it, and the byte)
-    const int action =
-        actions ? actions[env] : synthetic_action(run_seed, step_index, static_cast<uint32_t>(env_offset + env));
-    float reward;
-    bool terminated;
-    advance(s, env, action, reward, terminated);
-    io.reward[env] = reward;
-    io.done[env] = terminated ? 1 : 0;
-    io.pending[env] = terminated ? static_cast<uint8_t>(reset_due_mark(step_index + 1u)) : 0;  // (pg_prefetch.h: the byte)
+    logic_step<Gen, Step>(s, actions, run_seed, step_index, env_offset, io, prefetch, plan);
 }
 
 // render_game(true) (jumper.cpp:445-509): one workgroup of two wavefronts per env (pg_render.h).
@@ -1229,20 +1215,11 @@ __device__ void frame_draws(const State& s, const AtlasView& atlas, int env, Pai
     }
 }
 
-// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
-__global__ void __launch_bounds__(kFrameThreads) frame_kernel(State s, AtlasView atlas, int env, FrameTarget t) {
-    FramePainter P(t);
-    frame_draws(s, atlas, env, P);
-}
-
-// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames (pg_frame.h).
-__global__ void __launch_bounds__(kFrameThreads) frames_kernel(State s, AtlasView atlas, FrameBatch fb) {
-    __shared__ uint32_t tile[kTilePx];
-    TilePainter P(tile, fb);
-    const int env = P.env(fb);
-    if (env >= 0) frame_draws(s, atlas, env, P);
-    P.store(fb);
-}
+struct Frames {  // pg_frame.h frame_kernel<Frames> / frames_kernel<Frames>
+    using State = jumper::State;
+    template <class Painter>
+    static __device__ void draws(const State& s, const AtlasView& atlas, int env, Painter& P) { frame_draws(s, atlas, env, P); }
+};
 
 // The state row (pg_state_obs.h): oracle/pgo_jumper.cpp Jumper::dump_state, column by column.  The 21 scalars come from the
 // field arrays; the puffs and the spike records — a spike stands in the middle of its cell — from each env's own tables.
@@ -1301,7 +1278,7 @@ struct PathRow {
     static constexpr int kGoalX = 18, kGoalY = 19;
 };
 
-class JumperGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow> {
+class JumperGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathRow, Frames> {
    public:
     const char* name() const override { return "jumper"; }
     std::vector<std::string> texture_names() const override {
@@ -1441,27 +1418,12 @@ class JumperGame final : public ViewedGame<PrefetchingGame<Gen>, StateRow, PathR
         s_.n = n;
         atlas_ = atlas;
     }
-    int blocks() const { return (s_.n + 63) / 64; }
     void launch_make(hipStream_t st, uint32_t seed_base, int env_offset) override {
-        hipLaunchKernelGGL(make_kernel, dim3(blocks()), dim3(64), 0, st, s_);
         make_levels(st, seed_base, env_offset);
     }
     void launch_logic(hipStream_t st, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
                       StepIO io) override {
-        // prefetched levels are installed beside the logic (its second row of blocks); the level kernel behind it
-        // generates, synchronously, the levels that were not ready — none in steady state (pg_prefetch.h install_prefetched)
-        const bool fused = prefetch() != 0;
-        reset_before_logic(st, step_index, io);
-        hipLaunchKernelGGL(logic_kernel, dim3((s_.n + 63) / 64, fused ? 2 : 1), dim3(64), 0, st, s_, actions, run_seed, step_index,
-                           env_offset, io, prefetch(), plan);
-        reset_after_logic(st, step_index, io);
-    }
-    bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
-        hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(kFrameThreads), 0, st, s_, atlas_, env, FrameTarget{d_px, w, h});
-        return true;
-    }
-    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
-        launch_frames_tiled(frames_kernel, st, s_, atlas_, d_indices, count, d_rgb, w, h, s_.n);
+        launch_fused_logic(logic_kernel, Step::kGang, st, actions, run_seed, step_index, env_offset, io);
     }
     static void carve_scratch(Carve& c, State& s, int n) {
         prep_carve(c, s.prep, n, kGrid, kBlitWords, true);

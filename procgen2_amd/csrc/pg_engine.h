@@ -311,5 +311,16 @@ PG_HD int synthetic_action(uint32_t run_seed, uint32_t step, uint32_t env) {
     uint32_t h = mix32(mix32(step * 0x9E3779B9u + run_seed) ^ (env * 0x85EBCA6Bu + 0xC2B2AE35u));
     return static_cast<int>((static_cast<uint64_t>(h) * 15u) >> 32);
 }
+// The two ends of an env's step in a logic kernel: its action — the caller's, or the synthetic one — and what the step
+// leaves in StepIO.  `mark`: what a terminated env leaves in `pending` (StepIO::pending: 1, 3, or the parity mark of
+// pg_prefetch.h reset_due_mark).
+PG_D int step_action(const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset, int env) {
+    return actions ? actions[env] : synthetic_action(run_seed, step_index, static_cast<uint32_t>(env_offset + env));
+}
+PG_D void step_results(const StepIO& io, int env, float reward, bool terminated, int mark) {
+    io.reward[env] = reward;
+    io.done[env] = terminated ? 1 : 0;
+    io.pending[env] = terminated ? static_cast<uint8_t>(mark) : 0;
+}
 
 }  // namespace pg

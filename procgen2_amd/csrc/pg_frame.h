@@ -1,7 +1,8 @@
 // The human-size frame of cenv_render (games/*/<game>.cpp `render_game(false)`): the same draw list as
 // the observation, rasterised at W×H with camera_scale = zoom · W / 64.
 //
-// A game walks its draw list here as `template <class Painter> frame_draws(State, AtlasView, env, Painter&)` — the draws
+// A game walks its draw list here as `template <class Painter> frame_draws(State, AtlasView, env, Painter&)`, which its
+// `Frames` struct hands to the two kernels at the end of this file (frame_kernel<F>, frames_kernel<F>) — the draws
 // themselves are the game's own statements (pg_geom.h DrawCall), shared with its observation paths — and reaches the
 // target only through the painter's methods (begin, clear, draw, draw_rotated, screen, window, desc, cam, width /
 // height, lead).  Two painters take it, with one statement of the raster spec between them (pg_raster.h, which the
@@ -196,15 +197,39 @@ inline long long frame_grid_limit() {
     return limit;
 }
 
-// A game's frames_kernel over count · tiles blocks, in as many launches as the grid limit asks for.
-template <class Kernel, class State>
-void launch_frames_tiled(Kernel kernel, hipStream_t st, const State& s, const AtlasView& atlas, const int32_t* d_indices,
-                         int count, uint8_t* d_rgb, int w, int h, int n) {
-    FrameBatch fb{d_indices, d_rgb, w, h, tiles_across(w) * tiles_across(h), n, 0};
+// The two kernels, once for every game.  F is the game's `Frames`: `using State`, and `draws(s, atlas, env, P)` — its
+// frame_draws — as a static member template over the painter.
+// One env, one workgroup, a W×H target in global memory: pgv_render_frame.
+template <class F>
+__global__ void __launch_bounds__(kFrameThreads) frame_kernel(typename F::State s, AtlasView atlas, int env, FrameTarget t) {
+    FramePainter P(t);
+    F::draws(s, atlas, env, P);
+}
+
+// The same draw list for one 64×64 tile of one env's frame, a workgroup per (frame, tile): pgv_render_frames.
+template <class F>
+__global__ void __launch_bounds__(kFrameThreads) frames_kernel(typename F::State s, AtlasView atlas, FrameBatch fb) {
+    __shared__ uint32_t tile[kTilePx];
+    TilePainter P(tile, fb);
+    const int env = P.env(fb);
+    if (env >= 0) F::draws(s, atlas, env, P);
+    P.store(fb);
+}
+
+// Their launches (pg_state_obs.h ViewedGame: a game's launch_frame / launch_frames); frames_kernel over count · tiles
+// blocks, in as many launches as the grid limit asks for.
+template <class F>
+void launch_frame_of(hipStream_t st, const typename F::State& s, const AtlasView& atlas, int env, uint32_t* d_px, int w, int h) {
+    hipLaunchKernelGGL(frame_kernel<F>, dim3(1), dim3(kFrameThreads), 0, st, s, atlas, env, FrameTarget{d_px, w, h});
+}
+template <class F>
+void launch_frames_of(hipStream_t st, const typename F::State& s, const AtlasView& atlas, const int32_t* d_indices, int count,
+                      uint8_t* d_rgb, int w, int h) {
+    FrameBatch fb{d_indices, d_rgb, w, h, tiles_across(w) * tiles_across(h), s.n, 0};
     const long long total = static_cast<long long>(count) * fb.tiles, limit = frame_grid_limit();
     for (; fb.b0 < total; fb.b0 += limit)
-        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(launch_blocks(total, fb.b0, limit))), dim3(kFrameThreads), 0, st, s,
-                           atlas, fb);
+        hipLaunchKernelGGL(frames_kernel<F>, dim3(static_cast<unsigned>(launch_blocks(total, fb.b0, limit))), dim3(kFrameThreads), 0,
+                           st, s, atlas, fb);
 }
 
 }  // namespace pg

@@ -318,9 +318,60 @@ PG_D void install_prefetched(const typename G::State& s, int base, int span, int
     }
 }
 
-// Host side of the same: the four launches a prefetching game needs.
+// The whole body of the logic kernel of a game that installs its prefetched levels in its own grid (maze, jumper, climber,
+// caveflyer) — the game's `__global__ logic_kernel` is one call of this and keeps what is its own: its name, its launch
+// bounds, its tuning macros.  Step says how an env steps:
+//     kGang                                       lanes that step ONE env together (pg_gang.h), 1 = a lane per env
+//     Lds                                         what a gang keeps in LDS while it steps (an empty struct: nothing)
+//     advance(s, lds, tid, env, action, reward, terminated)   every lane of the gang; reward and terminated as lane 0 has them
+// Rows of blocks: row 0 steps the envs, row 1 (blockIdx.y == 1, there with prefetch only) is the install row, which covers
+// the envs of the same blockIdx.x of row 0.  This is where the pending byte's protocol is kept ("two races to keep out",
+// above): a lane whose env is due or served in THIS step sits the step out, whichever of the two it saw, and an env that
+// terminates now is marked due for the NEXT step's parity, which this launch's install row does not look for.
+// One block is EITHER a row of gangs stepping their envs (an Lds each) OR the install row (a Level staged on its way from
+// the shadow slot to the live state): the same LDS serves both — as two arrays the logic blocks carried the Level's
+// 2–3 KB for nothing and fewer of them fitted a CU (caveflyer: 11.8 KB a block, 13 blocks instead of 16).
+template <class G, class Step>
+PG_D void logic_step(const typename G::State& s, const int32_t* actions, uint32_t run_seed, uint32_t step_index, int env_offset,
+                     StepIO io, int prefetch, LevelPlan plan) {
+    using Level = typename G::Level;
+    using Lds = typename Step::Lds;
+    constexpr int kGang = Step::kGang, kEnvs = 64 / kGang;  // envs a block steps, and its install row serves
+    static_assert(kGang >= 1 && kGang <= 64 && (kGang & (kGang - 1)) == 0, "a gang is a power of two of lanes within a wavefront");
+    constexpr size_t kLdsBytes = sizeof(Lds) * kEnvs > sizeof(Level) ? sizeof(Lds) * kEnvs : sizeof(Level);
+    __shared__ alignas(16) unsigned char lds_bytes[kLdsBytes];
+    const int tid = threadIdx.x;
+    if (blockIdx.y == 1) {  // (block-uniform) the auto-resets whose level lies ready: a copy, beside the envs that step
+        install_prefetched<G>(s, blockIdx.x * kEnvs, kEnvs, prefetch, io, plan, *reinterpret_cast<Level*>(lds_bytes), tid,
+                              reset_served_mark(step_index), reset_due_mark(step_index));
+        return;
+    }
+    const int env = (blockIdx.x * 64 + tid) / kGang;
+    if (env >= s.n) return;
+    if (resets_in_step(io.pending[env], step_index)) return;  // this step is the env's reset
+    const int action = step_action(actions, run_seed, step_index, env_offset, env);
+    float reward = 0.0f;
+    bool terminated = false;
+    Step::advance(s, reinterpret_cast<Lds*>(lds_bytes)[tid / kGang], tid, env, action, reward, terminated);
+    if ((tid & (kGang - 1)) == 0) step_results(io, env, reward, terminated, reset_due_mark(step_index + 1u));
+}
+
+// What cenv_make leaves in every env besides its RNG and level 0 (fresh_chain, fresh_live), a lane per env: in front of the
+// level kernel's mode 0.
+template <class G>
+__global__ void __launch_bounds__(64) fresh_kernel(typename G::State s) {
+    const int env = blockIdx.x * 64 + threadIdx.x;
+    if (env >= s.n) return;
+    G::fresh_chain(s, env);
+    G::fresh_live(s, env);
+}
+
+// Host side of the same: the launches a prefetching game needs.
 template <class G>
 struct LevelLaunch {
+    static void fresh(hipStream_t st, const typename G::State& s) {
+        hipLaunchKernelGGL(fresh_kernel<G>, dim3((s.n + 63) / 64), dim3(64), 0, st, s);
+    }
     static void make(hipStream_t st, const typename G::State& s, int prefetch, uint32_t seed_base, int env_offset,
                      LevelPlan plan) {
         hipLaunchKernelGGL(level_kernel<G>, dim3(s.n), dim3(64), 0, st, s, 0, 1, prefetch, seed_base, env_offset,
@@ -375,8 +426,22 @@ class PrefetchingGame : public BoundGame<typename G::State> {
 
    protected:
     int prefetch() const { return (debug_flags & kDebugNoPrefetch) ? 0 : 1; }
+    // kFresh: the game's fresh_chain / fresh_live leave something (maze's leave nothing: no launch, no kernel)
+    template <bool kFresh = true>
     void make_levels(hipStream_t st, uint32_t seed_base, int env_offset) {
+        if constexpr (kFresh) LevelLaunch<G>::fresh(st, s_);
         LevelLaunch<G>::make(st, s_, prefetch(), seed_base, env_offset, plan);
+    }
+    // The launch of a logic kernel that is logic_step (`gang`: its Step::kGang): prefetched levels are installed beside
+    // the logic (its second row of blocks); the level kernel behind it generates, synchronously, the levels that were
+    // not ready — none in steady state (install_prefetched).
+    template <class Kernel>
+    void launch_fused_logic(Kernel kernel, int gang, hipStream_t st, const int32_t* actions, uint32_t run_seed,
+                            uint32_t step_index, int env_offset, StepIO io) {
+        reset_before_logic(st, step_index, io);
+        hipLaunchKernelGGL(kernel, dim3((s_.n * gang + 63) / 64, prefetch() ? 2 : 1), dim3(64), 0, st, s_, actions, run_seed,
+                           step_index, env_offset, io, prefetch(), plan);
+        reset_after_logic(st, step_index, io);
     }
     void reset_before_logic(hipStream_t st, uint32_t step_index, StepIO io) {
         if (!prefetch()) auto_reset(st, step_index, io);

@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "pg_engine.h"
+#include "pg_frame.h"
 
 namespace pg {
 
@@ -159,10 +160,18 @@ struct HasTileMap<Row, decltype(static_cast<void>(&Row::map))> {
 };
 
 // The host side of the read-only views, written once: a game's class derives from ViewedGame<Base, its StateRow, its PathRow
-// or void> — Base: whatever it derived from otherwise, a BoundGame (pg_engine.h) — and has all six.
-template <class Base, class Row, class Points>
+// or void, its Frames> — Base: whatever it derived from otherwise, a BoundGame (pg_engine.h) — and has all six, and the
+// human-size frames (pg_frame.h), which are one more read-only view of the state.
+template <class Base, class Row, class Points, class Frames>
 class ViewedGame : public Base {
    public:
+    bool launch_frame(hipStream_t st, int env, uint32_t* d_px, int w, int h) override {
+        launch_frame_of<Frames>(st, this->s_, this->atlas_, env, d_px, w, h);
+        return true;
+    }
+    void launch_frames(hipStream_t st, const int32_t* d_indices, int count, uint8_t* d_rgb, int w, int h) override {
+        launch_frames_of<Frames>(st, this->s_, this->atlas_, d_indices, count, d_rgb, w, h);
+    }
     StateLayout state_layout() const override { return state_layout_of<Row>(map()); }
     std::string state_names() const override { return Row::names(); }
     void launch_state_rows(hipStream_t st, const int32_t* d_indices, int count, float* d_rows, int32_t* d_lengths) override {

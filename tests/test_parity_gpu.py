@@ -209,6 +209,45 @@ def test_pre_pass_with_a_partly_filled_last_workgroup(game):
         e.close()
 
 
+@pytest.mark.parametrize("game,seed_base", [("maze", 31), ("jumper", 22), ("climber", 2), ("caveflyer", 12)])
+def test_logic_shell_with_a_partly_filled_last_block(game, seed_base):
+    """The four games whose logic kernel is pg_prefetch.h logic_step — the install row beside the stepping envs — at a size
+    that is no multiple of 64, which no other lock-step runs: 67 envs.  A lane per env (maze, jumper): the second block has
+    three live lanes; a gang of eight per env (climber, caveflyer): the ninth block has three gangs; the install row's last
+    block has a span that runs past n in both.  Two engines on the same seeds, one plain and one without prefetch (bit 8:
+    every reset through the level kernel in front of the logic), against the oracle: a reset of every env, then 60
+    synthetic steps: observations, reward bits and dones at every step, state and tiles of envs 63 to 66 after the last.
+    (An OracleVec has had its first reset when it is made, so the engines' first reset only catches up with it; the reset
+    of all three is the one after.)  The seeds are chosen so that an env of the partly filled block (64..66) ends an
+    episode before step 58 — its reset and the steps after it ran in that block: maze (6, 64), (19, 65); jumper (7, 64),
+    (15, 66), (22, 66); climber (12, 66), (42, 66); caveflyer (7, 65), as (step, env).  Asserted on the oracle's dones: a
+    condition on the inputs."""
+    n = 67
+    engines = [EngineVec(game, n, seed_base=seed_base) for _ in range(2)]
+    engines[1].set_debug(256)
+    ora = OracleVec(game, n, seed_base=seed_base)
+    for first in (True, False):
+        want = ora.reset_obs() if first else ora.reset()
+        for k, eng in enumerate(engines):
+            assert np.array_equal(eng.reset(), want), "reset frame, engine %d" % k
+    ended_in_last_block = False
+    for s in range(60):
+        oo, ro, do = ora.step(None, run_seed=12)
+        ended_in_last_block = ended_in_last_block or (s < 58 and bool(do[64:].any()))
+        for k, eng in enumerate(engines):
+            oe, re_, de = eng.step(None, run_seed=12)
+            assert np.array_equal(de, do), "done, step %d, engine %d" % (s, k)
+            assert np.array_equal(re_.view(np.uint32), ro.view(np.uint32)), "reward bits, step %d, engine %d" % (s, k)
+            assert np.array_equal(oe, oo), "obs, step %d, engine %d: envs %s" % (s, k, np.nonzero((oe != oo).any(axis=1))[0][:8])
+    assert ended_in_last_block, "no env of 64..66 ended an episode before step 58"
+    for k, eng in enumerate(engines):
+        for e in range(63, n):
+            assert_same_dump(eng.state(e), ora.state(e), "state env %d, engine %d" % (e, k))
+            assert_same_dump(eng.tiles(e), ora.tiles(e), "tiles env %d, engine %d" % (e, k))
+        eng.close()
+    ora.close()
+
+
 def test_coinrun_other_seeds_and_action_stream():
     _lockstep("coinrun", 64, 300, seed_base=4294967000, run_seed=9)  # seeds wrap through 2^32 like `unsigned long`→u32
 

@@ -18,8 +18,8 @@ for line in sys.stdin:
         if m: d[key]=int(m.group(1))
     if 'LDS Size' in line and name:
         short=re.sub(r'^_ZN2pg8variant0\d+[a-z]+\d+','',name)[:28]
-        if '$G'=='engine':  # templates: the demangled name without its arguments, 'policy_push_kernel<4, 3>'
-            short=re.sub(r'^(void )?pg::|\(.*','',subprocess.run(['c++filt',name],capture_output=True,text=True).stdout.strip())
+        if '$G'=='engine' or short.startswith('_Z'):  # templates: the demangled name without its arguments, 'policy_push_kernel<4, 3>', 'fresh_kernel<climber::Gen>'
+            short=re.sub(r'^(void )?pg::|pg::variant0::|\(.*','',subprocess.run(['c++filt',name],capture_output=True,text=True).stdout.strip())
         print('%-10s %-30s vgpr %3d sgpr %3d scratch %4d spill %3d occupancy %d lds %d' % ('$G',short,d.get('VGPRs',0),d.get('TotalSGPRs',0),d.get('ScratchSize \[bytes/lane\]',0),d.get('VGPRs Spill',0),d.get('Occupancy \[waves/SIMD\]',0),d.get('LDS Size \[bytes/block\]',0)))
 "
 done
