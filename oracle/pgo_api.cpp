@@ -321,6 +321,19 @@ void pgo_vec_set_render(void* h, int on) {
     for (Env* e : v->envs) e->set_render_enabled(on != 0);
 }
 
+// TEST-ONLY (Env::set_fresh_containers): from now on every env of the batch starts its levels with newly constructed entity
+// sets.  A wrong oracle on purpose, never part of a config: tests/chain_util.py runs it beside the good one to show that a
+// protocol reaches states in which the carried bucket counts matter.  `mask` nullptr = every env.
+void pgo_vec_set_fresh_containers(void* h, const uint8_t* mask, int on) {
+    auto* v = static_cast<VecState*>(h);
+    for (size_t i = 0; i < v->envs.size(); i++)
+        if (!mask || mask[i]) v->envs[i]->set_fresh_containers(on != 0);
+}
+
+void pgo_set_fresh_containers(void* h, int on) {  // the same for a single env (pgo_make): tests/assign_util.py
+    static_cast<Env*>(h)->set_fresh_containers(on != 0);
+}
+
 void pgo_vec_reset_threads(void* h, int threads) {  // pgo_vec_reset(h, nullptr, nullptr) by `threads` threads
     auto* v = static_cast<VecState*>(h);
     const int n = static_cast<int>(v->envs.size());

@@ -77,8 +77,7 @@ class Bossfight final : public Env {
 
     void new_level() override {  // bossfight.cpp:426-504
         ids_.refill();
-        in_hazard_.clear();
-        in_sprite_.clear();
+        clear_sets(in_hazard_, in_sprite_);
         const V2 cs = painter_.cam_size;  // D15: whatever the last render left (64 / 1.0 for observation-only use)
         const float sc = painter_.cam_scale;
 

@@ -134,11 +134,7 @@ class Caveflyer final : public Env {
 
     void new_level() override {  // caveflyer.cpp:442-460
         ids_.refill();
-        in_sprite_.clear();
-        in_tilemap_.clear();
-        in_hazard_.clear();
-        in_mob_.clear();
-        in_goal_.clear();
+        clear_sets(in_sprite_, in_tilemap_, in_hazard_, in_mob_, in_goal_);
         n_things_ = 0;
 
         // tilemap.cpp:118-278

@@ -129,9 +129,7 @@ class Chaser final : public Env {
 
     void new_level() override {  // chaser.cpp:418-443
         ids_.refill();
-        in_sprite_.clear();
-        in_point_.clear();
-        in_mob_.clear();
+        clear_sets(in_sprite_, in_point_, in_mob_);
         n_things_ = 0;
 
         // tilemap.cpp:80-243

@@ -135,11 +135,7 @@ class Climber final : public Env {
 
     void new_level() override {  // climber.cpp:461-497
         ids_.refill();
-        in_sprite_.clear();
-        in_tilemap_.clear();
-        in_mob_.clear();
-        in_point_.clear();
-        in_agent_.clear();
+        clear_sets(in_sprite_, in_tilemap_, in_mob_, in_point_, in_agent_);
         n_things_ = 0;
 
         // tilemap.cpp:75-170

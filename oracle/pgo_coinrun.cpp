@@ -339,13 +339,7 @@ void Coinrun::build_level() {  // tilemap.cpp:97-292
 
 void Coinrun::new_level() {  // coinrun.cpp:472-507
     ids_.refill();  // ecs.cpp:52-97 clear_entities: sets keep their bucket arrays
-    in_sprite_.clear();
-    in_tilemap_.clear();
-    in_mob_.clear();
-    in_hazard_.clear();
-    in_goal_.clear();
-    in_agent_.clear();
-    in_sparks_.clear();
+    clear_sets(in_sprite_, in_tilemap_, in_mob_, in_hazard_, in_goal_, in_agent_, in_sparks_);
 
     build_level();
 

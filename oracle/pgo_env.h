@@ -48,6 +48,12 @@ class Env {
     void set_mode(int mode) { mode_ = mode; }
     // include/procgen2_vec.h pgv_config.game_flags (coinrun: PGV_COINRUN_NO_*).  Set before make().
     void set_flags(uint32_t flags) { flags_ = flags; }
+    // TEST-ONLY, off by default, and no part of any config the engine sees: from the next new_level() on, every entity set
+    // the game clears at a new level is a newly constructed one instead, so its bucket array starts at one bucket as a
+    // fresh env's would.  The reference never does this (ecs.cpp clear_entities keeps the arrays); the switch makes a
+    // WRONG oracle, the counterexample that shows a test of the carried bucket counts is not vacuous (tests/chain_util.py).
+    // The rng stream, the id pool, the camera and everything else stay as they are.
+    void set_fresh_containers(bool on) { fresh_containers_ = on; }
 
     // cenv_render (coinrun.cpp:393-411): render_game(false) into a width×height target, packed RGB.  Like the
     // reference it leaves the camera scale/size at the window's values afterwards: the next observation render sets
@@ -86,6 +92,15 @@ class Env {
     virtual void advance(int action) = 0;  // the sub-step loop of cenv_step
     virtual void paint() = 0;           // render_game(true)
 
+    // `set.clear()` of the game's reset(): keeps the bucket array, as libstdc++ does — unless the test-only switch is on.
+    template <class... Sets>
+    void clear_sets(Sets&... sets) {
+        if (fresh_containers_)
+            ((sets = IdSet()), ...);
+        else
+            (sets.clear(), ...);
+    }
+
     void observe() {
         if (!painter_.enabled) return;  // logic-only traces: no textures needed
         paint();
@@ -94,6 +109,7 @@ class Env {
 
     int mode_ = kHard;
     uint32_t flags_ = 0;
+    bool fresh_containers_ = false;
     int view_w_ = kObsW, view_h_ = kObsH;  // `width`, `height` of render_game(is_obs): the target being painted
     Rng rng_;
     Surface surface_;

@@ -129,7 +129,7 @@ class Jumper final : public Env {
 
     void new_level() override {  // jumper.cpp:511-533
         spikes_.clear();
-        in_sprite_.clear();
+        clear_sets(in_sprite_);
         ids_.refill();
 
         // tilemap.cpp:79-253

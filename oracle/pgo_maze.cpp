@@ -66,10 +66,7 @@ class Maze final : public Env {
 
     void new_level() override {  // maze.cpp:416-438
         ids_.refill();
-        in_sprite_.clear();
-        in_goal_.clear();
-        in_agent_.clear();
-        in_tilemap_.clear();
+        clear_sets(in_sprite_, in_goal_, in_agent_, in_tilemap_);
 
         // tilemap.cpp:31-109
         std::fill(tiles_.begin(), tiles_.end(), kWall);

@@ -35,12 +35,13 @@ class AssignModel:
     """N envs with the engine's auto-reset policy, level set and assignments; after construction every env has had its
     first reset (as OracleVec has)."""
 
-    def __init__(self, game, n, seed_base=1, num_levels=0, start_level=0):
+    def __init__(self, game, n, seed_base=1, num_levels=0, start_level=0, mode=0):
+        """mode: the distribution mode (0: the game's default), of the envs and of every level made by number."""
         register_textures(game)
         self.L = oracle()
-        self.game, self.n = game, n
+        self.game, self.n, self.mode = game, n, mode
         self.num_levels, self.start_level = num_levels, start_level
-        self.h = [self.L.pgo_make(game.encode(), (seed_base + i) & 0xFFFFFFFF, 1) for i in range(n)]  # level 0, never observed
+        self.h = [self.L.pgo_make_mode(game.encode(), (seed_base + i) & 0xFFFFFFFF, 1, mode) for i in range(n)]  # level 0, never observed
         self.chain_seed = [(seed_base + i) & 0xFFFFFFFF for i in range(n)]
         self.drawn = [1 if num_levels > 0 else 0] * n  # (the engine's make draws a number for its hidden level too)
         self.assigned = [None] * n
@@ -58,7 +59,7 @@ class AssignModel:
 
     def _remake(self, i, number):
         self.L.pgo_close(self.h[i])
-        self.h[i] = self.L.pgo_make(self.game.encode(), number, 1)
+        self.h[i] = self.L.pgo_make_mode(self.game.encode(), number, 1, self.mode)
         self.L.pgo_present(self.h[i])
 
     def _new_level(self, i, restart, seed, auto=False):

@@ -87,6 +87,10 @@ def oracle():
     L.pgo_vec_reset.argtypes = [c_void_p, c_void_p, c_void_p]
     L.pgo_vec_close.argtypes = [c_void_p]
     L.pgo_vec_set_render.argtypes = [c_void_p, c_int]
+    L.pgo_vec_set_fresh_containers.argtypes = [c_void_p, c_void_p, c_int]
+    L.pgo_vec_set_fresh_containers.restype = None
+    L.pgo_set_fresh_containers.argtypes = [c_void_p, c_int]
+    L.pgo_set_fresh_containers.restype = None
     L.pgo_vec_step.argtypes = [c_void_p, c_void_p, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.pgo_vec_run.argtypes = [c_void_p, c_int, c_uint32, c_int, c_void_p]
     L.pgo_vec_run.restype = None
@@ -201,6 +205,13 @@ class OracleVec:
     def set_render(self, on):
         """Drawing on / off from the next step on (logic is unaffected; obs is only meaningful for steps drawn)."""
         self.L.pgo_vec_set_render(self.h, 1 if on else 0)
+
+    def set_fresh_containers(self, on=True, mask=None):
+        """TEST-ONLY, a WRONG oracle on purpose: from now on the envs named (all of them without a mask) start every level
+        with newly constructed entity sets instead of cleared ones (oracle/pgo_env.h).  The counterexample of
+        tests/chain_util.py; nothing the engine is held to."""
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        self.L.pgo_vec_set_fresh_containers(self.h, None if m is None else m.ctypes.data_as(c_void_p), 1 if on else 0)
 
     def state(self, env, cap=None):
         """The env's whole state vector (Env::dump_state), or its first `cap` floats when a cap is given."""

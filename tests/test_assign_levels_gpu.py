@@ -21,11 +21,11 @@ PREFETCHING = ("coinrun", "maze", "climber", "caveflyer", "jumper")
 class Engine:
     """ProcgenVecEnv driven with host arrays, as the model is."""
 
-    def __init__(self, game, n, seed_base=1, num_levels=0, start_level=0, debug=0):
+    def __init__(self, game, n, seed_base=1, num_levels=0, start_level=0, debug=0, distribution_mode=0):
         import torch
         from procgen2_amd.vec_env import ProcgenVecEnv
         self.torch = torch
-        self.v = ProcgenVecEnv(game, n, seed_base=seed_base, num_levels=num_levels, start_level=start_level)
+        self.v = ProcgenVecEnv(game, n, seed_base=seed_base, num_levels=num_levels, start_level=start_level, distribution_mode=distribution_mode)
         self.n = n
         if debug:
             assert self.v.L.pgv_set_debug(self.v._h, debug) == 0

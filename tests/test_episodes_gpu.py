@@ -34,11 +34,11 @@ LIMIT_CASES = [(g, 23) for g in GAMES] + [("chaser", 60)]
 class Engine:
     """ProcgenVecEnv with episodes, driven with host arrays and read back as numpy, as the model is."""
 
-    def __init__(self, game, n, mode, max_episode_steps=0, final_capacity=0, distribution_mode=0):
+    def __init__(self, game, n, mode, max_episode_steps=0, final_capacity=0, distribution_mode=0, seed_base=1):
         import torch
         from procgen2_amd.vec_env import ProcgenVecEnv
         self.torch = torch
-        self.v = ProcgenVecEnv(game, n, seed_base=1, autoreset_mode=mode, max_episode_steps=max_episode_steps,
+        self.v = ProcgenVecEnv(game, n, seed_base=seed_base, autoreset_mode=mode, max_episode_steps=max_episode_steps,
                                final_obs_capacity=final_capacity, distribution_mode=distribution_mode)
         self.n = n
 
