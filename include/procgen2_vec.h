@@ -532,6 +532,60 @@ PGV_API int32_t pgv_history_gather_aug(pgv_env* env, const int64_t* d_pushes, co
 /* The draws of entry `entry` under `aug` (host, pure, no GPU, env not needed): h_params8[0..7] as `params` rows are. */
 PGV_API int32_t pgv_gather_aug_params(const pgv_gather_aug* aug, int32_t entry, int32_t* h_params8);
 
+/* Filtered gathers: the augmented gather's row, flipped and turned, then through a small filter in float32 — the
+ * augmentations that change values, mix colour planes or mix neighbouring pixels (random convolution / network
+ * randomisation, colour jitter's linear parts, grayscale, brightness, blur), in the gather's one pass and with an exact
+ * arithmetic definition.  The existing gathers and their bytes are as they were.
+ *
+ *   1. Input image.  For an entry and a frame slot, A_c(y, x) is the u8 image, H' x W' per plane c, that
+ *      pgv_history_gather_aug gives with PGV_POLICY_U8 for the same `aug`: the same walk, draws, window, edge rule and
+ *      cutout.  aug = NULL stands for H' = W' = 64, pad 0, no cutout, seed 0 and no params.
+ *   2. Flip and rotation, index-only and off by default.  With `flip` set f = word(7) >> 31, else 0; with `rot90` set
+ *      r = draw(4, 8), else 0 (refused unless H' = W'); word and draw are point 2 of the augmented gathers.  The image the
+ *      filter sees is G = rot90(A[..., ::-1] if f else A, r) over the last two axes, numpy's rot90: r quarter turns
+ *      counter-clockwise, G(y, x) = A'(x, W'-1-y) for r = 1.  One draw per entry, shared by its K frames and all planes.
+ *      params[e][7] = f | r << 1, 0 where neither is set, so the row keeps its meaning; pgv_gather_filter_params gives the
+ *      row on the host.
+ *   3. Values.  v_c(y, x) is the float32 value of byte G_c(y, x) under the policy observations' value rule,
+ *      float(byte) / 255.0f; outside 0 .. H'-1 x 0 .. W'-1 it is +0.0f: the zero padding of the published random-conv layer.
+ *   4. The filter.  kernel k is 1 or 3; weights float32 [C][C][k][k], indexed (output plane o, input plane i, ky, kx), C the
+ *      ring's planes (3, or 1 for gray); one set for the call (weights_stride = 0) or one per entry (weights_stride =
+ *      C*C*k*k floats, entry e's at weights + e*stride); bias float32 [C] with the same rule (bias_stride 0 or C), or NULL.
+ *          acc = bias ? bias[o] : +0.0f
+ *          for i in 0 .. C-1, ky in 0 .. k-1, kx in 0 .. k-1 (this order):
+ *              acc = acc + w[o][i][ky][kx] * v_i(y + ky - k/2, x + kx - k/2)
+ *      every product and every sum its own float32 rounding, nothing fused.  With `clamp` set acc = acc < lo ? lo :
+ *      acc > hi ? hi : acc.  The element is acc as float32, or rounded once to nearest-even to binary16 or bfloat16, with
+ *      IEEE subnormals and overflow to infinity.  For finite weights; with others the values are unspecified, nothing faults.
+ *   5. An entry that is not held, or whose env is outside the batch, gives a row of zero bytes, bias or not.
+ *   6. Laws.  With kernel = 1, the identity matrix, no bias, clamp, flip or rotation the output equals
+ *      pgv_history_gather_aug's bit for bit in the three float dtypes.  The call changes nothing and a second call gives the
+ *      same bytes.
+ *   7. Checked on the host before anything is enqueued, each refusal leaving a message and the engine as it was: everything
+ *      pgv_history_gather_aug refuses (of a non-NULL aug); filter NULL or its struct_size too small; kernel not 1 or 3;
+ *      weights NULL; a stride other than the two allowed; weights or bias not 4-byte aligned; rot90 with H' != W';
+ *      PGV_POLICY_U8 (a filtered value is not a byte); clamp with lo > hi or a NaN bound.  count = 0 succeeds and does
+ *      nothing.  The call is enqueued on the env's stream, allocates nothing, does not synchronise.  The caller's tensors
+ *      hold one set, or `count` sets where the stride is not 0. */
+typedef struct pgv_gather_filter {
+    uint32_t struct_size;
+    int32_t kernel;         /* 1 or 3 */
+    const float* weights;   /* device float32 [C][C][kernel][kernel], (o, i, ky, kx) */
+    const float* bias;      /* device float32 [C] or NULL */
+    int32_t weights_stride; /* 0: one set for the call; C*C*kernel*kernel: one per entry */
+    int32_t bias_stride;    /* 0 or C */
+    int32_t clamp;          /* not 0: clamp to lo .. hi */
+    float lo, hi;
+    int32_t flip, rot90;    /* not 0: draw a mirror image / a number of quarter turns per entry */
+} pgv_gather_filter;
+PGV_API int32_t pgv_history_gather_filter(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count,
+                                          int32_t stack, int32_t dtype, const pgv_gather_aug* aug /* or NULL */,
+                                          const pgv_gather_filter* filter, void* d_out);
+/* The params row of entry `entry` (host, pure, no GPU), the RGB form: pgv_gather_aug_params' with word 7 = f | r << 1.
+ * Checks `aug` (or NULL) as that does, filter's struct_size and the rot90 rule; reads no pointer of `filter`. */
+PGV_API int32_t pgv_gather_filter_params(const pgv_gather_aug* aug, const pgv_gather_filter* filter, int32_t entry,
+                                         int32_t* h_params8);
+
 /* Transitions on the device: the other half of a rollout beside the frame history — a ring of what every call did (the
  * action, the reward, how it ended), the n-step transition gather of replay learners and the GAE recurrence of on-policy
  * ones, each one launch.  The engine is the only party that knows, without a look from the host, the action of a synthetic

@@ -17,6 +17,7 @@
 #include "pg_order.h"
 #include "pg_history.h"
 #include "pg_history_aug.h"
+#include "pg_history_filter.h"
 #include "pg_transitions.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
@@ -1227,6 +1228,53 @@ int32_t pgv_history_gather_aug(pgv_env* e, const int64_t* d_pushes, const int32_
     if (q.g.count == 0) return 0;
     q.params = aug->params;
     pg::launch_history_gather_aug(e->stream, q, pg::policy_element_bytes(dtype));
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// What both filtered calls check of `filter` without a ring, and the aug that a NULL one stands for.
+static const pgv_gather_aug* gather_filter_aug(const pgv_gather_aug* aug, pgv_gather_aug& whole) {
+    whole = pgv_gather_aug{sizeof(pgv_gather_aug), pg::kObsH, pg::kObsW, 0, PGV_AUG_EDGE_REPLICATE, 0, 0, PGV_AUG_CUTOUT_BLACK, 0u, nullptr};
+    return aug ? aug : &whole;
+}
+static int32_t gather_filter_config(const char* who, const pgv_gather_filter* filter, pg::FilterConfig& f) {
+    if (!filter || filter->struct_size < sizeof(pgv_gather_filter)) return fail(std::string(who) + ": filter is NULL or struct_size too small");
+    f = pg::FilterConfig{filter->kernel, (filter->flip ? pg::kFilterFlip : 0) | (filter->rot90 ? pg::kFilterRot90 : 0), filter->clamp != 0,
+                         filter->lo, filter->hi, filter->weights_stride, filter->bias_stride};
+    return 0;
+}
+
+int32_t pgv_gather_filter_params(const pgv_gather_aug* aug, const pgv_gather_filter* filter, int32_t entry, int32_t* h_params8) {
+    const char* who = "pgv_gather_filter_params";
+    pgv_gather_aug whole;
+    pg::AugConfig cfg{};
+    pg::FilterConfig f{};
+    if (gather_aug_config(who, gather_filter_aug(aug, whole), cfg) || gather_filter_config(who, filter, f)) return 1;
+    if ((f.turns & pg::kFilterRot90) && cfg.out_h != cfg.out_w) return fail(std::string(who) + ": rot90 needs out_height = out_width");
+    if (entry < 0) return fail(std::string(who) + ": entry is negative");
+    if (!h_params8) return fail(std::string(who) + ": params8 is NULL");
+    pg::aug_params_row(pg::aug_params(cfg, static_cast<uint32_t>(entry)), 3, h_params8);
+    h_params8[7] = pg::filter_turn(cfg.seed, static_cast<uint32_t>(entry), f.turns);
+    return 0;
+}
+
+int32_t pgv_history_gather_filter(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype,
+                                  const pgv_gather_aug* aug, const pgv_gather_filter* filter, void* d_out) {
+    const char* who = "pgv_history_gather_filter";
+    pgv_gather_aug whole;
+    aug = gather_filter_aug(aug, whole);
+    pg::HistoryGatherFilter q{};
+    if (gather_arguments(who, e, d_pushes, d_envs, count, stack, dtype, d_out, q.g, aug, &q.cfg)) return 1;
+    if (gather_filter_config(who, filter, q.f)) return 1;
+    if (const char* why = pg::filter_config_error(q.f, e->hist.planes, q.cfg.out_h, q.cfg.out_w)) return fail(std::string(who) + ": " + why);
+    if (!filter->weights) return fail(std::string(who) + ": weights is NULL");
+    if ((reinterpret_cast<uintptr_t>(filter->weights) | reinterpret_cast<uintptr_t>(filter->bias)) & 3u)
+        return fail(std::string(who) + ": weights and bias must be 4-byte aligned");
+    if (dtype == pg::kPolicyU8) return fail(std::string(who) + ": dtype uint8 is refused: a filtered value is not a byte");
+    if (q.g.count == 0) return 0;
+    q.g.table = e->hist.table + pg::kPolicyF32 * 256;  // a byte's float32, whatever the elements are
+    q.params = aug->params, q.weights = filter->weights, q.bias = filter->bias, q.bf16 = dtype == pg::kPolicyBF16;
+    pg::launch_history_gather_filter(e->stream, q, pg::policy_element_bytes(dtype));
     PG_HIP(hipGetLastError());
     return 0;
 }

@@ -227,6 +227,19 @@ def gather_aug(out_height, out_width, pad=0, edge="replicate", cutout_min=0, cut
                      int(seed) & 0xFFFFFFFF, params)
 
 
+class GatherFilter(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_gather_filter`."""
+    _fields_ = [("struct_size", c_uint32), ("kernel", c_int32), ("weights", c_void_p), ("bias", c_void_p), ("weights_stride", c_int32),
+                ("bias_stride", c_int32), ("clamp", c_int32), ("lo", c_float), ("hi", c_float), ("flip", c_int32), ("rot90", c_int32)]
+
+
+def gather_filter(kernel, weights, bias=None, weights_stride=0, bias_stride=0, clamp=None, flip=False, rot90=False):
+    """A filled-in GatherFilter.  weights, bias: device pointers (integers) or None; clamp: None or (lo, hi)."""
+    lo, hi = (0.0, 0.0) if clamp is None else clamp
+    return GatherFilter(ctypes.sizeof(GatherFilter), int(kernel), weights, bias, int(weights_stride), int(bias_stride), int(clamp is not None),
+                        float(lo), float(hi), int(bool(flip)), int(bool(rot90)))
+
+
 # include/procgen2_vec.h PGV_FRAMES_*
 FRAMES = {"last": 0, "none": 1}
 
@@ -371,6 +384,8 @@ def load(path=None):
         "pgv_history_gather": (c_int32, [P, P, P, c_int32, c_int32, c_int32, P]),
         "pgv_history_gather_aug": (c_int32, [P, P, P, c_int32, c_int32, c_int32, POINTER(GatherAug), P]),
         "pgv_gather_aug_params": (c_int32, [POINTER(GatherAug), c_int32, POINTER(c_int32)]),
+        "pgv_history_gather_filter": (c_int32, [P, P, P, c_int32, c_int32, c_int32, POINTER(GatherAug), POINTER(GatherFilter), P]),
+        "pgv_gather_filter_params": (c_int32, [POINTER(GatherAug), POINTER(GatherFilter), c_int32, POINTER(c_int32)]),
         "pgv_transitions_enable": (c_int32, [P, POINTER(TransitionsConfig)]),
         "pgv_transitions_action": (P, [P]),
         "pgv_transitions_reward": (P, [P]),
@@ -425,7 +440,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_step_sequence", "pgv_step_sequence_host", "pgv_render_obs", "pgv_render_obs_host",
     "pgv_policy_obs_enable", "pgv_policy_obs", "pgv_policy_obs_bytes_per_env", "pgv_policy_obs_restart", "pgv_policy_obs_push", "pgv_policy_obs_push_host",
     "pgv_history_enable", "pgv_history_frames", "pgv_history_began", "pgv_history_pending", "pgv_history_head", "pgv_history_capacity", "pgv_history_push",
-    "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params",
+    "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params", "pgv_history_gather_filter", "pgv_gather_filter_params",
     "pgv_transitions_enable", "pgv_transitions_action", "pgv_transitions_reward", "pgv_transitions_flags", "pgv_transitions_gather", "pgv_transitions_gae",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",

@@ -11,6 +11,7 @@ index, so results do not depend on the GPU count).  There is no collective in re
 """
 import collections
 import ctypes
+import math
 import os
 from ctypes import c_void_p
 
@@ -355,7 +356,7 @@ class ProcgenVecEnv:
         self._after()
         return self.history.head - 1
 
-    def history_gather(self, pushes, envs, stack=4, dtype="float16", out=None, augment=None, return_params=False):
+    def history_gather(self, pushes, envs, stack=4, dtype="float16", out=None, augment=None, return_params=False, filter=None):
         """Rows [B, K*C, 64, 64] of `dtype` ("uint8", "float16", "bfloat16", "float32") for the B pairs (pushes[b], envs[b])
         — int64 and int32 device tensors, or anything torch.as_tensor takes: row slot K-1 is the frame of that push, the
         slots in front of it the env's frames before it, never across the start of an episode nor past the oldest push held
@@ -368,8 +369,24 @@ class ProcgenVecEnv:
         and the row's position, on the stored bytes (pgv_history_gather_aug): [B, K*C, H', W'].  size: H' in 1 .. 64, W' in
         8 .. 64 and a multiple of 8; pad 0 .. 16: how far a window may hang over the frame, where `edge` fills in; cutout:
         the range of the rectangle's sides, 1 <= lo <= hi <= 64.  seed is required: the same seed gives the same rows.
-        return_params=True: (rows, params int32 [B, 8]) — oy, ox, cy, cx, ch, cw, colour, 0 of every row."""
+        return_params=True: (rows, params int32 [B, 8]) — oy, ox, cy, cx, ch, cw, colour, 0 of every row.
+
+        filter = None | dict(weights=float32 tensor [C, C, k, k] or [B, C, C, k, k], bias=None | float32 tensor [C] or [B, C],
+        clamp=None | (lo, hi)), and the boolean keys flip= and rot90= of `augment` (rot90 needs H' = W'): the augmented row
+        mirrored and turned by quarter turns, drawn per row, then through the filter in float32 — out[o] = clamp(bias[o] +
+        sum over (i, ky, kx) of weights[o, i, ky, kx] * in[i] at (y + ky - k // 2, x + kx - k // 2)), zero padding, k = 1 or
+        3, one set for the call or one per row (pgv_history_gather_filter; include/procgen2_vec.h has the exact arithmetic).
+        Not for dtype "uint8".  flip or rot90 without filter= uses the identity matrix.  The eighth params word is
+        flip | turns << 1."""
         aug = None if augment is None else _augment_config(augment)
+        turns = (False, False) if augment is None else (bool(augment.get("flip", False)), bool(augment.get("rot90", False)))
+        filtered = filter is not None or (augment is not None and ("flip" in augment or "rot90" in augment))
+        if filtered:
+            if dtype == "uint8":
+                raise ValueError("history_gather: a filtered gather has no uint8 rows")
+            if turns[1] and aug.out_height != aug.out_width:
+                raise ValueError("augment: rot90 needs a square size")
+            filter = _filter_config(filter)
         if return_params and aug is None:
             raise ValueError("history_gather: return_params needs augment=dict(...)")
         self._needs_history("history_gather")
@@ -388,9 +405,16 @@ class ProcgenVecEnv:
         elif tuple(out.shape) != shape or out.dtype != tdtype or out.device != self.device or not out.is_contiguous():
             raise ValueError("out: expected a contiguous %s tensor of shape %s on %s" % (tdtype, shape, self.device))
         params = torch.empty((p.numel(), 8), dtype=torch.int32, device=self.device) if return_params else None
+        flt, held = self._gather_filter(filter, turns, p.numel(), self.history.frames.shape[2]) if filtered else (None, None)
         if p.numel():
             self._before()
-            if aug is None:
+            if filtered:
+                if aug is not None:
+                    aug.params = params.data_ptr() if return_params else None
+                pglib.check(self.L, self.L.pgv_history_gather_filter(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
+                                                                     pglib.POLICY_DTYPES[dtype][0], None if aug is None else ctypes.byref(aug),
+                                                                     ctypes.byref(flt), c_void_p(out.data_ptr())), "pgv_history_gather_filter")
+            elif aug is None:
                 pglib.check(self.L, self.L.pgv_history_gather(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
                                                               pglib.POLICY_DTYPES[dtype][0], c_void_p(out.data_ptr())), "pgv_history_gather")
             else:
@@ -399,8 +423,32 @@ class ProcgenVecEnv:
                                                                   pglib.POLICY_DTYPES[dtype][0], ctypes.byref(aug), c_void_p(out.data_ptr())),
                             "pgv_history_gather_aug")
             self._after()
-            self._keep_gather = (p, i, out, params)
+            self._keep_gather = (p, i, out, params, held)
         return (out, params) if return_params else out
+
+    def _gather_filter(self, filter, turns, count, planes):
+        """(the pglib.GatherFilter, the tensors it points into) of a checked filter= dict for `count` rows of a ring of
+        `planes` planes; ValueError for shapes the engine would refuse."""
+        weights, bias, clamp = filter
+        if weights is None:  # flip or rot90 alone: the identity matrix
+            weights = torch.eye(planes, dtype=torch.float32).view(planes, planes, 1, 1)
+
+        def tensor(x, what, tail):
+            t = torch.as_tensor(x)
+            if t.dtype != torch.float32:
+                raise ValueError("filter: %s must be float32" % what)
+            t = t.to(self.device).contiguous()
+            if tuple(t.shape) != tail and tuple(t.shape) != (count,) + tail:
+                raise ValueError("filter: %s must have the shape %s or %s" % (what, tail, (count,) + tail))
+            return t, 0 if tuple(t.shape) == tail else math.prod(tail)
+
+        k = weights.shape[-1] if getattr(weights, "ndim", 0) >= 4 else 0
+        if k not in (1, 3):
+            raise ValueError("filter: weights must be [C, C, k, k] or [B, C, C, k, k] with k = 1 or 3")
+        w, wstride = tensor(weights, "weights", (planes, planes, k, k))
+        b, bstride = (None, 0) if bias is None else tensor(bias, "bias", (planes,))
+        flt = pglib.gather_filter(k, w.data_ptr(), None if b is None else b.data_ptr(), wstride, bstride, clamp, turns[0], turns[1])
+        return flt, (w, b)
 
     def _needs_transitions(self, who):
         if self.transitions is None:
@@ -937,7 +985,7 @@ def _augment_config(augment):
 
     if not isinstance(augment, dict):
         raise ValueError("augment must be None or a dict with the keys size, pad, edge, cutout, cutout_color, seed")
-    unknown = set(augment) - {"size", "pad", "edge", "cutout", "cutout_color", "seed"}
+    unknown = set(augment) - {"size", "pad", "edge", "cutout", "cutout_color", "seed", "flip", "rot90"}
     if unknown:
         raise ValueError("augment: unknown key(s) %s" % ", ".join(sorted(unknown)))
     if "size" not in augment or "seed" not in augment:
@@ -972,7 +1020,32 @@ def _augment_config(augment):
     seed = augment["seed"]
     if not integer(seed) or not 0 <= seed <= 0xFFFFFFFF:
         raise ValueError("augment: seed must be an integer in 0 .. 2^32 - 1")
+    for key in ("flip", "rot90"):  # (the filtered gather's: history_gather reads them)
+        if not isinstance(augment.get(key, False), bool):
+            raise ValueError("augment: %s must be a boolean" % key)
     return pglib.gather_aug(height, width, pad, edge, lo, hi, color, seed)
+
+
+def _filter_config(filter):
+    """(weights, bias, clamp) of history_gather's filter= dict, or (None, None, None) for None; ValueError for keys it does
+    not know and a clamp the engine would refuse.  The tensors' shapes are checked against the ring (_gather_filter)."""
+    if filter is None:
+        return None, None, None
+    if not isinstance(filter, dict) or "weights" not in filter:
+        raise ValueError("filter must be None or a dict with the keys weights, bias, clamp")
+    unknown = set(filter) - {"weights", "bias", "clamp"}
+    if unknown:
+        raise ValueError("filter: unknown key(s) %s" % ", ".join(sorted(unknown)))
+    clamp = filter.get("clamp")
+    if clamp is not None:
+        if not isinstance(clamp, (tuple, list)) or len(clamp) != 2 or not all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in clamp):
+            raise ValueError("filter: clamp must be None or a pair (lo, hi) of numbers")
+        if not clamp[0] <= clamp[1]:
+            raise ValueError("filter: clamp needs lo <= hi, neither a NaN")
+        clamp = (float(clamp[0]), float(clamp[1]))
+    if filter["weights"] is None:
+        raise ValueError("filter: weights is required")
+    return filter["weights"], filter.get("bias"), clamp
 
 
 def _history_config(history):
