@@ -1180,32 +1180,51 @@ static int32_t gather_aug_config(const char* who, const pgv_gather_aug* aug, pg:
     return 0;
 }
 
-// What both gathers check of their arguments, in the order they check it, and the entry list they hand their kernel.  `cfg`
-// (the augmented gather): its config is checked between the count and the tensor.  Leaves q.count = 0 where nothing is asked for.
-// `out_optional` (the transition gather, whose rows are): a NULL tensor passes.
-static int32_t gather_arguments(const char* who, pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack,
-                                int32_t dtype, void* d_out, pg::HistoryGather& q, const pgv_gather_aug* aug = nullptr, pg::AugConfig* cfg = nullptr,
-                                bool out_optional = false) {
-    if (!e) return fail(std::string(who) + ": env is NULL");
-    if (!e->history) return fail(std::string(who) + ": call pgv_history_enable first");
-    if (stack < 1 || stack > pg::kPolicyMaxStack) return fail(std::string(who) + ": stack must be in 1 .. 8");
-    if (!pg::policy_dtype_known(dtype)) return fail(std::string(who) + ": unknown dtype " + std::to_string(dtype));
-    if (count < 0) return fail(std::string(who) + ": count is negative");
-    if (cfg && gather_aug_config(who, aug, *cfg)) return 1;
-    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail(std::string(who) + ": out must be 16-byte aligned");
-    if (count == 0) return 0;
-    if (!d_pushes || !d_envs || (!d_out && !out_optional)) return fail(std::string(who) + ": pushes, envs or out is NULL");
+// What every gather checks of its arguments, in the order it checks them, and the entry list it hands its kernel.  Leaves
+// q.count = 0 where nothing is asked for.  A call fills a GatherCall by name (designated initialisers, which the compiler takes
+// in C++17 as well).
+struct GatherCall {
+    const char* who;
+    const int64_t* pushes;
+    const int32_t* envs;
+    int32_t count, stack, dtype;
+    void* out;
+    const pgv_gather_aug* aug = nullptr;  // (the augmented gathers, with cfg: checked into it between the count and the tensor)
+    pg::AugConfig* cfg = nullptr;
+    bool out_optional = false;  // (the transition gather, whose rows are: a NULL tensor passes)
+};
+static int32_t gather_arguments(pgv_env* e, const GatherCall& c, pg::HistoryGather& q) {
+    const std::string who = c.who;
+    if (!e) return fail(who + ": env is NULL");
+    if (!e->history) return fail(who + ": call pgv_history_enable first");
+    if (c.stack < 1 || c.stack > pg::kPolicyMaxStack) return fail(who + ": stack must be in 1 .. 8");
+    if (!pg::policy_dtype_known(c.dtype)) return fail(who + ": unknown dtype " + std::to_string(c.dtype));
+    if (c.count < 0) return fail(who + ": count is negative");
+    if (c.cfg && gather_aug_config(c.who, c.aug, *c.cfg)) return 1;
+    if (reinterpret_cast<uintptr_t>(c.out) & 15u) return fail(who + ": out must be 16-byte aligned");
+    if (c.count == 0) return 0;
+    if (!c.pushes || !c.envs || (!c.out && !c.out_optional)) return fail(who + ": pushes, envs or out is NULL");
     PG_HIP(hipSetDevice(e->device));
     (void)hipGetLastError();
-    q.n = e->n, q.stack = stack, q.count = count, q.head = e->history_head;
-    q.pushes = d_pushes, q.envs = d_envs, q.table = e->hist.table + dtype * 256, q.out = static_cast<uint8_t*>(d_out);
+    q.n = e->n, q.stack = c.stack, q.count = c.count, q.head = e->history_head;
+    q.pushes = c.pushes, q.envs = c.envs, q.table = e->hist.table + c.dtype * 256, q.out = static_cast<uint8_t*>(c.out);
     q.b = e->hist;
+    return 0;
+}
+// The tail of both *_params calls: the entry's row as the kernels write it for RGB, its eighth word `word7`.
+static int32_t gather_params_tail(const char* who, const pg::AugConfig& cfg, int32_t entry, int32_t word7, int32_t* h_params8) {
+    if (entry < 0) return fail(std::string(who) + ": entry is negative");
+    if (!h_params8) return fail(std::string(who) + ": params8 is NULL");
+    pg::aug_params_row(pg::aug_params(cfg, static_cast<uint32_t>(entry)), 3, h_params8);
+    h_params8[7] = word7;
     return 0;
 }
 
 int32_t pgv_history_gather(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype, void* d_out) {
     pg::HistoryGather q{};
-    if (gather_arguments("pgv_history_gather", e, d_pushes, d_envs, count, stack, dtype, d_out, q)) return 1;
+    const GatherCall c{.who = "pgv_history_gather", .pushes = d_pushes, .envs = d_envs, .count = count,
+                       .stack = stack, .dtype = dtype, .out = d_out};
+    if (gather_arguments(e, c, q)) return 1;
     if (q.count == 0) return 0;
     pg::launch_history_gather(e->stream, q, pg::policy_element_bytes(dtype));
     PG_HIP(hipGetLastError());
@@ -1215,16 +1234,15 @@ int32_t pgv_history_gather(pgv_env* e, const int64_t* d_pushes, const int32_t* d
 int32_t pgv_gather_aug_params(const pgv_gather_aug* aug, int32_t entry, int32_t* h_params8) {
     pg::AugConfig cfg{};
     if (gather_aug_config("pgv_gather_aug_params", aug, cfg)) return 1;
-    if (entry < 0) return fail("pgv_gather_aug_params: entry is negative");
-    if (!h_params8) return fail("pgv_gather_aug_params: params8 is NULL");
-    pg::aug_params_row(pg::aug_params(cfg, static_cast<uint32_t>(entry)), 3, h_params8);
-    return 0;
+    return gather_params_tail("pgv_gather_aug_params", cfg, entry, 0, h_params8);
 }
 
 int32_t pgv_history_gather_aug(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype,
                                const pgv_gather_aug* aug, void* d_out) {
     pg::HistoryGatherAug q{};
-    if (gather_arguments("pgv_history_gather_aug", e, d_pushes, d_envs, count, stack, dtype, d_out, q.g, aug, &q.cfg)) return 1;
+    const GatherCall c{.who = "pgv_history_gather_aug", .pushes = d_pushes, .envs = d_envs, .count = count,
+                       .stack = stack, .dtype = dtype, .out = d_out, .aug = aug, .cfg = &q.cfg};
+    if (gather_arguments(e, c, q.g)) return 1;
     if (q.g.count == 0) return 0;
     q.params = aug->params;
     pg::launch_history_gather_aug(e->stream, q, pg::policy_element_bytes(dtype));
@@ -1251,11 +1269,7 @@ int32_t pgv_gather_filter_params(const pgv_gather_aug* aug, const pgv_gather_fil
     pg::FilterConfig f{};
     if (gather_aug_config(who, gather_filter_aug(aug, whole), cfg) || gather_filter_config(who, filter, f)) return 1;
     if ((f.turns & pg::kFilterRot90) && cfg.out_h != cfg.out_w) return fail(std::string(who) + ": rot90 needs out_height = out_width");
-    if (entry < 0) return fail(std::string(who) + ": entry is negative");
-    if (!h_params8) return fail(std::string(who) + ": params8 is NULL");
-    pg::aug_params_row(pg::aug_params(cfg, static_cast<uint32_t>(entry)), 3, h_params8);
-    h_params8[7] = pg::filter_turn(cfg.seed, static_cast<uint32_t>(entry), f.turns);
-    return 0;
+    return gather_params_tail(who, cfg, entry, pg::filter_turn(cfg.seed, static_cast<uint32_t>(entry), f.turns), h_params8);
 }
 
 int32_t pgv_history_gather_filter(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, int32_t stack, int32_t dtype,
@@ -1264,7 +1278,9 @@ int32_t pgv_history_gather_filter(pgv_env* e, const int64_t* d_pushes, const int
     pgv_gather_aug whole;
     aug = gather_filter_aug(aug, whole);
     pg::HistoryGatherFilter q{};
-    if (gather_arguments(who, e, d_pushes, d_envs, count, stack, dtype, d_out, q.g, aug, &q.cfg)) return 1;
+    const GatherCall c{.who = who, .pushes = d_pushes, .envs = d_envs, .count = count,
+                       .stack = stack, .dtype = dtype, .out = d_out, .aug = aug, .cfg = &q.cfg};
+    if (gather_arguments(e, c, q.g)) return 1;
     if (gather_filter_config(who, filter, q.f)) return 1;
     if (const char* why = pg::filter_config_error(q.f, e->hist.planes, q.cfg.out_h, q.cfg.out_w)) return fail(std::string(who) + ": " + why);
     if (!filter->weights) return fail(std::string(who) + ": weights is NULL");
@@ -1325,8 +1341,9 @@ int32_t pgv_transitions_gather(pgv_env* e, const int64_t* d_pushes, const int32_
                           static_cast<const void*>(query->discount), static_cast<const void*>(query->steps)})
         if (reinterpret_cast<uintptr_t>(p) & 3u) return fail(std::string(who) + ": action, nstep_return, discount and steps must be 4-byte aligned");
     pg::TransitionGather q{};
-    // (what pgv_history_gather checks, the way it checks it)
-    if (gather_arguments(who, e, d_pushes, d_envs, count, query->stack, query->dtype, query->obs, q.g, nullptr, nullptr, /*out_optional=*/true)) return 1;
+    const GatherCall c{.who = who, .pushes = d_pushes, .envs = d_envs, .count = count,  // (what pgv_history_gather checks, the way it checks it)
+                       .stack = query->stack, .dtype = query->dtype, .out = query->obs, .out_optional = true};
+    if (gather_arguments(e, c, q.g)) return 1;
     if (q.g.count == 0) return 0;
     q.g.out = nullptr;  // (the two rows below)
     q.steps = query->n;

@@ -13,20 +13,25 @@
 // pending flag as the slot's began byte and clears it; no other lane touches either byte.  An env whose mask byte is 0 is left
 // before anything is read or written.  The form pgv_reset uses (`reset` set) writes into the newest slot and files began = 1.
 //
-// The gather kernel: one workgroup of 256 lanes per entry, begun by gather_entry and fed by history_fetch (both shared with
-// pg_history_aug.h); its body behind the head is gather_row, which pg_transitions.h calls for its two rows as well.  Per frame and plane a lane looks its 16 stored bytes up: 16·ES bytes, which at ES = 2 and 4 the wave
-// exchanges (measured against each lane storing its own units as they lie: -7 % at 2 bytes, -36 % at 4, docs/OPTLOG.md).
-// Where the walk repeats a frame the values already in registers are stored again.  An entry that is not held, or whose env
-// is outside the batch, gets a row of zero bytes.
-// Plain vector loads and stores, no atomics.
+// What every gather kernel (this one, pg_history_aug.h, pg_history_filter.h, pg_transitions.h) shares is stated once here: one
+// workgroup of 256 lanes per entry; a GatherHead in LDS filled by gather_entry; history_fetch for each DISTINCT frame of the
+// walk.  The loop over the K slots stays written out in each kernel — row pointer, the row of zero bytes of an entry that is
+// not held or whose env is outside the batch, then per slot the test `j == 0 || f != frame[j - 1]` — because every form of it as
+// a template over callables changed the kernels' schedules (docs/OPTLOG.md, "The gathers' shell, once").  That test reads the
+// shared walk, so it is workgroup-uniform: every barrier a kernel puts under it is met by all lanes or none.
+// The plain gather's body is gather_row, which pg_transitions.h calls for its two rows as well: per frame and plane a lane
+// looks its 16 stored bytes up: 16·ES bytes, which at ES = 2 and 4 the wave exchanges (measured against each lane storing its
+// own units as they lie: -7 % at 2 bytes, -36 % at 4, docs/OPTLOG.md).  Where the walk repeats a frame the values already in
+// registers are stored again.  Plain vector loads and stores, no atomics.
 // Bounds.  Push: the grid is n workgroups, env = blockIdx.x < n, slot < T by the host; a lane reads obs[env·12 288 + 48t ..
 // + 47] and writes frames[((slot·n + env)·C + c)·4096 + 16t .. + 15], c < C, t < 256  <  T·n·C·4096; began[slot·n + env],
-// pending[env].  Gather: the grid is `count` workgroups, entry = blockIdx.x < count; pushes[entry], envs[entry]; nothing of
-// the ring is read unless 0 <= env < n and max(0, head - T) <= p < head, and the walk only ever moves to a held push, so
-// every slot is f % T < T with f >= 0; a lane writes channel ch < K·C, wave w < 4, unit u < 64·ES at
-// entry·K·C·4096·ES + policy_unit_offset(ES, ch, w, u) .. + 15  <  (entry + 1)·K·C·4096·ES; the zero row writes units
-// u < 256·ES of 16 bytes of every channel, the same bytes.  The table is indexed by a byte.
-// Offsets are size_t: 65 536 envs, T = 32, RGB are 25.8 GB.
+// pending[env].  Every gather's head (the other gather headers refer to this): the grid is `count` workgroups, entry =
+// blockIdx.x < count; pushes[entry], envs[entry]; nothing of the ring is read unless 0 <= env < n and max(0, head - T) <= p
+// < head, and the walk only ever moves to a held push, so every slot is f % T < T with f >= 0 and a lane reads frames[frame
+// offset + p·4096 + 16t .. + 15], p < C, t < 256; the head's table is indexed by a byte; a zero row writes the units u <
+// channel / sizeof(Unit) of every channel ch < K·C of the entry's row: the bytes the kernel's own stores write.  The plain
+// gather: a lane writes channel ch < K·C, wave w < 4, unit u < 64·ES at entry·K·C·4096·ES + policy_unit_offset(ES, ch, w, u)
+// .. + 15  <  (entry + 1)·K·C·4096·ES.  Offsets are size_t: 65 536 envs, T = 32, RGB are 25.8 GB.
 #pragma once
 
 #include "pg_carve.h"
@@ -112,23 +117,25 @@ __global__ void __launch_bounds__(kHistoryBlock) history_push_kernel(HistoryPush
     }
 }
 
-// The head of a gather kernel: all lanes copy the dtype's 256 table words into `table` while lane 0 validates the entry and,
-// where it is valid, walks back from its push (history_walk: at most K-1 dependent byte loads of began) into `frame`; one
-// barrier shares both (all three in LDS).  Returns the verdict (workgroup-uniform).  gather_entry_at: the entry's push and env
-// are the caller's (pg_transitions.h: the push behind an n-step walk); gather_entry reads them from the lists, and hands back `env`.
-PG_D bool gather_entry_at(const HistoryGather& q, int64_t push, int env, int tid, uint32_t* table, int64_t* frame, int* valid) {
-    table[tid] = q.table[tid];
+// The head of a gather kernel, one __shared__ object: the dtype's value table, the walk of the entry and the verdict.
+struct GatherHead { uint32_t table[256]; int64_t frame[kPolicyMaxStack]; int valid; };
+// All lanes copy the dtype's 256 table words into the head while lane 0 validates the entry and, where it is valid, walks
+// back from its push (history_walk: at most K-1 dependent byte loads of began); one barrier shares both.  Returns the verdict
+// (workgroup-uniform).  gather_entry_at: the entry's push and env are the caller's (pg_transitions.h: the push behind an
+// n-step walk); gather_entry reads them from the lists, and hands back `env`.
+PG_D bool gather_entry_at(const HistoryGather& q, int64_t push, int env, int tid, GatherHead& head) {
+    head.table[tid] = q.table[tid];
     if (tid == 0) {
         const int ok = env >= 0 && env < q.n && history_held(push, q.head, q.b.capacity);
-        *valid = ok;
-        if (ok) history_walk(q.b.began, q.n, q.b.capacity, q.head, push, env, q.stack, frame);
+        head.valid = ok;
+        if (ok) history_walk(q.b.began, q.n, q.b.capacity, q.head, push, env, q.stack, head.frame);
     }
     __syncthreads();  // the table is whole; the walk is shared
-    return *valid != 0;
+    return head.valid != 0;
 }
-PG_D bool gather_entry(const HistoryGather& q, size_t entry, int tid, uint32_t* table, int64_t* frame, int* valid, int& env) {
+PG_D bool gather_entry(const HistoryGather& q, size_t entry, int tid, GatherHead& head, int& env) {
     env = q.envs[entry];
-    return gather_entry_at(q, q.pushes[entry], env, tid, table, frame, valid);
+    return gather_entry_at(q, q.pushes[entry], env, tid, head);
 }
 // Lane tid's 16 stored bytes of each of the C planes of env's frame f (a held push).
 template <int C>
@@ -138,14 +145,14 @@ PG_D void history_fetch(const HistoryGather& q, int64_t f, int env, int tid, Pol
     for (int p = 0; p < C; p++) in[p] = *reinterpret_cast<const PolicyVec16*>(from + size_t(p) * kPolicyPlane);
 }
 
-// The body of a gather kernel behind its head: the row of an entry whose verdict is `ok` (workgroup-uniform) and whose walk
-// lies in `frame`, at `out` — the K frames through the value table, or the row of zero bytes.
+// The body of a gather kernel behind its head: row `entry` of `rows` for an entry whose verdict is `ok` (workgroup-uniform)
+// and whose walk lies in the head — the K frames through the value table, or the row of zero bytes.
 template <int ES, int C>  // element bytes; planes
-PG_D void gather_row(const HistoryGather& q, bool ok, int env, int tid, const uint32_t* table, const int64_t* frame, PolicyVec16* exchange,
-                     uint8_t* out) {
+PG_D void gather_row(const HistoryGather& q, bool ok, int env, int tid, const GatherHead& head, PolicyVec16* exchange, uint8_t* rows, size_t entry) {
     const int lane = tid & 63, wave = tid >> 6;
     const int K = q.stack;
     const size_t channel = size_t(kPolicyPlane) * ES;
+    uint8_t* const out = rows + entry * (size_t(K) * C * channel);
     if (!ok) {  // (workgroup-uniform)
         zero_row<PolicyVec16>(out, K * C, channel, kHistoryBlock * ES, tid);
         return;
@@ -155,14 +162,14 @@ PG_D void gather_row(const HistoryGather& q, bool ok, int env, int tid, const ui
     for (int k = 0; k < ES; k++) unit[k] = policy_unit_offset(ES, 0, wave, policy_unit(true, ES, lane, k));
     PolicyVec16 held[C * ES];
     for (int j = 0; j < K; j++) {
-        const int64_t f = frame[j];
-        if (j == 0 || f != frame[j - 1]) {  // (workgroup-uniform)
+        const int64_t f = head.frame[j];
+        if (j == 0 || f != head.frame[j - 1]) {  // (workgroup-uniform)
             PolicyVec16 in[C];
             history_fetch<C>(q, f, env, tid, in);
 #pragma unroll
             for (int p = 0; p < C; p++) {
                 uint32_t v[kPolicyLanePixels];
-                plane_values(table, in[p], v);
+                plane_values(head.table, in[p], v);
                 PolicyVec16 mine[ES];
                 policy_pack<ES>(v, mine);
                 if (ES > 1) wave_exchange<ES>(exchange, wave, lane, mine);
@@ -180,15 +187,13 @@ PG_D void gather_row(const HistoryGather& q, bool ok, int env, int tid, const ui
 
 template <int ES, int C>
 __global__ void __launch_bounds__(kHistoryBlock) history_gather_kernel(HistoryGather q) {
-    __shared__ uint32_t table[256];
-    __shared__ int64_t frame[kPolicyMaxStack];
-    __shared__ int valid;
+    __shared__ GatherHead head;
     __shared__ PolicyVec16 exchange[ES > 1 ? kHistoryBlock * ES : 1];  // a wave's units of one plane, in the wave's own quarter
     const int tid = static_cast<int>(threadIdx.x);
     const size_t entry = blockIdx.x;
     int env = 0;
-    const bool ok = gather_entry(q, entry, tid, table, frame, &valid, env);
-    gather_row<ES, C>(q, ok, env, tid, table, frame, exchange, q.out + entry * policy_bytes_per_env(q.stack, C, ES));
+    const bool ok = gather_entry(q, entry, tid, head, env);
+    gather_row<ES, C>(q, ok, env, tid, head, exchange, q.out, entry);
 }
 
 inline void launch_history_push(hipStream_t st, const HistoryPush& q) {

@@ -6,23 +6,21 @@
 //     element (slot, plane, y, x) = table[byte], byte by aug_source_byte_index: the plane's colour byte inside the rectangle,
 //     else the stored byte at (oy + y, ox + x), outside the frame the nearest pixel's (REPLICATE) or 0 (ZERO).
 //
-// The kernel: one workgroup of 256 lanes per entry, begun as the plain gather's is (pg_history.h gather_entry); lane 0 writes
-// the params row behind it.  Every lane works the entry's draws out for itself (they are workgroup-uniform).  Per DISTINCT
-// frame of the walk a lane fetches its stored bytes of each plane (history_fetch) and the workgroup stages the C planes in LDS
-// (C·4096 bytes) between two barriers under a workgroup-uniform condition; a frame the walk repeats is neither fetched nor
-// staged again.  The lanes then write the output plane in dense order: unit u (U bytes, U/ES elements) of a plane is written
+// The kernel: pg_history.h's head and fetch, the slot loop written out as there; lane 0 writes the params row behind the head (gather_params_row).
+// Every lane works the entry's draws out for itself (they are workgroup-uniform).  Per DISTINCT frame of the walk the
+// workgroup stages the C fetched planes in LDS (stage_planes: C·4096 bytes, between two barriers); a frame the walk repeats
+// is not staged again.  The lanes then write the output plane in dense order: unit u (U bytes, U/ES elements) of a plane is written
 // by lane u % 256 in its store number u / 256, so the lanes of one store instruction lie U bytes apart.  A lane reads its
 // source bytes from the staged planes one byte at a time (neighbouring lanes read neighbouring bytes: the same or the next LDS
 // word), through aug_source_byte_index, then through the table, and packs them.
 // U is 16 where a plane's H'·W'·ES bytes are a multiple of 16 — then every row and plane starts 16-byte aligned — and 8
 // otherwise: W' is a multiple of 8, so a plane is always a whole number of 8-byte units, starts 8-byte aligned, and no store
-// is ever narrower than a unit or reaches past its plane.  An entry that is not held, or whose env is outside the batch,
-// gets a row of zero bytes by the same units (pg_planes.h zero_row).  Plain vector loads and stores, no atomics.
-// Bounds.  The grid is `count` workgroups, entry = blockIdx.x < count; pushes[entry], envs[entry], params[entry·8 .. + 7];
-// nothing of the ring is read unless 0 <= env < n and the push is held, and the walk only moves to held pushes (pg_history.h):
-// a lane reads frames[frame offset + p·4096 + 16t .. + 15], p < C, t < 256.  The staged planes are indexed by
+// is ever narrower than a unit or reaches past its plane; the zero row is written by the same units.  Plain vector loads
+// and stores, no atomics.
+// Bounds.  The head, the ring and the zero row: pg_history.h.  params[entry·8 .. + 7], entry < count.  The staged planes
+// are written at p·256 + t, p < C, t < 256, of C·256 units and indexed by
 // p·4096 + aug_source_byte_index(...) with the index in 0 .. 4095 for every (oy, ox, y, x) (or a sentinel, which reads
-// nothing of them: tests/cpp/test_history_aug.cpp, exhaustively); the table by a byte.  A lane writes unit u < H'·W'·ES / U of
+// nothing of them: tests/cpp/test_history_aug.cpp, exhaustively).  A lane writes unit u < H'·W'·ES / U of
 // channel ch < K·C at  entry·K·C·H'·W'·ES + ch·H'·W'·ES + u·U .. + U-1  <  (entry + 1)·K·C·H'·W'·ES  (aug_unit_offset).
 // Offsets are size_t: 65 536 rows of K = 8 RGB f32 are 25.8 GB.
 #pragma once
@@ -120,29 +118,42 @@ struct HistoryGatherAug {
 #if defined(__HIPCC__)
 typedef uint32_t AugVec8 __attribute__((ext_vector_type(2)));  // 8 bytes a lane
 
+// Lane 0 writes the entry's params row where the caller asked for the rows: aug_params_row's words, the eighth `word7`.
+PG_D void gather_params_row(int32_t* params, size_t entry, const AugParams& ap, int planes, int32_t word7, int tid) {
+    if (tid != 0 || !params) return;
+    int32_t row[kAugParamWords];
+    aug_params_row(ap, planes, row);
+    row[7] = word7;
+#pragma unroll
+    for (int k = 0; k < kAugParamWords; k++) params[entry * kAugParamWords + k] = row[k];
+}
+// The lanes' fetched planes of one frame into `staged` (C·256 units, as stored).  Two workgroup barriers: every lane has done
+// with the frame staged before, and with whatever the kernel built from it; then the planes are whole.  Only under the slot
+// loop's distinct-frame test (pg_history.h: met by all lanes or none).
+template <int C>
+PG_D void stage_planes(PolicyVec16* staged, const PolicyVec16 (&in)[C], int tid) {
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < C; p++) staged[p * (kPolicyPlane / 16) + tid] = in[p];
+    __syncthreads();
+}
+
 template <int ES, int C, int U>  // element bytes; planes; bytes a store unit
 __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(HistoryGatherAug q) {
     typedef std::conditional_t<U == 16, PolicyVec16, AugVec8> Unit;
     constexpr int kPerWord = 4 / ES, kPerUnit = U / ES;  // pixels a word; pixels a unit
     constexpr int kRun = kPerUnit < 8 ? kPerUnit : 8;                    // pixels in a row of the output for certain: W' % 8 == 0
-    __shared__ uint32_t table[256];
-    __shared__ int64_t frame[kPolicyMaxStack];
-    __shared__ int valid;
+    __shared__ GatherHead head;
     __shared__ PolicyVec16 staged[C * kPolicyPlane / 16];  // the C planes of one frame, as stored
     const int tid = static_cast<int>(threadIdx.x);
     const size_t entry = blockIdx.x;
-    const int K = q.g.stack;
     const AugParams ap = aug_params(q.cfg, static_cast<uint32_t>(entry));
     int env = 0;
-    const bool ok = gather_entry(q.g, entry, tid, table, frame, &valid, env);
-    if (tid == 0 && q.params) {
-        int32_t row[kAugParamWords];
-        aug_params_row(ap, C, row);
-#pragma unroll
-        for (int k = 0; k < kAugParamWords; k++) q.params[entry * kAugParamWords + k] = row[k];
-    }
+    const bool ok = gather_entry(q.g, entry, tid, head, env);
+    gather_params_row(q.params, entry, ap, C, 0, tid);
     const int W = q.cfg.out_w, edge = q.cfg.edge;
     const int units = q.cfg.out_h * W / kPerUnit;  // (exact: aug_unit_bytes)
+    const int K = q.g.stack;
     const size_t channel = aug_plane_bytes(q.cfg.out_h, W, ES);
     uint8_t* const out = q.g.out + entry * (size_t(K) * C * channel);
     if (!ok) {  // (workgroup-uniform)
@@ -151,14 +162,11 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(Histo
     }
     const uint8_t* const bytes = reinterpret_cast<const uint8_t*>(staged);
     for (int j = 0; j < K; j++) {
-        const int64_t f = frame[j];
-        if (j == 0 || f != frame[j - 1]) {  // (workgroup-uniform)
+        const int64_t f = head.frame[j];
+        if (j == 0 || f != head.frame[j - 1]) {  // (workgroup-uniform)
             PolicyVec16 in[C];
             history_fetch<C>(q.g, f, env, tid, in);
-            __syncthreads();  // every lane has done with the frame staged before
-#pragma unroll
-            for (int p = 0; p < C; p++) staged[p * (kPolicyPlane / 16) + tid] = in[p];
-            __syncthreads();
+            stage_planes<C>(staged, in, tid);
         }
         uint8_t* const to = out + size_t(K - 1 - j) * C * channel;
 #pragma unroll
@@ -175,7 +183,7 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(Histo
                         const int at = aug_source_byte_index(ap, edge, y, x0 + i);
                         const uint32_t byte = at == kAugCutout ? colour : at == kAugZero ? 0u : plane[at];
                         const int px = r * kRun + i;
-                        w[px / kPerWord] |= table[byte] << (8 * ES * (px % kPerWord));
+                        w[px / kPerWord] |= head.table[byte] << (8 * ES * (px % kPerWord));
                     }
                 }
                 *reinterpret_cast<Unit*>(to + p * channel + size_t(u) * U) = w;
@@ -187,9 +195,8 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_aug_kernel(Histo
 inline void launch_history_gather_aug(hipStream_t st, const HistoryGatherAug& q, int es) {
     for_es_planes(es, q.g.b.planes, [&](auto es_c, auto planes_c) {
         constexpr int ES = decltype(es_c)::value, C = decltype(planes_c)::value;
-        void (*kernel)(HistoryGatherAug) = history_gather_aug_kernel<ES, C, 8>;
-        if (aug_unit_bytes(q.cfg.out_h, q.cfg.out_w, ES) == 16) kernel = history_gather_aug_kernel<ES, C, 16>;
-        hipLaunchKernelGGL(kernel, dim3(q.g.count), dim3(kHistoryBlock), 0, st, q);
+        hipLaunchKernelGGL((aug_unit_bytes(q.cfg.out_h, q.cfg.out_w, ES) == 16 ? history_gather_aug_kernel<ES, C, 16> : history_gather_aug_kernel<ES, C, 8>),
+                           dim3(q.g.count), dim3(kHistoryBlock), 0, st, q);
     });
 }
 #endif

@@ -8,11 +8,11 @@
 //     out_o(y, x) = clamp(bias_o + sum over (i, ky, kx), in that order, of w[o][i][ky][kx] * v_i(y + ky - k/2, x + kx - k/2)),
 //                   as float32, or rounded once to binary16 or bfloat16.
 //
-// The kernel: one workgroup of 256 lanes per entry, begun as every gather's is (pg_history.h gather_entry, here with the f32
-// table, so that `table` in LDS maps a byte to its float's bits); lane 0 writes the params row.  The entry's weights and bias
+// The kernel: pg_history.h's head and fetch, the slot loop written out as there, here with the f32 table, so that the head's table maps a byte to
+// its float's bits; lane 0 writes the params row, its eighth word the turn.  The entry's weights and bias
 // (C·C·k·k + C floats) are workgroup-uniform: every lane reads them once, before anything is stored, by uniform loads into
-// registers, never per pixel.  Per DISTINCT frame of the walk the lanes fetch the C stored planes (history_fetch) and stage
-// them in LDS as the aug kernel does (C·4096 bytes).
+// registers, never per pixel.  Per DISTINCT frame of the walk the C fetched planes are staged in LDS as the aug kernel's
+// are (stage_planes, C·4096 bytes).
 //   k = 3: the workgroup then builds G ONCE per frame into a second LDS image, so that the window, cutout, flip and turn
 //   arithmetic is done once per pixel and plane-independently, not once per tap: C planes of H'+2 rows of W'+8 bytes each
 //   (filter_image_stride), pixel (y, x) at byte (y + 1)·stride + x + 1; the row above, the row below, byte 0 of a row and
@@ -32,27 +32,25 @@
 // 27 multiplies it feeds), and an MFMA's internal sum order and fused products would break the float32 definition above.
 // The 8 results of a plane are clamped by comparisons, converted, packed and stored as 16-byte units (ES = 2: one, ES = 4:
 // two) at aug_unit_offset with U = 16: W' % 8 == 0 makes every run, row and plane of 2- or 4-byte elements start 16-byte
-// aligned, so the unit is always 16 (aug_unit_bytes).  An entry that is not held, or whose env is outside the batch, gets a
-// row of zero bytes by the same units (zero_row), bias or not.  Plain vector loads and stores, no atomics.
+// aligned, so the unit is always 16 (aug_unit_bytes); the zero row is written by the same units, bias or not.  Plain vector
+// loads and stores, no atomics.
 // LDS: 1 KB table + 12 KB staged + 13.9 KB image (k = 3, RGB) + the walk = 27.0 KB a workgroup; gfx950's 160 KB a CU hold
 // five such workgroups (20 waves), k = 1 (13.1 KB) twelve.  At k = 3, RGB, it is the register file that limits them
 // first: the compiler keeps the 30 values, 24 accumulators and what it hoists of the 84 weights in 118 (f32) to 201 (f16)
 // VGPRs, two to four workgroups a CU; the kernel is bound by its 1 296 multiplies and adds a run, not by LDS or memory
 // (docs/OPTLOG.md has the times).
-// Bounds.  The grid is `count` workgroups, entry = blockIdx.x < count; pushes[entry], envs[entry], params[entry·8 .. + 7],
-// weights[entry·wstride .. + C·C·k·k - 1] and bias[entry·bstride .. + C - 1] with the strides 0 or exactly the set's size
-// (checked on the host: the caller's tensors hold one set or `count` sets).  Nothing of the ring is read unless 0 <= env < n
-// and the push is held, and the walk only moves to held pushes (pg_history.h): a lane reads frames[frame offset + p·4096 +
-// 16t .. + 15], p < C, t < 256.  The staged planes are indexed by p·4096 + s where s = filter_image_source(...) is in
-// 0 .. 4095 or a sentinel, which reads nothing of them, for every (oy, ox, flip, r, y, x): filter_turn maps 0 .. H'-1 x
-// 0 .. W'-1 onto itself (r > 0 only where H' = W', the host refuses it otherwise) and aug_source_byte_index takes it from
-// there (tests/cpp/test_history_filter.cpp and test_history_aug.cpp, exhaustively).  The image is written by words
-// wi < (H'+2)·stride/4 <= kFilterImageWords of each plane p < C at p·kFilterImageWords + wi, and read at
-// p·kFilterImageWords + ((y + ky)·stride + x0)/4 + 0 .. 2 with y + ky <= H'+1, x0 <= W'-8: the last byte read is
-// (H'+1)·stride + W' + 3 < (H'+2)·stride (filter_run_word, swept in the same test).  The table by a byte.  A lane writes runs
-// run < H'·W'/8 of channel ch < K·C at aug_unit_offset(entry, K, C, H', W', ES, ch, run·ES/2 + 0 .. ES/2 - 1, 16): bytes
-// run·8·ES .. + 8·ES - 1 of the channel's H'·W'·ES.  A refused call launches nothing; a zero row writes the same bytes and
-// reads neither weights nor ring.  Offsets are size_t: 65 536 rows of K = 8 RGB f32 are 25.8 GB.
+// Bounds.  The head, the ring and the zero row: pg_history.h; the staging: pg_history_aug.h.  params[entry·8 .. + 7],
+// weights[entry·wstride .. + C·C·k·k - 1] and bias[entry·bstride .. + C - 1], entry < count, with the strides 0 or exactly
+// the set's size (checked on the host: the caller's tensors hold one set or `count` sets).  The staged planes are indexed by
+// p·4096 + s where s = filter_image_source(...) is in 0 .. 4095 or a sentinel, which reads nothing of them, for every (oy,
+// ox, flip, r, y, x): filter_turn maps 0 .. H'-1 x 0 .. W'-1 onto itself (r > 0 only where H' = W', the host refuses it
+// otherwise) and aug_source_byte_index takes it from there (tests/cpp/test_history_filter.cpp and test_history_aug.cpp,
+// exhaustively).  The image is written by words wi < (H'+2)·stride/4 <= kFilterImageWords of each plane p < C at
+// p·kFilterImageWords + wi, and read at p·kFilterImageWords + ((y + ky)·stride + x0)/4 + 0 .. 2 with y + ky <= H'+1, x0 <=
+// W'-8: the last byte read is (H'+1)·stride + W' + 3 < (H'+2)·stride (filter_run_word, swept in the same test).  A lane
+// writes runs run < H'·W'/8 of channel ch < K·C at aug_unit_offset(entry, K, C, H', W', ES, ch, run·ES/2 + 0 .. ES/2 - 1,
+// 16): bytes run·8·ES .. + 8·ES - 1 of the channel's H'·W'·ES.  A refused call launches nothing; a zero row writes the same
+// bytes and reads neither weights nor ring.  Offsets are size_t: 65 536 rows of K = 8 RGB f32 are 25.8 GB.
 #pragma once
 
 #include "pg_history_aug.h"
@@ -140,9 +138,7 @@ PG_D uint32_t filter_element(float v, int bf16) {
 template <int ES, int C, int KS>  // element bytes (2, 4); planes; kernel
 __global__ void __launch_bounds__(kHistoryBlock) history_gather_filter_kernel(HistoryGatherFilter q) {
     constexpr int kTaps = KS * KS, kSpan = kFilterRun + KS - 1;  // bytes of a row a run needs
-    __shared__ uint32_t table[256];
-    __shared__ int64_t frame[kPolicyMaxStack];
-    __shared__ int valid;
+    __shared__ GatherHead head;
     __shared__ PolicyVec16 staged[C * kPolicyPlane / 16];          // the C planes of one frame, as stored
     __shared__ uint64_t image[KS == 3 ? C * kFilterImageWords / 2 : 1];  // G with its border (k = 3)
     const int tid = static_cast<int>(threadIdx.x);
@@ -160,33 +156,25 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_filter_kernel(Hi
         for (int o = 0; o < C; o++) b[o] = q.bias ? q.bias[entry * size_t(q.f.bias_stride) + o] : 0.0f;
     }
     int env = 0;
-    const bool ok = gather_entry(q.g, entry, tid, table, frame, &valid, env);
-    if (tid == 0 && q.params) {
-        int32_t row[kAugParamWords];
-        aug_params_row(ap, C, row);
-        row[7] = turn;
-#pragma unroll
-        for (int k = 0; k < kAugParamWords; k++) q.params[entry * kAugParamWords + k] = row[k];
-    }
+    const bool ok = gather_entry(q.g, entry, tid, head, env);
+    gather_params_row(q.params, entry, ap, C, turn, tid);
     const size_t channel = aug_plane_bytes(H, W, ES);
     uint8_t* const out = q.g.out + entry * (size_t(K) * C * channel);
     if (!ok) {  // (workgroup-uniform)
         zero_row<PolicyVec16>(out, K * C, channel, static_cast<int>(channel / 16), tid);
         return;
     }
+    const uint32_t* const table = head.table;
     const uint8_t* const bytes = reinterpret_cast<const uint8_t*>(staged);
     uint32_t* const image_words = reinterpret_cast<uint32_t*>(image);
     const int runs = H * W / kFilterRun, runs_a_row = W / kFilterRun;
     const float lo = q.f.lo, hi = q.f.hi;
     for (int j = 0; j < K; j++) {
-        const int64_t f = frame[j];
-        if (j == 0 || f != frame[j - 1]) {  // (workgroup-uniform)
+        const int64_t f = head.frame[j];
+        if (j == 0 || f != head.frame[j - 1]) {  // (workgroup-uniform)
             PolicyVec16 in[C];
             history_fetch<C>(q.g, f, env, tid, in);
-            __syncthreads();  // every lane has done with the frame staged, and the image built, before
-#pragma unroll
-            for (int p = 0; p < C; p++) staged[p * (kPolicyPlane / 16) + tid] = in[p];
-            __syncthreads();
+            stage_planes<C>(staged, in, tid);
             if (KS == 3) {
                 const int stride = filter_image_stride(W), words_a_row = stride / 4, words = filter_image_words(H, W);
                 for (int wi = tid; wi < words; wi += kHistoryBlock) {
@@ -278,14 +266,11 @@ __global__ void __launch_bounds__(kHistoryBlock) history_gather_filter_kernel(Hi
 }
 
 inline void launch_history_gather_filter(hipStream_t st, const HistoryGatherFilter& q, int es) {
-    auto with = [&](auto es_c, auto planes_c) {
+    for_es_planes<2>(es, q.g.b.planes, [&](auto es_c, auto planes_c) {  // (u8 is refused)
         constexpr int ES = decltype(es_c)::value, C = decltype(planes_c)::value;
-        void (*kernel)(HistoryGatherFilter) = history_gather_filter_kernel<ES, C, 3>;
-        if (q.f.kernel == 1) kernel = history_gather_filter_kernel<ES, C, 1>;
-        hipLaunchKernelGGL(kernel, dim3(q.g.count), dim3(kHistoryBlock), 0, st, q);
-    };
-    auto with_planes = [&](auto es_c) { q.g.b.planes == 1 ? with(es_c, std::integral_constant<int, 1>{}) : with(es_c, std::integral_constant<int, 3>{}); };
-    es == 2 ? with_planes(std::integral_constant<int, 2>{}) : with_planes(std::integral_constant<int, 4>{});  // (u8 is refused)
+        hipLaunchKernelGGL((q.f.kernel == 1 ? history_gather_filter_kernel<ES, C, 1> : history_gather_filter_kernel<ES, C, 3>), dim3(q.g.count),
+                           dim3(kHistoryBlock), 0, st, q);
+    });
 }
 #endif
 

@@ -67,11 +67,14 @@ PG_HD size_t policy_unit_offset(int es, int ch, int wave, int unit) {
 PG_HD size_t policy_bytes_per_env(int stack, int planes, int es) { return size_t(stack) * planes * kPolicyPlane * es; }
 
 // f(ES, C) with the element bytes and the planes as compile-time constants (std::integral_constant): the launchers pick
-// their kernel's instantiation through it.
-template <class F>
+// their kernel's instantiation through it.  LowestES = 2: a kernel that has no one-byte elements (its caller refuses them)
+// is not instantiated for them.
+template <int LowestES = 1, class F>
 inline void for_es_planes(int es, int planes, F&& f) {
     auto with_es = [&](auto c) {
-        es == 1 ? f(std::integral_constant<int, 1>{}, c) : es == 2 ? f(std::integral_constant<int, 2>{}, c) : f(std::integral_constant<int, 4>{}, c);
+        if constexpr (LowestES == 1)
+            if (es == 1) return f(std::integral_constant<int, 1>{}, c);
+        es == 2 ? f(std::integral_constant<int, 2>{}, c) : f(std::integral_constant<int, 4>{}, c);
     };
     planes == 1 ? with_es(std::integral_constant<int, 1>{}) : with_es(std::integral_constant<int, 3>{});
 }

@@ -184,9 +184,7 @@ __global__ void __launch_bounds__(kTrBlock) transition_record_kernel(TransitionR
 
 template <int ES, int C>
 __global__ void __launch_bounds__(kHistoryBlock) transition_gather_kernel(TransitionGather q) {
-    __shared__ uint32_t table[256];
-    __shared__ int64_t frame[kPolicyMaxStack];
-    __shared__ int valid;
+    __shared__ GatherHead head;
     __shared__ int walked;  // steps, 0 = an invalid entry
     __shared__ PolicyVec16 exchange[ES > 1 ? kHistoryBlock * ES : 1];
     const int tid = static_cast<int>(threadIdx.x);
@@ -234,8 +232,8 @@ __global__ void __launch_bounds__(kHistoryBlock) transition_gather_kernel(Transi
     __syncthreads();
     const int m = walked;
     // a valid entry's two pushes are held: p by row p, p + m by row p + m - 1; an invalid one gets the zero row through env = -1
-    const bool ok = gather_entry_at(q.g, which == 0 ? p : p + m, m ? env : -1, tid, table, frame, &valid);
-    gather_row<ES, C>(q.g, ok, env, tid, table, frame, exchange, rows + entry * policy_bytes_per_env(q.g.stack, C, ES));
+    const bool ok = gather_entry_at(q.g, which == 0 ? p : p + m, m ? env : -1, tid, head);
+    gather_row<ES, C>(q.g, ok, env, tid, head, exchange, rows, entry);
 }
 
 __global__ void __launch_bounds__(kTrBlock) transition_gae_kernel(TransitionGae q) {

@@ -390,14 +390,8 @@ class ProcgenVecEnv:
         if return_params and aug is None:
             raise ValueError("history_gather: return_params needs augment=dict(...)")
         self._needs_history("history_gather")
-        if dtype not in pglib.POLICY_DTYPES:
-            raise ValueError("history_gather: dtype must be one of %s" % ", ".join(pglib.POLICY_DTYPES))
-        if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= 8:
-            raise ValueError("history_gather: stack must be an integer in 1 .. 8")
-        p = torch.as_tensor(pushes, device=self.device).to(torch.int64).reshape(-1).contiguous()
-        i = torch.as_tensor(envs, device=self.device).to(torch.int32).reshape(-1).contiguous()
-        if p.numel() != i.numel():
-            raise ValueError("history_gather: %d pushes but %d envs" % (p.numel(), i.numel()))
+        self._gather_checks("history_gather", stack, dtype)
+        p, i = self._gather_entries("history_gather", pushes, envs)
         shape = (p.numel(), stack * self.history.frames.shape[2]) + ((64, 64) if aug is None else (aug.out_height, aug.out_width))
         tdtype = getattr(torch, dtype)
         if out is None:
@@ -407,24 +401,34 @@ class ProcgenVecEnv:
         params = torch.empty((p.numel(), 8), dtype=torch.int32, device=self.device) if return_params else None
         flt, held = self._gather_filter(filter, turns, p.numel(), self.history.frames.shape[2]) if filtered else (None, None)
         if p.numel():
-            self._before()
-            if filtered:
-                if aug is not None:
-                    aug.params = params.data_ptr() if return_params else None
-                pglib.check(self.L, self.L.pgv_history_gather_filter(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
-                                                                     pglib.POLICY_DTYPES[dtype][0], None if aug is None else ctypes.byref(aug),
-                                                                     ctypes.byref(flt), c_void_p(out.data_ptr())), "pgv_history_gather_filter")
-            elif aug is None:
-                pglib.check(self.L, self.L.pgv_history_gather(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
-                                                              pglib.POLICY_DTYPES[dtype][0], c_void_p(out.data_ptr())), "pgv_history_gather")
-            else:
+            if aug is not None:
                 aug.params = params.data_ptr() if return_params else None
-                pglib.check(self.L, self.L.pgv_history_gather_aug(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
-                                                                  pglib.POLICY_DTYPES[dtype][0], ctypes.byref(aug), c_void_p(out.data_ptr())),
-                            "pgv_history_gather_aug")
+            by_ref = None if aug is None else ctypes.byref(aug)
+            # the three calls differ in their name and in the structs between the dtype and the rows
+            name, more = (("pgv_history_gather_filter", (by_ref, ctypes.byref(flt))) if filtered else
+                          ("pgv_history_gather", ()) if aug is None else ("pgv_history_gather_aug", (by_ref,)))
+            self._before()
+            pglib.check(self.L, getattr(self.L, name)(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), stack,
+                                                      pglib.POLICY_DTYPES[dtype][0], *more, c_void_p(out.data_ptr())), name)
             self._after()
             self._keep_gather = (p, i, out, params, held)
         return (out, params) if return_params else out
+
+    @staticmethod
+    def _gather_checks(who, stack, dtype):
+        """Every gather's checks of dtype and stack; `who` heads the ValueErrors."""
+        if dtype not in pglib.POLICY_DTYPES:
+            raise ValueError("%s: dtype must be one of %s" % (who, ", ".join(pglib.POLICY_DTYPES)))
+        if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= 8:
+            raise ValueError("%s: stack must be an integer in 1 .. 8" % who)
+
+    def _gather_entries(self, who, pushes, envs):
+        """A gather's B pairs as the device tensors (pushes int64 [B], envs int32 [B]) its launch reads."""
+        p = torch.as_tensor(pushes, device=self.device).to(torch.int64).reshape(-1).contiguous()
+        i = torch.as_tensor(envs, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        if p.numel() != i.numel():
+            raise ValueError("%s: %d pushes but %d envs" % (who, p.numel(), i.numel()))
+        return p, i
 
     def _gather_filter(self, filter, turns, count, planes):
         """(the pglib.GatherFilter, the tensors it points into) of a checked filter= dict for `count` rows of a ring of
@@ -463,16 +467,10 @@ class ProcgenVecEnv:
         successor, not recorded or a reset's own step, or whose env is outside the batch, gives zeros.  frames=False: the
         scalars alone (obs and next_obs None).  Same stream hand-shake as step(), no host synchronisation."""
         self._needs_transitions("transition_gather")
-        if dtype not in pglib.POLICY_DTYPES:
-            raise ValueError("transition_gather: dtype must be one of %s" % ", ".join(pglib.POLICY_DTYPES))
-        if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= 8:
-            raise ValueError("transition_gather: stack must be an integer in 1 .. 8")
+        self._gather_checks("transition_gather", stack, dtype)
         if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 64:
             raise ValueError("transition_gather: n must be an integer in 1 .. 64")
-        p = torch.as_tensor(pushes, device=self.device).to(torch.int64).reshape(-1).contiguous()
-        i = torch.as_tensor(envs, device=self.device).to(torch.int32).reshape(-1).contiguous()
-        if p.numel() != i.numel():
-            raise ValueError("transition_gather: %d pushes but %d envs" % (p.numel(), i.numel()))
+        p, i = self._gather_entries("transition_gather", pushes, envs)
         B = p.numel()
         shape = (B, stack * self.history.frames.shape[2], 64, 64)
         obs = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device) if frames else None

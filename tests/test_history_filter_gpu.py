@@ -99,6 +99,28 @@ def test_the_identity_law(random_ring, dtype):
     assert np.array_equal(bits(got), bits(r.v.history_gather(r.pushes, r.envs, stack=4, dtype=dtype)))
 
 
+@pytest.mark.parametrize("kernel", [1, 3])
+@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[3]], ids=["%dx%d_pad%d" % s[:3] for s in (SHAPES[1], SHAPES[3])])
+def test_a_full_stack_matches_the_model(random_ring, shape, kernel):
+    """K = 8, all the head's walk holds, over T = 4: every held entry's walk repeats a frame at least four times, so every
+    row takes both sides of the distinct-frame test, restaging (and at kernel 3 rebuilding the image) in between.  Per-entry
+    weights, bias and clamp, float32, held to the model as every other case is."""
+    test_filter_matches_the_model(random_ring, shape, kernel, True, True, 8, "float32")
+
+
+@pytest.mark.parametrize("dtype", list(HALF_ULP))
+def test_the_identity_chain_at_a_full_stack(random_ring, dtype):
+    """K = 8 at 64 x 64, pad 0, no cutout: the plain gather's rows are the augmented gather's, and those the filtered
+    gather's with the identity matrix — the four kernels' one walk."""
+    r, C = random_ring, random_ring.ring.C
+    _, augment = arguments(SHAPES[0])
+    plain = r.v.history_gather(r.pushes, r.envs, stack=8, dtype=dtype)
+    augmented = r.v.history_gather(r.pushes, r.envs, stack=8, dtype=dtype, augment=augment)
+    filtered = r.v.history_gather(r.pushes, r.envs, stack=8, dtype=dtype, augment=augment, filter=dict(weights=torch.eye(C).view(C, C, 1, 1)))
+    assert tuple(plain.shape) == (ENTRIES, 8 * C, 64, 64) and bool(plain.any())
+    assert np.array_equal(bits(plain), bits(augmented)) and np.array_equal(bits(augmented), bits(filtered))
+
+
 def test_refusals_guards_and_nothing_to_gather(random_ring):
     """Every refusal of the filter by name with no byte written; a good call writes its rows and params and nothing beside
     them, a zero row at the very end included; count = 0 succeeds and writes nothing."""
