@@ -677,6 +677,60 @@ PGV_API int32_t pgv_transitions_gather(pgv_env* env, const int64_t* d_pushes, co
                                        const pgv_transition_query* query);
 PGV_API int32_t pgv_transitions_gae(pgv_env* env, int64_t first, int32_t length, const pgv_gae* gae);
 
+/* Prioritised sampling over the transition ring: the engine hands out the (push, env) pairs a replay learner reads, drawn in
+ * proportion to a priority over exactly the rows pgv_transitions_gather calls VALID — it is the only party that knows,
+ * without a look from the host, what is held and what is VOID.  With all priorities equal the call is a uniform sampler
+ * over the valid rows.  Opt-in per engine, on top of the transitions: an engine that never enables it launches nothing new
+ * and gives the same bytes as before at every entry point.
+ *
+ *   1. pgv_priorities_enable needs pgv_transitions_enable first, T·N < 2^31, and may be called once.  It allocates
+ *      `priority` uint32 [T][N], laid out as `flags` is (row q in slot q % T), one uint32 running maximum, and the sampler's
+ *      scratch; nothing is allocated afterwards.  Every row and the maximum start at 65536.  A refusal leaves a message and
+ *      the engine as it was.  The ring travels neither in records nor in snapshots.
+ *   2. Fixed point, so that every sum is an exact integer and a parallel scan is the sequential one bit for bit.  For a
+ *      float32 p: t = p * 65536.0f; fix(p) = 1 if t is NaN or t < 1; 2147483647 if t >= 2147483648.0f; else rintf(t)
+ *      (nearest-even).  The caller applies its own exponent alpha; the engine stores what it is given.
+ *   3. Opening a row: every call that writes the transitions' row head - 1 writes priority[slot][i] = the running maximum
+ *      behind it, one more small launch (the PER convention: a new transition is drawn at least once).
+ *   4. pgv_priorities_set: entry (p, i) stores fix(value) into row p of env i and raises the running maximum (an integer
+ *      atomic max: order-independent) where 0 <= i < N and row p is held with its successor, by head as the call finds it;
+ *      any other entry is skipped, nothing faults for any index values.  Of two entries that name one row, one wins whole.
+ *      One launch, nothing allocated, no host synchronisation.  Refused: NULL pointers with count > 0, count < 0, pointers
+ *      not 4-byte aligned.
+ *   5. pgv_priorities_sample.  A row is ELIGIBLE when it is held with its successor, RECORDED and not VOID, by head as the
+ *      call finds it.  w(s, i) = the priority where the row living in slot s is eligible, else 0; rows are ordered by the
+ *      flat index j = s*N + i (the layout, not time); S = the sum of all w (uint64, < 2^62), M = the eligible rows.  Sample
+ *      k of `count`, unsigned 64-bit arithmetic throughout, mix32 the engine's hash:
+ *          word = mix32(mix32(seed + 0x9E3779B9*(k+1)) ^ 0xC2B2AE35)        (word 0 of the augmented gathers' rule)
+ *          stratified: base = S / count, rem = S % count, lo_k = k*base + (k*rem)/count = floor(k*S/count),
+ *                      width = lo_(k+1) - lo_k;     else: lo_k = 0, width = S
+ *          target = lo_k + word*(width >> 32) + ((word*(width & 0xFFFFFFFF)) >> 32)
+ *      and the sample is the row j with P[j] <= target < P[j] + w[j], P the exclusive prefix sums of w (numpy's
+ *      searchsorted(cumsum(w), target, side="right")); its weight is > 0.  Outputs, device pointers of `count` entries, each
+ *      optional: `pushes` int64 (the row number q, not the slot) and `envs` int32, ready for pgv_transitions_gather;
+ *      `priority` uint32; `prob` float32 = float(w) / float(S), two correctly rounded conversions and one division; `totals`
+ *      uint64 [2] = {S, M}.  With S = 0 every push and env is -1, every priority 0 and every prob +0.0f.  Importance
+ *      weights (M * prob)^(-beta) / max are the caller's.  Checked before anything is enqueued: the struct and its
+ *      struct_size, count in 0 .. 2^20 (0 succeeds and writes nothing), 4-byte alignment of envs, priority and prob, 8-byte
+ *      of pushes and totals, priorities enabled.  Three launches (chunk sums over 4096 rows each, their scan, a wavefront
+ *      per sample); the call changes nothing of the engine, and the same seed gives the same bytes. */
+typedef struct pgv_priority_sample {
+    uint32_t struct_size;
+    uint32_t seed;
+    int32_t stratified; /* 0: every target over the whole of S */
+    int64_t* pushes;    /* device [count] or NULL, and so on */
+    int32_t* envs;
+    uint32_t* priority;
+    float* prob;
+    uint64_t* totals;   /* device [2] or NULL */
+} pgv_priority_sample;
+PGV_API int32_t pgv_priorities_enable(pgv_env* env);
+PGV_API const uint32_t* pgv_priorities(pgv_env* env);     /* device uint32 [T][N]; NULL before enable */
+PGV_API const uint32_t* pgv_priorities_max(pgv_env* env); /* device uint32 [1]; NULL before enable */
+PGV_API int32_t pgv_priorities_set(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count,
+                                   const float* d_values);
+PGV_API int32_t pgv_priorities_sample(pgv_env* env, int32_t count, const pgv_priority_sample* sample);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

@@ -19,6 +19,7 @@
 #include "pg_history_aug.h"
 #include "pg_history_filter.h"
 #include "pg_transitions.h"
+#include "pg_priorities.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
 #include "pg_sequence.h"
@@ -299,6 +300,11 @@ struct pgv_env {
     bool transitions = false;
     void* d_transitions = nullptr;
     pg::TransitionBuffers tr{};
+    // prioritised sampling (pg_priorities.h; pgv_priorities_enable): off unless asked for, on top of the transitions.  One
+    // device block holds the [T][N] priorities, the running maximum and the sampler's scratch.
+    bool priorities = false;
+    void* d_priorities = nullptr;
+    pg::PriorityBuffers pr{};
     // both features' value tables, dtype by dtype (pg_planes.h): the uploads' source, so they live as long as the env
     uint32_t value_tables[pg::kPolicyTables][256];  // (filled where the env is made)
 
@@ -387,6 +393,7 @@ void pgv_close(pgv_env* e) {
     if (e->own_policy_out && e->d_policy_out) hipFree(e->d_policy_out);
     if (e->d_history) hipFree(e->d_history);
     if (e->d_transitions) hipFree(e->d_transitions);
+    if (e->d_priorities) hipFree(e->d_priorities);
     if (e->d_host_i32) hipFree(e->d_host_i32);
     if (e->d_host_u8) hipFree(e->d_host_u8);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -655,6 +662,7 @@ static int32_t transition_record(pgv_env* e, const RowOf& row) {
     q.truncated = row.episodes ? e->ep.truncated : nullptr;
     q.b = e->tr;
     pg::launch_transition_record(e->stream, q);
+    if (e->priorities && q.slot >= 0) pg::launch_priority_open(e->stream, pg::PriorityOpen{e->n, q.slot, e->pr});  // the new row at the running maximum
     PG_HIP(hipGetLastError());
     return 0;
 }
@@ -1379,6 +1387,78 @@ int32_t pgv_transitions_gae(pgv_env* e, int64_t first, int32_t length, const pgv
     q.values = gae->values, q.trunc_values = gae->trunc_values, q.advantages = gae->advantages, q.returns = gae->returns;
     q.ring = transition_ring(e);
     pg::launch_transition_gae(e->stream, q);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Prioritised sampling over the transition ring (pg_priorities.h)
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_priorities_enable(pgv_env* e) {
+    if (!e) return fail("pgv_priorities_enable: env is NULL");
+    if (e->priorities) return fail("pgv_priorities_enable: priorities are enabled already (once per env)");
+    if (!e->transitions) return fail("pgv_priorities_enable: call pgv_transitions_enable first");
+    if (int64_t(e->hist.capacity) * e->n >= (int64_t(1) << 31)) return fail("pgv_priorities_enable: capacity * num_envs must be below 2^31");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::PriorityBuffers b{};
+    b.capacity = e->hist.capacity;
+    const size_t bytes = pg::Carve::size(pg::list_priorities, e->n, b);
+    void* mem = nullptr;
+    hipError_t err = hipMalloc(&mem, bytes);
+    if (err == hipSuccess) {
+        pg::Carve::bind(pg::list_priorities, mem, b, e->n);
+        pg::launch_priority_fill(e->stream, b, e->n);  // every row and the maximum at 1.0
+        err = hipGetLastError();
+    }
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        if (mem) (void)hipFree(mem);
+        return fail(std::string("pgv_priorities_enable: ") + hipGetErrorString(err));
+    }
+    e->d_priorities = mem;
+    e->pr = b;
+    e->priorities = true;
+    return 0;
+}
+
+const uint32_t* pgv_priorities(pgv_env* e) { return e && e->priorities ? e->pr.priority : nullptr; }
+const uint32_t* pgv_priorities_max(pgv_env* e) { return e && e->priorities ? e->pr.max : nullptr; }
+
+int32_t pgv_priorities_set(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, const float* d_values) {
+    const char* who = "pgv_priorities_set";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!e->priorities) return fail(std::string(who) + ": call pgv_priorities_enable first");
+    if (count < 0) return fail(std::string(who) + ": count is negative");
+    if ((reinterpret_cast<uintptr_t>(d_pushes) | reinterpret_cast<uintptr_t>(d_envs) | reinterpret_cast<uintptr_t>(d_values)) & 3u)
+        return fail(std::string(who) + ": pushes, envs and values must be 4-byte aligned");
+    if (count == 0) return 0;
+    if (!d_pushes || !d_envs || !d_values) return fail(std::string(who) + ": pushes, envs or values is NULL");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::launch_priority_set(e->stream, pg::PrioritySet{e->n, count, e->history_head, d_pushes, d_envs, d_values, e->pr});
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_priorities_sample(pgv_env* e, int32_t count, const pgv_priority_sample* s) {
+    const char* who = "pgv_priorities_sample";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!s || s->struct_size < sizeof(pgv_priority_sample)) return fail(std::string(who) + ": sample is NULL or struct_size too small");
+    if (count < 0 || count > pg::kPrMaxCount) return fail(std::string(who) + ": count must be in 0 .. 2^20");
+    if ((reinterpret_cast<uintptr_t>(s->envs) | reinterpret_cast<uintptr_t>(s->priority) | reinterpret_cast<uintptr_t>(s->prob)) & 3u)
+        return fail(std::string(who) + ": envs, priority and prob must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(s->pushes) | reinterpret_cast<uintptr_t>(s->totals)) & 7u)
+        return fail(std::string(who) + ": pushes and totals must be 8-byte aligned");
+    if (!e->priorities) return fail(std::string(who) + ": call pgv_priorities_enable first");
+    if (count == 0) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::PrioritySample q{};
+    q.ring = pg::PriorityRing{e->n, e->hist.capacity, e->history_head, e->tr.flags, e->pr};
+    q.count = static_cast<uint32_t>(count), q.seed = s->seed, q.stratified = s->stratified;
+    q.pushes = s->pushes, q.envs = s->envs, q.priority = s->priority, q.prob = s->prob, q.totals = s->totals;
+    pg::launch_priority_sample(e->stream, q);
     PG_HIP(hipGetLastError());
     return 0;
 }

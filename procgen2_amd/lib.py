@@ -114,6 +114,20 @@ def gae(gamma, lam, values, advantages, trunc_values=None, returns=None):
     return Gae(ctypes.sizeof(Gae), float(gamma), float(lam), values, trunc_values, advantages, returns)
 
 
+class PrioritySample(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_priority_sample` (device pointers, each optional)."""
+    _fields_ = [("struct_size", c_uint32), ("seed", c_uint32), ("stratified", c_int32), ("pushes", c_void_p), ("envs", c_void_p),
+                ("priority", c_void_p), ("prob", c_void_p), ("totals", c_void_p)]
+
+
+PRIORITY_ONE = 65536  # a priority of 1.0 in the ring's fixed point
+
+
+def priority_sample(seed, stratified=True, pushes=None, envs=None, priority=None, prob=None, totals=None):
+    """A filled-in PrioritySample; the outputs: device pointers (integers) or None."""
+    return PrioritySample(ctypes.sizeof(PrioritySample), int(seed) & 0xFFFFFFFF, int(bool(stratified)), pushes, envs, priority, prob, totals)
+
+
 class StateLayoutStruct(ctypes.Structure):
     """include/procgen2_vec.h `pgv_state_layout`."""
     _fields_ = [("struct_size", c_uint32), ("width", c_int32), ("fixed", c_int32), ("record", c_int32), ("max_records", c_int32),
@@ -392,6 +406,11 @@ def load(path=None):
         "pgv_transitions_flags": (P, [P]),
         "pgv_transitions_gather": (c_int32, [P, P, P, c_int32, POINTER(TransitionQuery)]),
         "pgv_transitions_gae": (c_int32, [P, c_int64, c_int32, POINTER(Gae)]),
+        "pgv_priorities_enable": (c_int32, [P]),
+        "pgv_priorities": (P, [P]),
+        "pgv_priorities_max": (P, [P]),
+        "pgv_priorities_set": (c_int32, [P, P, P, c_int32, P]),
+        "pgv_priorities_sample": (c_int32, [P, c_int32, POINTER(PrioritySample)]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -442,6 +461,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_history_enable", "pgv_history_frames", "pgv_history_began", "pgv_history_pending", "pgv_history_head", "pgv_history_capacity", "pgv_history_push",
     "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params", "pgv_history_gather_filter", "pgv_gather_filter_params",
     "pgv_transitions_enable", "pgv_transitions_action", "pgv_transitions_reward", "pgv_transitions_flags", "pgv_transitions_gather", "pgv_transitions_gae",
+    "pgv_priorities_enable", "pgv_priorities", "pgv_priorities_max", "pgv_priorities_set", "pgv_priorities_sample",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",
     "pgv_tile_paths_rows", "pgv_tile_paths_rows_host", "pgv_path_layout_of",

@@ -33,8 +33,14 @@ def shard_range(total_envs, world_size, rank):
 class ProcgenVecEnv:
     def __init__(self, game, num_envs, device=0, seed_base=1, env_offset=0, lib_path=None, num_levels=0,
                  start_level=0, distribution_mode=None, game_flags=0, out=None, autoreset_mode=None, max_episode_steps=0,
-                 final_obs_capacity=0, policy_obs=None, history=None, transitions=False):
-        """transitions = False | True (needs history=): the record ring beside the frame history (include/procgen2_vec.h
+                 final_obs_capacity=0, policy_obs=None, history=None, transitions=False, priorities=False):
+        """priorities = False | True (needs transitions=True): prioritised sampling over the record ring (include/procgen2_vec.h
+        pgv_priorities_enable) — `transitions.priority`, a zero-copy [T, N] view of the fixed-point priorities (int32 bits of the
+        engine's uint32, pglib.PRIORITY_ONE = 1.0); every new row is opened at the running maximum.  transition_sample() draws
+        (push, env) pairs over exactly the rows transition_gather() calls valid, transition_priorities() stores a learner's new
+        priorities.  False changes nothing at all.
+
+        transitions = False | True (needs history=): the record ring beside the frame history (include/procgen2_vec.h
         pgv_transitions_enable) — `transitions`, a TransitionTensors: zero-copy [T, N] views `action` int32, `reward` float32,
         `flags` u8 (pglib.TR_* bits); row q describes the call that made push q + 1.  transition_gather() for n-step
         transitions of any (push, env) pairs, transition_gae() for advantages over a stretch of the ring.  False changes nothing
@@ -75,6 +81,10 @@ class ProcgenVecEnv:
             raise ValueError("transitions=True needs history=dict(capacity=T, ...) with T >= 2")
         if transitions and ring[0] < 2:
             raise ValueError("transitions=True needs a history capacity >= 2")
+        if priorities not in (False, True):
+            raise ValueError("priorities must be True or False")
+        if priorities and not transitions:
+            raise ValueError("priorities=True needs transitions=True")
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         # The engine gets a stream of its own (a torch stream, so torch can order against it): torch's default stream
@@ -170,8 +180,10 @@ class ProcgenVecEnv:
             try:
                 self._before()
                 pglib.transitions_enable(self.L, h)
+                if priorities:
+                    pglib.check(self.L, self.L.pgv_priorities_enable(h), "pgv_priorities_enable")
                 self._after()
-                self.transitions = TransitionTensors(self)
+                self.transitions = TransitionTensors(self, priorities)
             except Exception:
                 self.close()
                 raise
@@ -517,6 +529,51 @@ class ProcgenVecEnv:
         self._after()
         self._keep_gae = (v, tv, adv, ret)
         return adv, ret
+
+    def _needs_priorities(self, who):
+        if self.transitions is None or self.transitions.priority is None:
+            raise pglib.EngineError(who + " needs an env made with transitions=True, priorities=True")
+
+    def transition_priorities(self, pushes, envs, values):
+        """Store the float32 priorities values[b] for the rows (pushes[b], envs[b]) in one launch (pgv_priorities_set), in the
+        ring's fixed point — round(value * 65536), at least 1, at most 2^31 - 1 — and raise the running maximum new rows are
+        opened at.  A pair whose row is not held with its successor, or whose env is outside the batch, is skipped.  The
+        exponent alpha is the caller's.  Same stream hand-shake as step(), no host synchronisation."""
+        self._needs_priorities("transition_priorities")
+        p, i = self._gather_entries("transition_priorities", pushes, envs)
+        v = torch.as_tensor(values, device=self.device).to(torch.float32).reshape(-1).contiguous()
+        if v.numel() != p.numel():
+            raise ValueError("transition_priorities: %d pushes but %d values" % (p.numel(), v.numel()))
+        if p.numel():
+            self._before()
+            pglib.check(self.L, self.L.pgv_priorities_set(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), p.numel(), c_void_p(v.data_ptr())),
+                        "pgv_priorities_set")
+            self._after()
+            self._keep_priorities = (p, i, v)
+
+    def transition_sample(self, count, seed, stratified=True):
+        """`count` (0 .. 2^20) rows of the record ring drawn in proportion to their priorities, over exactly the rows
+        transition_gather() calls valid (pgv_priorities_sample): a TransitionSample of pushes int64 [count] and envs int32
+        [count], ready for transition_gather(); prob float32 [count], a row's priority over the total; priority int32 [count],
+        fixed point; total and eligible, int64 scalars: the sum of the eligible rows' priorities and their number — importance
+        weights are (eligible * prob) ** -beta over their maximum.  stratified: sample k is drawn from the k-th of `count` equal
+        parts of the total.  With no eligible row every push and env is -1 and every prob 0.  The same seed gives the same
+        sample.  Three launches, no host synchronisation."""
+        self._needs_priorities("transition_sample")
+        if isinstance(count, bool) or not isinstance(count, int) or not 0 <= count <= 1 << 20:
+            raise ValueError("transition_sample: count must be an integer in 0 .. 2**20")
+        pushes = torch.empty(count, dtype=torch.int64, device=self.device)
+        envs = torch.empty(count, dtype=torch.int32, device=self.device)
+        prob = torch.empty(count, dtype=torch.float32, device=self.device)
+        priority = torch.empty(count, dtype=torch.int32, device=self.device)
+        totals = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if count:
+            s = pglib.priority_sample(seed, stratified, pushes.data_ptr(), envs.data_ptr(), priority.data_ptr(), prob.data_ptr(), totals.data_ptr())
+            self._before()
+            pglib.check(self.L, self.L.pgv_priorities_sample(self._h, count, ctypes.byref(s)), "pgv_priorities_sample")
+            self._after()
+            self._keep_sample = (pushes, envs, prob, priority, totals)
+        return TransitionSample(pushes, envs, prob, priority, totals[0], totals[1])
 
     def _before(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -963,16 +1020,21 @@ class HistoryTensors:
 class TransitionTensors:
     """The record ring of a ProcgenVecEnv made with transitions=True: zero-copy [T, N] views; row q lives in slot q % T."""
 
-    def __init__(self, env):
+    def __init__(self, env, priorities=False):
+        """priorities: the engine has them enabled — `priority`, the fixed-point ring (its uint32 never exceeds 2^31 - 1, so the
+        view is int32, which torch computes with) and `priority_max`, the running maximum [1]; None otherwise."""
         L, h, n = env.L, env._h, env.num_envs
         T = int(L.pgv_history_capacity(h))
         self.capacity = T
+        self.priority = _device_view(L.pgv_priorities(h), T * n, "<i4", env.device).view(T, n) if priorities else None
+        self.priority_max = _device_view(L.pgv_priorities_max(h), 1, "<i4", env.device) if priorities else None
         self.action = _device_view(L.pgv_transitions_action(h), T * n, "<i4", env.device).view(T, n)
         self.reward = _device_view(L.pgv_transitions_reward(h), T * n, "<f4", env.device).view(T, n)
         self.flags = _device_view(L.pgv_transitions_flags(h), T * n, "|u1", env.device).view(T, n)
 
 
 Transition = collections.namedtuple("Transition", "obs next_obs action nstep_return discount steps status")
+TransitionSample = collections.namedtuple("TransitionSample", "pushes envs prob priority total eligible")
 
 
 def _augment_config(augment):
