@@ -200,31 +200,70 @@ static const Variant* find_variant(int game, int mode) {
     return nullptr;
 }
 
-// Device buffers for one call of a host-pointer entry point, filled from and read back to host memory on the env's stream.
-// The first error is kept and what follows it skipped; on every way out the stream is drained before the buffers are freed.
+// A hipMalloc'ed block and its one owner: freed where the owner goes, handed on by move alone.
+template <class T>
+struct DeviceBlock {
+    T* p = nullptr;
+    DeviceBlock() = default;
+    DeviceBlock(DeviceBlock&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DeviceBlock& operator=(DeviceBlock&& o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~DeviceBlock() {
+        if (p) (void)hipFree(p);
+    }
+    operator T*() const { return p; }
+};
+
+// The device mirrors of a host-pointer entry point's buffers, for one call, on the env's stream.  A buffer is declared once,
+// as an input (`in`: copied up) or an output (`out`: fetched back by `run`); a NULL host pointer gives a NULL device pointer
+// and no traffic.  The first error is kept and what follows it skipped; on every way out the stream is drained before the
+// buffers are freed (the host buffers are the caller's, and a kernel may still read the device ones).
 struct Staged {
     hipStream_t stream;
     hipError_t err = hipSuccess;
-    std::vector<void*> held;
-    ~Staged() {
-        (void)hipStreamSynchronize(stream);
-        for (void* p : held) (void)hipFree(p);
+    struct Out {
+        void* h_to;
+        const void* d_from;
+        size_t bytes;
+    };
+    std::vector<DeviceBlock<void>> held;
+    std::vector<Out> outs;
+    ~Staged() { (void)hipStreamSynchronize(stream); }  // (in front of `held`'s frees)
+    template <class T>
+    T* in(const T* h_from, size_t count) {  // device T[count], a copy of h_from[count]
+        T* d = alloc<T>(h_from, count);
+        if (d && err == hipSuccess) err = hipMemcpyAsync(d, h_from, count * sizeof(T), hipMemcpyHostToDevice, stream);
+        return d;
     }
     template <class T>
-    T* alloc(size_t count, const T* h_from = nullptr) {  // device T[count], with a copy of h_from[count] where given
-        void* p = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T));
-        if (p) held.push_back(p);
-        if (h_from) upload(p, h_from, count * sizeof(T));
-        return static_cast<T*>(p);
+    T* out(T* h_to, size_t count) {  // device T[count], h_to[count] once the call has run
+        T* d = alloc<T>(h_to, count);
+        if (d) outs.push_back({h_to, d, count * sizeof(T)});
+        return d;
     }
-    void upload(void* d_to, const void* h_from, size_t bytes) {
-        if (err == hipSuccess) err = hipMemcpyAsync(d_to, h_from, bytes, hipMemcpyHostToDevice, stream);
+    // The device form's call, where nothing failed so far: its refusal is returned as it is (the message is its own), else
+    // the stream is drained and every output fetched.  A HIP error of any step is said under `who`.
+    template <class Call>
+    int32_t run(const char* who, Call&& device_form) {
+        if (err == hipSuccess) {
+            if (const int32_t rc = device_form()) return rc;
+            if (err == hipSuccess) err = hipStreamSynchronize(stream);
+            for (const Out& o : outs)
+                if (err == hipSuccess) err = hipMemcpy(o.h_to, o.d_from, o.bytes, hipMemcpyDeviceToHost);
+        }
+        if (err != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(err));
+        return 0;
     }
-    void finish() { err = err == hipSuccess ? hipStreamSynchronize(stream) : err; }
-    void fetch(void* h_to, const void* d_from, size_t bytes) {  // behind everything the stream holds
-        finish();
-        if (err == hipSuccess) err = hipMemcpy(h_to, d_from, bytes, hipMemcpyDeviceToHost);
+
+private:
+    template <class T>
+    T* alloc(const void* host, size_t count) {
+        if (!host || err != hipSuccess) return nullptr;
+        held.emplace_back();
+        err = hipMalloc(&held.back().p, count * sizeof(T));
+        return static_cast<T*>(held.back().p);
     }
 };
 
@@ -241,15 +280,15 @@ struct pgv_env {
     bool own_stream = false;
     std::unique_ptr<pg::Game> game;
     pg::Atlas atlas;
-    void* d_state = nullptr;
+    pg::DeviceBlock<void> d_state;
     bool counted = false;       // among g_live_engines (note_engine_made)
-    void* d_scratch = nullptr;  // Game::scratch_bytes: per-frame hand-over between a game's kernels, not part of any snapshot
+    pg::DeviceBlock<void> d_scratch;  // Game::scratch_bytes: per-frame hand-over between a game's kernels, not part of any snapshot
     uint8_t* d_obs = nullptr;
     float* d_reward = nullptr;
     uint8_t* d_done = nullptr;
-    uint8_t* d_pending = nullptr;
-    int32_t* d_host_i32 = nullptr;  // staging for the *_host entry points
-    uint8_t* d_host_u8 = nullptr;
+    pg::DeviceBlock<uint8_t> d_pending;
+    pg::DeviceBlock<int32_t> d_host_i32;  // staging for the *_host entry points
+    pg::DeviceBlock<uint8_t> d_host_u8;
     bool own_obs = false, own_reward = false, own_done = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // level prefetch (pg_prefetch.h): generator launches on a side stream, ordered behind the main stream by events
@@ -271,39 +310,39 @@ struct pgv_env {
     // the engine's own rows and level words are filled in per call (pgv_bind_outputs may move the rows).
     bool episodes = false;
     int ep_autoreset = 0;
-    void* d_episodes = nullptr;
+    pg::DeviceBlock<void> d_episodes;
     pg::EpisodeBuffers ep{};
     // steps without frames (pg_sequence.h; pgv_step_sequence): the running values of the summary, one block
-    void* d_sequence = nullptr;
+    pg::DeviceBlock<void> d_sequence;
     pg::SequenceBuffers seq{};
     // caller-made levels (pg_levels.h; pgv_set_levels): an install's claim words and mask, one block, for a game that has them
-    void* d_levels = nullptr;
+    pg::DeviceBlock<void> d_levels;
     pg::LevelBuffers lev{};
     // the debug taps (pgv_dump_state / pgv_dump_tiles): room for one env's state row and tile row, one block
-    void* d_tap = nullptr;
+    pg::DeviceBlock<void> d_tap;
     pg::TapBuffers tap{};
     // policy-ready observations (pg_policy_obs.h; pgv_policy_obs_enable): off unless asked for.  One device block holds the
     // restart flags and the value table; the tensor is the caller's, or the engine's own.
     bool policy = false, own_policy_out = false;
     int policy_stack = 0, policy_planes = 0, policy_es = 0;
-    void* d_policy = nullptr;
+    pg::DeviceBlock<void> d_policy;
     uint8_t* d_policy_out = nullptr;
     pg::PolicyObsBuffers pol{};
     // frame history (pg_history.h; pgv_history_enable): off unless asked for.  One device block holds the pending flags, the
     // began bytes, the value tables and — unless the caller brought them — the frames.  `history_head` counts the pushes.
     bool history = false;
     int64_t history_head = 0;
-    void* d_history = nullptr;
+    pg::DeviceBlock<void> d_history;
     pg::HistoryBuffers hist{};
     // transitions (pg_transitions.h; pgv_transitions_enable): off unless asked for, on top of the frame history.  One device
     // block holds the pending bytes and the three [T][N] arrays; a row's slot follows `history_head`.
     bool transitions = false;
-    void* d_transitions = nullptr;
+    pg::DeviceBlock<void> d_transitions;
     pg::TransitionBuffers tr{};
     // prioritised sampling (pg_priorities.h; pgv_priorities_enable): off unless asked for, on top of the transitions.  One
     // device block holds the [T][N] priorities, the running maximum and the sampler's scratch.
     bool priorities = false;
-    void* d_priorities = nullptr;
+    pg::DeviceBlock<void> d_priorities;
     pg::PriorityBuffers pr{};
     // both features' value tables, dtype by dtype (pg_planes.h): the uploads' source, so they live as long as the env
     uint32_t value_tables[pg::kPolicyTables][256];  // (filled where the env is made)
@@ -314,7 +353,7 @@ struct pgv_env {
     struct Row { void** d; size_t bytes_per_env; };
     std::array<Row, 4> rows() {
         return {{{reinterpret_cast<void**>(&d_reward), 4}, {reinterpret_cast<void**>(&d_done), 1},
-                 {reinterpret_cast<void**>(&d_pending), 1}, {reinterpret_cast<void**>(&d_obs), size_t(pg::kObsBytes)}}};
+                 {reinterpret_cast<void**>(&d_pending.p), 1}, {reinterpret_cast<void**>(&d_obs), size_t(pg::kObsBytes)}}};
     }
 };
 
@@ -342,6 +381,27 @@ static void pregen(pgv_env* e, bool bulk, bool force) {
 }
 
 using pg::fail;
+
+// An opt-in feature's device block (the *_enable calls): sized and bound by the feature's listing, filled on the env's stream
+// by `fill(block, bytes)`, and `owner`'s only when all of that went well.  On a HIP error the stream is drained before the
+// block is freed: a fill may be queued on it.
+template <class B, class Fill>
+static int32_t enable_block(const char* who, pgv_env* e, void (*list)(pg::Carve&, B&, int), B& b, pg::DeviceBlock<void>& owner, Fill&& fill) {
+    const size_t bytes = pg::Carve::size(list, e->n, b);
+    pg::DeviceBlock<void> mem;
+    hipError_t err = hipMalloc(&mem.p, bytes);
+    if (err == hipSuccess) {
+        pg::Carve::bind(list, mem.p, b, e->n);
+        err = fill(mem.p, bytes);
+    }
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(e->stream);
+        return fail(std::string(who) + ": " + hipGetErrorString(err));
+    }
+    owner = std::move(mem);
+    return 0;
+}
 
 extern "C" {
 
@@ -379,25 +439,12 @@ void pgv_close(pgv_env* e) {
     if (e->reset_fork) hipEventDestroy(e->reset_fork);
     if (e->reset_join) hipEventDestroy(e->reset_join);
     if (e->rec_ev) hipEventDestroy(e->rec_ev);
-    if (e->d_state) hipFree(e->d_state);
-    if (e->d_scratch) hipFree(e->d_scratch);
     if (e->own_obs && e->d_obs) hipFree(e->d_obs);
     if (e->own_reward && e->d_reward) hipFree(e->d_reward);
     if (e->own_done && e->d_done) hipFree(e->d_done);
-    if (e->d_pending) hipFree(e->d_pending);
-    if (e->d_episodes) hipFree(e->d_episodes);
-    if (e->d_sequence) hipFree(e->d_sequence);
-    if (e->d_levels) hipFree(e->d_levels);
-    if (e->d_tap) hipFree(e->d_tap);
-    if (e->d_policy) hipFree(e->d_policy);
     if (e->own_policy_out && e->d_policy_out) hipFree(e->d_policy_out);
-    if (e->d_history) hipFree(e->d_history);
-    if (e->d_transitions) hipFree(e->d_transitions);
-    if (e->d_priorities) hipFree(e->d_priorities);
-    if (e->d_host_i32) hipFree(e->d_host_i32);
-    if (e->d_host_u8) hipFree(e->d_host_u8);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
-    delete e;
+    delete e;  // (the blocks the engine owns outright go with it: DeviceBlock; the streams above are drained)
 }
 
 // The device state blob: the game's SoA state followed by the level plan's per-env arrays (pg_carve.h list_plan), so that
@@ -545,7 +592,7 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
     e->game->extend_atlas(e->atlas);
     if (!e->atlas.upload(err)) return fail("pgv_make: " + err);
     const size_t sb = state_blob_bytes(e.get());
-    PG_HIP(hipMalloc(&e->d_state, sb));
+    PG_HIP(hipMalloc(&e->d_state.p, sb));
     PG_HIP(hipMemsetAsync(e->d_state, 0, sb, e->stream));
     e->own_obs = e->own_reward = e->own_done = true;
     for (const pgv_env::Row& row : e->rows()) {
@@ -553,26 +600,26 @@ int32_t pgv_make_config(const pgv_config* cfg, pgv_env** out) {
         PG_HIP(hipMemsetAsync(*row.d, 0, size_t(num_envs) * row.bytes_per_env, e->stream));
     }
 
-    PG_HIP(hipMalloc(&e->d_sequence, pg::Carve::size(pg::list_sequence, num_envs)));  // (written before it is read: pg_sequence.h)
+    PG_HIP(hipMalloc(&e->d_sequence.p, pg::Carve::size(pg::list_sequence, num_envs)));  // (written before it is read: pg_sequence.h)
     pg::Carve::bind(pg::list_sequence, e->d_sequence, e->seq, num_envs);
     if (e->game->level_layout().supported) {  // (zeroed in front of every install)
-        PG_HIP(hipMalloc(&e->d_levels, pg::Carve::size(pg::list_levels, num_envs)));
+        PG_HIP(hipMalloc(&e->d_levels.p, pg::Carve::size(pg::list_levels, num_envs)));
         pg::Carve::bind(pg::list_levels, e->d_levels, e->lev, num_envs);
     }
 
     e->game->bind(e->d_state, num_envs, e->atlas.view());
     if (const size_t scratch = e->game->scratch_bytes(num_envs)) {
-        PG_HIP(hipMalloc(&e->d_scratch, scratch));
+        PG_HIP(hipMalloc(&e->d_scratch.p, scratch));
         PG_HIP(hipMemsetAsync(e->d_scratch, 0, scratch, e->stream));
         e->game->bind_scratch(e->d_scratch, num_envs);
     }
     pg::EnvRegions planned;
     e->game->plan = pg::LevelPlan{num_levels, start_level};
-    pg::Carve::bind(pg::list_plan, static_cast<uint8_t*>(e->d_state) + game_state_bytes(e.get()), e->game->plan, num_envs, &planned);
+    pg::Carve::bind(pg::list_plan, static_cast<uint8_t*>(e->d_state.p) + game_state_bytes(e.get()), e->game->plan, num_envs, &planned);
     if (plan_records(e.get(), planned)) return 1;
     // (the last allocation of the call: a debug buffer does not move the addresses of what the step works on)
     e->tap.width = e->game->state_layout().width, e->tap.cells = e->game->state_layout().cells;
-    PG_HIP(hipMalloc(&e->d_tap, pg::Carve::size(pg::list_tap, 1, e->tap)));  // (written before it is read, by every tap)
+    PG_HIP(hipMalloc(&e->d_tap.p, pg::Carve::size(pg::list_tap, 1, e->tap)));  // (written before it is read, by every tap)
     pg::Carve::bind(pg::list_tap, e->d_tap, e->tap, 1);
     e->game->launch_make(e->stream, seed_base, env_offset);
     PG_HIP(hipGetLastError());
@@ -799,8 +846,15 @@ int32_t pgv_step_synthetic_many(pgv_env* const* envs, int32_t count, int32_t ste
 }
 
 static int32_t ensure_staging(pgv_env* e) {
-    if (!e->d_host_i32) PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_host_i32), size_t(e->n) * 4));
-    if (!e->d_host_u8) PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_host_u8), size_t(e->n)));
+    if (!e->d_host_i32) PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_host_i32.p), size_t(e->n) * 4));
+    if (!e->d_host_u8) PG_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_host_u8.p), size_t(e->n)));
+    return 0;
+}
+// A host caller's actions for one step, in the engine's own staging row: the per-step path allocates nothing per call.
+static int32_t stage_actions(pgv_env* e, const int32_t* h_actions) {
+    if (ensure_staging(e)) return 1;
+    PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
+    PG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is the caller's: do not keep reading it
     return 0;
 }
 
@@ -809,9 +863,7 @@ int32_t pgv_step_host(pgv_env* e, const int32_t* h_actions) {
     if (!h_actions) return fail("pgv_step_host: actions is NULL");
     if (slab_ready("pgv_step_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
-    if (ensure_staging(e)) return 1;
-    PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
-    PG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is the caller's: do not keep reading it
+    if (stage_actions(e, h_actions)) return 1;
     return pgv_step(e, e->d_host_i32);
 }
 
@@ -850,16 +902,9 @@ int32_t pgv_episodes_enable(pgv_env* e, const pgv_episode_config* cfg) {
     b.capacity = cfg->final_capacity;
     b.level_number = e->game->plan.number;
     b.level_known = e->game->plan.known;
-    const size_t bytes = pg::Carve::size(pg::list_episodes, e->n, b);
-    void* mem = nullptr;
-    PG_HIP(hipMalloc(&mem, bytes));
-    hipError_t err = hipMemsetAsync(mem, 0, bytes, e->stream);
-    if (err != hipSuccess) {
-        (void)hipFree(mem);
-        return fail(std::string("pgv_episodes_enable: ") + hipGetErrorString(err));
-    }
-    pg::Carve::bind(pg::list_episodes, mem, b, e->n);
-    e->d_episodes = mem;
+    if (enable_block("pgv_episodes_enable", e, pg::list_episodes, b, e->d_episodes,
+                     [&](void* mem, size_t bytes) { return hipMemsetAsync(mem, 0, bytes, e->stream); }))
+        return 1;
     e->ep = b;
     e->ep_autoreset = cfg->autoreset;
     e->episodes = true;
@@ -944,9 +989,7 @@ int32_t pgv_step_episodes_host(pgv_env* e, const int32_t* h_actions) {
     if (!e->episodes) return fail("pgv_step_episodes_host: call pgv_episodes_enable first");
     if (slab_ready("pgv_step_episodes_host", e)) return 1;
     PG_HIP(hipSetDevice(e->device));
-    if (ensure_staging(e)) return 1;
-    PG_HIP(hipMemcpyAsync(e->d_host_i32, h_actions, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
-    PG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is the caller's: do not keep reading it
+    if (stage_actions(e, h_actions)) return 1;
     return step_episodes_push("pgv_step_episodes_host", e, e->d_host_i32, 0);
 }
 
@@ -1005,23 +1048,13 @@ int32_t pgv_step_sequence_host(pgv_env* e, const pgv_sequence* q) {
     const size_t n = size_t(e->n), rows = size_t(q->steps) * n;
     pg::Staged dev{e->stream};
     pgv_sequence d = *q;
-    if (q->actions) d.actions = dev.alloc(q->action_stride ? size_t(q->steps - 1) * size_t(q->action_stride) + n : n, q->actions);
-    if (q->rewards) d.rewards = dev.alloc<float>(rows);
-    if (q->dones) d.dones = dev.alloc<uint8_t>(rows);
-    if (q->seq_return) d.seq_return = dev.alloc<float>(n);
-    if (q->seq_length) d.seq_length = dev.alloc<int32_t>(n);
-    if (q->seq_done) d.seq_done = dev.alloc<uint8_t>(n);
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_step_sequence(e, &d)) return rc;
-        if (q->rewards) dev.fetch(q->rewards, d.rewards, rows * 4);
-        if (q->dones) dev.fetch(q->dones, d.dones, rows);
-        if (q->seq_return) dev.fetch(q->seq_return, d.seq_return, n * 4);
-        if (q->seq_length) dev.fetch(q->seq_length, d.seq_length, n * 4);
-        if (q->seq_done) dev.fetch(q->seq_done, d.seq_done, n);
-        dev.finish();
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_step_sequence_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    d.actions = dev.in(q->actions, q->action_stride ? size_t(q->steps - 1) * size_t(q->action_stride) + n : n);
+    d.rewards = dev.out(q->rewards, rows);
+    d.dones = dev.out(q->dones, rows);
+    d.seq_return = dev.out(q->seq_return, n);
+    d.seq_length = dev.out(q->seq_length, n);
+    d.seq_done = dev.out(q->seq_done, n);
+    return dev.run("pgv_step_sequence_host", [&] { return pgv_step_sequence(e, &d); });
 }
 
 // The frames of the state as it stands, by the launches pgv_reset draws its frames with: the pre-pass and the render launch
@@ -1045,13 +1078,8 @@ int32_t pgv_render_obs_host(pgv_env* e, const uint8_t* h_mask) {
     if (!e) return fail("pgv_render_obs_host: env is NULL");
     PG_HIP(hipSetDevice(e->device));
     pg::Staged dev{e->stream};
-    const uint8_t* d_mask = h_mask ? dev.alloc(size_t(e->n), h_mask) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_render_obs(e, d_mask)) return rc;
-        dev.finish();
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_render_obs_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    const uint8_t* d_mask = dev.in(h_mask, size_t(e->n));
+    return dev.run("pgv_render_obs_host", [&] { return pgv_render_obs(e, d_mask); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1068,27 +1096,19 @@ int32_t pgv_policy_obs_enable(pgv_env* e, const pgv_policy_obs_config* cfg) {
     PG_HIP(hipSetDevice(e->device));
     const int planes = cfg->gray ? 1 : 3, es = pg::policy_element_bytes(cfg->dtype);
     const size_t out_bytes = size_t(e->n) * pg::policy_bytes_per_env(cfg->stack, planes, es);
-    void* mem = nullptr;
-    void* out = cfg->out;
+    pg::DeviceBlock<void> own_out;  // the engine's own tensor, where the caller brought none
     pg::PolicyObsBuffers b{};
-    hipError_t err = hipMalloc(&mem, pg::Carve::size(pg::list_policy_obs, e->n));
-    if (err == hipSuccess && !out) err = hipMalloc(&out, out_bytes);
-    if (err == hipSuccess && !cfg->out) err = hipMemsetAsync(out, 0, out_bytes, e->stream);
-    if (err == hipSuccess) {
-        pg::Carve::bind(pg::list_policy_obs, mem, b, e->n);
-        err = hipMemsetAsync(b.restart, 1, size_t(e->n), e->stream);  // the first push fills every stack
-    }
-    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->value_tables[cfg->dtype], sizeof(e->value_tables[0]), hipMemcpyHostToDevice, e->stream);
-    if (err != hipSuccess) {
-        (void)hipStreamSynchronize(e->stream);
-        if (mem) (void)hipFree(mem);
-        if (out && !cfg->out) (void)hipFree(out);
-        return fail(std::string("pgv_policy_obs_enable: ") + hipGetErrorString(err));
-    }
-    e->d_policy = mem;
+    auto fill = [&](void*, size_t) {
+        hipError_t err = cfg->out ? hipSuccess : hipMalloc(&own_out.p, out_bytes);
+        if (err == hipSuccess && !cfg->out) err = hipMemsetAsync(own_out, 0, out_bytes, e->stream);
+        if (err == hipSuccess) err = hipMemsetAsync(b.restart, 1, size_t(e->n), e->stream);  // the first push fills every stack
+        if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->value_tables[cfg->dtype], sizeof(e->value_tables[0]), hipMemcpyHostToDevice, e->stream);
+        return err;
+    };
+    if (enable_block("pgv_policy_obs_enable", e, pg::list_policy_obs, b, e->d_policy, fill)) return 1;
     e->pol = b;
-    e->d_policy_out = static_cast<uint8_t*>(out);
     e->own_policy_out = !cfg->out;
+    e->d_policy_out = static_cast<uint8_t*>(cfg->out ? cfg->out : std::exchange(own_out.p, nullptr));
     e->policy_stack = cfg->stack;
     e->policy_planes = planes;
     e->policy_es = es;
@@ -1116,13 +1136,8 @@ int32_t pgv_policy_obs_push_host(pgv_env* e, const uint8_t* h_mask) {
     if (!e->policy) return fail("pgv_policy_obs_push_host: call pgv_policy_obs_enable first");
     PG_HIP(hipSetDevice(e->device));
     pg::Staged dev{e->stream};
-    const uint8_t* d_mask = h_mask ? dev.alloc(size_t(e->n), h_mask) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_policy_obs_push(e, d_mask)) return rc;
-        dev.finish();
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_policy_obs_push_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    const uint8_t* d_mask = dev.in(h_mask, size_t(e->n));
+    return dev.run("pgv_policy_obs_push_host", [&] { return pgv_policy_obs_push(e, d_mask); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1140,23 +1155,14 @@ int32_t pgv_history_enable(pgv_env* e, const pgv_history_config* cfg) {
     b.capacity = cfg->capacity;
     b.planes = cfg->gray ? 1 : 3;
     b.own_frames = cfg->frames ? 0 : 1;
-    const size_t bytes = pg::Carve::size(pg::list_history, e->n, b);
-    void* mem = nullptr;
-    hipError_t err = hipMalloc(&mem, bytes);
-    if (err == hipSuccess) {
-        pg::Carve::bind(pg::list_history, mem, b, e->n);
-        err = hipMemsetAsync(mem, 0, bytes, e->stream);  // began, and the engine's own frames
-    }
-    if (err == hipSuccess) err = hipMemsetAsync(b.pending, 1, size_t(e->n), e->stream);  // every env's first frame begins its history
-    if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->value_tables, sizeof(e->value_tables), hipMemcpyHostToDevice, e->stream);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(e->stream);
-        if (mem) (void)hipFree(mem);
-        return fail(std::string("pgv_history_enable: ") + hipGetErrorString(err));
-    }
+    auto fill = [&](void* mem, size_t bytes) {
+        hipError_t err = hipMemsetAsync(mem, 0, bytes, e->stream);  // began, and the engine's own frames
+        if (err == hipSuccess) err = hipMemsetAsync(b.pending, 1, size_t(e->n), e->stream);  // every env's first frame begins its history
+        if (err == hipSuccess) err = hipMemcpyAsync(b.table, e->value_tables, sizeof(e->value_tables), hipMemcpyHostToDevice, e->stream);
+        return err;
+    };
+    if (enable_block("pgv_history_enable", e, pg::list_history, b, e->d_history, fill)) return 1;
     if (cfg->frames) b.frames = static_cast<uint8_t*>(cfg->frames);
-    e->d_history = mem;
     e->hist = b;
     e->history_head = 0;
     e->history = true;
@@ -1316,17 +1322,9 @@ int32_t pgv_transitions_enable(pgv_env* e, const pgv_transitions_config* cfg) {
     PG_HIP(hipSetDevice(e->device));
     pg::TransitionBuffers b{};
     b.capacity = e->hist.capacity;
-    const size_t bytes = pg::Carve::size(pg::list_transitions, e->n, b);
-    void* mem = nullptr;
-    hipError_t err = hipMalloc(&mem, bytes);
-    if (err == hipSuccess) err = hipMemsetAsync(mem, 0, bytes, e->stream);  // no row recorded, no reset found
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        if (mem) (void)hipFree(mem);
-        return fail(std::string("pgv_transitions_enable: ") + hipGetErrorString(err));
-    }
-    pg::Carve::bind(pg::list_transitions, mem, b, e->n);
-    e->d_transitions = mem;
+    if (enable_block("pgv_transitions_enable", e, pg::list_transitions, b, e->d_transitions,  // no row recorded, no reset found
+                     [&](void* mem, size_t bytes) { return hipMemsetAsync(mem, 0, bytes, e->stream); }))
+        return 1;
     e->tr = b;
     e->transitions = true;
     return 0;
@@ -1403,20 +1401,11 @@ int32_t pgv_priorities_enable(pgv_env* e) {
     (void)hipGetLastError();
     pg::PriorityBuffers b{};
     b.capacity = e->hist.capacity;
-    const size_t bytes = pg::Carve::size(pg::list_priorities, e->n, b);
-    void* mem = nullptr;
-    hipError_t err = hipMalloc(&mem, bytes);
-    if (err == hipSuccess) {
-        pg::Carve::bind(pg::list_priorities, mem, b, e->n);
+    auto fill = [&](void*, size_t) {
         pg::launch_priority_fill(e->stream, b, e->n);  // every row and the maximum at 1.0
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        if (mem) (void)hipFree(mem);
-        return fail(std::string("pgv_priorities_enable: ") + hipGetErrorString(err));
-    }
-    e->d_priorities = mem;
+        return hipGetLastError();
+    };
+    if (enable_block("pgv_priorities_enable", e, pg::list_priorities, b, e->d_priorities, fill)) return 1;
     e->pr = b;
     e->priorities = true;
     return 0;
@@ -1511,7 +1500,7 @@ static size_t snapshot_bytes(pgv_env* e) {
 }
 // What follows the header: the state blob, then the output rows — device to host (save) or back (load).
 static int32_t snapshot_copy(pgv_env* e, uint8_t* h_body, size_t blob_bytes, bool load) {
-    std::vector<std::pair<void*, size_t>> parts{{e->d_state, blob_bytes}};
+    std::vector<std::pair<void*, size_t>> parts{{e->d_state.p, blob_bytes}};
     for (const pgv_env::Row& row : e->rows()) parts.push_back({*row.d, size_t(e->n) * row.bytes_per_env});
     for (const auto& [d, bytes] : parts) {
         PG_HIP(load ? hipMemcpy(d, h_body, bytes, hipMemcpyHostToDevice) : hipMemcpy(h_body, d, bytes, hipMemcpyDeviceToHost));
@@ -1586,15 +1575,17 @@ static pg::RecordTable records_table(const pgv_env* e) {
     t.due_mark = t.due_code = e->game->pending_has_parity() ? pg::reset_due_mark(e->step_index) : 1;
     return t;
 }
-static int32_t records_arguments(const char* who, pgv_env* e, int32_t count, const void* records) {
+// What the calls over a list of `count` envs check first, a device form and its host twin the same way; `who` heads the
+// message.  `buffer`, where `what` names one: the array a call of count > 0 cannot do without.
+static int32_t list_arguments(const char* who, const pgv_env* e, int32_t count, const void* buffer = nullptr, const char* what = nullptr) {
     if (!e) return fail(std::string(who) + ": env is NULL");
     if (count < 0) return fail(std::string(who) + ": count is negative");
-    if (count > 0 && !records) return fail(std::string(who) + ": the record buffer is NULL");
+    if (what && count > 0 && !buffer) return fail(std::string(who) + ": the " + what + " buffer is NULL");
     return 0;
 }
 
 int32_t pgv_save_envs(pgv_env* e, const int32_t* d_indices, int32_t count, void* d_records) {
-    if (records_arguments("pgv_save_envs", e, count, d_records)) return 1;
+    if (list_arguments("pgv_save_envs", e, count, d_records, "record")) return 1;
     if (count == 0) return 0;
     if (reinterpret_cast<uintptr_t>(d_records) & 15u) return fail("pgv_save_envs: the record buffer must be 16-byte aligned");
     PG_HIP(hipSetDevice(e->device));
@@ -1607,7 +1598,7 @@ int32_t pgv_save_envs(pgv_env* e, const int32_t* d_indices, int32_t count, void*
 }
 
 int32_t pgv_load_envs(pgv_env* e, const int32_t* d_indices, int32_t count, const void* d_records, uint64_t tag) {
-    if (records_arguments("pgv_load_envs", e, count, d_records)) return 1;
+    if (list_arguments("pgv_load_envs", e, count, d_records, "record")) return 1;
     if (tag != e->rec_tag)
         return fail("pgv_load_envs: records of another configuration (game, mode, game_flags, level set or record layout): tag " +
                     std::to_string(tag) + ", this engine's is " + std::to_string(e->rec_tag));
@@ -1630,21 +1621,16 @@ int32_t pgv_load_envs(pgv_env* e, const int32_t* d_indices, int32_t count, const
 // Host-pointer forms: device buffers for the call, a synchronous copy either way.
 static int32_t records_host(pgv_env* e, const int32_t* h_indices, int32_t count, void* h_records, bool load, uint64_t tag) {
     const char* who = load ? "pgv_load_envs_host" : "pgv_save_envs_host";
-    if (records_arguments(who, e, count, h_records)) return 1;
+    if (list_arguments(who, e, count, h_records, "record")) return 1;
     if (load && tag != e->rec_tag) return pgv_load_envs(e, nullptr, count, h_records, tag);  // (refused there, before anything is touched)
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
     const size_t bytes = size_t(count) * e->rec.record_bytes;
     pg::Staged dev{e->stream};
-    uint8_t* d_records = dev.alloc<uint8_t>(bytes);
-    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
-    if (load) dev.upload(d_records, h_records, bytes);
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = load ? pgv_load_envs(e, d_indices, count, d_records, tag) : pgv_save_envs(e, d_indices, count, d_records)) return rc;
-        if (load) dev.finish(); else dev.fetch(h_records, d_records, bytes);
-    }
-    if (dev.err != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(dev.err));
-    return 0;
+    uint8_t* h_bytes = static_cast<uint8_t*>(h_records);
+    uint8_t* d_records = load ? dev.in(h_bytes, bytes) : dev.out(h_bytes, bytes);
+    const int32_t* d_indices = dev.in(h_indices, size_t(count));
+    return dev.run(who, [&] { return load ? pgv_load_envs(e, d_indices, count, d_records, tag) : pgv_save_envs(e, d_indices, count, d_records); });
 }
 int32_t pgv_save_envs_host(pgv_env* e, const int32_t* h_indices, int32_t count, void* h_records) {
     return records_host(e, h_indices, count, h_records, false, 0);
@@ -1686,9 +1672,7 @@ __global__ void __launch_bounds__(256) assign_levels_kernel(LevelPlan plan, int3
 extern "C" {
 
 int32_t pgv_assign_levels(pgv_env* e, const int32_t* d_indices, int32_t count, const int32_t* d_levels) {
-    if (!e) return fail("pgv_assign_levels: env is NULL");
-    if (count < 0) return fail("pgv_assign_levels: count is negative");
-    if (count > 0 && !d_levels) return fail("pgv_assign_levels: the level buffer is NULL");
+    if (list_arguments("pgv_assign_levels", e, count, d_levels, "level")) return 1;
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
     (void)hipGetLastError();
@@ -1704,16 +1688,13 @@ int32_t pgv_assign_levels(pgv_env* e, const int32_t* d_indices, int32_t count, c
 }
 
 int32_t pgv_assign_levels_host(pgv_env* e, const int32_t* h_indices, int32_t count, const int32_t* h_levels) {
-    if (!e) return fail("pgv_assign_levels_host: env is NULL");
-    if (count < 0) return fail("pgv_assign_levels_host: count is negative");
-    if (count > 0 && !h_levels) return fail("pgv_assign_levels_host: the level buffer is NULL");
+    if (list_arguments("pgv_assign_levels_host", e, count, h_levels, "level")) return 1;
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
     pg::Staged dev{e->stream};  // (a call may name more indices than the batch has envs: not the staging buffers)
-    const int32_t* d_levels = dev.alloc(size_t(count), h_levels);
-    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
-    if (dev.err != hipSuccess) return fail(std::string("pgv_assign_levels_host: ") + hipGetErrorString(dev.err));
-    return pgv_assign_levels(e, d_indices, count, d_levels);  // (the host buffers are the caller's: drained on the way out)
+    const int32_t* d_levels = dev.in(h_levels, size_t(count));
+    const int32_t* d_indices = dev.in(h_indices, size_t(count));
+    return dev.run("pgv_assign_levels_host", [&] { return pgv_assign_levels(e, d_indices, count, d_levels); });
 }
 
 const uint32_t* pgv_level_numbers(pgv_env* e) { return e ? e->game->plan.number : nullptr; }
@@ -1890,13 +1871,15 @@ int32_t pgv_render_frame(pgv_env* e, int32_t index, int32_t width, int32_t heigh
     PG_HIP(hipSetDevice(e->device));
     const size_t px = size_t(width) * height;
     pg::Staged dev{e->stream};
-    uint32_t* d_px = dev.alloc<uint32_t>(px);
-    if (dev.err == hipSuccess && !e->game->launch_frame(e->stream, index, d_px, width, height))
-        return fail(std::string("pgv_render_frame: not implemented for ") + e->game->name());
     std::vector<uint32_t> host(px);
-    if (dev.err == hipSuccess) dev.err = hipGetLastError();
-    dev.fetch(host.data(), d_px, px * 4);
-    if (dev.err != hipSuccess) return fail(std::string("pgv_render_frame: ") + hipGetErrorString(dev.err));
+    uint32_t* d_px = dev.out(host.data(), px);
+    const int32_t rc = dev.run("pgv_render_frame", [&] {
+        if (!e->game->launch_frame(e->stream, index, d_px, width, height))
+            return fail(std::string("pgv_render_frame: not implemented for ") + e->game->name());
+        dev.err = hipGetLastError();
+        return 0;
+    });
+    if (rc) return rc;
     for (size_t k = 0; k < px; k++) {  // RGBA → RGB, row-major (coinrun.cpp:401-407)
         h_rgb[3 * k + 0] = static_cast<uint8_t>(host[k]);
         h_rgb[3 * k + 1] = static_cast<uint8_t>(host[k] >> 8);
@@ -1905,11 +1888,14 @@ int32_t pgv_render_frame(pgv_env* e, int32_t index, int32_t width, int32_t heigh
     return 0;
 }
 
+static int32_t frames_arguments(const char* who, const pgv_env* e, int32_t count, int32_t width, int32_t height, const uint8_t* rgb) {
+    if (list_arguments(who, e, count)) return 1;
+    if (width < 1 || height < 1 || width > 4096 || height > 4096 || !rgb) return fail(std::string(who) + ": bad frame size or NULL buffer");
+    return 0;
+}
+
 int32_t pgv_render_frames(pgv_env* e, const int32_t* d_indices, int32_t count, int32_t width, int32_t height, uint8_t* d_rgb) {
-    if (!e) return fail("pgv_render_frames: env is NULL");
-    if (count < 0) return fail("pgv_render_frames: count is negative");
-    if (width < 1 || height < 1 || width > 4096 || height > 4096 || !d_rgb)
-        return fail("pgv_render_frames: bad frame size or NULL buffer");
+    if (frames_arguments("pgv_render_frames", e, count, width, height, d_rgb)) return 1;
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
     e->game->launch_frames(e->stream, d_indices, count, d_rgb, width, height);
@@ -1919,22 +1905,13 @@ int32_t pgv_render_frames(pgv_env* e, const int32_t* d_indices, int32_t count, i
 
 int32_t pgv_render_frames_host(pgv_env* e, const int32_t* h_indices, int32_t count, int32_t width, int32_t height,
                                uint8_t* h_rgb) {
-    if (!e) return fail("pgv_render_frames_host: env is NULL");
-    if (count < 0) return fail("pgv_render_frames_host: count is negative");
-    if (width < 1 || height < 1 || width > 4096 || height > 4096 || !h_rgb)
-        return fail("pgv_render_frames_host: bad frame size or NULL buffer");
+    if (frames_arguments("pgv_render_frames_host", e, count, width, height, h_rgb)) return 1;
     if (count == 0) return 0;
     PG_HIP(hipSetDevice(e->device));
-    const size_t bytes = size_t(count) * size_t(height) * size_t(width) * 3;
     pg::Staged dev{e->stream};
-    uint8_t* d_rgb = dev.alloc<uint8_t>(bytes);
-    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_render_frames(e, d_indices, count, width, height, d_rgb)) return rc;
-        dev.fetch(h_rgb, d_rgb, bytes);
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_render_frames_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    uint8_t* d_rgb = dev.out(h_rgb, size_t(count) * size_t(height) * size_t(width) * 3);
+    const int32_t* d_indices = dev.in(h_indices, size_t(count));
+    return dev.run("pgv_render_frames_host", [&] { return pgv_render_frames(e, d_indices, count, width, height, d_rgb); });
 }
 
 int32_t pgv_set_debug(pgv_env* e, int32_t flags) {
@@ -2035,10 +2012,8 @@ int64_t pgv_state_names(int32_t game_id, int32_t mode, char* buf, int64_t cap) {
 }
 
 int32_t pgv_state_rows(pgv_env* e, const int32_t* d_indices, int32_t count, float* d_rows, int32_t* d_lengths) {
-    if (!e) return fail("pgv_state_rows: env is NULL");
-    if (count < 0) return fail("pgv_state_rows: count is negative");
+    if (list_arguments("pgv_state_rows", e, count, d_rows, "output")) return 1;
     if (count == 0) return 0;
-    if (!d_rows) return fail("pgv_state_rows: the output buffer is NULL");
     if (reinterpret_cast<uintptr_t>(d_rows) % 16) return fail("pgv_state_rows: d_rows is not 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_lengths) % 4) return fail("pgv_state_rows: d_lengths is not 4-byte aligned");
     PG_HIP(hipSetDevice(e->device));
@@ -2048,8 +2023,7 @@ int32_t pgv_state_rows(pgv_env* e, const int32_t* d_indices, int32_t count, floa
 }
 
 int32_t pgv_tile_rows(pgv_env* e, const int32_t* d_indices, int32_t count, uint8_t* d_tiles) {
-    if (!e) return fail("pgv_tile_rows: env is NULL");
-    if (count < 0) return fail("pgv_tile_rows: count is negative");
+    if (list_arguments("pgv_tile_rows", e, count)) return 1;
     if (e->game->state_layout().cells == 0 || count == 0) return 0;  // (a game without a tile map: nothing to write)
     if (!d_tiles) return fail("pgv_tile_rows: the output buffer is NULL");
     if (reinterpret_cast<uintptr_t>(d_tiles) % 16) return fail("pgv_tile_rows: d_tiles is not 16-byte aligned");
@@ -2060,41 +2034,26 @@ int32_t pgv_tile_rows(pgv_env* e, const int32_t* d_indices, int32_t count, uint8
 }
 
 int32_t pgv_state_rows_host(pgv_env* e, const int32_t* h_indices, int32_t count, float* h_rows, int32_t* h_lengths) {
-    if (!e) return fail("pgv_state_rows_host: env is NULL");
-    if (count < 0) return fail("pgv_state_rows_host: count is negative");
+    if (list_arguments("pgv_state_rows_host", e, count, h_rows, "output")) return 1;
     if (count == 0) return 0;
-    if (!h_rows) return fail("pgv_state_rows_host: the output buffer is NULL");
     PG_HIP(hipSetDevice(e->device));
-    const size_t floats = size_t(count) * size_t(e->game->state_layout().width);
     pg::Staged dev{e->stream};
-    float* d_rows = dev.alloc<float>(floats);
-    int32_t* d_lengths = h_lengths ? dev.alloc<int32_t>(size_t(count)) : nullptr;
-    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_state_rows(e, d_indices, count, d_rows, d_lengths)) return rc;
-        dev.fetch(h_rows, d_rows, floats * 4);
-        if (h_lengths) dev.fetch(h_lengths, d_lengths, size_t(count) * 4);
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_state_rows_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    float* d_rows = dev.out(h_rows, size_t(count) * size_t(e->game->state_layout().width));
+    int32_t* d_lengths = dev.out(h_lengths, size_t(count));
+    const int32_t* d_indices = dev.in(h_indices, size_t(count));
+    return dev.run("pgv_state_rows_host", [&] { return pgv_state_rows(e, d_indices, count, d_rows, d_lengths); });
 }
 
 int32_t pgv_tile_rows_host(pgv_env* e, const int32_t* h_indices, int32_t count, uint8_t* h_tiles) {
-    if (!e) return fail("pgv_tile_rows_host: env is NULL");
-    if (count < 0) return fail("pgv_tile_rows_host: count is negative");
-    const size_t bytes = size_t(count > 0 ? count : 0) * size_t(e->game->state_layout().cells);
+    if (list_arguments("pgv_tile_rows_host", e, count)) return 1;
+    const size_t bytes = size_t(count) * size_t(e->game->state_layout().cells);
     if (bytes == 0) return 0;
     if (!h_tiles) return fail("pgv_tile_rows_host: the output buffer is NULL");
     PG_HIP(hipSetDevice(e->device));
     pg::Staged dev{e->stream};
-    uint8_t* d_tiles = dev.alloc<uint8_t>(bytes);
-    const int32_t* d_indices = h_indices ? dev.alloc(size_t(count), h_indices) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_tile_rows(e, d_indices, count, d_tiles)) return rc;
-        dev.fetch(h_tiles, d_tiles, bytes);
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_tile_rows_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    uint8_t* d_tiles = dev.out(h_tiles, bytes);
+    const int32_t* d_indices = dev.in(h_indices, size_t(count));
+    return dev.run("pgv_tile_rows_host", [&] { return pgv_tile_rows(e, d_indices, count, d_tiles); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2156,22 +2115,14 @@ int32_t pgv_tile_paths_rows_host(pgv_env* e, const int32_t* h_indices, int32_t c
     const size_t rows = size_t(count), dists = rows * size_t(e->game->state_layout().cells);
     pg::Staged dev{e->stream};
     pgv_tile_paths d = *p;
-    d.source_cells = p->source == PGV_PATH_CELLS ? dev.alloc(rows, p->source_cells) : nullptr;
-    d.probe_cells = p->probe == PGV_PATH_CELLS ? dev.alloc(rows, p->probe_cells) : nullptr;
-    d.dist = p->dist ? dev.alloc<int16_t>(dists) : nullptr;
-    d.probe_dist = p->probe_dist ? dev.alloc<int32_t>(rows) : nullptr;
-    d.probe_step = p->probe_step ? dev.alloc<uint8_t>(rows) : nullptr;
-    d.cells_out = p->cells_out ? dev.alloc<int32_t>(rows * 2) : nullptr;
-    const int32_t* d_indices = h_indices ? dev.alloc(rows, h_indices) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_tile_paths_rows(e, d_indices, count, &d)) return rc;
-        if (p->dist) dev.fetch(p->dist, d.dist, dists * 2);
-        if (p->probe_dist) dev.fetch(p->probe_dist, d.probe_dist, rows * 4);
-        if (p->probe_step) dev.fetch(p->probe_step, d.probe_step, rows);
-        if (p->cells_out) dev.fetch(p->cells_out, d.cells_out, rows * 8);
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_tile_paths_rows_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    d.source_cells = dev.in(p->source == PGV_PATH_CELLS ? p->source_cells : nullptr, rows);  // (cells are read for PGV_PATH_CELLS alone)
+    d.probe_cells = dev.in(p->probe == PGV_PATH_CELLS ? p->probe_cells : nullptr, rows);
+    d.dist = dev.out(p->dist, dists);
+    d.probe_dist = dev.out(p->probe_dist, rows);
+    d.probe_step = dev.out(p->probe_step, rows);
+    d.cells_out = dev.out(p->cells_out, rows * 2);
+    const int32_t* d_indices = dev.in(h_indices, rows);
+    return dev.run("pgv_tile_paths_rows_host", [&] { return pgv_tile_paths_rows(e, d_indices, count, &d); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2245,23 +2196,14 @@ int32_t pgv_get_levels_host(pgv_env* e, const int32_t* h_indices, int32_t count,
     const size_t rows = size_t(count), bytes = rows * size_t(e->game->level_layout().cells);
     pg::Staged dev{e->stream};
     pgv_level_rows d = *out;
-    d.tiles = out->tiles ? dev.alloc<uint8_t>(bytes) : nullptr;
-    d.agent_cell = out->agent_cell ? dev.alloc<int32_t>(rows) : nullptr;
-    d.goal_cell = out->goal_cell ? dev.alloc<int32_t>(rows) : nullptr;
-    d.background = out->background ? dev.alloc<int32_t>(rows) : nullptr;
-    d.background_shift = out->background_shift ? dev.alloc<float>(rows) : nullptr;
+    d.tiles = dev.out(out->tiles, bytes);
+    d.agent_cell = dev.out(out->agent_cell, rows);
+    d.goal_cell = dev.out(out->goal_cell, rows);
+    d.background = dev.out(out->background, rows);
+    d.background_shift = dev.out(out->background_shift, rows);
     d.ids = nullptr, d.status = nullptr;
-    const int32_t* d_indices = h_indices ? dev.alloc(rows, h_indices) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_get_levels(e, d_indices, count, &d)) return rc;
-        if (out->tiles) dev.fetch(out->tiles, d.tiles, bytes);
-        if (out->agent_cell) dev.fetch(out->agent_cell, d.agent_cell, rows * 4);
-        if (out->goal_cell) dev.fetch(out->goal_cell, d.goal_cell, rows * 4);
-        if (out->background) dev.fetch(out->background, d.background, rows * 4);
-        if (out->background_shift) dev.fetch(out->background_shift, d.background_shift, rows * 4);
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_get_levels_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    const int32_t* d_indices = dev.in(h_indices, rows);
+    return dev.run("pgv_get_levels_host", [&] { return pgv_get_levels(e, d_indices, count, &d); });
 }
 
 int32_t pgv_set_levels_host(pgv_env* e, const int32_t* h_indices, int32_t count, const pgv_level_rows* in) {
@@ -2272,21 +2214,15 @@ int32_t pgv_set_levels_host(pgv_env* e, const int32_t* h_indices, int32_t count,
     const size_t rows = size_t(count), bytes = rows * size_t(e->game->level_layout().cells);
     pg::Staged dev{e->stream};
     pgv_level_rows d = *in;
-    d.tiles = dev.alloc(bytes, in->tiles);
-    d.agent_cell = dev.alloc(rows, in->agent_cell);
-    d.goal_cell = dev.alloc(rows, in->goal_cell);
-    d.background = in->background ? dev.alloc(rows, in->background) : nullptr;
-    d.background_shift = in->background_shift ? dev.alloc(rows, in->background_shift) : nullptr;
-    d.ids = in->ids ? dev.alloc(rows, in->ids) : nullptr;
-    d.status = in->status ? dev.alloc<int32_t>(rows) : nullptr;
-    const int32_t* d_indices = h_indices ? dev.alloc(rows, h_indices) : nullptr;
-    if (dev.err == hipSuccess) {
-        if (const int32_t rc = pgv_set_levels(e, d_indices, count, &d)) return rc;
-        if (in->status) dev.fetch(in->status, d.status, rows * 4);
-        dev.finish();  // (the host buffers are the caller's)
-    }
-    if (dev.err != hipSuccess) return fail(std::string("pgv_set_levels_host: ") + hipGetErrorString(dev.err));
-    return 0;
+    d.tiles = dev.in(in->tiles, bytes);
+    d.agent_cell = dev.in(in->agent_cell, rows);
+    d.goal_cell = dev.in(in->goal_cell, rows);
+    d.background = dev.in(in->background, rows);
+    d.background_shift = dev.in(in->background_shift, rows);
+    d.ids = dev.in(in->ids, rows);
+    d.status = dev.out(in->status, rows);
+    const int32_t* d_indices = dev.in(h_indices, rows);
+    return dev.run("pgv_set_levels_host", [&] { return pgv_set_levels(e, d_indices, count, &d); });
 }
 
 // ------------------------------------------------------------------------------------------------

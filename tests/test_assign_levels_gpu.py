@@ -352,4 +352,10 @@ def test_assign_levels_arguments():
         numbers, known = eng.levels()
         assert known[7] == 1 and numbers[7] in (21, 22, 23)
         assert first.shape == obs.shape
+        # the host form without indices (NULL): level k for env k
+        every = np.arange(300, 316, dtype=np.int32)
+        pglib.check(L, L.pgv_assign_levels_host(h, None, 16, every.ctypes.data_as(c_void_p)), "pgv_assign_levels_host")
+        eng.reset()
+        numbers, known = eng.levels()
+        assert (known == 1).all() and np.array_equal(np.asarray(numbers, np.int64), every)
         eng.close()

@@ -406,6 +406,54 @@ def test_host_refusals():
         other.close()
 
 
+@pytest.mark.parametrize("case", ["get: tiles and background alone", "get: the cells and the shift alone", "set: the required rows alone"])
+def test_host_forms_with_pointers_left_out(case):
+    """Every optional host pointer of the two host forms NULL in one call (each is given in test_get_is_the_symbolic_observations
+    and test_round_trip).  5 envs, rows [4, 0, 2] for the read: what the host form gives is the device form's on the same
+    engine byte for byte, nothing round an output is written, and count = 0 passes with no buffer at all."""
+    mode, n, guard = 1, 5, 8
+    env = make(mode, n)
+    L, h = env.L, env._h
+    if case.startswith("get"):
+        names = ("tiles", "background") if "tiles" in case else ("agent_cell", "goal_cell", "background_shift")
+        idx = np.array([4, 0, 2], np.int32)
+        want = env.get_levels(idx.tolist())._asdict()
+        whole = {}
+        for name in names:
+            w = want[name].cpu().numpy()
+            whole[name] = np.full(w.size + 2 * guard, 0x5A, w.dtype)
+        host = {name: whole[name][guard:-guard] for name in names}
+        rows = pglib.level_rows(**{name: host[name].ctypes.data for name in names})
+        pglib.check(L, L.pgv_get_levels_host(h, ctypes.c_void_p(idx.ctypes.data), idx.size, ctypes.byref(rows)), "pgv_get_levels_host")
+        for name in names:
+            assert host[name].tobytes() == want[name].cpu().numpy().tobytes(), name
+            assert (whole[name][:guard] == 0x5A).all() and (whole[name][-guard:] == 0x5A).all(), "round " + name
+        assert L.pgv_get_levels_host(h, None, 0, ctypes.byref(pglib.level_rows())) == 0
+    else:  # no background, shift, ids, status or indices: row k into env k, every env keeps its floor
+        good, _ = random_levels(mode, n)
+        other, _ = random_levels(mode, n, seed=5)
+        required = lambda lv, ptr: pglib.level_rows(tiles=ptr(lv.tiles), agent_cell=ptr(lv.agent_cell), goal_cell=ptr(lv.goal_cell))
+
+        def device_install(levels):
+            lv = on_device(env, levels)
+            torch.cuda.synchronize()
+            env._before()
+            pglib.check(L, L.pgv_set_levels(h, None, n, ctypes.byref(required(lv, lambda x: x.data_ptr()))), "pgv_set_levels")
+            env._after()
+            env.sync()
+            return rows_of(env)
+
+        want = device_install(good)
+        assert (want["known"] == 2).all() and not want["number"].any()
+        between = device_install(other)  # (the same envs in other levels: the host install below has something to do)
+        assert not np.array_equal(between["tiles"], want["tiles"])
+        lv = Levels(*(np.ascontiguousarray(x) for x in good))
+        pglib.check(L, L.pgv_set_levels_host(h, None, n, ctypes.byref(required(lv, lambda x: x.ctypes.data))), "pgv_set_levels_host")
+        assert_same(rows_of(env), want, "the host install against the device install")
+        assert L.pgv_set_levels_host(h, None, 0, ctypes.byref(pglib.level_rows())) == 0
+    env.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # What an install does not touch.
 # ---------------------------------------------------------------------------------------------------------------------

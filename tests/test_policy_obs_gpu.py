@@ -347,6 +347,10 @@ def test_enabling_mid_rollout():
     pglib.check(v.L, v.L.pgv_policy_obs_push_host(v._h, mask.ctypes.data_as(c_void_p)), "pgv_policy_obs_push_host")
     model.stack.push(model.obs, mask)
     check(v, model.stack, model.obs, "masked push")
+    # … and the host form without a mask (NULL): every env
+    pglib.check(v.L, v.L.pgv_policy_obs_push_host(v._h, None), "pgv_policy_obs_push_host")
+    model.stack.push(model.obs)
+    check(v, model.stack, model.obs, "host push, NULL mask")
     v.close(), model.close()
 
 

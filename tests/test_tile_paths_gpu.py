@@ -356,6 +356,42 @@ def test_the_host_form(game):
     env.close()
 
 
+# Between them (and test_the_host_form) every optional host pointer is NULL in one call and given in another.
+HOST_POINTERS = {"source cells given, probe_dist NULL": (True, CELLS, NONE, ("dist", "probe_step", "cells_out")),
+                 "probe cells given, probe_dist alone, NULL indices": (False, AGENT, CELLS, ("probe_dist",))}
+
+
+@pytest.mark.parametrize("case", sorted(HOST_POINTERS))
+def test_the_host_form_pointer_by_pointer(case):
+    """5 envs, rows [4, 0, 2]: the host form's outputs equal the device form's on the same engine byte for byte, and nothing
+    round them is written."""
+    import torch
+    indexed, source, probe, asked = HOST_POINTERS[case]
+    env = settled("maze", 4, 5)
+    lay = env.path_layout
+    k, guard = 3, 8
+    idx = np.array([4, 0, 2], np.int32) if indexed else None
+    cells = np.array([lay.cells - 1, 0, 17], np.int32)
+    sc, pc = cells if source == CELLS else None, cells if probe == CELLS else None
+    kinds = {"dist": ((k, lay.cells), np.int16, 0x5A5A), "probe_dist": ((k,), np.int32, -7), "probe_step": ((k,), np.uint8, 77),
+             "cells_out": ((k, 2), np.int32, -7)}
+    on_device = lambda x: None if x is None else torch.from_numpy(x).to(env.device)
+    dev = {name: on_device(np.full(kinds[name][0], kinds[name][2], kinds[name][1])) for name in asked}
+    d_idx, d_sc, d_pc = on_device(idx), on_device(sc), on_device(pc)
+    torch.cuda.synchronize()
+    assert raw(env, k, d_idx, 1, source, probe, d_sc, d_pc, **dev) == 0, env.L.pgv_last_error()
+    env.sync()
+    whole = {name: np.full(int(np.prod(kinds[name][0])) + 2 * guard, kinds[name][2], kinds[name][1]) for name in asked}
+    host = {name: whole[name][guard:-guard].reshape(kinds[name][0]) for name in asked}
+    assert raw(env, k, idx, 1, source, probe, sc, pc, host=True, **host) == 0, env.L.pgv_last_error()
+    for name in asked:
+        want = dev[name].cpu().numpy()
+        assert (want != kinds[name][2]).any(), name  # (the device form wrote it)
+        assert host[name].tobytes() == want.tobytes(), "%s: %s" % (case, name)
+        assert (whole[name][:guard] == kinds[name][2]).all() and (whole[name][-guard:] == kinds[name][2]).all(), "%s: round %s" % (case, name)
+    env.close()
+
+
 def test_the_maze_law_on_the_engine():
     """tile_paths → MAZE_STEP_ACTIONS → step, nothing copied to the host inside the loop: every env's first done arrives at
     its reset-time probe_dist (a distance of 0: at step 1) with reward 10."""
