@@ -636,7 +636,21 @@ PGV_API int32_t pgv_gather_filter_params(const pgv_gather_aug* aug, const pgv_ga
  *      TRUNCATED; a = gamma * nv; b = r + a; delta = b - V[t]; adv = delta + c * carry with c = gamma * lambda computed
  *      once if the row ends nothing, else delta — the product and the sum separate roundings —; carry = adv; ret = adv +
  *      V[t].  One launch, nothing allocated, no atomics, no host synchronisation.
- *   6. pgv_transitions_enable needs pgv_history_enable first and a capacity T >= 2, and may be called once, at any time; the
+ *   6. pgv_transitions_vtrace over rows first .. first + L - 1, the range and the checks of point 5 (values and vs not NULL,
+ *      all five pointers 4-byte aligned, struct_size): V-trace (Espeholt et al. 2018, with the paper's lambda) under the
+ *      caller's importance ratios rhos f32 [L][N] = pi(a|x) / mu(a|x) of the recorded action — the ratios, not their
+ *      logarithms; NULL: all 1 —, values f32 [L+1][N], optional trunc_values f32 [L][N], vs f32 [L][N], optional
+ *      pg_advantages f32 [L][N].  Per env, t = L-1 .. 0, carry = 0, vs_next = V[L]: a row that is not RECORDED or is VOID
+ *      gives vs = V[t], pg = 0, carry = 0, vs_next = V[t]; else nv as in point 5; s = r * reward_scale; r' = s if
+ *      reward_clip <= 0, else s > clip ? clip : (s < -clip ? -clip : s); rho = rhos[t]; rc = rho < rho_bar ? rho : rho_bar;
+ *      cm = rho < c_bar ? rho : c_bar; cc = lambda * cm; pr = rho < pg_rho_bar ? rho : pg_rho_bar; a = gamma * nv; b = r' +
+ *      a; d = b - V[t]; delta = rc * d; x = delta if the row ends something, else k = gamma * cc; e = k * carry; x = delta +
+ *      e; vs = x + V[t]; qn = vs_next if the row ends nothing, else nv; pa = gamma * qn; pb = r' + pa; pd = pb - V[t]; pg =
+ *      pr * pd; carry = x; vs_next = vs — every product, sum and difference its own float32 rounding.  With rhos NULL, the
+ *      three thresholds >= 1, reward_scale 1 and reward_clip 0, vs is point 5's returns bit for bit; with a scale and a
+ *      clip it is GAE on scaled and clipped rewards.  One launch, nothing allocated, no atomics, no host synchronisation;
+ *      the call changes nothing of the engine.
+ *   7. pgv_transitions_enable needs pgv_history_enable first and a capacity T >= 2, and may be called once, at any time; the
  *      rows start as zeros (not recorded).  Each refusal leaves a message and the engine as it was. */
 #define PGV_TR_RECORDED 1
 #define PGV_TR_TERMINATED 2
@@ -669,6 +683,15 @@ typedef struct pgv_gae {
     float* advantages;         /* device f32 [L][N] */
     float* returns;            /* device f32 [L][N] or NULL */
 } pgv_gae;
+typedef struct pgv_vtrace {
+    uint32_t struct_size;
+    float gamma, lambda, rho_bar, c_bar, pg_rho_bar, reward_scale, reward_clip;
+    const float* values;       /* device f32 [L+1][N]; the last row bootstraps */
+    const float* rhos;         /* device f32 [L][N]: pi(a|x)/mu(a|x) of the recorded action, or NULL: all 1 */
+    const float* trunc_values; /* device f32 [L][N] or NULL */
+    float* vs;                 /* device f32 [L][N] */
+    float* pg_advantages;      /* device f32 [L][N] or NULL */
+} pgv_vtrace; /* 72 bytes */
 PGV_API int32_t pgv_transitions_enable(pgv_env* env, const pgv_transitions_config* config);
 PGV_API const int32_t* pgv_transitions_action(pgv_env* env); /* device int32 [T][N]; NULL before enable */
 PGV_API const float* pgv_transitions_reward(pgv_env* env);   /* device f32 [T][N]; NULL before enable */
@@ -676,6 +699,7 @@ PGV_API const uint8_t* pgv_transitions_flags(pgv_env* env);  /* device u8 [T][N]
 PGV_API int32_t pgv_transitions_gather(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count,
                                        const pgv_transition_query* query);
 PGV_API int32_t pgv_transitions_gae(pgv_env* env, int64_t first, int32_t length, const pgv_gae* gae);
+PGV_API int32_t pgv_transitions_vtrace(pgv_env* env, int64_t first, int32_t length, const pgv_vtrace* vt);
 
 /* Prioritised sampling over the transition ring: the engine hands out the (push, env) pairs a replay learner reads, drawn in
  * proportion to a priority over exactly the rows pgv_transitions_gather calls VALID — it is the only party that knows,

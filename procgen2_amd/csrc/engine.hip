@@ -19,6 +19,7 @@
 #include "pg_history_aug.h"
 #include "pg_history_filter.h"
 #include "pg_transitions.h"
+#include "pg_vtrace.h"
 #include "pg_priorities.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
@@ -1385,6 +1386,33 @@ int32_t pgv_transitions_gae(pgv_env* e, int64_t first, int32_t length, const pgv
     q.values = gae->values, q.trunc_values = gae->trunc_values, q.advantages = gae->advantages, q.returns = gae->returns;
     q.ring = transition_ring(e);
     pg::launch_transition_gae(e->stream, q);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int32_t pgv_transitions_vtrace(pgv_env* e, int64_t first, int32_t length, const pgv_vtrace* vt) {
+    const char* who = "pgv_transitions_vtrace";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!e->transitions) return fail(std::string(who) + ": call pgv_transitions_enable first");
+    if (!vt || vt->struct_size < sizeof(pgv_vtrace)) return fail(std::string(who) + ": vtrace is NULL or struct_size too small");
+    if (length < 1) return fail(std::string(who) + ": length must be >= 1");
+    const int64_t head = e->history_head;
+    // (pgv_transitions_gae's range: rows first .. first + length - 1, each with head - T <= q and q + 1 < head)
+    if (first < 0 || first < head - e->hist.capacity || first >= head || int64_t(length) > head - 1 - first)
+        return fail(std::string(who) + ": rows " + std::to_string(first) + " .. + " + std::to_string(length) + " are not all held with their successors (head " +
+                    std::to_string(head) + ", capacity " + std::to_string(e->hist.capacity) + ")");
+    if (!vt->values || !vt->vs) return fail(std::string(who) + ": values or vs is NULL");
+    for (const void* p : {static_cast<const void*>(vt->values), static_cast<const void*>(vt->rhos), static_cast<const void*>(vt->trunc_values),
+                          static_cast<const void*>(vt->vs), static_cast<const void*>(vt->pg_advantages)})
+        if (reinterpret_cast<uintptr_t>(p) & 3u) return fail(std::string(who) + ": values, rhos, trunc_values, vs and pg_advantages must be 4-byte aligned");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::TransitionVtrace q{};
+    q.n = e->n, q.length = length, q.first = first;
+    q.rule = pg::VtraceRule{vt->gamma, vt->lambda, vt->rho_bar, vt->c_bar, vt->pg_rho_bar, vt->reward_scale, vt->reward_clip};
+    q.values = vt->values, q.rhos = vt->rhos, q.trunc_values = vt->trunc_values, q.vs = vt->vs, q.pg = vt->pg_advantages;
+    q.ring = transition_ring(e);
+    pg::launch_transition_vtrace(e->stream, q);
     PG_HIP(hipGetLastError());
     return 0;
 }

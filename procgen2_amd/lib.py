@@ -92,6 +92,16 @@ class Gae(ctypes.Structure):
                 ("advantages", c_void_p), ("returns", c_void_p)]
 
 
+class Vtrace(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_vtrace` (`lam`: the header's `lambda`)."""
+    _fields_ = [("struct_size", c_uint32), ("gamma", c_float), ("lam", c_float), ("rho_bar", c_float), ("c_bar", c_float),
+                ("pg_rho_bar", c_float), ("reward_scale", c_float), ("reward_clip", c_float), ("values", c_void_p), ("rhos", c_void_p),
+                ("trunc_values", c_void_p), ("vs", c_void_p), ("pg_advantages", c_void_p)]
+
+
+VTRACE_ROWS = 16  # csrc/pg_vtrace.h kVtRows: the rows of a chunk of the V-trace kernel's walk
+
+
 # include/procgen2_vec.h PGV_TR_*
 TR_RECORDED, TR_TERMINATED, TR_TRUNCATED, TR_VOID, TR_CUT = 1, 2, 4, 8, 16
 
@@ -112,6 +122,13 @@ def transition_query(n, gamma, stack, dtype, obs=None, next_obs=None, action=Non
 def gae(gamma, lam, values, advantages, trunc_values=None, returns=None):
     """A filled-in Gae of device pointers (integers)."""
     return Gae(ctypes.sizeof(Gae), float(gamma), float(lam), values, trunc_values, advantages, returns)
+
+
+def vtrace(gamma, lam, values, vs, rhos=None, pg_advantages=None, trunc_values=None, rho_bar=1.0, c_bar=1.0, pg_rho_bar=1.0,
+           reward_scale=1.0, reward_clip=0.0):
+    """A filled-in Vtrace of device pointers (integers)."""
+    return Vtrace(ctypes.sizeof(Vtrace), float(gamma), float(lam), float(rho_bar), float(c_bar), float(pg_rho_bar), float(reward_scale),
+                  float(reward_clip), values, rhos, trunc_values, vs, pg_advantages)
 
 
 class PrioritySample(ctypes.Structure):
@@ -406,6 +423,7 @@ def load(path=None):
         "pgv_transitions_flags": (P, [P]),
         "pgv_transitions_gather": (c_int32, [P, P, P, c_int32, POINTER(TransitionQuery)]),
         "pgv_transitions_gae": (c_int32, [P, c_int64, c_int32, POINTER(Gae)]),
+        "pgv_transitions_vtrace": (c_int32, [P, c_int64, c_int32, POINTER(Vtrace)]),
         "pgv_priorities_enable": (c_int32, [P]),
         "pgv_priorities": (P, [P]),
         "pgv_priorities_max": (P, [P]),
@@ -460,7 +478,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_policy_obs_enable", "pgv_policy_obs", "pgv_policy_obs_bytes_per_env", "pgv_policy_obs_restart", "pgv_policy_obs_push", "pgv_policy_obs_push_host",
     "pgv_history_enable", "pgv_history_frames", "pgv_history_began", "pgv_history_pending", "pgv_history_head", "pgv_history_capacity", "pgv_history_push",
     "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params", "pgv_history_gather_filter", "pgv_gather_filter_params",
-    "pgv_transitions_enable", "pgv_transitions_action", "pgv_transitions_reward", "pgv_transitions_flags", "pgv_transitions_gather", "pgv_transitions_gae",
+    "pgv_transitions_enable", "pgv_transitions_action", "pgv_transitions_reward", "pgv_transitions_flags", "pgv_transitions_gather", "pgv_transitions_gae", "pgv_transitions_vtrace",
     "pgv_priorities_enable", "pgv_priorities", "pgv_priorities_max", "pgv_priorities_set", "pgv_priorities_sample",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",

@@ -530,6 +530,40 @@ class ProcgenVecEnv:
         self._keep_gae = (v, tv, adv, ret)
         return adv, ret
 
+    def transition_vtrace(self, first, steps, values, rhos=None, gamma=0.999, lam=1.0, rho_bar=1.0, c_bar=1.0, pg_rho_bar=1.0,
+                          trunc_values=None, reward_scale=1.0, reward_clip=0.0, advantages=True):
+        """(vs, pg_advantages), float32 [steps, N], of V-trace over rows first .. first + steps - 1 of the record ring in one
+        launch (pgv_transitions_vtrace): values float32 [steps + 1, N] (the last row bootstraps), rhos float32 [steps, N] the
+        importance ratios pi(a|x) / mu(a|x) of the recorded actions — the ratios, not their logarithms; None: all 1 —, clipped
+        at rho_bar for the value targets' deltas, at c_bar for the trace and at pg_rho_bar for the advantages; the ring's
+        rewards times reward_scale, then clipped to +-reward_clip where that is > 0; trunc_values as in transition_gae().
+        advantages=False: the value targets alone (pg_advantages None).  The rows must be held as for transition_gae(), and
+        they end, or give vs = V and advantage 0, as there; with rhos None and the defaults, vs is transition_gae()'s
+        returns for the same gamma and lam, bit for bit."""
+        self._needs_transitions("transition_vtrace")
+        steps = int(steps)
+        n = self.num_envs
+
+        def rows(x, count, name):
+            x = torch.as_tensor(x, device=self.device).to(torch.float32).contiguous()
+            if tuple(x.shape) != (count, n):
+                raise ValueError("transition_vtrace: %s must have shape (%d, %d)" % (name, count, n))
+            return x
+        if steps < 1:
+            raise ValueError("transition_vtrace: steps must be >= 1")
+        v = rows(values, steps + 1, "values")
+        rho = None if rhos is None else rows(rhos, steps, "rhos")
+        tv = None if trunc_values is None else rows(trunc_values, steps, "trunc_values")
+        vs = torch.empty((steps, n), dtype=torch.float32, device=self.device)
+        pg = torch.empty((steps, n), dtype=torch.float32, device=self.device) if advantages else None
+        q = pglib.vtrace(gamma, lam, v.data_ptr(), vs.data_ptr(), None if rho is None else rho.data_ptr(), None if pg is None else pg.data_ptr(),
+                         None if tv is None else tv.data_ptr(), rho_bar, c_bar, pg_rho_bar, reward_scale, reward_clip)
+        self._before()
+        pglib.check(self.L, self.L.pgv_transitions_vtrace(self._h, int(first), steps, ctypes.byref(q)), "pgv_transitions_vtrace")
+        self._after()
+        self._keep_vtrace = (v, rho, tv, vs, pg)
+        return vs, pg
+
     def _needs_priorities(self, who):
         if self.transitions is None or self.transitions.priority is None:
             raise pglib.EngineError(who + " needs an env made with transitions=True, priorities=True")
