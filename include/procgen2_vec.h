@@ -755,6 +755,82 @@ PGV_API int32_t pgv_priorities_set(pgv_env* env, const int64_t* d_pushes, const 
                                    const float* d_values);
 PGV_API int32_t pgv_priorities_sample(pgv_env* env, int32_t count, const pgv_priority_sample* sample);
 
+/* Level replay scores: a table of one score per level, folded from a caller's per-step signal — normally the advantages of
+ * pgv_transitions_gae — over a stretch of the transition ring, every episode filed under the level it was played on.  What
+ * prioritised level replay (PLR, robust PLR, ACCEL) computes every rollout: the mean of |GAE| or of max(GAE, 0) per episode.
+ * The engine is the only party that knows, without a look from the host, which level every ring row was played on and where
+ * every episode inside a stretch begins and ends.  Turning scores into sampling weights (rank, temperature, staleness) stays
+ * the caller's: a few tensor operations over `capacity` numbers.  Opt-in per engine, on top of the transitions: an engine
+ * that never enables it launches nothing new and gives the same bytes as before at every entry point.
+ *
+ *   1. pgv_level_scores_enable needs pgv_transitions_enable first and may be called once.  capacity K is 1 .. 2^24; known_mask
+ *      bit 1 accepts level-seed and assigned levels (pgv_level_known = 1), bit 2 the caller's labels of pgv_set_levels (= 2);
+ *      0, bit 0 and any other bit are refused.  It allocates `level` uint32 [T][N] and `level_known` u8 [T][N], laid out as
+ *      `began` is (push p in slot p % T), the table and the update's scratch; nothing is allocated afterwards.  The ring starts
+ *      as zeros: known = 0, "no level".  A refusal leaves a message and the engine as it was.  The ring travels neither in
+ *      records nor in snapshots.
+ *   2. The level ring.  level[p][i] / level_known[p][i] are pgv_level_numbers[i] / pgv_level_known[i] as they stand on the
+ *      env's stream where push p's frame is filed: every call that opens a history slot writes the whole row of the new slot;
+ *      a reset's rewrite of the newest slot (pgv_reset, pgv_set_levels) rewrites the named envs' words under the same mask.
+ *      One more small launch behind the push.  So the level of transition row q, the action taken on frame q, is level[q].
+ *   3. The table, device memory, K entries each: `score` float32 (starts 0), `episodes` uint32 (0), `max_return` float32
+ *      (-inf), `stamp` int64 (-1).  pgv_level_scores_get fills a struct of device pointers to the two rings and the four
+ *      columns (set struct_size first); the columns are the caller's to read and to overwrite.
+ *   4. A row's level is ACCEPTED when bit level_known of known_mask is set and k = level - first_level (uint32, wrapping) is
+ *      below K; k is its table index.
+ *   5. pgv_level_scores_update over rows first .. first + L - 1, the range of pgv_transitions_gae (each row head - T <= q and
+ *      q + 1 < head).  signal is device float32 [L][N].  fix(x): v = |x| for PGV_SCORE_ABS, x > 0 ? x : 0 for
+ *      PGV_SCORE_POSITIVE; t = v * 65536.0f; 0 if t is NaN, 2147483647 if t >= 2147483648.0f, else rintf(t) (nearest-even).
+ *      Per env i, forward over t = 0 .. L-1, q = first + t, nothing open at the start.  A row is LIVE when RECORDED and not
+ *      VOID.  A row that is not live closes an open segment as partial.  A live row with nothing open opens a segment: its
+ *      level words are level[q][i], level_known[q][i]; whole = began[q][i] != 0; sum = 0 (uint64), steps = 0, ret = +0.0f.
+ *      Every live row: sum += fix(signal[t][i]); steps += 1; ret = ret + reward (one float32 rounding a step, the rule of
+ *      ended_return).  Then the segment closes behind the row as complete if the row is TERMINATED or TRUNCATED, as partial if
+ *      it is CUT.  Behind the last row an open segment closes as partial.
+ *   6. Closing.  A partial segment is dropped unless include_partial is set; a segment whose level is not accepted is dropped.
+ *      Otherwise sum, steps and 1 are added to three scratch columns at k — integer adds: order does not matter — and, if the
+ *      segment is complete and whole, max_return[k] is raised to ret (a maximum: order-free; NaN is never stored, -0 counts
+ *      as +0).
+ *   7. Finish, a second launch over the table.  For every k with scratch steps > 0: a = float(sum), b = float(steps) (round
+ *      to nearest); m = (a / b) * (1.0f / 65536.0f); score = m if episodes == 0, else ((1.0f - alpha) * score) + (alpha * m)
+ *      — the subtraction, both products and the sum separate roundings —; episodes += segments; stamp = the update's stamp.
+ *      The scratch it read is cleared.  totals, where given, receives {segments filed, steps filed} of this call.
+ *   8. Everything is enqueued on the env's stream; nothing is allocated; no float atomics, no host synchronisation; two
+ *      launches.  Up to 1024 levels the adds go through a table of each workgroup's own in on-chip memory, above that straight
+ *      to device memory: the same bytes either way.
+ *   9. Refused on the host before anything is enqueued, each refusal leaving a message and the engine as it was: env or
+ *      struct NULL, struct_size too small, an unknown kind, alpha outside 0 .. 1 or NaN, signal NULL, signal not 4-byte
+ *      aligned, totals not 8-byte aligned, not enabled, length < 1, the range. */
+#define PGV_SCORE_ABS 0      /* |x|: the L1 value loss */
+#define PGV_SCORE_POSITIVE 1 /* max(x, 0): the positive value loss */
+typedef struct pgv_level_scores_config {
+    uint32_t struct_size;
+    uint32_t first_level;
+    int32_t capacity;    /* K, 1 .. 2^24 */
+    uint32_t known_mask; /* bit 1: level-seed and assigned levels; bit 2: the caller's labels */
+} pgv_level_scores_config;
+typedef struct pgv_level_score_table { /* device pointers */
+    uint32_t struct_size;
+    const uint32_t* level;      /* [T][N] */
+    const uint8_t* level_known; /* [T][N] */
+    float* score;               /* [K] */
+    uint32_t* episodes;         /* [K] */
+    float* max_return;          /* [K] */
+    int64_t* stamp;             /* [K] */
+} pgv_level_score_table; /* 56 bytes */
+typedef struct pgv_level_score_update {
+    uint32_t struct_size;
+    int32_t kind; /* PGV_SCORE_* */
+    float alpha;  /* 0 .. 1: the weight of this call's mean against the score so far */
+    int32_t include_partial;
+    int64_t stamp;
+    const float* signal; /* device f32 [L][N] */
+    uint64_t* totals;    /* device uint64 [2] or NULL */
+} pgv_level_score_update; /* 40 bytes */
+PGV_API int32_t pgv_level_scores_enable(pgv_env* env, const pgv_level_scores_config* config);
+PGV_API int32_t pgv_level_scores_get(pgv_env* env, pgv_level_score_table* out); /* set struct_size first */
+PGV_API int32_t pgv_level_scores_update(pgv_env* env, int64_t first, int32_t length, const pgv_level_score_update* update);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);
@@ -1007,7 +1083,8 @@ PGV_API int32_t pgv_step_phases_many(pgv_env* const* envs, int32_t count, int32_
  * observations stores each lane's own 16 values per plane as they lie (lanes 32 or 64 bytes apart for 2- and 4-byte elements)
  * instead of exchanging them inside the wave for dense stores.  Bit 27: coinrun draws a frame its pre-pass hands back in
  * that env's own block of the render launch instead of in one of the early blocks in front of the grid (what a frame
- * does anyway that finds the list of such frames full).  Any other bit is refused. */
+ * does anyway that finds the list of such frames full).  Bit 28: pgv_level_scores_update adds straight into device memory at
+ * every capacity instead of through the workgroups' own tables up to 1024 levels.  Any other bit is refused. */
 PGV_API int32_t pgv_set_debug(pgv_env* env, int32_t flags);
 
 /* Parity taps (host pointers): the state row / tile row of one env, read through the launches behind pgv_state_rows /

@@ -21,6 +21,7 @@
 #include "pg_transitions.h"
 #include "pg_vtrace.h"
 #include "pg_priorities.h"
+#include "pg_level_scores.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
 #include "pg_sequence.h"
@@ -345,6 +346,11 @@ struct pgv_env {
     bool priorities = false;
     pg::DeviceBlock<void> d_priorities;
     pg::PriorityBuffers pr{};
+    // level replay scores (pg_level_scores.h; pgv_level_scores_enable): off unless asked for, on top of the transitions.  One
+    // device block holds the [T][N] level words, the table's columns and the update's scratch.
+    bool level_scores = false;
+    pg::DeviceBlock<void> d_level_scores;
+    pg::LevelScoreBuffers ls{};
     // both features' value tables, dtype by dtype (pg_planes.h): the uploads' source, so they live as long as the env
     uint32_t value_tables[pg::kPolicyTables][256];  // (filled where the env is made)
 
@@ -683,6 +689,8 @@ static int32_t history_push(pgv_env* e, bool reset, const uint8_t* d_mask) {
     q.mask = d_mask;
     q.b = e->hist;
     pg::launch_history_push(e->stream, q);
+    // the slot's level words, as they stand here on the env's stream: the whole row of a new slot, the named envs' of a rewritten one
+    if (e->level_scores) pg::launch_level_words(e->stream, pg::LevelWords{e->n, q.slot, open ? nullptr : d_mask, e->game->plan.number, e->game->plan.known, e->ls});
     PG_HIP(hipGetLastError());
     if (open) e->history_head++;
     return 0;
@@ -1480,6 +1488,74 @@ int32_t pgv_priorities_sample(pgv_env* e, int32_t count, const pgv_priority_samp
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Level replay scores (pg_level_scores.h)
+// ------------------------------------------------------------------------------------------------
+int32_t pgv_level_scores_enable(pgv_env* e, const pgv_level_scores_config* cfg) {
+    const char* who = "pgv_level_scores_enable";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!cfg || cfg->struct_size < sizeof(pgv_level_scores_config)) return fail(std::string(who) + ": config is NULL or struct_size too small");
+    if (cfg->capacity < 1 || cfg->capacity > pg::kLsMaxLevels) return fail(std::string(who) + ": capacity must be in 1 .. 2^24");
+    if (cfg->known_mask == 0 || (cfg->known_mask & ~(pg::kLsMaskSeeded | pg::kLsMaskCustom)))
+        return fail(std::string(who) + ": known_mask must be bit 1 (level-seed and assigned levels), bit 2 (the caller's labels) or both");
+    if (e->level_scores) return fail(std::string(who) + ": level scores are enabled already (once per env)");
+    if (!e->transitions) return fail(std::string(who) + ": call pgv_transitions_enable first");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::LevelScoreBuffers b{};
+    b.capacity = e->hist.capacity, b.levels = cfg->capacity;
+    b.first_level = cfg->first_level, b.known_mask = cfg->known_mask;
+    auto fill = [&](void* mem, size_t bytes) {  // no level, an empty table, clean scratch
+        const hipError_t err = hipMemsetAsync(mem, 0, bytes, e->stream);
+        if (err != hipSuccess) return err;
+        pg::launch_level_score_init(e->stream, b);  // max_return -inf, stamp -1
+        return hipGetLastError();
+    };
+    if (enable_block(who, e, pg::list_level_scores, b, e->d_level_scores, fill)) return 1;
+    e->ls = b;
+    e->level_scores = true;
+    return 0;
+}
+
+int32_t pgv_level_scores_get(pgv_env* e, pgv_level_score_table* out) {
+    const char* who = "pgv_level_scores_get";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!out || out->struct_size < sizeof(pgv_level_score_table)) return fail(std::string(who) + ": out is NULL or struct_size too small");
+    if (!e->level_scores) return fail(std::string(who) + ": call pgv_level_scores_enable first");
+    out->level = e->ls.level, out->level_known = e->ls.known;
+    out->score = e->ls.score, out->episodes = e->ls.episodes, out->max_return = e->ls.max_return, out->stamp = e->ls.stamp;
+    return 0;
+}
+
+int32_t pgv_level_scores_update(pgv_env* e, int64_t first, int32_t length, const pgv_level_score_update* up) {
+    const char* who = "pgv_level_scores_update";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!up || up->struct_size < sizeof(pgv_level_score_update)) return fail(std::string(who) + ": update is NULL or struct_size too small");
+    if (up->kind != PGV_SCORE_ABS && up->kind != PGV_SCORE_POSITIVE) return fail(std::string(who) + ": unknown kind");
+    if (!(up->alpha >= 0.0f && up->alpha <= 1.0f)) return fail(std::string(who) + ": alpha must be in 0 .. 1");
+    if (!up->signal) return fail(std::string(who) + ": signal is NULL");
+    if (reinterpret_cast<uintptr_t>(up->signal) & 3u) return fail(std::string(who) + ": signal must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(up->totals) & 7u) return fail(std::string(who) + ": totals must be 8-byte aligned");
+    if (!e->level_scores) return fail(std::string(who) + ": call pgv_level_scores_enable first");
+    if (length < 1) return fail(std::string(who) + ": length must be >= 1");
+    const int64_t head = e->history_head;
+    // (pgv_transitions_gae's range: rows first .. first + length - 1, each with head - T <= q and q + 1 < head)
+    if (first < 0 || first < head - e->hist.capacity || first >= head || int64_t(length) > head - 1 - first)
+        return fail(std::string(who) + ": rows " + std::to_string(first) + " .. + " + std::to_string(length) + " are not all held with their successors (head " +
+                    std::to_string(head) + ", capacity " + std::to_string(e->hist.capacity) + ")");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::LevelScoreUpdate q{};
+    q.n = e->n, q.length = length, q.first = first;
+    q.kind = up->kind, q.include_partial = up->include_partial != 0, q.alpha = up->alpha, q.stamp = up->stamp;
+    q.signal = up->signal, q.totals = up->totals;
+    q.ring = transition_ring(e);
+    q.b = e->ls;
+    pg::launch_level_score_update(e->stream, q, (e->game->debug_flags & pg::kDebugLevelScoresGlobal) != 0);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
 int32_t pgv_decode_png(const char* path, int32_t* w, int32_t* h, uint8_t* h_rgba, int64_t cap) {
     pg::Image img;
     std::string err;
@@ -1945,8 +2021,8 @@ int32_t pgv_render_frames_host(pgv_env* e, const int32_t* h_indices, int32_t cou
 int32_t pgv_set_debug(pgv_env* e, int32_t flags) {
     if (!e) return fail("pgv_set_debug: env is NULL");
 #ifndef PG_ABLATE
-    if (flags & ~(1 | pg::kDebugNoPrefetch | pg::kDebugNoPrepass | pg::kDebugFatThirds | pg::kDebugCoinrunNoReach | pg::kDebugChaserSerialMobs | pg::kDebugPolicyStrided | pg::kDebugFatInPlace))
-        return fail("pgv_set_debug: only bit 0 (draw-list replay), bit 8 (no level prefetch), bit 21 (no render pre-pass), bit 23 (every third frame by the complete path), bit 24 (coinrun: hazards the long way), bit 25 (chaser: enemies the long way), bit 26 (policy observations: lane-strided stores) and bit 27 (coinrun: handed-back frames in their own blocks) exist in this build");
+    if (flags & ~(1 | pg::kDebugNoPrefetch | pg::kDebugNoPrepass | pg::kDebugFatThirds | pg::kDebugCoinrunNoReach | pg::kDebugChaserSerialMobs | pg::kDebugPolicyStrided | pg::kDebugFatInPlace | pg::kDebugLevelScoresGlobal))
+        return fail("pgv_set_debug: only bit 0 (draw-list replay), bit 8 (no level prefetch), bit 21 (no render pre-pass), bit 23 (every third frame by the complete path), bit 24 (coinrun: hazards the long way), bit 25 (chaser: enemies the long way), bit 26 (policy observations: lane-strided stores), bit 27 (coinrun: handed-back frames in their own blocks) and bit 28 (level scores: global adds at every capacity) exist in this build");
 #endif
     if (e->side) hipStreamSynchronize(e->side);
     e->game->debug_flags = flags;

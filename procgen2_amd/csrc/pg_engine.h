@@ -241,6 +241,7 @@ constexpr int kDebugCoinrunNoReach = 1 << 24;
 constexpr int kDebugChaserSerialMobs = 1 << 25;  // chaser: the enemies one after the other on the stream itself (chaser.hip advance)
 constexpr int kDebugPolicyStrided = 1 << 26;     // policy observations: each lane stores its own units (pg_policy_obs.h), no exchange
 constexpr int kDebugFatInPlace = 1 << 27;        // coinrun: no early blocks in the render launch — a handed-back frame is drawn by its env's own block (coinrun.hip render_kernel)
+constexpr int kDebugLevelScoresGlobal = 1 << 28;  // level scores: an update's closes go to global memory at every capacity (pg_level_scores.h)
 
 // What every game's host class keeps: its device view and the atlas, left there by its bind().
 template <class S>

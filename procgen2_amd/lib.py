@@ -145,6 +145,48 @@ def priority_sample(seed, stratified=True, pushes=None, envs=None, priority=None
     return PrioritySample(ctypes.sizeof(PrioritySample), int(seed) & 0xFFFFFFFF, int(bool(stratified)), pushes, envs, priority, prob, totals)
 
 
+class LevelScoresConfig(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_level_scores_config`."""
+    _fields_ = [("struct_size", c_uint32), ("first_level", c_uint32), ("capacity", c_int32), ("known_mask", c_uint32)]
+
+
+class LevelScoreTable(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_level_score_table` (device pointers)."""
+    _fields_ = [("struct_size", c_uint32), ("level", c_void_p), ("level_known", c_void_p), ("score", c_void_p), ("episodes", c_void_p),
+                ("max_return", c_void_p), ("stamp", c_void_p)]
+
+
+class LevelScoreUpdate(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_level_score_update`."""
+    _fields_ = [("struct_size", c_uint32), ("kind", c_int32), ("alpha", c_float), ("include_partial", c_int32), ("stamp", c_int64),
+                ("signal", c_void_p), ("totals", c_void_p)]
+
+
+SCORE_KINDS = {"abs": 0, "positive": 1}       # include/procgen2_vec.h PGV_SCORE_*
+SCORE_KNOWN = {"seeded": 1 << 1, "custom": 1 << 2}  # known_mask: bit `level_known`
+# csrc/pg_level_scores.h kLsRows, kLsEnvs, kLsLdsLevels: the rows of a chunk and the envs of a workgroup of the update kernel's
+# walk, and the largest capacity whose adds go through the workgroups' own tables
+LEVEL_SCORE_ROWS, LEVEL_SCORE_ENVS, LEVEL_SCORE_LDS_LEVELS = 16, 64, 1024
+DEBUG_LEVEL_SCORES_GLOBAL = 1 << 28  # pgv_set_debug: global adds at every capacity
+
+
+def level_scores_enable(lib, h, first_level, capacity, known=("seeded",)):
+    """pgv_level_scores_enable (after transitions_enable) and pgv_level_scores_get: the filled-in LevelScoreTable.  known: names
+    of SCORE_KNOWN, or the mask itself."""
+    mask = int(known) if isinstance(known, int) else sum(SCORE_KNOWN[name] for name in set(known))
+    cfg = LevelScoresConfig(ctypes.sizeof(LevelScoresConfig), int(first_level) & 0xFFFFFFFF, int(capacity), mask)
+    check(lib, lib.pgv_level_scores_enable(h, ctypes.byref(cfg)), "pgv_level_scores_enable")
+    out = LevelScoreTable(ctypes.sizeof(LevelScoreTable))
+    check(lib, lib.pgv_level_scores_get(h, ctypes.byref(out)), "pgv_level_scores_get")
+    return out
+
+
+def level_score_update(signal, kind="abs", alpha=1.0, include_partial=True, stamp=0, totals=None):
+    """A filled-in LevelScoreUpdate; signal, totals: device pointers (integers).  kind: a name of SCORE_KINDS or the number."""
+    number = SCORE_KINDS[kind] if kind in SCORE_KINDS else int(kind)
+    return LevelScoreUpdate(ctypes.sizeof(LevelScoreUpdate), number, float(alpha), int(bool(include_partial)), int(stamp), signal, totals)
+
+
 class StateLayoutStruct(ctypes.Structure):
     """include/procgen2_vec.h `pgv_state_layout`."""
     _fields_ = [("struct_size", c_uint32), ("width", c_int32), ("fixed", c_int32), ("record", c_int32), ("max_records", c_int32),
@@ -429,6 +471,9 @@ def load(path=None):
         "pgv_priorities_max": (P, [P]),
         "pgv_priorities_set": (c_int32, [P, P, P, c_int32, P]),
         "pgv_priorities_sample": (c_int32, [P, c_int32, POINTER(PrioritySample)]),
+        "pgv_level_scores_enable": (c_int32, [P, POINTER(LevelScoresConfig)]),
+        "pgv_level_scores_get": (c_int32, [P, POINTER(LevelScoreTable)]),
+        "pgv_level_scores_update": (c_int32, [P, c_int64, c_int32, POINTER(LevelScoreUpdate)]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -480,6 +525,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_history_gather", "pgv_history_gather_aug", "pgv_gather_aug_params", "pgv_history_gather_filter", "pgv_gather_filter_params",
     "pgv_transitions_enable", "pgv_transitions_action", "pgv_transitions_reward", "pgv_transitions_flags", "pgv_transitions_gather", "pgv_transitions_gae", "pgv_transitions_vtrace",
     "pgv_priorities_enable", "pgv_priorities", "pgv_priorities_max", "pgv_priorities_set", "pgv_priorities_sample",
+    "pgv_level_scores_enable", "pgv_level_scores_get", "pgv_level_scores_update",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",
     "pgv_tile_paths_rows", "pgv_tile_paths_rows_host", "pgv_path_layout_of",

@@ -33,8 +33,15 @@ def shard_range(total_envs, world_size, rank):
 class ProcgenVecEnv:
     def __init__(self, game, num_envs, device=0, seed_base=1, env_offset=0, lib_path=None, num_levels=0,
                  start_level=0, distribution_mode=None, game_flags=0, out=None, autoreset_mode=None, max_episode_steps=0,
-                 final_obs_capacity=0, policy_obs=None, history=None, transitions=False, priorities=False):
-        """priorities = False | True (needs transitions=True): prioritised sampling over the record ring (include/procgen2_vec.h
+                 final_obs_capacity=0, policy_obs=None, history=None, transitions=False, priorities=False, level_scores=None):
+        """level_scores = None | dict(first_level=0, capacity=K, known=("seeded", "custom")) (needs transitions=True): level replay
+        scores on the device (include/procgen2_vec.h pgv_level_scores_enable) — `level_scores`, a LevelScoreTensors: zero-copy
+        [T, N] views `level` (int32 bits of the engine's uint32) and `level_known` u8, the level every ring row was played on,
+        and the table `score` float32, `episodes` int32, `max_return` float32, `stamp` int64 [K] of levels first_level ..
+        first_level + K - 1.  known: which level words are filed — "seeded" (num_levels / assign_levels), "custom" (the ids of
+        set_levels).  level_scores_update() folds a per-step signal into the table.  None changes nothing at all.
+
+        priorities = False | True (needs transitions=True): prioritised sampling over the record ring (include/procgen2_vec.h
         pgv_priorities_enable) — `transitions.priority`, a zero-copy [T, N] view of the fixed-point priorities (int32 bits of the
         engine's uint32, pglib.PRIORITY_ONE = 1.0); every new row is opened at the running maximum.  transition_sample() draws
         (push, env) pairs over exactly the rows transition_gather() calls valid, transition_priorities() stores a learner's new
@@ -85,6 +92,9 @@ class ProcgenVecEnv:
             raise ValueError("priorities must be True or False")
         if priorities and not transitions:
             raise ValueError("priorities=True needs transitions=True")
+        scores = _level_scores_config(level_scores)
+        if scores is not None and not transitions:
+            raise ValueError("level_scores= needs transitions=True")
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         # The engine gets a stream of its own (a torch stream, so torch can order against it): torch's default stream
@@ -184,6 +194,16 @@ class ProcgenVecEnv:
                     pglib.check(self.L, self.L.pgv_priorities_enable(h), "pgv_priorities_enable")
                 self._after()
                 self.transitions = TransitionTensors(self, priorities)
+            except Exception:
+                self.close()
+                raise
+        self.level_scores = None
+        if scores is not None:
+            try:
+                self._before()
+                table = pglib.level_scores_enable(self.L, h, *scores)
+                self._after()
+                self.level_scores = LevelScoreTensors(self, table, scores[1])
             except Exception:
                 self.close()
                 raise
@@ -563,6 +583,31 @@ class ProcgenVecEnv:
         self._after()
         self._keep_vtrace = (v, rho, tv, vs, pg)
         return vs, pg
+
+    def level_scores_update(self, first, steps, signal, kind="abs", alpha=1.0, include_partial=True, stamp=None, totals=False):
+        """Fold signal float32 [steps, N] — normally transition_gae()'s advantages — over rows first .. first + steps - 1 of the
+        record ring into the level score table, two launches (pgv_level_scores_update): per episode inside the stretch the mean
+        of |signal| (kind "abs") or of max(signal, 0) ("positive"), in 16-bit fixed point, filed under the level the episode was
+        opened on; score = mean where the level had no episode yet, else (1 - alpha) * score + alpha * mean over all of the
+        call's episodes of that level.  include_partial: episodes the stretch (or a reset) cuts count too.  max_return is raised
+        by episodes the stretch holds whole.  stamp (None: the history's head) goes to `stamp` of every level touched.  The rows
+        must be held as for transition_gae().  totals=True: returns (segments, steps), int64 scalars on the device."""
+        if self.level_scores is None:
+            raise pglib.EngineError("level_scores_update needs an env made with transitions=True, level_scores=dict(...)")
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("level_scores_update: steps must be >= 1")
+        x = torch.as_tensor(signal, device=self.device).to(torch.float32).contiguous()
+        if tuple(x.shape) != (steps, self.num_envs):
+            raise ValueError("level_scores_update: signal must have shape (%d, %d)" % (steps, self.num_envs))
+        out = torch.zeros(2, dtype=torch.int64, device=self.device) if totals else None
+        q = pglib.level_score_update(x.data_ptr(), kind, alpha, include_partial, self.history.head if stamp is None else stamp,
+                                     None if out is None else out.data_ptr())
+        self._before()
+        pglib.check(self.L, self.L.pgv_level_scores_update(self._h, int(first), steps, ctypes.byref(q)), "pgv_level_scores_update")
+        self._after()
+        self._keep_level_scores = (x, out)
+        return (out[0], out[1]) if totals else None
 
     def _needs_priorities(self, who):
         if self.transitions is None or self.transitions.priority is None:
@@ -1065,6 +1110,40 @@ class TransitionTensors:
         self.action = _device_view(L.pgv_transitions_action(h), T * n, "<i4", env.device).view(T, n)
         self.reward = _device_view(L.pgv_transitions_reward(h), T * n, "<f4", env.device).view(T, n)
         self.flags = _device_view(L.pgv_transitions_flags(h), T * n, "|u1", env.device).view(T, n)
+
+
+class LevelScoreTensors:
+    """The level replay scores of a ProcgenVecEnv made with level_scores=dict(...): zero-copy views of the level ring [T, N] and
+    of the table [K]; entry k is level first_level + k.  The engine's uint32 columns are viewed as int32, which torch computes
+    with (a level number >= 2^31 reads negative; episodes never gets there)."""
+
+    def __init__(self, env, table, capacity):
+        n, T = env.num_envs, env.transitions.capacity
+        self.capacity = K = int(capacity)
+        self.level = _device_view(table.level, T * n, "<i4", env.device).view(T, n)
+        self.level_known = _device_view(table.level_known, T * n, "|u1", env.device).view(T, n)
+        self.score = _device_view(table.score, K, "<f4", env.device)
+        self.episodes = _device_view(table.episodes, K, "<i4", env.device)
+        self.max_return = _device_view(table.max_return, K, "<f4", env.device)
+        self.stamp = _device_view(table.stamp, K, "<i8", env.device)
+
+
+def _level_scores_config(level_scores):
+    """(first_level, capacity, known) of the level_scores= dict, or None; ValueError for what the engine would refuse, and for
+    unknown keys."""
+    if level_scores is None:
+        return None
+    if not isinstance(level_scores, dict) or set(level_scores) - {"first_level", "capacity", "known"} or "capacity" not in level_scores:
+        raise ValueError("level_scores must be None or a dict with the keys capacity and, optionally, first_level and known")
+    capacity, first = level_scores["capacity"], level_scores.get("first_level", 0)
+    known = tuple(level_scores.get("known", ("seeded",)))
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= 1 << 24:
+        raise ValueError("level_scores: capacity must be an integer in 1 .. 2**24")
+    if isinstance(first, bool) or not isinstance(first, int) or not 0 <= first < 1 << 32:
+        raise ValueError("level_scores: first_level must be an integer in 0 .. 2**32 - 1")
+    if not known or any(name not in pglib.SCORE_KNOWN for name in known):
+        raise ValueError("level_scores: known must name one or both of 'seeded' and 'custom'")
+    return first, capacity, known
 
 
 Transition = collections.namedtuple("Transition", "obs next_obs action nstep_return discount steps status")
