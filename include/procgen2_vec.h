@@ -831,6 +831,72 @@ PGV_API int32_t pgv_level_scores_enable(pgv_env* env, const pgv_level_scores_con
 PGV_API int32_t pgv_level_scores_get(pgv_env* env, pgv_level_score_table* out); /* set struct_size first */
 PGV_API int32_t pgv_level_scores_update(pgv_env* env, int64_t first, int32_t length, const pgv_level_score_update* update);
 
+/* Frame codes and visit counts: how new is a stored frame.  SimHash over the frame ring as in "#Exploration" — project a frame
+ * onto k directions with int8 matrix instructions, keep the signs, count the code in a device hash table — for count-based
+ * bonuses and, with a salt per row, their episodic and per-env forms.  Opt-in per engine, on top of the history: an engine
+ * that never enables it launches nothing new, allocates nothing new and gives the same bytes as before at every entry point.
+ *
+ *   1. pgv_frame_codes_enable needs pgv_history_enable first and may be called once.  bits = k is a multiple of 32 in 32 ..
+ *      256; table_capacity is 0 (no table) or a power of two in 8 .. 2^28.  weights NULL: the engine generates w int8 [k][D],
+ *      D = C*4096 in the ring's plane order, once, on the device: w[j][d] = (mix32(mix32(seed ^ j*0x9E3779B9) + d) & 1) ? +1 :
+ *      -1, mix32 the hash of pgv_level_numbers' level-seed mode.  Otherwise weights is the caller's device int8 [k][D], 16-byte
+ *      aligned, used in place and never copied (ternary or quantised Gaussian features, a learnt probe); seed is ignored.  A
+ *      refusal leaves a message and the engine as it was.  Weights and table travel neither in records nor in snapshots.
+ *   2. Entry b of a call names (pushes[b], envs[b]) exactly as pgv_history_gather does, and is VALID when 0 <= env < N and the
+ *      push is held.  There is no walk back and no stack: one entry is one stored frame.
+ *   3. proj[b][j] = sum over d of w[j][d] * ((int)frame_b[d] - 128), exact int32 (|proj| <= 12288*128*128 = 201 326 592).
+ *      codes[b] is k/32 uint32 words: bit j % 32 of word j / 32 is proj[b][j] >= 0.  An entry that is not valid has valid =
+ *      0, zero proj, zero words, visits 0, and is never counted.
+ *   4. The key of a row: lo = mix32(salt + 0x9E3779B9), hi = mix32(salt ^ 0x85EBCA6B); for every word in order lo = mix32(lo ^
+ *      word), hi = mix32(hi + (word ^ 0xC2B2AE35)); key = hi << 32 | lo, 0 mapped to 1.  salt = (uint32)salts[b], 0 without
+ *      salts: pass the env index or an episode number to count per env or per episode.
+ *   5. The table: keys uint64 [cap] (0 = empty), visits uint32 [cap], open addressing: a key's slots are ((uint32)key + i) &
+ *      (cap - 1) for i < min(cap, 128).  Counters used (slots claimed) and dropped, uint32.  All of it is the caller's to read.
+ *   6. count_mode PGV_COUNT_ADD: every valid row claims its key's slot (a 64-bit compare-and-swap) and adds 1; a row whose
+ *      key finds no slot within the probes is dropped: it reports visits 0 and adds 1 to dropped, nothing else changes.
+ *      A second launch then reads, so visits[b] is the key's total after the whole batch, whatever the order of the atomics.
+ *      PGV_COUNT_LOOK only reads: an absent key reports 0.  PGV_COUNT_NONE touches no table and writes no visits.  clear != 0
+ *      empties the table (and both counters) on the stream first.
+ *   7. Everything is enqueued on the env's stream: no allocation, no host synchronisation; all pointers are device pointers,
+ *      a NULL output is skipped.  count == 0 launches nothing but a clear that was asked for.
+ *   8. Refused on the host before anything is enqueued: env or struct NULL, struct_size too small, not enabled, count < 0,
+ *      an unknown count_mode, a count_mode other than NONE or a clear on an engine enabled without a table, pushes or envs
+ *      NULL with count > 0, proj, codes, salts or visits not 4-byte aligned. */
+#define PGV_COUNT_NONE 0
+#define PGV_COUNT_LOOK 1
+#define PGV_COUNT_ADD 2
+typedef struct pgv_frame_codes_config {
+    uint32_t struct_size;
+    int32_t bits;           /* k: 32, 64, .. 256 */
+    uint32_t seed;          /* of the generated weights */
+    int32_t table_capacity; /* 0, or a power of two in 8 .. 2^28 */
+    const int8_t* weights;  /* device int8 [k][C*4096], or NULL = generate */
+} pgv_frame_codes_config; /* 24 bytes */
+typedef struct pgv_frame_code_table { /* device pointers; the table's four are NULL without a table */
+    uint32_t struct_size;
+    int32_t bits;
+    int32_t capacity;
+    int32_t planes; /* C */
+    const int8_t* weights; /* [k][C*4096] */
+    uint64_t* keys;        /* [capacity] */
+    uint32_t* visits;      /* [capacity] */
+    uint32_t* used;        /* [1] */
+    uint32_t* dropped;     /* [1] */
+} pgv_frame_code_table; /* 56 bytes */
+typedef struct pgv_frame_code_query {
+    uint32_t struct_size;
+    int32_t count_mode;   /* PGV_COUNT_* */
+    int32_t clear;
+    const int32_t* salts; /* device int32 [count] or NULL */
+    int32_t* proj;        /* device int32 [count][k] or NULL */
+    uint32_t* codes;      /* device uint32 [count][k/32] or NULL */
+    uint8_t* valid;       /* device u8 [count] or NULL */
+    uint32_t* visits;     /* device uint32 [count] or NULL */
+} pgv_frame_code_query; /* 56 bytes */
+PGV_API int32_t pgv_frame_codes_enable(pgv_env* env, const pgv_frame_codes_config* config);
+PGV_API int32_t pgv_frame_codes_get(pgv_env* env, pgv_frame_code_table* out); /* set struct_size first */
+PGV_API int32_t pgv_frame_codes(pgv_env* env, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, const pgv_frame_code_query* query);
+
 /* cenv_render for one env of the batch (games/coinrun/coinrun.cpp:393-411, render_game(false)): the human-size frame,
  * width x height x 3 bytes row-major RGB into a HOST buffer.  Synchronises the env's stream.  Debug / viewer path. */
 PGV_API int32_t pgv_render_frame(pgv_env* env, int32_t index, int32_t width, int32_t height, uint8_t* h_rgb);

@@ -22,6 +22,7 @@
 #include "pg_vtrace.h"
 #include "pg_priorities.h"
 #include "pg_level_scores.h"
+#include "pg_frame_codes.h"
 #include "pg_policy_obs.h"
 #include "pg_records.h"
 #include "pg_sequence.h"
@@ -351,6 +352,11 @@ struct pgv_env {
     bool level_scores = false;
     pg::DeviceBlock<void> d_level_scores;
     pg::LevelScoreBuffers ls{};
+    // frame codes (pg_frame_codes.h; pgv_frame_codes_enable): off unless asked for, on top of the history.  One device block
+    // holds the generated weights and the visit table; a caller's weights are used where they lie.
+    bool frame_codes = false;
+    pg::DeviceBlock<void> d_frame_codes;
+    pg::FrameCodeBuffers fc{};
     // both features' value tables, dtype by dtype (pg_planes.h): the uploads' source, so they live as long as the env
     uint32_t value_tables[pg::kPolicyTables][256];  // (filled where the env is made)
 
@@ -1552,6 +1558,74 @@ int32_t pgv_level_scores_update(pgv_env* e, int64_t first, int32_t length, const
     q.ring = transition_ring(e);
     q.b = e->ls;
     pg::launch_level_score_update(e->stream, q, (e->game->debug_flags & pg::kDebugLevelScoresGlobal) != 0);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Frame codes and visit counts (pg_frame_codes.h)
+// ------------------------------------------------------------------------------------------------
+static_assert(PGV_COUNT_NONE == pg::kFcCountNone && PGV_COUNT_LOOK == pg::kFcCountLook && PGV_COUNT_ADD == pg::kFcCountAdd, "the header's count modes are the kernels'");
+int32_t pgv_frame_codes_enable(pgv_env* e, const pgv_frame_codes_config* cfg) {
+    const char* who = "pgv_frame_codes_enable";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!cfg || cfg->struct_size < sizeof(pgv_frame_codes_config)) return fail(std::string(who) + ": config is NULL or struct_size too small");
+    if (cfg->bits < pg::kFcMinBits || cfg->bits > pg::kFcMaxBits || cfg->bits % 32) return fail(std::string(who) + ": bits must be a multiple of 32 in 32 .. 256");
+    const int32_t cap = cfg->table_capacity;
+    if (cap != 0 && (cap < pg::kFcMinCapacity || cap > pg::kFcMaxCapacity || (cap & (cap - 1)))) return fail(std::string(who) + ": table_capacity must be 0 or a power of two in 8 .. 2^28");
+    if (reinterpret_cast<uintptr_t>(cfg->weights) & 15u) return fail(std::string(who) + ": weights must be 16-byte aligned");
+    if (e->frame_codes) return fail(std::string(who) + ": frame codes are enabled already (once per env)");
+    if (!e->history) return fail(std::string(who) + ": call pgv_history_enable first");
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::FrameCodeBuffers b{};
+    b.bits = cfg->bits, b.capacity = cap, b.planes = e->hist.planes, b.own_weights = cfg->weights ? 0 : 1;
+    auto fill = [&](void*, size_t) {
+        if (b.own_weights) pg::launch_frame_weights(e->stream, b, cfg->seed);
+        if (b.capacity) pg::launch_frame_table_clear(e->stream, b);
+        return hipGetLastError();
+    };
+    if (!b.own_weights && !b.capacity) {  // nothing of the engine's own to hold
+        b.weights = const_cast<int8_t*>(cfg->weights);
+    } else {
+        if (enable_block(who, e, pg::list_frame_codes, b, e->d_frame_codes, fill)) return 1;
+        if (cfg->weights) b.weights = const_cast<int8_t*>(cfg->weights);
+    }
+    e->fc = b;
+    e->frame_codes = true;
+    return 0;
+}
+
+int32_t pgv_frame_codes_get(pgv_env* e, pgv_frame_code_table* out) {
+    const char* who = "pgv_frame_codes_get";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!out || out->struct_size < sizeof(pgv_frame_code_table)) return fail(std::string(who) + ": out is NULL or struct_size too small");
+    if (!e->frame_codes) return fail(std::string(who) + ": call pgv_frame_codes_enable first");
+    out->bits = e->fc.bits, out->capacity = e->fc.capacity, out->planes = e->fc.planes;
+    out->weights = e->fc.weights, out->keys = e->fc.keys, out->visits = e->fc.visits, out->used = e->fc.used, out->dropped = e->fc.dropped;
+    return 0;
+}
+
+int32_t pgv_frame_codes(pgv_env* e, const int64_t* d_pushes, const int32_t* d_envs, int32_t count, const pgv_frame_code_query* qy) {
+    const char* who = "pgv_frame_codes";
+    if (!e) return fail(std::string(who) + ": env is NULL");
+    if (!qy || qy->struct_size < sizeof(pgv_frame_code_query)) return fail(std::string(who) + ": query is NULL or struct_size too small");
+    if (!e->frame_codes) return fail(std::string(who) + ": call pgv_frame_codes_enable first");
+    if (count < 0) return fail(std::string(who) + ": count is negative");
+    if (qy->count_mode != PGV_COUNT_NONE && qy->count_mode != PGV_COUNT_LOOK && qy->count_mode != PGV_COUNT_ADD) return fail(std::string(who) + ": unknown count_mode");
+    if ((qy->count_mode != PGV_COUNT_NONE || qy->clear) && !e->fc.capacity) return fail(std::string(who) + ": counting and clear need an engine enabled with a table (table_capacity > 0)");
+    if (count > 0 && (!d_pushes || !d_envs)) return fail(std::string(who) + ": pushes or envs is NULL");
+    if ((reinterpret_cast<uintptr_t>(qy->salts) | reinterpret_cast<uintptr_t>(qy->proj) | reinterpret_cast<uintptr_t>(qy->codes) | reinterpret_cast<uintptr_t>(qy->visits)) & 3u)
+        return fail(std::string(who) + ": salts, proj, codes and visits must be 4-byte aligned");
+    if (count == 0 && !qy->clear) return 0;
+    PG_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    pg::FrameCodes q{};
+    q.n = e->n, q.count = count, q.count_mode = qy->count_mode, q.head = e->history_head;
+    q.pushes = d_pushes, q.envs = d_envs, q.salts = qy->salts;
+    q.proj = qy->proj, q.codes = qy->codes, q.valid = qy->valid, q.visits = qy->count_mode == PGV_COUNT_NONE ? nullptr : qy->visits;
+    q.ring = e->hist, q.b = e->fc;
+    pg::launch_frame_codes(e->stream, q, qy->clear != 0);
     PG_HIP(hipGetLastError());
     return 0;
 }

@@ -187,6 +187,43 @@ def level_score_update(signal, kind="abs", alpha=1.0, include_partial=True, stam
     return LevelScoreUpdate(ctypes.sizeof(LevelScoreUpdate), number, float(alpha), int(bool(include_partial)), int(stamp), signal, totals)
 
 
+class FrameCodesConfig(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_frame_codes_config`."""
+    _fields_ = [("struct_size", c_uint32), ("bits", c_int32), ("seed", c_uint32), ("table_capacity", c_int32), ("weights", c_void_p)]
+
+
+class FrameCodeTable(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_frame_code_table` (device pointers)."""
+    _fields_ = [("struct_size", c_uint32), ("bits", c_int32), ("capacity", c_int32), ("planes", c_int32), ("weights", c_void_p),
+                ("keys", c_void_p), ("visits", c_void_p), ("used", c_void_p), ("dropped", c_void_p)]
+
+
+class FrameCodeQuery(ctypes.Structure):
+    """include/procgen2_vec.h `pgv_frame_code_query`."""
+    _fields_ = [("struct_size", c_uint32), ("count_mode", c_int32), ("clear", c_int32), ("salts", c_void_p), ("proj", c_void_p),
+                ("codes", c_void_p), ("valid", c_void_p), ("visits", c_void_p)]
+
+
+COUNT_MODES = {None: 0, "look": 1, "add": 2}  # include/procgen2_vec.h PGV_COUNT_*
+FRAME_CODE_ROWS = 32  # csrc/pg_frame_codes.h: the entries of a row block of the projection kernel's tile (two blocks up to 128 bits, one above)
+
+
+def frame_codes_enable(lib, h, bits, seed, table, weights=None):
+    """pgv_frame_codes_enable (after history_enable) and pgv_frame_codes_get: the filled-in FrameCodeTable.  weights: a device
+    pointer (integer) to the caller's int8 [bits][C*4096], or None."""
+    cfg = FrameCodesConfig(ctypes.sizeof(FrameCodesConfig), int(bits), int(seed) & 0xFFFFFFFF, int(table), weights)
+    check(lib, lib.pgv_frame_codes_enable(h, ctypes.byref(cfg)), "pgv_frame_codes_enable")
+    out = FrameCodeTable(ctypes.sizeof(FrameCodeTable))
+    check(lib, lib.pgv_frame_codes_get(h, ctypes.byref(out)), "pgv_frame_codes_get")
+    return out
+
+
+def frame_code_query(count=None, clear=False, salts=None, proj=None, codes=None, valid=None, visits=None):
+    """A filled-in FrameCodeQuery; the pointers are device pointers (integers).  count: a key of COUNT_MODES or the number."""
+    mode = COUNT_MODES[count] if count in COUNT_MODES else int(count)
+    return FrameCodeQuery(ctypes.sizeof(FrameCodeQuery), mode, int(bool(clear)), salts, proj, codes, valid, visits)
+
+
 class StateLayoutStruct(ctypes.Structure):
     """include/procgen2_vec.h `pgv_state_layout`."""
     _fields_ = [("struct_size", c_uint32), ("width", c_int32), ("fixed", c_int32), ("record", c_int32), ("max_records", c_int32),
@@ -474,6 +511,9 @@ def load(path=None):
         "pgv_level_scores_enable": (c_int32, [P, POINTER(LevelScoresConfig)]),
         "pgv_level_scores_get": (c_int32, [P, POINTER(LevelScoreTable)]),
         "pgv_level_scores_update": (c_int32, [P, c_int64, c_int32, POINTER(LevelScoreUpdate)]),
+        "pgv_frame_codes_enable": (c_int32, [P, POINTER(FrameCodesConfig)]),
+        "pgv_frame_codes_get": (c_int32, [P, POINTER(FrameCodeTable)]),
+        "pgv_frame_codes": (c_int32, [P, P, P, c_int32, POINTER(FrameCodeQuery)]),
         "pgv_step_synthetic_many": (c_int32, [P, c_int32, c_int32, c_uint32]),
         "pgv_timed_steps": (c_int32, [P, c_int32, c_uint32, POINTER(c_double), POINTER(c_double)]),
         "pgv_step_times": (c_int32, [P, c_int32, c_uint32, c_void_p, c_void_p]),
@@ -526,6 +566,7 @@ EXPORTED_VEC_SYMBOLS = [
     "pgv_transitions_enable", "pgv_transitions_action", "pgv_transitions_reward", "pgv_transitions_flags", "pgv_transitions_gather", "pgv_transitions_gae", "pgv_transitions_vtrace",
     "pgv_priorities_enable", "pgv_priorities", "pgv_priorities_max", "pgv_priorities_set", "pgv_priorities_sample",
     "pgv_level_scores_enable", "pgv_level_scores_get", "pgv_level_scores_update",
+    "pgv_frame_codes_enable", "pgv_frame_codes_get", "pgv_frame_codes",
     "pgv_timed_steps", "pgv_step_times", "pgv_step_phases", "pgv_step_phases_many", "pgv_set_debug", "pgv_dump_state", "pgv_dump_tiles",
     "pgv_state_layout_of", "pgv_state_names", "pgv_state_rows", "pgv_tile_rows", "pgv_state_rows_host", "pgv_tile_rows_host",
     "pgv_tile_paths_rows", "pgv_tile_paths_rows_host", "pgv_path_layout_of",

@@ -33,8 +33,15 @@ def shard_range(total_envs, world_size, rank):
 class ProcgenVecEnv:
     def __init__(self, game, num_envs, device=0, seed_base=1, env_offset=0, lib_path=None, num_levels=0,
                  start_level=0, distribution_mode=None, game_flags=0, out=None, autoreset_mode=None, max_episode_steps=0,
-                 final_obs_capacity=0, policy_obs=None, history=None, transitions=False, priorities=False, level_scores=None):
-        """level_scores = None | dict(first_level=0, capacity=K, known=("seeded", "custom")) (needs transitions=True): level replay
+                 final_obs_capacity=0, policy_obs=None, history=None, transitions=False, priorities=False, level_scores=None,
+                 frame_codes=None):
+        """frame_codes = None | dict(bits=64, seed=0, table=1 << 20, weights=None) (needs history=dict(...)): SimHash codes and visit
+        counts of stored frames on the device (include/procgen2_vec.h pgv_frame_codes_enable).  bits: a multiple of 32 in 32 ..
+        256; table: 0 or a power of two in 8 .. 2**28, the slots of the visit table; weights: None for the engine's own +-1
+        directions from `seed`, or a contiguous int8 device tensor [bits, C*4096] used in place.  frame_codes() projects, codes
+        and counts; `frame_code_table`, a FrameCodeTensors, holds the zero-copy views.  None changes nothing at all.
+
+        level_scores = None | dict(first_level=0, capacity=K, known=("seeded", "custom")) (needs transitions=True): level replay
         scores on the device (include/procgen2_vec.h pgv_level_scores_enable) — `level_scores`, a LevelScoreTensors: zero-copy
         [T, N] views `level` (int32 bits of the engine's uint32) and `level_known` u8, the level every ring row was played on,
         and the table `score` float32, `episodes` int32, `max_return` float32, `stamp` int64 [K] of levels first_level ..
@@ -92,6 +99,9 @@ class ProcgenVecEnv:
             raise ValueError("priorities must be True or False")
         if priorities and not transitions:
             raise ValueError("priorities=True needs transitions=True")
+        codes = _frame_codes_config(frame_codes)
+        if codes is not None and history is None:
+            raise ValueError("frame_codes= needs history=dict(...)")
         scores = _level_scores_config(level_scores)
         if scores is not None and not transitions:
             raise ValueError("level_scores= needs transitions=True")
@@ -204,6 +214,22 @@ class ProcgenVecEnv:
                 table = pglib.level_scores_enable(self.L, h, *scores)
                 self._after()
                 self.level_scores = LevelScoreTensors(self, table, scores[1])
+            except Exception:
+                self.close()
+                raise
+
+        self.frame_code_table = None
+        if codes is not None:
+            try:
+                bits, seed, table, weights = codes
+                planes = self.history.frames.shape[2]
+                if weights is not None and (weights.dtype != torch.int8 or weights.device != self.device or not weights.is_contiguous() or
+                                            tuple(weights.shape) != (bits, planes * 4096)):
+                    raise ValueError("frame_codes: weights must be a contiguous int8 tensor of shape (%d, %d) on %s" % (bits, planes * 4096, self.device))
+                self._before()
+                got = pglib.frame_codes_enable(self.L, h, bits, seed, table, None if weights is None else weights.data_ptr())
+                self._after()
+                self.frame_code_table = FrameCodeTensors(self, got, weights)
             except Exception:
                 self.close()
                 raise
@@ -608,6 +634,40 @@ class ProcgenVecEnv:
         self._after()
         self._keep_level_scores = (x, out)
         return (out[0], out[1]) if totals else None
+
+    def frame_codes(self, pushes, envs, salts=None, count=None, proj=False, clear=False):
+        """SimHash codes of the B stored frames (pushes[b], envs[b]) — named as for history_gather(), one frame an entry, no stack
+        — and their visit counts, on the device with no host synchronisation (pgv_frame_codes).  Returns a FrameCodes: `codes`
+        int32 [B, bits/32] (the engine's uint32 words: bit j % 32 of word j / 32 is proj[b, j] >= 0), `valid` uint8 [B], `visits`
+        int32 [B] or None, `proj` int32 [B, bits] (proj=True: the exact projections sum_d w[j, d] * (frame[d] - 128)) or None.
+        An entry that is not held or whose env is outside the batch has valid 0 and zeros everywhere, and is never counted.
+        count="add": every valid row's key gains a visit, then `visits` is each key's total after the whole batch; "look": the
+        totals as they stand, 0 for a code never added; None: the table is not touched.  salts: int32 [B], part of the key —
+        the env index or an episode number counts per env or per episode.  clear=True empties the table first.  A row whose
+        key finds no slot in a full table reports 0 and counts in `frame_code_table.dropped`."""
+        t = self.frame_code_table
+        if t is None:
+            raise pglib.EngineError("frame_codes needs an env made with history=dict(...), frame_codes=dict(...)")
+        if count not in pglib.COUNT_MODES:
+            raise ValueError("frame_codes: count must be 'add', 'look' or None")
+        p, i = self._gather_entries("frame_codes", pushes, envs)
+        B = p.numel()
+        s = None
+        if salts is not None:
+            s = torch.as_tensor(salts, device=self.device).to(torch.int32).reshape(-1).contiguous()
+            if s.numel() != B:
+                raise ValueError("frame_codes: %d pushes but %d salts" % (B, s.numel()))
+        out = FrameCodes(torch.zeros((B, t.bits // 32), dtype=torch.int32, device=self.device),
+                         torch.zeros(B, dtype=torch.uint8, device=self.device),
+                         torch.zeros(B, dtype=torch.int32, device=self.device) if count is not None else None,
+                         torch.zeros((B, t.bits), dtype=torch.int32, device=self.device) if proj else None)
+        ptr = lambda x: None if x is None else x.data_ptr()
+        q = pglib.frame_code_query(count, clear, ptr(s), ptr(out.proj), ptr(out.codes), ptr(out.valid), ptr(out.visits))
+        self._before()
+        pglib.check(self.L, self.L.pgv_frame_codes(self._h, c_void_p(p.data_ptr()), c_void_p(i.data_ptr()), B, ctypes.byref(q)), "pgv_frame_codes")
+        self._after()
+        self._keep_frame_codes = (p, i, s, out)
+        return out
 
     def _needs_priorities(self, who):
         if self.transitions is None or self.transitions.priority is None:
@@ -1128,6 +1188,40 @@ class LevelScoreTensors:
         self.stamp = _device_view(table.stamp, K, "<i8", env.device)
 
 
+class FrameCodeTensors:
+    """The frame codes of a ProcgenVecEnv made with frame_codes=dict(...): zero-copy views of `weights` int8 [bits, C*4096] (the
+    caller's own tensor where one was given) and, where there is a table, `keys` int64 [capacity] (the engine's uint64; 0 = an
+    empty slot), `visits` int32 [capacity], `used` and `dropped` int32 [1]; None without one."""
+
+    def __init__(self, env, table, weights=None):
+        self.bits, self.capacity, self.planes = int(table.bits), int(table.capacity), int(table.planes)
+        D = self.planes * 4096
+        self.weights = weights if weights is not None else _device_view(table.weights, self.bits * D, "|i1", env.device).view(self.bits, D)
+        self.keys = self.visits = self.used = self.dropped = None
+        if self.capacity:
+            self.keys = _device_view(table.keys, self.capacity, "<i8", env.device)
+            self.visits = _device_view(table.visits, self.capacity, "<i4", env.device)
+            self.used = _device_view(table.used, 1, "<i4", env.device)
+            self.dropped = _device_view(table.dropped, 1, "<i4", env.device)
+
+
+def _frame_codes_config(frame_codes):
+    """(bits, seed, table, weights) of the frame_codes= dict, or None; ValueError for what the engine would refuse, and for
+    unknown keys."""
+    if frame_codes is None:
+        return None
+    if not isinstance(frame_codes, dict) or set(frame_codes) - {"bits", "seed", "table", "weights"}:
+        raise ValueError("frame_codes must be None or a dict with the keys bits, seed, table, weights")
+    bits, seed, table = frame_codes.get("bits", 64), frame_codes.get("seed", 0), frame_codes.get("table", 1 << 20)
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 32 <= bits <= 256 or bits % 32:
+        raise ValueError("frame_codes: bits must be a multiple of 32 in 32 .. 256")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError("frame_codes: seed must be an integer")
+    if isinstance(table, bool) or not isinstance(table, int) or (table != 0 and (not 8 <= table <= 1 << 28 or table & (table - 1))):
+        raise ValueError("frame_codes: table must be 0 or a power of two in 8 .. 2**28")
+    return bits, seed, table, frame_codes.get("weights")
+
+
 def _level_scores_config(level_scores):
     """(first_level, capacity, known) of the level_scores= dict, or None; ValueError for what the engine would refuse, and for
     unknown keys."""
@@ -1146,6 +1240,7 @@ def _level_scores_config(level_scores):
     return first, capacity, known
 
 
+FrameCodes = collections.namedtuple("FrameCodes", "codes valid visits proj")
 Transition = collections.namedtuple("Transition", "obs next_obs action nstep_return discount steps status")
 TransitionSample = collections.namedtuple("TransitionSample", "pushes envs prob priority total eligible")
 
